@@ -19,11 +19,13 @@ time; `value_compute_only` the same steps without any exchange.  `python bench.p
 the single-GPU benchmark below, unchanged.
 
 Prints ONE JSON line on rank 0 (see the contract in the task description) with extra objects:
-`roofline` (HBM roofline of the fused kernel, measured live with HIP events), `cpu_baseline` (this build's
-own C++ restatement - the CPU twin of the C-ABI, host build of the kernels' source - on 1 thread and on all
-host threads, the NumPy oracle and upstream's probed Python time quoted beside it) and `parity` (cells of
-the timed workload the kernel decides differently from the oracle, each checked against the derived
-rounding band).
+`roofline` (HBM roofline of the fused kernel, measured live with HIP events in the timed steps).  A plain
+N = 1 run does only that: set up, warm up, the K timed steps, the line.  `--full` adds the secondary legs:
+`cpu_baseline` (this build's own C++ restatement - the CPU twin of the C-ABI, host build of the kernels'
+source - on 1 thread and on all host threads, the NumPy oracle and upstream's probed Python time quoted
+beside it), `parity` (cells of the timed workload the kernel decides differently from the oracle, each
+checked against the derived rounding band), the side kernels, the sampled and default modes, the package
+power and the `pipeline` leg.  `--dump-outputs DIR` writes what the last timed step returned (last_step_outputs).
 """
 from __future__ import annotations
 
@@ -91,7 +93,13 @@ def parse_args():
     ap.add_argument("--cpu-sample-refs", type=int, default=24,
                     help="references of the workload timed on the CPU twin (0 = skip the cpu_baseline leg)")
     ap.add_argument("--spinup-s", type=float, default=0.25, help="untimed spin-up (bursts of 32 back-to-back launches) before the warm-up steps")
-    ap.add_argument("--light", action="store_true", help="headline only: skip the secondary legs (profiling passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the headline, also the second bracketed pass (fresh_batch_ms, kernel_ms_bracketed) and the secondary legs "
+                         "(power, side kernels, sampled and default modes, parity, cpu_baseline, the pipeline leg); a plain run times the headline only")
+    ap.add_argument("--light", action="store_true", help="with --full: skip the secondary legs (profiling passes)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="N = 1: write what the last timed step returned as DIR/<name>.npy (every reference's survivor count; xyz / rgb / err "
+                         "of a seeded sample of references)")
     ap.add_argument("--parity-refs", type=int, default=2, help="references of the workload checked cell by cell against the oracle (0 = skip)")
     ap.add_argument("--scene-root", default=os.environ.get("LFD_SCENE_ROOT"),
                     help="a COLMAP scene (images*/ + sparse/0/) for the END-TO-END leg: dense_init through the real RoMa-v2 matcher; needs the `romav2` package "
@@ -106,6 +114,8 @@ def parse_args():
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per launch from a rocprofv3 --pmc run of this same command (profiles/)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     many = args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1
     if args.workload is None:
         args.workload = "config4" if many else "config2"
@@ -1319,6 +1329,34 @@ def launch_ranks(args):
         raise SystemExit(f"rank exit codes {codes}")
 
 
+DUMP_BUDGET_BYTES = 60 << 20      # --dump-outputs stays under 64 MB
+
+
+def last_step_outputs(out, rot, cells_per_ref):
+    """What a caller of the timed path receives from its last step, on the host, in the workload's reference order (the last batch holds
+    `refs` rotated by `rot`): every reference's survivor count, and xyz / rgb / err (f32, the kernel's ordered output) of the survivors of a
+    seeded sample of whole references - as many as fit in DUMP_BUDGET_BYTES at the grid's capacity of 28 bytes per cell, so that the choice
+    depends on the arguments alone, never on the outputs."""
+    res = out.collect()
+    offs = res.ref_offsets
+    n_refs = len(offs) - 1
+    pos = (np.arange(n_refs) - rot) % n_refs                    # batch position of workload reference g
+    n_take = max(1, min(n_refs, DUMP_BUDGET_BYTES // (cells_per_ref * 28)))
+    pick = np.sort(np.random.default_rng(0).choice(n_refs, n_take, replace=False))
+    spans = [(int(offs[pos[g]]), int(offs[pos[g] + 1])) for g in pick]
+    arrays = {"points_per_reference": np.diff(offs)[pos].astype(np.float64), "sample_references": pick.astype(np.float64)}
+    for name in ("xyz", "rgb", "err"):
+        t = getattr(res, name)
+        arrays[name] = torch.cat([t[a:b] for a, b in spans]).cpu().numpy().astype(np.float32)
+    return arrays
+
+
+def dump_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     args = parse_args()
     if args.dry_run:
@@ -1359,6 +1397,8 @@ def main():
             dist.init_process_group("gloo", rank=rank, world_size=world, timeout=limit)
 
     if dist is not None:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the N = 1 line's outputs; the sharded leg has none to write")
         return run_sharded(args, world, rank, dev, dist, backend)
     cams, refs, srefs, dims, mine, total_refs = build_workload(args, rank, world, dev)
     H, W, wm, hm = dims
@@ -1423,17 +1463,20 @@ def main():
     if len(per_launch) != args.steps:
         raise SystemExit(f"{len(per_launch)} kernel timings for {args.steps} steps")
     kernel_ms = float(np.mean(per_launch))
-    # A second pass of the same K steps, outside the value: events recorded AROUND the two calls of a step - what is left of the batch
-    # preparation in the launch stream (`fresh_batch_ms`) and the launch as a caller's events see it (`kernel_ms_bracketed`: the
-    # kernel plus the dispatch gap in front of it).  Three more packets per step, which is why this is not the timed region.
-    ev = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) for _ in range(args.steps)]
-    for i, e3 in enumerate(ev):
-        step(i, e3)
-    barrier()
-    per_bracket = [e1.elapsed_time(e2) for _e0, e1, e2 in ev]
-    per_prepare = [e0.elapsed_time(e1) for e0, e1, _e2 in ev]
-    kernel_ms_bracketed = float(np.mean(per_bracket))
-    fresh_batch_ms = float(np.mean(per_prepare))
+    rot = (args.steps - 1) % len(batches)      # the last launch's references are `refs` rotated by this much
+    dumped = last_step_outputs(out, rot, H * W) if args.dump_outputs else None
+    if args.full:
+        # A second pass of the same K steps, outside the value: events recorded AROUND the two calls of a step - what is left of the batch
+        # preparation in the launch stream (`fresh_batch_ms`) and the launch as a caller's events see it (`kernel_ms_bracketed`: the
+        # kernel plus the dispatch gap in front of it).  Three more packets per step, which is why this is not the timed region.
+        ev = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) for _ in range(args.steps)]
+        for i, e3 in enumerate(ev):
+            step(i, e3)
+        barrier()
+        per_bracket = [e1.elapsed_time(e2) for _e0, e1, e2 in ev]
+        per_prepare = [e0.elapsed_time(e1) for e0, e1, _e2 in ev]
+        kernel_ms_bracketed = float(np.mean(per_bracket))
+        fresh_batch_ms = float(np.mean(per_prepare))
     kernel_pct = {"p50": float(np.percentile(per_launch, 50)), "p95": float(np.percentile(per_launch, 95)),
                   "min": float(np.min(per_launch)), "max": float(np.max(per_launch))}
     if os.environ.get("LFD_BENCH_DEBUG"):
@@ -1441,9 +1484,10 @@ def main():
         print(f"[rank {rank}] per-launch ms: min {min(per_launch):.3f} max {max(per_launch):.3f} mean {kernel_ms:.3f}; "
               f"wall {elapsed * 1e3:.2f} ms for {args.steps} steps", file=sys.stderr)
     dens.check_launches()
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
     res = out.collect()
     n_pts = res.count
-    rot = (args.steps - 1) % len(batches) if args.steps > 0 else 0      # the last launch's references are `refs` rotated by this much
 
     total_pts = float(n_pts)
 
@@ -1472,7 +1516,7 @@ def main():
             "cells_per_s": total_refs * H * W * args.steps / elapsed,
             "survivor_fraction": s_frac,
             # one step = lfd_prepare_batch (descriptor upload + per-pair constants of a batch the context has not just seen) + the dense kernel
-            "compute_ms": elapsed / args.steps * 1e3, "kernel_ms": kernel_ms, "fresh_batch_ms": fresh_batch_ms,
+            "compute_ms": elapsed / args.steps * 1e3, "kernel_ms": kernel_ms,
             "host": getattr(args, "host", None),
             "end_to_end": None,
             "end_to_end_note": "points/s including the RoMa-v2 forward (SURVEY 8d iii) is unmeasured: neither the RoMa-v2 weights nor torchvision are on the box",
@@ -1481,18 +1525,21 @@ def main():
                          "traffic": traffic, "traffic_source": traffic_source,
                          "kernel": "lfd_dense_kernel", "kernel_ms": kernel_ms, "kernel_ms_percentiles": kernel_pct,
                          "kernel_ms_source": "HIP start/stop events of each timed launch (hipExtLaunchKernelGGL) on the launch stream, mean over the timed region",
-                         "kernel_ms_bracketed": kernel_ms_bracketed,      # events recorded around the call instead: they include the dispatch gap before the kernel
                          "algorithmic_bytes_per_launch": algo_bytes, "bytes_per_cell": bytes_per_cell},
         }
         # the same time priced against the byte count of a kernel that reads the warps of ALL k neighbours coalesced
         # (12k + 3 + 28 s per cell) - what lfd_dense_kernel physically does for references with at most LFD_DENSE_ALL_WARPS (2) neighbours
         line["roofline"]["achieved_all_warps_bytes"] = cells * (12 * args.k + 3 + 28 * s_frac) / (kernel_ms * 1e-3) / 1e9
-        if not args.light and world == 1:
+        if args.full:
+            line["fresh_batch_ms"] = fresh_batch_ms
+            line["roofline"]["kernel_ms_bracketed"] = kernel_ms_bracketed     # events recorded around the call instead: they include the dispatch gap before the kernel
+        side_legs = args.full and not args.light and world == 1
+        if side_legs:
             line["roofline"]["device_copy_GBps"] = device_copy_bandwidth(dev)      # what a plain device-to-device copy reaches on this box
         line["roofline"]["valu_busy_frac"] = valu_busy_frac(args)     # the f64 geometry makes the kernel vector-ALU-bound, not HBM-bound (same source as `traffic`)
         line["roofline"]["valu"] = valu_roofline(args, kernel_ms)      # ... and that bound itself: issue time of the vector instructions / kernel time
         line["roofline"]["traffic_over_algorithmic"] = (line["roofline"]["traffic"] / algo_bytes) if line["roofline"]["traffic"] else None
-        if not args.light and world == 1:
+        if side_legs:
             e2e, why = end_to_end(args)
             line["end_to_end"] = e2e
             if why:
@@ -1502,7 +1549,7 @@ def main():
             line["roofline"]["power"] = power_under_kernel(dens, batches, params, out, dev)      # the bound that binds: the package's power cap
             line["unordered_retirement"] = unordered_rate(args, dens, batch, params, out, H, W, algo_bytes)
             line["ply_output"] = ply_output_rate(args, dens, batch, params, H, W, cells, s_frac)
-        if not args.light and world == 1:     # the side legs (and the CPU baseline) belong to the N = 1 line; at N > 1 the other ranks are waiting
+        if side_legs:     # the side legs (and the CPU baseline) belong to the N = 1 line; at N > 1 the other ranks are waiting
             line["with_d2h"] = d2h_inclusive_rate(dens, batch, params, out, dev)
             line["sampled_mode"] = sampled_mode_rate(args, dens, refs, dims, cfg, cams_for_hot=cams)
             line["secondary_kernels"] = secondary_kernels(args, dens, batch, refs, dims, cfg, res)

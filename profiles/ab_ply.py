@@ -10,7 +10,7 @@ res = {os.path.basename(l)[:-3]: ([], []) for l in libs}
 for p in range(a.passes):
     for lib in libs:
         name = os.path.basename(lib)[:-3]
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-sample-refs", "0", "--parity-refs", "0", "--pipeline-cams", "0", "--steps", "50"],
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--cpu-sample-refs", "0", "--parity-refs", "0", "--pipeline-cams", "0", "--steps", "50"],
                              env=dict(os.environ, LFD_DENSIFY_LIB=lib), capture_output=True, text=True)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if out.returncode or not line:

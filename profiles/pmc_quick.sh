@@ -12,7 +12,7 @@ for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_BUSY
            "SQ_INST_LEVEL_VMEM SQ_INST_LEVEL_LDS SQ_INSTS_SMEM SQ_THREAD_CYCLES_VALU SQ_WAVES SQ_INSTS_FLAT SQ_INST_LEVEL_SMEM SQ_ACTIVE_INST_FLAT" \
            "TCP_PENDING_STALL_CYCLES_sum TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $OUT/p$i -o p -- python3 $REPO/bench.py --steps 4 --warmup 1 --cpu-sample-refs 0 > $OUT/p$i.log 2>&1
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $OUT/p$i -o p -- python3 $REPO/bench.py --full --steps 4 --warmup 1 --cpu-sample-refs 0 > $OUT/p$i.log 2>&1
 done
 python3 - <<PY | tee $OUT/summary.txt
 import csv, glob, collections

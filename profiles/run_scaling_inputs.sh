@@ -5,7 +5,7 @@
 REPO=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 for n in 1 2 4 8; do
   refs=$(( (56 + n - 1) / n ))
-  python $REPO/bench.py --workload config4 --scaling strong --refs $refs --light --steps 100 --cpu-sample-refs 0 2>/dev/null | python -c "
+  python $REPO/bench.py --workload config4 --scaling strong --refs $refs --full --light --steps 100 --cpu-sample-refs 0 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,7 +2,7 @@
 # selection kernel: workgroups vs time per reference (synchronising call, 512x512, M=10000)
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 for g in 0 4 8 16 32 64; do
-  LFD_SELECT_WORKGROUPS=$g python $REPO/bench.py --cpu-sample-refs 0 --steps 5 --spinup-s 0.02 2>/dev/null | python -c "
+  LFD_SELECT_WORKGROUPS=$g python $REPO/bench.py --full --cpu-sample-refs 0 --steps 5 --spinup-s 0.02 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

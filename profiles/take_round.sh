@@ -2,7 +2,7 @@
 # One box, one lease: everything the round's numbers come from (run on the GPU box from the repo root: bash profiles/take_round.sh r5).
 #   1. rocprofv3 --kernel-trace --stats of the bench's timed loop, the PMC passes (SQ, FETCH_SIZE, WRITE_SIZE in separate passes), the instruction mix
 #   2. profiles/traffic.json regenerated from them (what `roofline.traffic` / `roofline.valu` of the bench line quote)
-#   3. the full default `python bench.py` (headline, side legs, cpu_baseline, parity, the pipeline leg) -> gpurun_out/<tag>/bench.json
+#   3. `python bench.py --full` (headline, side legs, cpu_baseline, parity, the pipeline leg) -> $OUT/bench.json
 # The summaries land in gpurun_out/<tag>/ ; copy what is to be judged into profiles/<tag>/ .
 set -u
 TAG=${1:-r5}
@@ -16,7 +16,7 @@ cp $REPO/gpurun_out/prof_${TAG}_mix/summary.txt $OUT/instruction_mix.txt
 f=$(find $REPO/gpurun_out/prof_$TAG/trace -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/kernel_stats.csv
 python3 $REPO/profiles/make_traffic_json.py $REPO/gpurun_out/prof_$TAG $REPO/gpurun_out/prof_${TAG}_mix profiles/$TAG > $OUT/traffic.json
 cp $OUT/traffic.json $REPO/profiles/traffic.json
-cd $REPO && python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+cd $REPO && python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 python3 - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))

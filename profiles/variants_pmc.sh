@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 for so in $REPO/build/variants/*.so; do
   name=$(basename $so .so)
   export LFD_DENSIFY_LIB=$so
-  rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d $OUT/$name -o p -- python3 $REPO/bench.py --steps 4 --warmup 1 --cpu-sample-refs 0 > $OUT/$name.log 2>&1
+  rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d $OUT/$name -o p -- python3 $REPO/bench.py --full --steps 4 --warmup 1 --cpu-sample-refs 0 > $OUT/$name.log 2>&1
   python3 - <<PY
 import csv, glob, collections
 acc = collections.defaultdict(list)

@@ -1,5 +1,5 @@
 """The N = 1 line of bench.py carries what the contract asks for (small shape, seconds): metric / value / unit / config, `roofline` with both
-bounds (HBM bytes and vector-issue time), `cpu_baseline`, `parity`, and the round-4 side keys."""
+bounds (HBM bytes and vector-issue time), and with --full `cpu_baseline`, `parity` and the round-4 side keys."""
 import json
 import os
 import subprocess
@@ -15,7 +15,7 @@ def test_single_gpu_bench_line_contract():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LFD_BENCH_FORCE_DIST"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "5", "--warmup", "2", "--refs", "6", "--preset", "turbo", "--cpu-sample-refs", "2",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--refs", "6", "--preset", "turbo", "--cpu-sample-refs", "2",
            "--parity-refs", "1", "--spinup-s", "0.05", "--pipeline-cams", "8", "--pipeline-size", "320x208", "--pipeline-latency-ms", "1"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=REPO)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -53,3 +53,40 @@ def test_single_gpu_bench_line_contract():
     assert d["end_to_end"] is None and "unmeasured" in d["end_to_end_note"]
     assert len(s["default_config_passes_ms_per_reference"]) == 5 and s["default_config_ms_per_reference"] == min(s["default_config_passes_ms_per_reference"])
     assert d["host"]["torch_threads"] >= 1 and d["host"]["cpus_visible"] >= d["host"]["torch_threads"]       # threads fitted to the container's quota (core/hostenv.py)
+
+
+def _plain_run(dump_dir):
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LFD_BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--refs", "6", "--preset", "turbo",
+           "--spinup-s", "0.05", "--dump-outputs", str(dump_dir)]
+    res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_plain_bench_line_is_the_headline_and_dumps_its_last_step(tmp_path):
+    """Without --full: the headline keys, none of the secondary legs; --dump-outputs writes the last timed step's survivors, the same
+    bytes from run to run."""
+    import numpy as np
+    d = _plain_run(tmp_path / "a")
+    assert d["metric"].startswith("triangulated points/sec") and d["unit"] == "points/s" and d["value"] > 0 and d["higher_is_better"] is True
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "f32 (+f64 Sampson/DLT solve)"
+    assert d["roofline"]["kernel_ms"] > 0 and "power" not in d["roofline"] and "kernel_ms_bracketed" not in d["roofline"]
+    for key in ("fresh_batch_ms", "cpu_baseline", "parity", "sampled_mode", "default_mode", "secondary_kernels", "pipeline", "with_d2h",
+                "unordered_retirement", "ply_output"):
+        assert key not in d, key
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("points_per_reference", "sample_references", "xyz", "rgb", "err")}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    counts = a["points_per_reference"]
+    assert counts.shape == (6,) and abs(counts.sum() - d["value"] * d["ms_per_step"] * 1e-3) <= 1e-6 * counts.sum()
+    n = int(counts[a["sample_references"].astype(int)].sum())
+    assert n > 0 and a["xyz"].shape == (n, 3) and a["rgb"].shape == (n, 3) and a["err"].shape == (n,)
+    b = _plain_run(tmp_path / "b")
+    for name, v in a.items():
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / f"{name}.npy"), v, err_msg=name)
+    assert b["steps"] == 4
