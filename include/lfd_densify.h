@@ -291,6 +291,20 @@ int lfd_pack_points3d(lfd_context* ctx, const float* xyz, const float* rgb, cons
                       uint64_t id_base, uint8_t* out);
 int lfd_quantise_rgb(lfd_context* ctx, const float* rgb, int64_t n, uint8_t* out);
 
+/* The GUI's distance filter (densify._voxel_downsample, NumPy branch; upstream densify.py:29-50 with Open3D): one point per occupied voxel,
+ * bit for bit and in the same order as the NumPy branch for the same arrays.  xyz, rgb: n x 3 f32 on the device.
+ *   origin_c = (f64) min_c x - 0.5 voxel_size;  key_c = floor(((f64) x_c - origin_c) / voxel_size)  (IEEE f64 subtract and divide)
+ *   voxels in ascending lexicographic (k0, k1, k2) - np.unique(axis=0)'s row order
+ *   per voxel, in f64 from 0.0 over its points in ascending index (np.add.at's order): the sum of (f64) xyz and of (f64) rgb / s, where
+ *   s = 255 if max(rgb) > 1 else 1 (a NaN colour makes the max NaN: s = 1); xyz_out / rgb_out = (f32) (sum / count), round to nearest even.
+ * xyz_out and rgb_out hold n rows (there are never more voxels than points); *n_out_host receives the voxel count (n = 0 gives 0).
+ * Synchronous.  The workspace lives on the context (grown on demand, freed by lfd_destroy).
+ * LFD_ERR_INVALID: a null pointer, n < 0 or n > 2^31 - 1, a voxel_size <= 0 or not finite, and - decided in the min / max pass, before
+ * anything is sorted - "non-finite coordinate" (an inf / NaN in xyz) or "key range" (the linear key k0 E1 E2 + k1 E2 + k2, E_c = max key_c + 1,
+ * does not fit 63 bits); lfd_last_error names which. */
+int lfd_voxel_downsample(lfd_context* ctx, const float* xyz, const float* rgb, int64_t n, double voxel_size,
+                         float* xyz_out, float* rgb_out, int64_t* n_out_host);
+
 /* (e) multi-GPU exchange, placement step (no upstream counterpart - upstream has no multi-GPU code): n copies
  * dst[dst_offset .. +nbytes) = src[src_offset .. +nbytes) in ONE launch on `hip_stream` of device `device_index` (offsets and lengths in
  * bytes, no alignment required: 15-byte PLY records).  The overlapped exchange receives every rank's records of a round as one padded block

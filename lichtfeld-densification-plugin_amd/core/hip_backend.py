@@ -10,7 +10,7 @@ import ctypes as C
 import threading
 import dataclasses
 import os
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -33,6 +33,11 @@ class SelectionInexact(HipBackendError):
     """The device selection met a normalised weight below 2^-29 (LFD_SELECT_INEXACT): its exact parallel cumulative sum
     is not guaranteed for such input, so it refused - WITHOUT consuming the MT19937 stream.  The caller runs the host
     stage (core/sampling.py) on the same map with the device's stream state instead (core/pipeline.py does)."""
+
+
+class VoxelInputRefused(HipBackendError):
+    """lfd_voxel_downsample refused its input - a non-finite coordinate, or a linear voxel key beyond 63 bits - before sorting anything.
+    The caller filters on the host instead (densify.dense_init_from_lfs does)."""
 
 
 class lfd_params(C.Structure):
@@ -165,6 +170,7 @@ def load_library() -> C.CDLL:
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.lfd_pack_ply.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.lfd_pack_points3d.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p]
+    lib.lfd_voxel_downsample.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.lfd_quantise_rgb.argtypes = [ctxp, C.c_void_p, C.c_int64, C.c_void_p]
     lib.lfd_copy_segments.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.lfd_launch_status.argtypes = [ctxp, C.POINTER(C.c_int32)]
@@ -200,7 +206,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -731,6 +737,25 @@ class HipDensifier:
         self._check(self._lib.lfd_pack_points3d(self._ctx, xyz.data_ptr(), rgb.data_ptr(), e.data_ptr() if e is not None else None,
                                                 n, int(id_base), out.data_ptr()), "lfd_pack_points3d")
         return out[:n * 43]
+
+    def voxel_downsample(self, xyz: torch.Tensor, rgb: torch.Tensor, voxel_size: float) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The distance filter on the device (lfd_voxel_downsample): (xyz_v, rgb_v), f32 device tensors of one row per occupied voxel, bit for bit
+        and in the order of the NumPy branch of ``densify._voxel_downsample``.  Synchronous.  Raises ``VoxelInputRefused`` for a non-finite
+        coordinate or a voxel key range beyond 63 bits."""
+        xyz, rgb = self._pts(xyz, 3, "xyz"), self._pts(rgb, 3, "rgb")
+        n = int(xyz.shape[0])
+        if int(rgb.shape[0]) != n:
+            raise ValueError("xyz and rgb must have the same number of rows")
+        xo = torch.empty((max(n, 1), 3), dtype=torch.float32, device=xyz.device)
+        ro = torch.empty((max(n, 1), 3), dtype=torch.float32, device=xyz.device)
+        nv = C.c_int64(0)
+        rc = self._lib.lfd_voxel_downsample(self._ctx, xyz.data_ptr(), rgb.data_ptr(), n, float(voxel_size), xo.data_ptr(), ro.data_ptr(), C.byref(nv))
+        if rc != 0:
+            msg = self._lib.lfd_last_error(self._ctx).decode()
+            if "non-finite coordinate" in msg or "key range" in msg:
+                raise VoxelInputRefused(f"lfd_voxel_downsample refused its input ({rc}): {msg}")
+            self._check(rc, "lfd_voxel_downsample")
+        return xo[:nv.value], ro[:nv.value]
 
     def quantise_rgb(self, rgb: torch.Tensor) -> torch.Tensor:
         rgb = self._pts(rgb, 3, "rgb")

@@ -40,6 +40,22 @@ extern "C" __global__ void lfd_pack_points3d_kernel(const float* xyz, const floa
                                                     unsigned long long id_base, unsigned char* out);
 extern "C" __global__ void lfd_copy_segments_kernel(LfdCopyArgs A, const unsigned char* src, unsigned char* dst);
 extern "C" __global__ void lfd_quantise_rgb_kernel(const float* rgb, long long n3, unsigned char* out);
+extern "C" __global__ void lfd_voxel_minmax_kernel(const float* xyz, const float* rgb, long long n, LfdVoxStats* part);
+extern "C" __global__ void lfd_voxel_final_kernel(const LfdVoxStats* part, int n_part, LfdVoxStats* out);
+extern "C" __global__ void lfd_voxel_keys_kernel(const float* xyz, long long n, double o0, double o1, double o2, double vs, unsigned long long e1,
+                                                 unsigned long long e2, unsigned long long* keys, unsigned* idx);
+extern "C" __global__ void lfd_voxel_hist_kernel(const unsigned long long* keys, long long n, long long chunk, int shift, unsigned* counts);
+extern "C" __global__ void lfd_voxel_scan_kernel(unsigned* v, int m, unsigned* total);
+extern "C" __global__ void lfd_voxel_scatter_kernel(const unsigned long long* kin, const unsigned* iin, long long n, long long chunk, int shift,
+                                                    const unsigned* counts, unsigned long long* kout, unsigned* iout);
+extern "C" __global__ void lfd_voxel_head_count_kernel(const unsigned long long* keys, long long n, long long chunk, unsigned* counts);
+extern "C" __global__ void lfd_voxel_head_scatter_kernel(const unsigned long long* keys, long long n, long long chunk, const unsigned* counts,
+                                                         unsigned* vstart);
+extern "C" __global__ void lfd_voxel_sums_kernel(const float* xyz, const float* rgb, long long n, const unsigned* sorted_idx, const unsigned* vstart,
+                                                 const unsigned* nv_p, double cscale, float* xyz_out, float* rgb_out, unsigned* big, unsigned* n_big);
+extern "C" __global__ void lfd_voxel_sums_big_kernel(const float* xyz, const float* rgb, long long n, const unsigned* sorted_idx, const unsigned* vstart,
+                                                     const unsigned* nv_p, double cscale, const unsigned* big, const unsigned* n_big, float* xyz_out,
+                                                     float* rgb_out);
 extern "C" __global__ void lfd_select_topm_kernel(LfdSelectArgs A);
 extern "C" __global__ void lfd_select_filter_mw_kernel(LfdSelectArgs A, LfdSelectNorms norms);
 extern "C" __global__ void lfd_select_begins_kernel(long long* pairs, long long stride, int n);
@@ -514,7 +530,7 @@ void lfd_destroy(lfd_context* ctx) {
     }
     for (hipEvent_t ev : ctx->kt_start) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->kt_stop) (void)hipEventDestroy(ev);
-    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan})
+    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->vox})
         if (b->ptr) (void)hipFree(b->ptr);
     if (ctx->pinned_words) (void)hipHostFree(ctx->pinned_words);
     delete ctx;
@@ -1296,6 +1312,93 @@ int lfd_pack_points3d(lfd_context* ctx, const float* xyz, const float* rgb, cons
     hipLaunchKernelGGL(lfd_pack_points3d_kernel, dim3(grid), dim3(256), 0, ctx->stream, xyz, rgb, err, (long long)n,
                        (unsigned long long)id_base, out);
     LFD_HIP(ctx, hipGetLastError());
+    return LFD_OK;
+}
+
+// ---- the distance filter (lfd_voxel.hip) -----------------------------------------------------------------------------------------------
+int lfd_voxel_downsample(lfd_context* ctx, const float* xyz, const float* rgb, int64_t n, double voxel_size, float* xyz_out, float* rgb_out,
+                         int64_t* n_out_host) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (!n_out_host || n < 0 || (n > 0 && (!xyz || !rgb || !xyz_out || !rgb_out))) return fail(ctx, LFD_ERR_INVALID, "lfd_voxel_downsample: bad arguments");
+    if (!(voxel_size > 0.0) || !std::isfinite(voxel_size)) return fail(ctx, LFD_ERR_INVALID, "lfd_voxel_downsample: voxel_size must be finite and > 0");
+    if (n > 0x7fffffffLL) return fail(ctx, LFD_ERR_INVALID, "lfd_voxel_downsample: at most 2^31 - 1 points");
+    *n_out_host = 0;
+    if (n == 0) return LFD_OK;
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // radix passes: workgroup b of G owns the items [b * chunk, (b + 1) * chunk); chunk is a multiple of the scatter's 512-item round
+    long long G = std::min<long long>(1024, (n + 4095) / 4096);
+    const long long chunk = (((n + G - 1) / G) + 511) / 512 * 512;
+    G = (n + chunk - 1) / chunk;
+    const int n_part = (int)std::min<long long>(1024, (n + 255) / 256);
+    // workspace: partials | stats, voxel count, big-voxel count | digit counts | keys x 2 | indices x 2 | voxel starts | big-voxel list
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t o_part = 0, o_small = al(o_part + 1024 * sizeof(LfdVoxStats)), o_counts = al(o_small + sizeof(LfdVoxStats) + 8);
+    const size_t o_ka = al(o_counts + 256 * 1024 * sizeof(unsigned)), o_kb = al(o_ka + 8 * (size_t)n), o_ia = al(o_kb + 8 * (size_t)n);
+    const size_t o_ib = al(o_ia + 4 * (size_t)n), o_vs = al(o_ib + 4 * (size_t)n), o_big = al(o_vs + 4 * (size_t)n);
+    const size_t total = al(o_big + 4 * ((size_t)n / (LFD_VOX_BIG + 1) + 1));
+    if (int rc = ensure(ctx, ctx->vox, total)) return rc;
+    unsigned char* w = static_cast<unsigned char*>(ctx->vox.ptr);
+    LfdVoxStats* part = reinterpret_cast<LfdVoxStats*>(w + o_part);
+    LfdVoxStats* stats = reinterpret_cast<LfdVoxStats*>(w + o_small);
+    unsigned* nv_dev = reinterpret_cast<unsigned*>(w + o_small + sizeof(LfdVoxStats));
+    unsigned* n_big = nv_dev + 1;
+    unsigned* counts = reinterpret_cast<unsigned*>(w + o_counts);
+    unsigned long long* keys[2] = {reinterpret_cast<unsigned long long*>(w + o_ka), reinterpret_cast<unsigned long long*>(w + o_kb)};
+    unsigned* idx[2] = {reinterpret_cast<unsigned*>(w + o_ia), reinterpret_cast<unsigned*>(w + o_ib)};
+    unsigned* vstart = reinterpret_cast<unsigned*>(w + o_vs);
+    unsigned* big = reinterpret_cast<unsigned*>(w + o_big);
+
+    // min / max pass; the refusals are decided before anything is sorted
+    hipLaunchKernelGGL(lfd_voxel_minmax_kernel, dim3(n_part), dim3(256), 0, st, xyz, rgb, (long long)n, part);
+    hipLaunchKernelGGL(lfd_voxel_final_kernel, dim3(1), dim3(256), 0, st, part, n_part, stats);
+    LFD_HIP(ctx, hipGetLastError());
+    LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, stats, sizeof(LfdVoxStats), hipMemcpyDeviceToHost, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));
+    LfdVoxStats s;
+    std::memcpy(&s, ctx->pinned_words, sizeof(s));
+    if (s.flags & LFD_VOX_NONFINITE) return fail(ctx, LFD_ERR_INVALID, "lfd_voxel_downsample: non-finite coordinate in the input");
+    double origin[3];
+    unsigned long long E[3];
+    for (int c = 0; c < 3; ++c) {
+        origin[c] = (double)s.lo[c] - 0.5 * voxel_size;
+        const double kmax = std::floor(((double)s.hi[c] - origin[c]) / voxel_size);   // the key is monotone in the coordinate
+        if (!(kmax < 9223372036854775808.0))
+            return fail(ctx, LFD_ERR_INVALID, "lfd_voxel_downsample: key range: the linear voxel key does not fit 63 bits");
+        E[c] = (unsigned long long)kmax + 1ull;
+    }
+    unsigned __int128 cells = (unsigned __int128)E[0] * E[1];              // every E_c <= 2^63: neither product overflows 128 bits
+    if (cells <= ((unsigned __int128)1 << 63)) cells *= E[2];
+    if (cells > ((unsigned __int128)1 << 63))
+        return fail(ctx, LFD_ERR_INVALID, "lfd_voxel_downsample: key range: the linear voxel key does not fit 63 bits");
+    const unsigned long long max_key = (unsigned long long)cells - 1ull;
+    const int bits = max_key ? 64 - __builtin_clzll(max_key) : 0;
+    const double cscale = (s.flags & LFD_VOX_NAN_RGB) ? 1.0 : ((double)s.cmax > 1.0 ? 255.0 : 1.0);
+
+    const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(lfd_voxel_keys_kernel, dim3(grid), dim3(256), 0, st, xyz, (long long)n, origin[0], origin[1], origin[2], voxel_size, E[1], E[2],
+                       keys[0], idx[0]);
+    int cur = 0;
+    for (int shift = 0; shift < bits; shift += 8, cur ^= 1) {
+        hipLaunchKernelGGL(lfd_voxel_hist_kernel, dim3((unsigned)G), dim3(256), 0, st, keys[cur], (long long)n, chunk, shift, counts);
+        hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, counts, (int)(256 * G), (unsigned*)nullptr);
+        hipLaunchKernelGGL(lfd_voxel_scatter_kernel, dim3((unsigned)G), dim3(512), 0, st, keys[cur], idx[cur], (long long)n, chunk, shift, counts,
+                           keys[cur ^ 1], idx[cur ^ 1]);
+    }
+    hipLaunchKernelGGL(lfd_voxel_head_count_kernel, dim3((unsigned)G), dim3(256), 0, st, keys[cur], (long long)n, chunk, counts);
+    hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, counts, (int)G, nv_dev);
+    hipLaunchKernelGGL(lfd_voxel_head_scatter_kernel, dim3((unsigned)G), dim3(512), 0, st, keys[cur], (long long)n, chunk, counts, vstart);
+    LFD_HIP(ctx, hipMemsetAsync(n_big, 0, sizeof(unsigned), st));
+    hipLaunchKernelGGL(lfd_voxel_sums_kernel, dim3(grid), dim3(256), 0, st, xyz, rgb, (long long)n, idx[cur], vstart, nv_dev, cscale, xyz_out, rgb_out,
+                       big, n_big);
+    const unsigned big_grid = (unsigned)std::min<long long>(n / (LFD_VOX_BIG + 1) + 1, 8192);
+    hipLaunchKernelGGL(lfd_voxel_sums_big_kernel, dim3(big_grid), dim3(64), 0, st, xyz, rgb, (long long)n, idx[cur], vstart, nv_dev, cscale, big, n_big,
+                       xyz_out, rgb_out);
+    LFD_HIP(ctx, hipGetLastError());
+    LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, nv_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));
+    *n_out_host = (int64_t)(unsigned)ctx->pinned_words[0];
     return LFD_OK;
 }
 

@@ -91,6 +91,7 @@ struct lfd_context {
     DeviceBuffer sel_chain;                      // lfd_triangulate_sampled_chain: chain block, the stream's ring of doubles, the keys of its twists
     DeviceBuffer stamps;           // profiling builds: phase stamps of the dense kernel
     DeviceBuffer seg_scan;         // tile segments: exclusive prefix of the last table handed to lfd_order_segments / lfd_pack_*_segments
+    DeviceBuffer vox;              // lfd_voxel_downsample: statistics, digit counts, keys / indices (x 2), voxel starts; grown on demand
     // N3 image preparation: coefficient / index tables of the last size pair
     DeviceBuffer img_tab, msk_tab;
     int img_key[4] = {0, 0, 0, 0}, img_ks[2] = {0, 0};

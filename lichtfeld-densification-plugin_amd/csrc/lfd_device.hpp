@@ -97,6 +97,15 @@ struct LfdCopyArgs {               // by value in the kernel arguments (2.7 KB):
     int n_segs;
 };
 
+// lfd_voxel_downsample: statistics of the input, per workgroup of lfd_voxel_minmax_kernel, then global (lfd_voxel_final_kernel)
+struct LfdVoxStats {
+    float lo[3], hi[3];     // coordinate min / max over the finite coordinates
+    float cmax;             // colour max over the non-NaN values
+    unsigned flags;         // LFD_VOX_NONFINITE: some coordinate is inf / NaN; LFD_VOX_NAN_RGB: some colour is NaN (NumPy's max is then NaN)
+};
+#define LFD_VOX_NONFINITE 1u
+#define LFD_VOX_NAN_RGB 2u
+#define LFD_VOX_BIG 64      // voxels of more points than this are summed by a whole wave (lfd_voxel_sums_big_kernel)
 struct LfdTileSeg { int32_t offset, count; };     // == lfd_tile_segment of the C-ABI
 
 struct LfdLaunch {              // kernel argument, passed by value

@@ -161,6 +161,20 @@ def _voxel_downsample(xyz: np.ndarray, rgb: np.ndarray, voxel_size: float) -> Tu
         return (p / cnt[:, None]).astype(np.float32), (c / cnt[:, None]).astype(np.float32)
 
 
+def _voxel_filter_on_device(device_points, voxel_size: float):
+    """``_voxel_downsample`` where the points are (lfd_voxel_downsample): ``(xyz, rgb)`` device tensors, bit for bit and in the order of its
+    NumPy branch.  None when the library refuses the cloud (a non-finite coordinate, a voxel key range beyond 63 bits): the host filters it."""
+    from .core import hip_backend as hb
+    dens = hb.HipDensifier(device_points[0].device)
+    try:
+        return dens.voxel_downsample(device_points[0], device_points[1], voxel_size)
+    except hb.VoxelInputRefused as exc:
+        log.warn(f"Distance filter: {exc}; filtering on the host")
+        return None
+    finally:
+        dens.close()
+
+
 def _is_writer_rank() -> bool:
     """True unless this process is a non-zero rank of an initialised torch.distributed job."""
     try:
@@ -170,8 +184,8 @@ def _is_writer_rank() -> bool:
         return True
 
 
-def _write_output(path: str, xyz, rgb, err, device_points=None, clock=None) -> None:
-    """``.ply`` -> upstream's PLY, anything else -> upstream's points3D.bin (densify.py:129-135).  When
+def _write_output(path: str, xyz, rgb, err, device_points=None, clock=None, as_ply: Optional[bool] = None) -> None:
+    """``.ply`` -> upstream's PLY, anything else -> upstream's points3D.bin (densify.py:129-135); ``as_ply`` overrides the suffix.  When
     the points are still on the GPU the records are quantised and packed there (lfd_pack_*) and only
     the final bytes are copied to the host; the files are byte-identical either way."""
     if not _is_writer_rank():        # sharded run: every rank holds the gathered cloud, rank 0 alone writes the file
@@ -179,7 +193,7 @@ def _write_output(path: str, xyz, rgb, err, device_points=None, clock=None) -> N
     d = os.path.dirname(path)
     if d:
         os.makedirs(d, exist_ok=True)
-    as_ply = path.lower().endswith(".ply")
+    as_ply = path.lower().endswith(".ply") if as_ply is None else bool(as_ply)
     if device_points is not None and device_points[0].is_cuda and int(device_points[0].shape[0]) == int(xyz.shape[0]):
         from .core import hip_backend as hb
         from .core.writers import write_ply_packed, write_points3D_bin_packed
@@ -335,10 +349,29 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
         if progress_callback:
             progress_callback(100.0, f"Done! {n_written:,} points")
         return 0, config.output_path
+    announced = False
+    if config.voxel_size > 0.0 and result.device_points is not None and result.device_points[0].is_cuda:
+        # the distance filter where the points are: only the PLY payload crosses PCIe (the host route below is taken if the library refuses the cloud)
+        if progress_callback:
+            progress_callback(93.0, "Applying distance filter...")
+        announced = True
+        dev_pts = _cap_device_points(result.device_points, int(result.device_points[0].shape[0]), config.max_points, config.seed)
+        voxels = _voxel_filter_on_device(dev_pts, config.voxel_size)
+        if voxels is not None:
+            n_vox = int(voxels[0].shape[0])
+            log.info(f"Distance filter ({config.voxel_size:.4f}): {n_vox:,} points remaining")
+            if progress_callback:
+                progress_callback(95.0, "Writing output PLY...")
+            # upstream always writes a PLY here, whatever the name
+            _write_output(config.output_path, np.empty((n_vox, 0), np.float32), None, None, voxels, clock=pipeline_kwargs.get("stage_clock"), as_ply=True)
+            log.info(f"Dense point cloud saved to {config.output_path} ({n_vox:,} points)")
+            if progress_callback:
+                progress_callback(100.0, f"Done! {n_vox:,} points")
+            return 0, config.output_path
     xyz, rgb, err = _apply_point_cap(result.xyz, result.rgb, result.err, config.max_points, config.seed)
     dev_pts = _cap_device_points(result.device_points, result.xyz.shape[0], config.max_points, config.seed)
     if config.voxel_size > 0.0:
-        if progress_callback:
+        if progress_callback and not announced:
             progress_callback(93.0, "Applying distance filter...")
         xyz, rgb = _voxel_downsample(xyz, rgb, config.voxel_size)
         dev_pts = None                                   # the voxel average lives on the host
