@@ -9,6 +9,8 @@ import os
 import shutil
 import subprocess
 import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(os.path.dirname(HERE), "liblfd_densify.so")
@@ -16,8 +18,20 @@ SOURCES = ["lfd_api.hip", "lfd_kernels.hip", "lfd_select.hip", "lfd_writer.hip",
 HEADERS = ["lfd_device.hpp", "lfd_geometry.hpp", "lfd_context.hpp", os.path.join("..", "..", "include", "lfd_densify.h")]
 # -amdgpu-sched-strategy=max-ilp: the dense kernel is bound by its vector arithmetic (long dependent f64 chains); the
 # ILP-first machine scheduler is worth 3.5 % on it (profiles/history.md (r1/ablation.txt)), instruction semantics are unchanged
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
          "-fno-fast-math", "-Wall", "-Wno-unused-function", "-pthread", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
+# Flags of one source only.  lfd_kernels.hip without the SLP vectoriser: a v_pk_*_f32 is cheaper per operation than two scalar instructions only
+# when both halves already sit in a register pair (profiles/r7/fma_f32_packing.txt); in the dense kernels the pairing costs more than it saves - moves to
+# assemble the pairs, scalar instructions, SGPR spill reloads inside the geometry loop.  Same arithmetic, same bits; -1.7 % of the dense kernel's time
+# (profiles/r7/ab_solver_stream.txt).  The other sources keep the default.
+FILE_FLAGS = {"lfd_kernels.hip": ["-fno-slp-vectorize"]}
+LINK_FLAGS = ["--offload-arch=gfx950", "-fPIC", "-shared", "-pthread"]
+
+
+def compile_command(source: str, out: str, extra=()) -> list:
+    """The hipcc command that compiles one source of SOURCES to an object (tests/test_dense_kernel_resources.py reuses it)."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    return [hipcc] + FLAGS + FILE_FLAGS.get(source, []) + list(extra) + ["-c", os.path.join(HERE, source), "-o", out]
 
 
 def needs_build() -> bool:
@@ -31,16 +45,25 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if not force and not needs_build():
         return OUT
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    cmd = [hipcc] + FLAGS + [os.path.join(HERE, s) for s in SOURCES] + ["-o", OUT]
-    if verbose:
-        cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
-        print(" ".join(cmd))
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    if res.returncode != 0:
-        sys.stderr.write(res.stdout + res.stderr)
-        raise RuntimeError("hipcc failed building liblfd_densify.so")
-    if verbose:
-        sys.stderr.write(res.stderr)
+    extra = ["-Rpass-analysis=kernel-resource-usage"] if verbose else []
+    with tempfile.TemporaryDirectory(prefix="lfd_build_") as tmp:
+        objs = [os.path.join(tmp, os.path.splitext(f)[0] + ".o") for f in SOURCES]
+        cmds = [compile_command(f, o, extra) for f, o in zip(SOURCES, objs)]
+        with ThreadPoolExecutor(max_workers=min(len(cmds), int(os.environ.get("MAX_JOBS", "8")))) as pool:
+            results = list(pool.map(lambda c: subprocess.run(c, capture_output=True, text=True), cmds))
+        link = [hipcc] + LINK_FLAGS + objs + ["-o", OUT]
+        for cmd, res in zip(cmds, results):
+            if verbose:
+                print(" ".join(cmd))
+            if res.returncode != 0:
+                sys.stderr.write(res.stdout + res.stderr)
+                raise RuntimeError("hipcc failed building liblfd_densify.so (" + os.path.basename(cmd[-3]) + ")")
+            if verbose:
+                sys.stderr.write(res.stderr)
+        res = subprocess.run(link, capture_output=True, text=True)
+        if res.returncode != 0:
+            sys.stderr.write(res.stdout + res.stderr)
+            raise RuntimeError("hipcc failed linking liblfd_densify.so")
     return OUT
 
 

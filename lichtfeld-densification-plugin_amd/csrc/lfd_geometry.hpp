@@ -267,6 +267,27 @@ LFD_HD double lfd_recip_refined(double d) {
 #endif
 }
 
+// Has the iteration settled?  n: the iterate just computed, o: the one before it.  The direction change of the last solve is
+// measured on the inhomogeneous coordinates x_i / x_3 (cross-multiplied): it is ~ the error of the PREVIOUS iterate, the one
+// returned is q times closer.  A vanishing x_3 (point at infinity) gives ref == 0, never passes and runs into the iteration
+// limits; a NaN anywhere counts as settled: the solver leaves at once and the cell is dropped by the caller's finite tests.
+//
+//   ref        e0, e1, e2                       settled
+//   NaN        anything                         yes   (NaN)
+//   any        at least one NaN                 yes   (NaN)
+//   0          none NaN                         no    (whatever the e_i, 0 included)
+//   > 0, +Inf  none NaN, all  e_i <= ref        yes   (converged)
+//   > 0, +Inf  none NaN, some e_i >  ref        no
+//
+// ref and the e_i are absolute values: never negative, never -0.
+LFD_HD bool lfd_nullvec_settled(double n0, double n1, double n2, double n3, double o0, double o1, double o2, double o3) {
+    const double ref = fabs(n3 * o3) * LFD_NULLVEC_TOL;
+    const double e0 = fabs(fma(n0, o3, -(n3 * o0))), e1 = fabs(fma(n1, o3, -(n3 * o1))), e2 = fabs(fma(n2, o3, -(n3 * o2)));
+    const bool more = (e0 > ref) || (e1 > ref) || (e2 > ref) || !(ref > 0.0);
+    const bool bad = !(e0 == e0) || !(e1 == e1) || !(e2 == e2) || !(ref == ref);     // NaN: leave at once
+    return !more || bad;
+}
+
 // c[4]: un-normalised multiple of the singular vector; returns the number of solves made.
 // `rows(Af)` fills the 4x4 matrix (row-major f32).  It is called at the start of EVERY pass, so neither the matrix
 // nor M = A^T A stays live across the solves (30 registers on the device); the shifted passes, which are the only
@@ -291,65 +312,84 @@ LFD_HD int lfd_null_vector_rows(RowFn rows, double* c) {
             m22 = fma(a2, a2, m22); m23 = fma(a2, a3, m23); m33 = fma(a3, a3, m33);                                     \
         }                                                                                                               \
     }
+    // M - sh I = L D L^T from the diagonal q_ii = m_ii - sh (pass 0: the m_ii themselves); s_i = d3 / d_i
+#define LFD_FACTORISE(q00, q11, q22, q33)                                                                               \
+    const double r0 = lfd_recip_refined(q00);                                                                           \
+    const double l10 = m01 * r0, l20 = m02 * r0, l30 = m03 * r0;                                                        \
+    const double d1 = fma(-l10, m01, q11);                                                                              \
+    const double n12 = fma(-l10, m02, m12), n13 = fma(-l10, m03, m13);                                                  \
+    const double n22 = fma(-l20, m02, q22), n23 = fma(-l20, m03, m23), n33 = fma(-l30, m03, q33);                       \
+    const double r1 = lfd_recip_refined(d1);                                                                            \
+    const double l21 = n12 * r1, l31 = n13 * r1;                                                                        \
+    const double d2 = fma(-l21, n12, n22);                                                                              \
+    const double p23 = fma(-l21, n13, n23), p33 = fma(-l31, n13, n33);                                                  \
+    const double r2 = lfd_recip_refined(d2);                                                                            \
+    const double l32 = p23 * r2;                                                                                        \
+    const double d3 = fma(-l32, p23, p33);                                                                              \
+    const double s0 = d3 * r0, s1 = d3 * r1, s2 = d3 * r2
+    // b <- d3 * (M - sh I)^-1 a : forward (L), diagonal, backward (L^T).  Every read of a precedes the first write of b, so b may be the very variables of a
+#define LFD_SOLVE(a0, a1, a2, a3, b0, b1, b2, b3)                                                                       \
+    {                                                                                                                   \
+        const double y1 = fma(-l10, a0, a1);                                                                            \
+        const double y2 = fma(-l21, y1, fma(-l20, a0, a2));                                                             \
+        const double y3 = fma(-l32, y2, fma(-l31, y1, fma(-l30, a0, a3)));                                              \
+        const double z0 = a0 * s0, z1 = y1 * s1, z2 = y2 * s2;                                                          \
+        b3 = y3;                                                                                                        \
+        b2 = fma(-l32, b3, z2);                                                                                         \
+        b1 = fma(-l21, b2, fma(-l31, b3, z1));                                                                          \
+        b0 = fma(-l10, b1, fma(-l20, b2, fma(-l30, b3, z0)));                                                           \
+    }
     // Convergence monitor: the direction change between successive iterates is the error of the older one (the
     // iteration is linear with ratio q), so once it drops below LFD_NULLVEC_TOL the iterate just computed is within
     // q * TOL of v4.  Ordinary cells (q ~ 1e-4) settle after two solves.
     // A pass that has not settled after LFD_NULLVEC_MAXIT solves (sigma4/sigma3 close to 1) is followed by a
     // pass shifted by the Rayleigh quotient of its result, which separates the two smallest eigenvalues.
-    double sh = 0.0;
-    double x0 = 0.0, x1 = 0.0, x2 = 0.0, x3 = 1.0;
-    int it = 0;
-    for (int pass = 0;; ++pass) {
+    //
+    // Pass 0 is written out: it factorises M itself (no shift to subtract), takes the first solve from e4 for free and makes the
+    // loop solves k = 1..4 alternately x -> w and w -> x, so that the test after each reads the previous iterate where it already
+    // is instead of from a copy made before every solve.  A lane that settles leaves with the iterate of ITS solve while the rest
+    // of its wave goes on (k = 2 and 4 end in x, k = 3 in w and is moved once).  Solves 5..MAXIT of pass 0 and the shifted passes
+    // are rare and stay loops.
+#if LFD_NULLVEC_MAXIT < 4
+#error "pass 0 of lfd_null_vector_rows is written out for LFD_NULLVEC_MAXIT >= 4"
+#endif
+    double x0, x1, x2, x3;
+    int it;
+    bool settled;
+    {
         LFD_BUILD_M();
-        // M - sh I = L D L^T
-        const double q00 = m00 - sh, q11 = m11 - sh, q22 = m22 - sh, q33 = m33 - sh;
-        const double r0 = lfd_recip_refined(q00);
-        const double l10 = m01 * r0, l20 = m02 * r0, l30 = m03 * r0;
-        const double d1 = fma(-l10, m01, q11);
-        const double n12 = fma(-l10, m02, m12), n13 = fma(-l10, m03, m13);
-        const double n22 = fma(-l20, m02, q22), n23 = fma(-l20, m03, m23), n33 = fma(-l30, m03, q33);
-        const double r1 = lfd_recip_refined(d1);
-        const double l21 = n12 * r1, l31 = n13 * r1;
-        const double d2 = fma(-l21, n12, n22);
-        const double p23 = fma(-l21, n13, n23), p33 = fma(-l31, n13, n33);
-        const double r2 = lfd_recip_refined(d2);
-        const double l32 = p23 * r2;
-        const double d3 = fma(-l32, p23, p33);
-        const double s0 = d3 * r0, s1 = d3 * r1, s2 = d3 * r2;     // d3 / d_i
-        if (pass == 0) {        // first solve from e4: the last column of L^-T
-            x3 = 1.0;
-            x2 = -l32;
-            x1 = fma(-l21, x2, -l31);
-            x0 = fma(-l10, x1, fma(-l20, x2, -l30));
-            it = 1;
-        }
-        bool settled = false;
-        for (int k = 1;; ++k) {
-            const double o0 = x0, o1 = x1, o2 = x2, o3 = x3;
-            // x <- d3 * (M - sh I)^-1 x : forward (L), diagonal, backward (L^T)
-            const double y1 = fma(-l10, x0, x1);
-            const double y2 = fma(-l21, y1, fma(-l20, x0, x2));
-            const double y3 = fma(-l32, y2, fma(-l31, y1, fma(-l30, x0, x3)));
-            const double z0 = x0 * s0, z1 = y1 * s1, z2 = y2 * s2;
-            x3 = y3;
-            x2 = fma(-l32, x3, z2);
-            x1 = fma(-l21, x2, fma(-l31, x3, z1));
-            x0 = fma(-l10, x1, fma(-l20, x2, fma(-l30, x3, z0)));
-            ++it;
-            if (k >= 2) {
-                // direction change of the last solve, measured on the inhomogeneous coordinates x_i / x_3 (cross-multiplied):
-                // it is ~ the error of the PREVIOUS iterate, the one returned is q times closer.  A vanishing x_3 (point at
-                // infinity) never passes and runs into the iteration limits.
-                const double ref = fabs(x3 * o3) * LFD_NULLVEC_TOL;
-                const double e0 = fabs(fma(x0, o3, -(x3 * o0))), e1 = fabs(fma(x1, o3, -(x3 * o1))), e2 = fabs(fma(x2, o3, -(x3 * o2)));
-                const bool more = (e0 > ref) || (e1 > ref) || (e2 > ref) || !(ref > 0.0);
-                const bool bad = !(e0 == e0) || !(e1 == e1) || !(e2 == e2) || !(ref == ref);     // NaN: leave at once
-                if (!more || bad) { settled = true; break; }
-                if (k >= LFD_NULLVEC_MAXIT) break;
+        LFD_FACTORISE(m00, m11, m22, m33);
+        // first solve from e4: the last column of L^-T
+        x3 = 1.0;
+        x2 = -l32;
+        x1 = fma(-l21, x2, -l31);
+        x0 = fma(-l10, x1, fma(-l20, x2, -l30));
+        double w0, w1, w2, w3;
+        LFD_SOLVE(x0, x1, x2, x3, w0, w1, w2, w3);                    // k = 1: never tested
+        LFD_SOLVE(w0, w1, w2, w3, x0, x1, x2, x3);                    // k = 2
+        it = 3;
+        settled = lfd_nullvec_settled(x0, x1, x2, x3, w0, w1, w2, w3);
+        if (!settled) {
+            LFD_SOLVE(x0, x1, x2, x3, w0, w1, w2, w3);                // k = 3
+            it = 4;
+            settled = lfd_nullvec_settled(w0, w1, w2, w3, x0, x1, x2, x3);
+            if (settled) { x0 = w0; x1 = w1; x2 = w2; x3 = w3; }
+            else {
+                LFD_SOLVE(w0, w1, w2, w3, x0, x1, x2, x3);            // k = 4
+                it = 5;
+                settled = lfd_nullvec_settled(x0, x1, x2, x3, w0, w1, w2, w3);
+                for (int k = 5; !settled && k <= LFD_NULLVEC_MAXIT; ++k) {
+                    const double o0 = x0, o1 = x1, o2 = x2, o3 = x3;
+                    LFD_SOLVE(x0, x1, x2, x3, x0, x1, x2, x3);
+                    ++it;
+                    settled = lfd_nullvec_settled(x0, x1, x2, x3, o0, o1, o2, o3);
+                }
             }
         }
-        if (settled || pass >= LFD_NULLVEC_PASSES - 1) break;
-        // Rayleigh quotient of x as the next shift; x rescaled by an exact power of two
+    }
+    for (int pass = 1; !settled && pass < LFD_NULLVEC_PASSES; ++pass) {
+        double sh;
+        // Rayleigh quotient of x as the shift; x rescaled by an exact power of two
         LFD_BUILD_M();
         {
             const double sc = lfd_pow2_inv_scale(fabs(x0) + fabs(x1) + fabs(x2) + fabs(x3));
@@ -369,7 +409,17 @@ LFD_HD int lfd_null_vector_rows(RowFn rows, double* c) {
             const double rr = fma(e3, e3, fma(e2, e2, fma(e1, e1, e0 * e0)));
             sh = rho - lfd_sqrt_rare(rr * rden);
         }
+        LFD_BUILD_M();
+        LFD_FACTORISE(m00 - sh, m11 - sh, m22 - sh, m33 - sh);
+        for (int k = 1; k <= LFD_NULLVEC_MAXIT; ++k) {
+            const double o0 = x0, o1 = x1, o2 = x2, o3 = x3;
+            LFD_SOLVE(x0, x1, x2, x3, x0, x1, x2, x3);
+            ++it;
+            if (k >= 2 && lfd_nullvec_settled(x0, x1, x2, x3, o0, o1, o2, o3)) { settled = true; break; }
+        }
     }
+#undef LFD_FACTORISE
+#undef LFD_SOLVE
     c[0] = x0; c[1] = x1; c[2] = x2; c[3] = x3;
     return it;
 #undef LFD_BUILD_M
