@@ -305,6 +305,24 @@ int lfd_quantise_rgb(lfd_context* ctx, const float* rgb, int64_t n, uint8_t* out
 int lfd_voxel_downsample(lfd_context* ctx, const float* xyz, const float* rgb, int64_t n, double voxel_size,
                          float* xyz_out, float* rgb_out, int64_t* n_out_host);
 
+/* Local correlation of RoMa-v2's conv refiners (RoMaV2/src/romav2/local_correlation.py looks for a CUDA-only extension `local_corr` and, without
+ * it, materialises the sampled neighbour features as a (C, h, w, K) tensor):
+ *
+ *   out[b, n, k] = sum_c A[b, n, c] * bilinear(Bf[b, :, :, c]; warp[b, n, k])
+ *
+ * A (B, N, C) f32, Bf (B, H1, W1, C) f32, warp (B, N, K, 2) f32 contiguous, (x, y) normalised as F.grid_sample(mode="bilinear",
+ * padding_mode="zeros", align_corners=False) reads them: ix = ((x + 1) W1 - 1) / 2 in f32, the four texels round (ix, iy), texels outside the
+ * map count as 0.  out (B, N, K) f32 contiguous.  a_strides[3] / bf_strides[4]: element strides of A / Bf in the order of their dimensions
+ * (NULL: contiguous); channels adjacent (stride 1), C % 4 == 0 and 16-byte aligned rows take the vector kernel, anything else the general one.
+ * Departure from grid_sample: a coordinate that is inf, NaN or beyond the map by any amount contributes exactly 0 - no address is formed from it.
+ * Deterministic (no atomics).  One launch on the context's stream, asynchronous.  LFD_ERR_INVALID: a null pointer, B, N, K < 0, C, H1, W1 < 1,
+ * H1 or W1 > 32768, B N > 2^26 - 1, B N K > 2^31 - 1, a negative stride.  lfd_local_corr_host: the same routine over host pointers on a host
+ * context's threads (the general kernel's summation order). */
+int lfd_local_corr(lfd_context* ctx, const float* A, const float* Bf, const float* warp, int32_t B, int32_t N, int32_t C, int32_t K,
+                   int32_t H1, int32_t W1, const int64_t* a_strides, const int64_t* bf_strides, float* out);
+int lfd_local_corr_host(lfd_context* ctx, const float* A, const float* Bf, const float* warp, int32_t B, int32_t N, int32_t C, int32_t K,
+                        int32_t H1, int32_t W1, const int64_t* a_strides, const int64_t* bf_strides, float* out);
+
 /* (e) multi-GPU exchange, placement step (no upstream counterpart - upstream has no multi-GPU code): n copies
  * dst[dst_offset .. +nbytes) = src[src_offset .. +nbytes) in ONE launch on `hip_stream` of device `device_index` (offsets and lengths in
  * bytes, no alignment required: 15-byte PLY records).  The overlapped exchange receives every rank's records of a round as one padded block
@@ -370,7 +388,7 @@ int lfd_host_eval_correspondence(const float* cam1, const float* cam2, float xa_
  * The per-cell arithmetic is the host build of the very source the kernels compile (csrc/lfd_geometry.hpp; IEEE
  * division / square root where the device uses the 1-ulp v_rcp / v_sqrt), spread over n_threads std::threads
  * (<= 0: all hardware threads).  A host context accepts lfd_upload_cameras, lfd_last_error, lfd_destroy and the
- * three *_host calls; every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
+ * *_host calls (the three below and lfd_local_corr_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
  * context: neither side ever stands in for the other.  Semantics (orders, counts, optional outputs, LFD_ERR_CAPACITY
  * with valid counts) are those of lfd_aggregate / lfd_triangulate_dense / lfd_triangulate_indexed. */
 int lfd_create_host(int32_t n_threads, lfd_context** out);

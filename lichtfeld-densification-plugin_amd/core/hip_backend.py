@@ -172,6 +172,8 @@ def load_library() -> C.CDLL:
     lib.lfd_pack_points3d.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p]
     lib.lfd_voxel_downsample.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.lfd_quantise_rgb.argtypes = [ctxp, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.lfd_local_corr.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]
+    lib.lfd_local_corr_host.argtypes = list(lib.lfd_local_corr.argtypes)
     lib.lfd_copy_segments.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.lfd_launch_status.argtypes = [ctxp, C.POINTER(C.c_int32)]
     lib.lfd_get_pair_fundamental.argtypes = [ctxp, C.c_int32, C.POINTER(C.c_double)]
@@ -206,7 +208,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -623,6 +625,28 @@ class OutputBuffers:
 
 
 
+def _local_corr_arguments(a, bf, warp, device):
+    """Shapes, dtype and device of a local_corr call checked; (a, bf, warp, (B, N, C, K, H1, W1)) with ``warp`` contiguous and ``a`` / ``bf``
+    in a layout the library reads well (see HipDensifier.local_corr)."""
+    for name, t, nd in (("a", a, 3), ("bf", bf, 4), ("warp", warp, 4)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != nd:
+            raise ValueError(f"local_corr: {name} must be a float32 tensor of {nd} dimensions")
+        if t.device != device:
+            raise ValueError(f"local_corr: {name} lives on {t.device}, this context computes on {device}")
+    B, N, Cc = (int(v) for v in a.shape)
+    H1, W1 = int(bf.shape[1]), int(bf.shape[2])
+    K = int(warp.shape[2])
+    if tuple(bf.shape) != (B, H1, W1, Cc) or tuple(warp.shape) != (B, N, K, 2):
+        raise ValueError(f"local_corr: a {tuple(a.shape)}, bf {tuple(bf.shape)}, warp {tuple(warp.shape)} are not (B, N, C), (B, H1, W1, C), (B, N, K, 2)")
+    if Cc % 4 == 0:
+        # the vector kernel's layout: channels adjacent, rows of channels 16-byte aligned
+        if a.stride(2) != 1 or any(s % 4 for s in a.stride()[:2]) or a.data_ptr() % 16:
+            a = a.contiguous()
+        if bf.stride(3) != 1 or any(s % 4 for s in bf.stride()[:3]) or bf.data_ptr() % 16:
+            bf = bf.contiguous()
+    return a.detach(), bf.detach(), warp.detach().contiguous(), (B, N, Cc, K, H1, W1)
+
+
 class HipDensifier:
     """One context = one GPU + one stream (``torch.cuda.current_stream`` of the device at creation,
     unless a stream is given).  Not thread-safe: use one per thread, as the C-ABI requires."""
@@ -756,6 +780,26 @@ class HipDensifier:
                 raise VoxelInputRefused(f"lfd_voxel_downsample refused its input ({rc}): {msg}")
             self._check(rc, "lfd_voxel_downsample")
         return xo[:nv.value], ro[:nv.value]
+
+    def set_stream(self, stream: "torch.cuda.Stream") -> None:
+        """Later calls are issued on ``stream`` (lfd_set_stream: what was issued on the previous one is waited for first).  A call with the
+        stream the context already uses does nothing."""
+        if int(stream.cuda_stream) == int(self.stream.cuda_stream):
+            return
+        self._check(self._lib.lfd_set_stream(self._ctx, C.c_void_p(stream.cuda_stream)), "lfd_set_stream")
+        self.stream = stream
+
+    def local_corr(self, a: torch.Tensor, bf: torch.Tensor, warp: torch.Tensor) -> torch.Tensor:
+        """RoMa-v2's local correlation (lfd_local_corr): ``out[b, n, k] = sum_c a[b, n, c] * bilinear(bf[b, :, :, c]; warp[b, n, k])``
+        for f32 tensors ``a`` (B, N, C), ``bf`` (B, H1, W1, C), ``warp`` (B, N, K, 2) of this context's device; (B, N, K) f32.  One launch on
+        the context's stream, no temporary of the size of the sampled features.  ``a`` and ``bf`` are read through their strides; when
+        C % 4 == 0 and the channels of one of them are not adjacent in memory, a channel-last copy of that tensor is made first so that the
+        vector kernel (16-byte loads) serves the call - same bits as for a contiguous input."""
+        a, bf, warp, dims = _local_corr_arguments(a, bf, warp, self.device)
+        out = torch.empty((dims[0], dims[1], dims[3]), dtype=torch.float32, device=self.device)
+        sa, sb = (C.c_int64 * 3)(*a.stride()), (C.c_int64 * 4)(*bf.stride())
+        self._check(self._lib.lfd_local_corr(self._ctx, a.data_ptr(), bf.data_ptr(), warp.data_ptr(), *dims, sa, sb, out.data_ptr()), "lfd_local_corr")
+        return out
 
     def quantise_rgb(self, rgb: torch.Tensor) -> torch.Tensor:
         rgb = self._pts(rgb, 3, "rgb")
@@ -1065,6 +1109,15 @@ class HostDensifier:
 
     def check_launches(self) -> None:
         pass
+
+    def local_corr(self, a: torch.Tensor, bf: torch.Tensor, warp: torch.Tensor) -> torch.Tensor:
+        """HipDensifier.local_corr over CPU tensors (lfd_local_corr_host: the general kernel's routine on this context's threads)."""
+        a, bf, warp, dims = _local_corr_arguments(a, bf, warp, self.device)
+        out = torch.empty((dims[0], dims[1], dims[3]), dtype=torch.float32)
+        sa, sb = (C.c_int64 * 3)(*a.stride()), (C.c_int64 * 4)(*bf.stride())
+        self._check(self._lib.lfd_local_corr_host(self._ctx, a.data_ptr(), bf.data_ptr(), warp.data_ptr(), *dims, sa, sb, out.data_ptr()),
+                    "lfd_local_corr_host")
+        return out
 
     def aggregate(self, batch: PreparedBatch, params: lfd_params):
         self._same_device(batch)

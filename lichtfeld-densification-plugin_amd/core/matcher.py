@@ -9,6 +9,7 @@ with the A-grid axes instead of being concatenated with a materialised identity 
 """
 from __future__ import annotations
 
+import contextlib
 import gc
 import os
 import sys
@@ -134,15 +135,36 @@ class _KeyedDescriptor(torch.nn.Module):
         return stacked[0] if isinstance(vals[0], torch.Tensor) else stacked
 
 
+@contextlib.contextmanager
+def _local_corr_installed(shim):
+    """While the block runs, ``romav2.local_correlation.local_corr`` - the name the model's refiners look up at every call, None where the
+    CUDA-only extension is missing - is ``shim``; the previous value comes back afterwards, also when the block raises.  ``shim`` None: nothing
+    is imported and nothing is touched."""
+    if shim is None:
+        yield
+        return
+    import importlib
+    module = importlib.import_module("romav2.local_correlation")
+    previous = module.local_corr
+    module.local_corr = shim
+    try:
+        yield
+    finally:
+        module.local_corr = previous
+
+
 class RomaMatcher:
     """Dense matcher with the reference image's features cached across its neighbours."""
 
     accepts_device_images = True      # match_grids_batch takes (h, w, 3) u8 device tensors as well as PIL images
     supports_feature_keys = True      # match_grids_batch(..., keys=(ref_key, [nbr_keys])) shares backbone features between references
+    supports_fused_local_corr = True  # set_fused_local_corr(True): the refiners' local correlation runs in this package's HIP kernel
 
     def __init__(self, device: str = "cuda", mode: str = "outdoor", setting: str = "fast", two_channel: bool = True,
-                 pairs_per_forward: int = 1):
-        """``pairs_per_forward`` > 1: the neighbours of a reference go through the model that many at a time (one batched forward,
+                 pairs_per_forward: int = 1, fused_local_corr: bool = False):
+        """``fused_local_corr``: the local correlation of the model's conv refiners is computed by lfd_local_corr (core/local_corr.py) instead
+        of the model's grid_sample fallback; results agree within the bound of DESIGN.md 4.6, not bit for bit, so the default is off.
+        ``pairs_per_forward`` > 1: the neighbours of a reference go through the model that many at a time (one batched forward,
         RoMaV2/tests/test_bidirectional.py runs B = 8) instead of one pair per forward as upstream's loop does (core/matcher.py:175-188
         there).  Batched GEMMs may round differently from single ones: the default stays 1, upstream's behaviour."""
         del mode
@@ -161,6 +183,8 @@ class RomaMatcher:
         self.w_resized, self.h_resized = int(self.model.W_lr), int(self.model.H_lr)
         self.two_channel = bool(two_channel)
         self.pairs_per_forward = max(1, int(pairs_per_forward))
+        self._local_corr = None
+        self.set_fused_local_corr(fused_local_corr)
         self._axes: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
         log.info(f"RoMaV2 initialized (setting={setting}, H_lr={self.model.H_lr}, W_lr={self.model.W_lr}, device={device})")
 
@@ -172,6 +196,22 @@ class RomaMatcher:
                                torch.linspace(-1 + 1 / H, 1 - 1 / H, H, device=self.device))
         return self._axes[key]
 
+    def set_fused_local_corr(self, on: bool) -> None:
+        """The model's files are not modified: for the duration of each ``match_grids_batch`` call the module attribute
+        ``romav2.local_correlation.local_corr`` is a core.local_corr.LocalCorr, and restored afterwards."""
+        if bool(on) == (self._local_corr is not None):
+            return
+        if on:
+            from .local_corr import LocalCorr
+            self._local_corr = LocalCorr()
+        else:
+            self._local_corr.close()
+            self._local_corr = None
+
+    @property
+    def fused_local_corr(self) -> bool:
+        return self._local_corr is not None
+
     def set_feature_cache(self, cache) -> None:
         """A core.scheduler.FeatureCache (or None to switch sharing off): backbone features (``model.f`` of the low-resolution
         image) are then computed once per camera key instead of once per (reference, neighbour) pair.  The vendored model is
@@ -180,13 +220,17 @@ class RomaMatcher:
         restored afterwards."""
         self._feature_cache = cache
 
-    @torch.inference_mode()
     def match_grids_batch(self, imA, imB_list: Sequence, keys=None) -> List[Tuple[torch.Tensor, torch.Tensor]]:
         """``keys`` = (reference key, [neighbour keys]): camera identities for the feature cache (core/scheduler.py)."""
         if self.model is None:
             raise RuntimeError("RoMaV2 model has been released; create a new matcher before matching.")
         if not imB_list:
             return []
+        with _local_corr_installed(self._local_corr):
+            return self._match_grids_batch(imA, imB_list, keys)
+
+    @torch.inference_mode()
+    def _match_grids_batch(self, imA, imB_list: Sequence, keys=None) -> List[Tuple[torch.Tensor, torch.Tensor]]:
         torch.set_float32_matmul_precision("highest")
         model = self.model
         cache = getattr(self, "_feature_cache", None)
@@ -262,6 +306,8 @@ class RomaMatcher:
         except Exception:
             pass
         self.model = None
+        if self._local_corr is not None:
+            self._local_corr.close()
         self._axes.clear()
         gc.collect()
         if torch.cuda.is_available():

@@ -83,7 +83,8 @@ def _make_matcher(config, dev, progress_callback):
     _announce(progress_callback, cached)
     if not cached:
         log.info("RoMaV2 weights not found in cache; expected cache paths: " + ", ".join(romav2_cached_weights_paths()))
-    matcher = RomaMatcher(device=str(dev), mode="outdoor", setting=config.roma_setting, pairs_per_forward=int(config.pairs_per_forward))
+    matcher = RomaMatcher(device=str(dev), mode="outdoor", setting=config.roma_setting, pairs_per_forward=int(config.pairs_per_forward),
+                          fused_local_corr=bool(config.exp("fused_local_corr")))
     if not cached and progress_callback is not None:
         progress_callback(10.0, "RoMa v2 model installation complete. Starting matching...")
     return matcher
@@ -197,6 +198,12 @@ def run_dense_pipeline(
         if own_matcher:
             matcher = _make_matcher(config, dev, progress_callback)
         else:
+            # an injected matcher: the knob is handed to it, or refused - never ignored
+            if bool(getattr(matcher, "supports_fused_local_corr", False)):
+                matcher.set_fused_local_corr(bool(config.exp("fused_local_corr")))
+            elif config.exp("fused_local_corr"):
+                raise ValueError("experimental['fused_local_corr'] asks the matcher to run RoMa-v2's local correlation in the HIP kernel, but the "
+                                 f"injected matcher ({type(matcher).__name__}) does not declare supports_fused_local_corr")
             _announce(progress_callback, True)
         raise_if_cancelled(cancel_requested)
         size_wh = (int(matcher.w_resized), int(matcher.h_resized))

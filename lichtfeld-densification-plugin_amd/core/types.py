@@ -42,6 +42,9 @@ EXPERIMENTAL_DEFAULTS = {
     "upstream_fundamental": True,
     # backend="host": threads of the CPU twin (0: all hardware threads)
     "host_threads": 0,
+    # RoMa-v2's local correlation (the conv refiners' one custom operator, CUDA-only upstream) through lfd_local_corr instead of the model's
+    # grid_sample fallback (core/local_corr.py): within the derived error bound of the fallback, not bit for bit - hence off
+    "fused_local_corr": False,
 }
 
 

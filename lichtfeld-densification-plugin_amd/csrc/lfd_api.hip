@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "lfd_context.hpp"
+#include "lfd_corr.hpp"
 
 extern "C" __global__ void lfd_aggregate_kernel(LfdLaunch L, float* best_cert, uint8_t* best_slot);
 extern "C" __global__ void lfd_dense_kernel(LfdLaunch L);
@@ -56,6 +57,7 @@ extern "C" __global__ void lfd_voxel_sums_kernel(const float* xyz, const float* 
 extern "C" __global__ void lfd_voxel_sums_big_kernel(const float* xyz, const float* rgb, long long n, const unsigned* sorted_idx, const unsigned* vstart,
                                                      const unsigned* nv_p, double cscale, const unsigned* big, const unsigned* n_big, float* xyz_out,
                                                      float* rgb_out);
+hipError_t lfd_corr_launch(const LfdCorrArgs& p, hipStream_t stream);     // lfd_corr.hip
 extern "C" __global__ void lfd_select_topm_kernel(LfdSelectArgs A);
 extern "C" __global__ void lfd_select_filter_mw_kernel(LfdSelectArgs A, LfdSelectNorms norms);
 extern "C" __global__ void lfd_select_begins_kernel(long long* pairs, long long stride, int n);
@@ -1399,6 +1401,20 @@ int lfd_voxel_downsample(lfd_context* ctx, const float* xyz, const float* rgb, i
     LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, nv_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     LFD_HIP(ctx, hipStreamSynchronize(st));
     *n_out_host = (int64_t)(unsigned)ctx->pinned_words[0];
+    return LFD_OK;
+}
+
+// ---- local correlation of RoMa-v2's refiners (lfd_corr.hip) ----------------------------------------------------------------------------
+int lfd_local_corr(lfd_context* ctx, const float* A, const float* Bf, const float* warp, int32_t B, int32_t N, int32_t C, int32_t K, int32_t H1,
+                   int32_t W1, const int64_t* a_strides, const int64_t* bf_strides, float* out) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    LfdCorrArgs p;
+    if (const char* why = lfd_corr_fill(A, Bf, warp, B, N, C, K, H1, W1, a_strides, bf_strides, out, p))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_local_corr: ") + why);
+    if ((long long)B * N * K == 0) return LFD_OK;
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    LFD_HIP(ctx, lfd_corr_launch(p, ctx->stream));
     return LFD_OK;
 }
 

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "lfd_context.hpp"
+#include "lfd_corr.hpp"
 
 void lfd_fill_kernel_params(const lfd_batch* b, const lfd_params* p, LfdKernelParams& kp);   // lfd_api.hip
 
@@ -253,6 +254,29 @@ int lfd_create_host(int32_t n_threads, lfd_context** out) {
 }
 
 int lfd_host_threads(const lfd_context* ctx) { return (ctx && ctx->is_host) ? ctx->host_threads : 0; }
+
+int lfd_local_corr_host(lfd_context* ctx, const float* A, const float* Bf, const float* warp, int32_t B, int32_t N, int32_t C, int32_t K, int32_t H1,
+                        int32_t W1, const int64_t* a_strides, const int64_t* bf_strides, float* out) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    LfdCorrArgs p;
+    if (const char* why = lfd_corr_fill(A, Bf, warp, B, N, C, K, H1, W1, a_strides, bf_strides, out, p))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_local_corr_host: ") + why);
+    const long long pixels = (long long)B * N;
+    if (pixels * K == 0) return LFD_OK;
+    const int per = 64;                                           // query pixels per chunk
+    parallel_chunks(ctx, (int)((pixels + per - 1) / per), [&](int c) {
+        const long long hi = std::min<long long>(pixels, (long long)(c + 1) * per);
+        for (long long px = (long long)c * per; px < hi; ++px) {
+            const int b = (int)(px / N), n = (int)(px - (long long)b * N);
+            for (int k = 0; k < K; ++k) {
+                const long long e = px * K + k;
+                out[e] = lfd_corr_sample(p.a + b * p.sa_b + n * p.sa_n, p.sa_c, p.bf + b * p.sb_b, p.sb_y, p.sb_x, p.sb_c, C, W1, H1, warp[2 * e], warp[2 * e + 1]);
+            }
+        }
+    });
+    return LFD_OK;
+}
 
 int lfd_aggregate_host(lfd_context* ctx, const lfd_batch* b, const lfd_params* p, float* best_cert, uint8_t* best_slot) {
     int rc = validate_host(ctx, b, p);
