@@ -323,6 +323,36 @@ int lfd_local_corr(lfd_context* ctx, const float* A, const float* Bf, const floa
 int lfd_local_corr_host(lfd_context* ctx, const float* A, const float* Bf, const float* warp, int32_t B, int32_t N, int32_t C, int32_t K,
                         int32_t H1, int32_t W1, const int64_t* a_strides, const int64_t* bf_strides, float* out);
 
+/* Forward-backward consistency gate on RoMa-v2's two warps (upstream has no counterpart: it reads warp_AB / overlap_AB only and its
+ * "certainty threshold" is a floor, so a match that slid along its epipolar line - what a dense matcher produces at occlusions and depth steps -
+ * passes every two-view test).  For each of n_pairs (reference, neighbour) pairs (1..LFD_MAX_SLOTS; the tables are HOST arrays of n_pairs DEVICE
+ * pointers, read before the call returns: they travel in the kernel arguments, nothing is uploaded and nothing synchronises) and each cell of the
+ * H x W grid, in f32 with every rounding written out (csrc/lfd_cycle.hpp):
+ *   c        = certainty floored at certainty_thresh (the floor of lfd_params.certainty_thresh, NaN stays NaN)
+ *   (xb, yb) = channels C-2, C-1 of warp_ab (C = warp_channels: 4 [xA,yA,xB,yB] or 2 [xB,yB]); (xa, ya) = channels 0, 1, or axis_x / axis_y
+ *              as in lfd_batch when C == 2 (both NULL: lfd_identity_axis values)
+ *   not (-1 <= xb <= 1 and -1 <= yb <= 1), NaN included: REJECTED, error +inf; no address is formed from such a coordinate
+ *   ix = ((xb + 1) Wb - 1) / 2, iy likewise; (xa', ya') = bilinear blend of warp_ba (f32 [Hb*Wb*2]: normalised A-coordinates on B's grid) with
+ *              the taps clamped to the grid (F.grid_sample(padding_mode="border", align_corners=False))
+ *   dx = (xa' - xa) 0.5 (w_match - 1), dy = (ya' - ya) 0.5 (h_match - 1), d2 = dx dx + dy dy   (upstream's pixel conversion)
+ *   kept iff d2 <= tau2, tau2 = the f32 square of cycle_thresh_px formed once on the host (a NaN rejects)
+ *   cert_out = kept ? c : 0.0f;   err_out = sqrtf(d2)
+ * cert_out[i] may be cert[i] (in place).  err_out: NULL, or a table of n_pairs planes f32 [H*W].  rejected: NULL, or device i32 [n_pairs] that the
+ * number of rejected cells of every pair is ADDED to (zero it once, read it once per run).  A gated plane already carries the floor: hand it to
+ * the entry points above with lfd_params.certainty_thresh = min(thresh, 0) and a rejected cell behaves like one that mask_b masks out.
+ * One launch on the context's stream, asynchronous, deterministic.  LFD_ERR_INVALID: a null pointer (table or element), n_pairs outside
+ * 1..LFD_MAX_SLOTS, H, W, Hb, Wb outside 1..32768, w_match or h_match < 1, warp_channels not 2 or 4, only one of the axes, a cycle_thresh_px that is
+ * <= 0 or not finite.  lfd_cycle_gate_host: the same routine over host pointers (rejected: host i32 [n_pairs]) on a host context's threads; its
+ * cert_out and counters equal the device's bit for bit. */
+int lfd_cycle_gate(lfd_context* ctx, int32_t n_pairs, const float* const* cert, const float* const* warp_ab, const float* const* warp_ba, int32_t H,
+                   int32_t W, int32_t warp_channels, int32_t Hb, int32_t Wb, const float* axis_x, const float* axis_y, int32_t w_match,
+                   int32_t h_match, float certainty_thresh, float cycle_thresh_px, float* const* cert_out, float* const* err_out,
+                   int32_t* rejected);
+int lfd_cycle_gate_host(lfd_context* ctx, int32_t n_pairs, const float* const* cert, const float* const* warp_ab, const float* const* warp_ba,
+                        int32_t H, int32_t W, int32_t warp_channels, int32_t Hb, int32_t Wb, const float* axis_x, const float* axis_y,
+                        int32_t w_match, int32_t h_match, float certainty_thresh, float cycle_thresh_px, float* const* cert_out,
+                        float* const* err_out, int32_t* rejected);
+
 /* (e) multi-GPU exchange, placement step (no upstream counterpart - upstream has no multi-GPU code): n copies
  * dst[dst_offset .. +nbytes) = src[src_offset .. +nbytes) in ONE launch on `hip_stream` of device `device_index` (offsets and lengths in
  * bytes, no alignment required: 15-byte PLY records).  The overlapped exchange receives every rank's records of a round as one padded block
@@ -388,7 +418,7 @@ int lfd_host_eval_correspondence(const float* cam1, const float* cam2, float xa_
  * The per-cell arithmetic is the host build of the very source the kernels compile (csrc/lfd_geometry.hpp; IEEE
  * division / square root where the device uses the 1-ulp v_rcp / v_sqrt), spread over n_threads std::threads
  * (<= 0: all hardware threads).  A host context accepts lfd_upload_cameras, lfd_last_error, lfd_destroy and the
- * *_host calls (the three below and lfd_local_corr_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
+ * *_host calls (the three below, lfd_local_corr_host and lfd_cycle_gate_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
  * context: neither side ever stands in for the other.  Semantics (orders, counts, optional outputs, LFD_ERR_CAPACITY
  * with valid counts) are those of lfd_aggregate / lfd_triangulate_dense / lfd_triangulate_indexed. */
 int lfd_create_host(int32_t n_threads, lfd_context** out);

@@ -174,6 +174,9 @@ def load_library() -> C.CDLL:
     lib.lfd_quantise_rgb.argtypes = [ctxp, C.c_void_p, C.c_int64, C.c_void_p]
     lib.lfd_local_corr.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]
     lib.lfd_local_corr_host.argtypes = list(lib.lfd_local_corr.argtypes)
+    lib.lfd_cycle_gate.argtypes = ([ctxp, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                   C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p])
+    lib.lfd_cycle_gate_host.argtypes = list(lib.lfd_cycle_gate.argtypes)
     lib.lfd_copy_segments.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.lfd_launch_status.argtypes = [ctxp, C.POINTER(C.c_int32)]
     lib.lfd_get_pair_fundamental.argtypes = [ctxp, C.c_int32, C.POINTER(C.c_double)]
@@ -208,7 +211,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -220,10 +223,16 @@ def load_library() -> C.CDLL:
 
 def make_params(config: DensePipelineConfig, sample_cap: float = 0.9, exact_colour: Optional[bool] = None) -> lfd_params:
     """``exact_colour``: dense mode blends colours in f64 like upstream (bit-identical rgb) instead of f32 (within 2.5e-7);
-    default: the configuration's ``exact_colour`` field (False)."""
+    default: the configuration's ``exact_colour`` field (False).
+    With ``experimental['cycle_thresh_px']`` > 0 the certainty planes reach the kernels GATED (lfd_cycle_gate): they carry the floor already
+    and a rejected cell is exactly 0, so the kernels' own floor is min(thresh, 0) - it leaves every value of a gated plane (>= thresh, 0, NaN)
+    as it is, and a rejected cell behaves like one that mask_b masks out."""
     if exact_colour is None:
         exact_colour = bool(config.exact_colour)
-    return lfd_params(sampson_thresh=float(config.sampson_thresh), certainty_thresh=float(config.certainty_thresh),
+    floor = float(config.certainty_thresh)
+    if float(config.exp("cycle_thresh_px")) > 0.0:
+        floor = min(floor, 0.0)
+    return lfd_params(sampson_thresh=float(config.sampson_thresh), certainty_thresh=floor,
                       sample_cap=float(sample_cap), reproj_thresh=float(config.reproj_thresh),
                       min_parallax_deg=float(config.min_parallax_deg), no_filter=1 if config.no_filter else 0,
                       flags=LFD_FLAG_EXACT_COLOUR if exact_colour else 0)
@@ -647,6 +656,50 @@ def _local_corr_arguments(a, bf, warp, device):
     return a.detach(), bf.detach(), warp.detach().contiguous(), (B, N, Cc, K, H1, W1)
 
 
+def _cycle_gate_arguments(cert, warp_ab, warp_ba, axes, device):
+    """Shapes, dtype and device of a cycle_gate call checked; (n_pairs, H, W, C, Hb, Wb, axis_x, axis_y).  The planes are handed to the library
+    as they are - nothing is copied, ``cert`` may be written in place - so every one has to be a contiguous f32 tensor of ``device``."""
+    cert, warp_ab, warp_ba = list(cert), list(warp_ab), list(warp_ba)
+    n = len(cert)
+    if n < 1 or len(warp_ab) != n or len(warp_ba) != n:
+        raise ValueError("cycle_gate: one certainty, one forward and one backward warp per pair, at least one pair")
+    for name, ts in (("cert", cert), ("warp_ab", warp_ab), ("warp_ba", warp_ba)):
+        for t in ts:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"cycle_gate: {name} must hold contiguous float32 tensors")
+            if t.device != device:
+                raise ValueError(f"cycle_gate: {name} lives on {t.device}, this context computes on {device}")
+    if cert[0].dim() != 2 or warp_ab[0].dim() != 3 or warp_ba[0].dim() != 3:
+        raise ValueError("cycle_gate: cert (H, W), warp_ab (H, W, C), warp_ba (Hb, Wb, 2)")
+    H, W = (int(v) for v in cert[0].shape)
+    Cc = int(warp_ab[0].shape[-1])
+    Hb, Wb = int(warp_ba[0].shape[0]), int(warp_ba[0].shape[1])
+    for c, wa, wb in zip(cert, warp_ab, warp_ba):
+        if tuple(c.shape) != (H, W) or tuple(wa.shape) != (H, W, Cc) or tuple(wb.shape) != (Hb, Wb, 2):
+            raise ValueError(f"cycle_gate: cert {tuple(c.shape)}, warp_ab {tuple(wa.shape)}, warp_ba {tuple(wb.shape)} are not (H, W), (H, W, C), (Hb, Wb, 2) "
+                             "of one size for all pairs")
+    ax = ay = None
+    if axes is not None:
+        ax, ay = (torch.as_tensor(a).to(device, torch.float32).contiguous() for a in axes)
+        if tuple(ax.shape) != (W,) or tuple(ay.shape) != (H,):
+            raise ValueError("cycle_gate: axes must be (axis_x [W], axis_y [H])")
+    return n, H, W, Cc, Hb, Wb, ax, ay
+
+
+def _cycle_gate_call(fn, ctx, cert, warp_ab, warp_ba, w_match, h_match, certainty_thresh, cycle_thresh_px, axes, inplace, with_err, rejected, device):
+    n, H, W, Cc, Hb, Wb, ax, ay = _cycle_gate_arguments(cert, warp_ab, warp_ba, axes, device)
+    if rejected is not None and (not isinstance(rejected, torch.Tensor) or rejected.dtype != torch.int32 or rejected.device != device
+                                 or not rejected.is_contiguous() or rejected.numel() < n):
+        raise ValueError("cycle_gate: rejected must be a contiguous int32 tensor of this context's device with one element per pair")
+    outs = list(cert) if inplace else [torch.empty_like(c) for c in cert]
+    errs = [torch.empty_like(c) for c in cert] if with_err else None
+    table = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+    rc = fn(ctx, n, table(cert), table(warp_ab), table(warp_ba), H, W, Cc, Hb, Wb, ax.data_ptr() if ax is not None else None,
+            ay.data_ptr() if ay is not None else None, int(w_match), int(h_match), float(certainty_thresh), float(cycle_thresh_px), table(outs),
+            table(errs) if errs is not None else None, rejected.data_ptr() if rejected is not None else None)
+    return rc, outs, errs
+
+
 class HipDensifier:
     """One context = one GPU + one stream (``torch.cuda.current_stream`` of the device at creation,
     unless a stream is given).  Not thread-safe: use one per thread, as the C-ABI requires."""
@@ -800,6 +853,20 @@ class HipDensifier:
         sa, sb = (C.c_int64 * 3)(*a.stride()), (C.c_int64 * 4)(*bf.stride())
         self._check(self._lib.lfd_local_corr(self._ctx, a.data_ptr(), bf.data_ptr(), warp.data_ptr(), *dims, sa, sb, out.data_ptr()), "lfd_local_corr")
         return out
+
+    def cycle_gate(self, cert, warp_ab, warp_ba, w_match: int, h_match: int, certainty_thresh: float, cycle_thresh_px: float, axes=None,
+                   inplace: bool = False, with_err: bool = False, rejected: Optional[torch.Tensor] = None):
+        """Forward-backward consistency gate (lfd_cycle_gate) over up to 16 pairs in one launch on the context's stream.
+        ``cert`` [(H, W)], ``warp_ab`` [(H, W, 2 | 4)], ``warp_ba`` [(Hb, Wb, 2)]: one contiguous f32 tensor of this device per pair, read in
+        place.  A cell keeps its certainty, floored at ``certainty_thresh``, iff following ``warp_ab`` and coming back with ``warp_ba`` lands
+        within ``cycle_thresh_px`` pixels of the match image (``w_match`` x ``h_match``) of where it started; else it becomes exactly 0.
+        ``axes``: (axis_x, axis_y) of the reference grid for 2-channel warps (None: the identity axes).  ``inplace``: the planes of ``cert`` are
+        overwritten.  ``rejected``: int32 [n_pairs] on this device, the rejected cells of every pair are ADDED to it.
+        Returns (gated planes, error planes in px or None)."""
+        rc, outs, errs = _cycle_gate_call(self._lib.lfd_cycle_gate, self._ctx, cert, warp_ab, warp_ba, w_match, h_match, certainty_thresh,
+                                          cycle_thresh_px, axes, inplace, with_err, rejected, self.device)
+        self._check(rc, "lfd_cycle_gate")
+        return outs, errs
 
     def quantise_rgb(self, rgb: torch.Tensor) -> torch.Tensor:
         rgb = self._pts(rgb, 3, "rgb")
@@ -1118,6 +1185,14 @@ class HostDensifier:
         self._check(self._lib.lfd_local_corr_host(self._ctx, a.data_ptr(), bf.data_ptr(), warp.data_ptr(), *dims, sa, sb, out.data_ptr()),
                     "lfd_local_corr_host")
         return out
+
+    def cycle_gate(self, cert, warp_ab, warp_ba, w_match: int, h_match: int, certainty_thresh: float, cycle_thresh_px: float, axes=None,
+                   inplace: bool = False, with_err: bool = False, rejected: Optional[torch.Tensor] = None):
+        """HipDensifier.cycle_gate over CPU tensors (lfd_cycle_gate_host): the same per-cell routine, the same bits in the gated planes and counters."""
+        rc, outs, errs = _cycle_gate_call(self._lib.lfd_cycle_gate_host, self._ctx, cert, warp_ab, warp_ba, w_match, h_match, certainty_thresh,
+                                          cycle_thresh_px, axes, inplace, with_err, rejected, self.device)
+        self._check(rc, "lfd_cycle_gate_host")
+        return outs, errs
 
     def aggregate(self, batch: PreparedBatch, params: lfd_params):
         self._same_device(batch)

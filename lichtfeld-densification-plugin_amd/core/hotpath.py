@@ -63,7 +63,41 @@ class HotPath:
         self._norm_masks: dict = {}
         self.dens.upload_cameras(cams)
         self.cams = list(cams) if bool(config.exp("upstream_fundamental")) else None
+        # the kernels' floor is min(thresh, 0) when the planes arrive gated (hb.make_params); everything on the host that reasons about the
+        # floor - the exactness checks below - keeps reading the CONFIGURED threshold
         self.params = hb.make_params(config, sample_cap)
+        self.cycle_thresh_px = float(config.exp("cycle_thresh_px"))
+        self._cycle_counter: Optional[torch.Tensor] = None      # int32 [LFD_MAX_SLOTS] where the kernels run: rejected cells per slot, added to
+        self._cycle_pending = 0                                 # cells per slot gated since the counter was last read (it must not wrap)
+        self.cycle_cells = self.cycle_rejected = 0
+
+    # -- forward-backward consistency filter (lfd_cycle_gate) -------------------------------------------------------------------
+    def cycle_gate(self, warps, certs, backs, axes) -> None:
+        """The certainty planes of one reference's pairs gated IN PLACE, one launch per 16 pairs on the densifier's stream - the stream the
+        matcher left them on - with nothing read back: the counters stay where the kernels run until ``cycle_totals``."""
+        if self._cycle_counter is None:
+            self._cycle_counter = torch.zeros(hb.LFD_MAX_SLOTS, dtype=torch.int32, device=self.dev)
+        hw = int(certs[0].numel())
+        if self._cycle_pending + hw > 0x7fffffff:
+            self._cycle_flush()
+        with self.clock.stage("kernel", sync=False):
+            for j0 in range(0, len(certs), hb.LFD_MAX_SLOTS):
+                j1 = min(len(certs), j0 + hb.LFD_MAX_SLOTS)
+                self.dens.cycle_gate(certs[j0:j1], warps[j0:j1], backs[j0:j1], self.w_match, self.h_match, float(self.config.certainty_thresh),
+                                     self.cycle_thresh_px, axes=axes, inplace=True, rejected=self._cycle_counter)
+        self._cycle_pending += hw
+        self.cycle_cells += hw * len(certs)
+
+    def _cycle_flush(self) -> None:
+        if self._cycle_counter is not None and self._cycle_pending:
+            self.cycle_rejected += int(self._cycle_counter.to(torch.int64).sum().item())
+            self._cycle_counter.zero_()
+            self._cycle_pending = 0
+
+    def cycle_totals(self) -> Tuple[int, int]:
+        """(cells gated, cells rejected) of the run so far: the one read of the device counters."""
+        self._cycle_flush()
+        return self.cycle_cells, self.cycle_rejected
 
     def close(self) -> None:
         self._prepared.clear()

@@ -153,12 +153,29 @@ def _local_corr_installed(shim):
         module.local_corr = previous
 
 
+@contextlib.contextmanager
+def _bidirectional_forced(model, on: bool):
+    """While the block runs, ``model.bidirectional`` is True when ``on`` - the presets turbo / fast / base run the model one way only, and the
+    backward warp exists only in a two-way forward; the previous value comes back afterwards, also when the block raises.  ``on`` False (or a
+    model that is bidirectional already): nothing is touched."""
+    if not on or bool(getattr(model, "bidirectional", False)):
+        yield
+        return
+    previous = model.bidirectional
+    model.bidirectional = True
+    try:
+        yield
+    finally:
+        model.bidirectional = previous
+
+
 class RomaMatcher:
     """Dense matcher with the reference image's features cached across its neighbours."""
 
     accepts_device_images = True      # match_grids_batch takes (h, w, 3) u8 device tensors as well as PIL images
     supports_feature_keys = True      # match_grids_batch(..., keys=(ref_key, [nbr_keys])) shares backbone features between references
     supports_fused_local_corr = True  # set_fused_local_corr(True): the refiners' local correlation runs in this package's HIP kernel
+    supports_backward_warp = True     # set_backward_warp(True): match_grids_batch returns (warp, cert, warp_BA) triples
 
     def __init__(self, device: str = "cuda", mode: str = "outdoor", setting: str = "fast", two_channel: bool = True,
                  pairs_per_forward: int = 1, fused_local_corr: bool = False):
@@ -184,6 +201,7 @@ class RomaMatcher:
         self.two_channel = bool(two_channel)
         self.pairs_per_forward = max(1, int(pairs_per_forward))
         self._local_corr = None
+        self._backward = False
         self.set_fused_local_corr(fused_local_corr)
         self._axes: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
         log.info(f"RoMaV2 initialized (setting={setting}, H_lr={self.model.H_lr}, W_lr={self.model.W_lr}, device={device})")
@@ -212,6 +230,17 @@ class RomaMatcher:
     def fused_local_corr(self) -> bool:
         return self._local_corr is not None
 
+    def set_backward_warp(self, on: bool) -> None:
+        """``match_grids_batch`` returns (warp, cert, warp_BA) triples: ``warp_BA`` (Hb, Wb, 2) is the model's own backward warp - normalised
+        A-coordinates on B's grid - which the bidirectional presets (high, precise) compute anyway and the forward-backward filter
+        (lfd_cycle_gate) consumes.  In a preset whose model runs one way, ``model.bidirectional`` is True for the duration of
+        each call and restored afterwards; the forward outputs are the same either way (tests/golden/g16_cycle_contract.json)."""
+        self._backward = bool(on)
+
+    @property
+    def backward_warp(self) -> bool:
+        return self._backward
+
     def set_feature_cache(self, cache) -> None:
         """A core.scheduler.FeatureCache (or None to switch sharing off): backbone features (``model.f`` of the low-resolution
         image) are then computed once per camera key instead of once per (reference, neighbour) pair.  The vendored model is
@@ -226,7 +255,7 @@ class RomaMatcher:
             raise RuntimeError("RoMaV2 model has been released; create a new matcher before matching.")
         if not imB_list:
             return []
-        with _local_corr_installed(self._local_corr):
+        with _local_corr_installed(self._local_corr), _bidirectional_forced(self.model, self._backward):
             return self._match_grids_batch(imA, imB_list, keys)
 
     @torch.inference_mode()
@@ -280,12 +309,13 @@ class RomaMatcher:
                     warp_ab = pred["warp_AB"][i]
                     cert = pred["overlap_AB"][i].squeeze(-1).contiguous()
                     H, W = cert.shape
+                    back = (pred["warp_BA"][i].contiguous(),) if self._backward else ()          # one chunk's own pair i: both branches above
                     if self.two_channel:
-                        out.append((warp_ab.contiguous(), cert))
+                        out.append((warp_ab.contiguous(), cert) + back)
                     else:
                         ax, ay = self.reference_axes(H, W)
                         grid = torch.stack([ax.view(1, W).expand(H, W), ay.view(H, 1).expand(H, W)], dim=-1)
-                        out.append((torch.cat([grid, warp_ab], dim=-1).contiguous(), cert))
+                        out.append((torch.cat([grid, warp_ab], dim=-1).contiguous(), cert) + back)
         finally:
             if keyed is not None:
                 model.f = plain_f

@@ -85,6 +85,8 @@ def _make_matcher(config, dev, progress_callback):
         log.info("RoMaV2 weights not found in cache; expected cache paths: " + ", ".join(romav2_cached_weights_paths()))
     matcher = RomaMatcher(device=str(dev), mode="outdoor", setting=config.roma_setting, pairs_per_forward=int(config.pairs_per_forward),
                           fused_local_corr=bool(config.exp("fused_local_corr")))
+    if float(config.exp("cycle_thresh_px")) > 0.0:       # (a matcher built here starts with the backward warp off)
+        matcher.set_backward_warp(True)
     if not cached and progress_callback is not None:
         progress_callback(10.0, "RoMa v2 model installation complete. Starting matching...")
     return matcher
@@ -119,14 +121,20 @@ def _match_reference(local_i: int, packed: PackedReference, matcher, hot: HotPat
         if not results:
             return None
         first_pair = outputs.note_pairs(local_i, len(results))
-        warps = [_as_device_map(w, dev) for w, _c in results]
-        certs = [_as_device_map(c, dev) for _w, c in results]
+        warps = [_as_device_map(r[0], dev) for r in results]
+        certs = [_as_device_map(r[1], dev) for r in results]
     H, W = certs[0].shape
     axes = None
     ax = getattr(matcher, "reference_axes", None)
     if warps[0].shape[-1] == 2 and callable(ax):
         a0, a1 = ax(H, W)
         axes = (torch.as_tensor(a0).to(dev, torch.float32).contiguous(), torch.as_tensor(a1).to(dev, torch.float32).contiguous())
+    if hot.cycle_thresh_px > 0.0:
+        # forward-backward filter: the certainty planes are gated in place, right behind the matcher on its stream; everything downstream
+        # sees a rejected cell as one mask_b masked out
+        if any(len(r) < 3 for r in results):
+            raise RuntimeError(f"experimental['cycle_thresh_px'] is set but {type(matcher).__name__}.match_grids_batch returned no backward warp")
+        hot.cycle_gate(warps, certs, [_as_device_map(r[2], dev) for r in results], axes)
     return Matched(local_i, packed, hot.inputs(packed, warps, certs), axes, int(H), int(W), first_pair, want_debug)
 
 
@@ -204,6 +212,11 @@ def run_dense_pipeline(
             elif config.exp("fused_local_corr"):
                 raise ValueError("experimental['fused_local_corr'] asks the matcher to run RoMa-v2's local correlation in the HIP kernel, but the "
                                  f"injected matcher ({type(matcher).__name__}) does not declare supports_fused_local_corr")
+            if bool(getattr(matcher, "supports_backward_warp", False)):
+                matcher.set_backward_warp(float(config.exp("cycle_thresh_px")) > 0.0)
+            elif float(config.exp("cycle_thresh_px")) > 0.0:
+                raise ValueError("experimental['cycle_thresh_px'] asks for the forward-backward filter, which needs the matcher's backward warp, but the "
+                                 f"injected matcher ({type(matcher).__name__}) does not declare supports_backward_warp")
             _announce(progress_callback, True)
         raise_if_cancelled(cancel_requested)
         size_wh = (int(matcher.w_resized), int(matcher.h_resized))
@@ -240,6 +253,9 @@ def run_dense_pipeline(
             if m is not None:
                 strategy.submit(m)
         strategy.drain()
+        if hot.cycle_thresh_px > 0.0:
+            cells, rejected = hot.cycle_totals()
+            log.info(f"Forward-backward filter: threshold {hot.cycle_thresh_px:g} px, {cells} cells, {100.0 * rejected / max(1, cells):.2f} % rejected")
     except BaseException as exc:
         if world == 1:
             raise

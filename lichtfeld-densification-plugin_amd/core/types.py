@@ -45,6 +45,10 @@ EXPERIMENTAL_DEFAULTS = {
     # RoMa-v2's local correlation (the conv refiners' one custom operator, CUDA-only upstream) through lfd_local_corr instead of the model's
     # grid_sample fallback (core/local_corr.py): within the derived error bound of the fallback, not bit for bit - hence off
     "fused_local_corr": False,
+    # forward-backward consistency filter on the matcher's two warps (lfd_cycle_gate): a cell whose round trip A -> B -> A misses
+    # its start by more than this many pixels of the match image loses the pair (certainty exactly 0, as if mask_b had masked it out).
+    # 0.0 = off: the backward warp is not asked for and no new code runs.  Needs a matcher that hands out warp_BA (supports_backward_warp).
+    "cycle_thresh_px": 0.0,
 }
 
 
@@ -168,6 +172,12 @@ class DensePipelineConfig:
             return "experimental['exchange_round'] must be >= 0"
         if not (0.0 <= float(self.exp("exchange_replicate")) <= 1.0):
             return "experimental['exchange_replicate'] must be a fraction in [0, 1]"
+        try:
+            tau = float(self.exp("cycle_thresh_px"))
+        except (TypeError, ValueError):
+            return "experimental['cycle_thresh_px'] must be a number (px of the match image; 0 = off)"
+        if not (0.0 <= tau < float("inf")):
+            return "experimental['cycle_thresh_px'] must be finite and >= 0 (px of the match image; 0 = off)"
         dense = self.triangulation_mode == "dense"
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):

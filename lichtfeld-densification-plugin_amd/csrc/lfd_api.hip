@@ -15,6 +15,7 @@
 
 #include "lfd_context.hpp"
 #include "lfd_corr.hpp"
+#include "lfd_cycle.hpp"
 
 extern "C" __global__ void lfd_aggregate_kernel(LfdLaunch L, float* best_cert, uint8_t* best_slot);
 extern "C" __global__ void lfd_dense_kernel(LfdLaunch L);
@@ -58,6 +59,7 @@ extern "C" __global__ void lfd_voxel_sums_big_kernel(const float* xyz, const flo
                                                      const unsigned* nv_p, double cscale, const unsigned* big, const unsigned* n_big, float* xyz_out,
                                                      float* rgb_out);
 hipError_t lfd_corr_launch(const LfdCorrArgs& p, hipStream_t stream);     // lfd_corr.hip
+hipError_t lfd_cycle_launch(const LfdCycleArgs& p, hipStream_t stream);   // lfd_cycle.hip
 extern "C" __global__ void lfd_select_topm_kernel(LfdSelectArgs A);
 extern "C" __global__ void lfd_select_filter_mw_kernel(LfdSelectArgs A, LfdSelectNorms norms);
 extern "C" __global__ void lfd_select_begins_kernel(long long* pairs, long long stride, int n);
@@ -1415,6 +1417,22 @@ int lfd_local_corr(lfd_context* ctx, const float* A, const float* Bf, const floa
     if ((long long)B * N * K == 0) return LFD_OK;
     LFD_HIP(ctx, hipSetDevice(ctx->device));
     LFD_HIP(ctx, lfd_corr_launch(p, ctx->stream));
+    return LFD_OK;
+}
+
+// ---- forward-backward consistency gate (lfd_cycle.hip) -----------------------------------------------------------------------------------
+int lfd_cycle_gate(lfd_context* ctx, int32_t n_pairs, const float* const* cert, const float* const* warp_ab, const float* const* warp_ba, int32_t H,
+                   int32_t W, int32_t warp_channels, int32_t Hb, int32_t Wb, const float* axis_x, const float* axis_y, int32_t w_match,
+                   int32_t h_match, float certainty_thresh, float cycle_thresh_px, float* const* cert_out, float* const* err_out,
+                   int32_t* rejected) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    LfdCycleArgs p;
+    if (const char* why = lfd_cycle_fill(n_pairs, cert, warp_ab, warp_ba, H, W, warp_channels, Hb, Wb, axis_x, axis_y, w_match, h_match,
+                                         certainty_thresh, cycle_thresh_px, cert_out, err_out, rejected, p))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_cycle_gate: ") + why);
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    LFD_HIP(ctx, lfd_cycle_launch(p, ctx->stream));
     return LFD_OK;
 }
 

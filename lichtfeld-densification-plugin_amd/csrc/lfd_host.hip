@@ -18,6 +18,7 @@
 
 #include "lfd_context.hpp"
 #include "lfd_corr.hpp"
+#include "lfd_cycle.hpp"
 
 void lfd_fill_kernel_params(const lfd_batch* b, const lfd_params* p, LfdKernelParams& kp);   // lfd_api.hip
 
@@ -275,6 +276,44 @@ int lfd_local_corr_host(lfd_context* ctx, const float* A, const float* Bf, const
             }
         }
     });
+    return LFD_OK;
+}
+
+int lfd_cycle_gate_host(lfd_context* ctx, int32_t n_pairs, const float* const* cert, const float* const* warp_ab, const float* const* warp_ba, int32_t H,
+                        int32_t W, int32_t warp_channels, int32_t Hb, int32_t Wb, const float* axis_x, const float* axis_y, int32_t w_match,
+                        int32_t h_match, float certainty_thresh, float cycle_thresh_px, float* const* cert_out, float* const* err_out,
+                        int32_t* rejected) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    LfdCycleArgs p;
+    if (const char* why = lfd_cycle_fill(n_pairs, cert, warp_ab, warp_ba, H, W, warp_channels, Hb, Wb, axis_x, axis_y, w_match, h_match,
+                                         certainty_thresh, cycle_thresh_px, cert_out, err_out, rejected, p))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_cycle_gate_host: ") + why);
+    const int HW = H * W, chunks_per_pair = (HW + kChunk - 1) / kChunk;
+    std::vector<int32_t> counts((size_t)n_pairs * chunks_per_pair, 0);
+    parallel_chunks(ctx, n_pairs * chunks_per_pair, [&](int c) {
+        const int pair = c / chunks_per_pair, c0 = (c - pair * chunks_per_pair) * kChunk, c1 = std::min(c0 + kChunk, HW);
+        int32_t n_rejected = 0;
+        for (int cell = c0; cell < c1; ++cell) {
+            const int y = cell / W, x = cell - y * W;
+            const float* wp = p.warp_ab[pair] + (size_t)cell * p.C;
+            float xa, ya, xb, yb;
+            if (p.C == 4) { xa = wp[0]; ya = wp[1]; xb = wp[2]; yb = wp[3]; }
+            else {
+                xb = wp[0]; yb = wp[1];
+                xa = p.axis_x ? p.axis_x[x] : lfd_axis_value(p.ax, x);
+                ya = p.axis_y ? p.axis_y[y] : lfd_axis_value(p.ay, y);
+            }
+            float d2;
+            const bool keep = lfd_cycle_cell(p.warp_ba[pair], Wb, Hb, xa, ya, xb, yb, p.wm1, p.hm1, p.tau2, d2);
+            p.cert_out[pair][cell] = keep ? lfd_cert_floor(p.cert[pair][cell], p.certainty_thresh) : 0.0f;
+            if (p.err_out[pair]) p.err_out[pair][cell] = sqrtf(d2);
+            n_rejected += keep ? 0 : 1;
+        }
+        counts[(size_t)c] = n_rejected;
+    });
+    if (rejected)
+        for (int c = 0; c < n_pairs * chunks_per_pair; ++c) rejected[c / chunks_per_pair] += counts[(size_t)c];
     return LFD_OK;
 }
 

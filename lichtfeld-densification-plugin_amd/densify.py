@@ -272,7 +272,8 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
         prefetch_packages=args.prefetch_packages, pack_workers=args.pack_workers,
         triangulation_mode=getattr(args, "triangulation_mode", "sampled"),
         refs_per_launch=getattr(args, "refs_per_launch", 0), backend=getattr(args, "backend", "device"),
-        stream_output=bool(getattr(args, "stream_output", False)), device_image_prep=bool(getattr(args, "device_image_prep", False)))
+        stream_output=bool(getattr(args, "stream_output", False)), device_image_prep=bool(getattr(args, "device_image_prep", False)),
+        experimental={"cycle_thresh_px": float(args.cycle_thresh_px)} if float(getattr(args, "cycle_thresh_px", 0.0)) != 0.0 else {})
     try:
         result = run_dense_pipeline(records, refs_local, nn_table, config, progress_callback=progress_callback,
                                     on_sequential_viz=None, debug_state=debug_state, cancel_requested=cancel_requested, **pipeline_kwargs)
@@ -424,6 +425,9 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--stream_output", action="store_true",
                     help="write the PLY while the run proceeds (15-byte records packed on the device; needs a .ply --out_name and no --max_points)")
     ap.add_argument("--device_image_prep", action="store_true", help="resize / mask the decoded images on the GPU (Pillow's arithmetic, bit for bit)")
+    ap.add_argument("--cycle_thresh_px", type=float, default=0.0,
+                    help="forward-backward consistency filter: drop a match whose round trip A -> B -> A misses its start by more than this many "
+                         "pixels of the match image (uses RoMa's backward warp; 0 = off)")
     ap.add_argument("--keep_threads", action="store_true",
                     help="leave torch's intra-op thread count alone (by default it is lowered to the container's CPU quota; the count decides the last "
                          "bits of upstream's sampling normaliser, so a run compared bit for bit with upstream keeps upstream's setting)")

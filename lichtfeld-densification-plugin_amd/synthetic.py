@@ -282,13 +282,19 @@ class SyntheticMatcher:
     sample_thresh = 0.9
     accepts_device_images = True
     supports_feature_keys = True
+    supports_backward_warp = True     # set_backward_warp(True): match_grids_batch returns (warp, cert, warp_BA) triples
 
     def __init__(self, cams: Sequence[CameraRecord], setting: str = "fast", device="cpu", *, noise_px: float = 0.5, outlier_frac: float = 0.05,
-                 channels: int = 2, seed: int = 0, latency_s_per_pair: float = 0.0, cert_mode: str = "smooth"):
+                 channels: int = 2, seed: int = 0, latency_s_per_pair: float = 0.0, cert_mode: str = "smooth", occlusion_steps: bool = False,
+                 out_of_range: float = 0.0):
         self.cams, self.device = list(cams), torch.device(device)
         h_lr, w_lr, self.H, self.W = ROMA_PRESETS[setting]
         self.w_resized, self.h_resized = int(w_lr), int(h_lr)
         self.kw = dict(noise_px=noise_px, outlier_frac=outlier_frac, channels=int(channels), seed=int(seed), cert_mode=cert_mode)
+        if occlusion_steps or out_of_range:
+            self.kw.update(occlusion_steps=bool(occlusion_steps), out_of_range=float(out_of_range))
+        self.backward = False
+        self.back_table: dict = {}
         self.latency = float(latency_s_per_pair)
         self.table: dict = {}
         self._axes: dict = {}
@@ -316,13 +322,25 @@ class SyntheticMatcher:
         """``image``: the camera's match-size image exactly as the driver's loader prepares it"""
         self.fingerprints[self._fingerprint(image)] = int(cam_index)
 
+    def set_backward_warp(self, on: bool) -> None:
+        """``match_grids_batch`` hands out (warp, cert, warp_BA) triples: warp_BA (H, W, 2) is the neighbour's own analytic field towards the
+        reference - ``synth_reference(cams, nbr, [ref])`` with the matcher's noise and outliers - i.e. normalised A-coordinates on B's grid."""
+        self.backward = bool(on)
+
     def fields(self, ref: int, nbrs: Sequence[int]):
         key = (int(ref), tuple(int(n) for n in nbrs))
         hit = self.table.get(key)
         if hit is None:
             s = synth_reference(self.cams, key[0], list(key[1]), self.H, self.W, self.w_resized, self.h_resized, device=self.device, **self.kw)
             hit = [(s.warp[j].contiguous(), s.cert[j].contiguous()) for j in range(len(key[1]))]
-        return key, hit
+        if not self.backward:
+            return key, hit
+        back = self.back_table.get(key)
+        if back is None:
+            back = [synth_reference(self.cams, n, [key[0]], self.H, self.W, self.w_resized, self.h_resized, device=self.device,
+                                    **self.kw).warp[0][..., -2:].contiguous() for n in key[1]]
+        # (the driver gates the certainty plane it is handed in place: the table keeps its own)
+        return key, [(w, c.clone(), b) for (w, c), b in zip(hit, back)]
 
     def precompute(self, refs: Sequence[int], nn_table, nns_per_ref: int) -> int:
         """The fields of these references with the neighbours the driver will load (``nn_table[r][:nns_per_ref]`` without r itself)."""
@@ -330,7 +348,9 @@ class SyntheticMatcher:
             nbrs = [int(n) for n in nn_table[int(r)][:int(nns_per_ref)] if self.cams[int(n)].uid != self.cams[int(r)].uid]
             if nbrs:
                 key, val = self.fields(int(r), nbrs)
-                self.table[key] = val
+                self.table[key] = [v[:2] for v in val]
+                if self.backward:
+                    self.back_table[key] = [v[2] for v in val]
         return len(self.table)
 
     def match_grids_batch(self, imA, imB_list, keys=None):
