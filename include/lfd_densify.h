@@ -353,6 +353,35 @@ int lfd_cycle_gate_host(lfd_context* ctx, int32_t n_pairs, const float* const* c
                         int32_t w_match, int32_t h_match, float certainty_thresh, float cycle_thresh_px, float* const* cert_out,
                         float* const* err_out, int32_t* rejected);
 
+/* Multi-view support filter BEHIND triangulation (upstream has no counterpart: it loads nns_per_ref neighbours per reference, keeps the
+ * most certain one per cell and never looks at the others again, so nothing checks a triangulated point against a third view - the only thing that
+ * can refute a match that slid along its epipolar line and triangulated cleanly to the wrong depth).  "Keep a point only if at least m other views
+ * agree with it", the fusion rule of multi-view stereo, on data that is resident anyway: `in` is what lfd_triangulate_dense / _indexed /
+ * _sampled* wrote for `batch` (in->cell and in->slot required), reference r's points are [ref_offsets_in[r], ref_offsets_in[r+1]) (device i64
+ * [n_refs + 1]; offsets beyond in->capacity count as in->capacity).  Per input point i of reference r with s = slot[i], cell = cell[i], X = xyz[i],
+ * for every slot j != s, j < n_slots[r], in f32 with every rounding written out (csrc/lfd_support.hpp):
+ *   live(j)      cert[r,j][cell] > 0 (the RAW plane: a NaN, and the exact 0 lfd_cycle_gate leaves, are not live) and, where mask_b[r,j] is given, the
+ *                mask pixel the slot's warp points at is non-zero - looked up as the kernels' certainty prologue does (lfd_grid_nearest, a
+ *                coordinate outside the grid: not live).  mask_a plays no part: the point exists.
+ *   (ub, vb)     = ((xb + 1) 0.5 (w_match - 1)) sx_j, ((yb + 1) 0.5 (h_match - 1)) sy_j - the pixel conversion and the camera-pixel scale of the
+ *                  triangulation kernels; (xb, yb) = channels C-2, C-1 of warp[r,j][cell]
+ *   (px, py, pz) = the rows of P_j applied to (X, 1): the FMA chain of the reprojection test, so a point projects to the same f32 everywhere
+ *   agree(j)     du = px - ub pz, dv = py - vb pz, d2 = du du + dv dv, t = support_thresh_px pz: pz > 0 and d2 <= t t   (a NaN rejects)
+ *   support_i    = the number of j that are live and agree; the point is KEPT iff support_i >= min_support
+ * A cell outside the grid has support 0 (no address is formed from it).  The kept points are compacted STABLY into `out` (input order inside and
+ * across references: dense raster order and the sampled mode's slot groups survive), every given array copied bit for bit; out->cell / out->slot
+ * optional.  ref_offsets_out: device i64 [n_refs + 1], always written (the counts stay on the device).  seg_counts_out: NULL, or device i32
+ * [n_refs*k], the kept points per (reference, winning slot), overwritten.  support: NULL, or device u8 [in->capacity], support_i of every INPUT point.
+ * Three launches on the context's stream, asynchronous, deterministic (integer atomics only).  The batch is prepared like the compute entry points
+ * above prepare it (only when it differs from the last one seen).  LFD_ERR_INVALID: a null required pointer, missing cell / slot, in->capacity
+ * > 2^31 - 1, min_support outside 1..LFD_MAX_SLOTS-1, a support_thresh_px that is <= 0 or not finite, overlapping in / out arrays;
+ * LFD_ERR_CAPACITY: out->capacity < in->capacity.  lfd_support_filter_host: the same routine over host pointers on a host context's threads; every
+ * output equals the device's bit for bit. */
+int lfd_support_filter(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets_in, int32_t min_support,
+                       float support_thresh_px, const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out, uint8_t* support);
+int lfd_support_filter_host(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets_in, int32_t min_support,
+                            float support_thresh_px, const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out, uint8_t* support);
+
 /* (e) multi-GPU exchange, placement step (no upstream counterpart - upstream has no multi-GPU code): n copies
  * dst[dst_offset .. +nbytes) = src[src_offset .. +nbytes) in ONE launch on `hip_stream` of device `device_index` (offsets and lengths in
  * bytes, no alignment required: 15-byte PLY records).  The overlapped exchange receives every rank's records of a round as one padded block
@@ -418,7 +447,7 @@ int lfd_host_eval_correspondence(const float* cam1, const float* cam2, float xa_
  * The per-cell arithmetic is the host build of the very source the kernels compile (csrc/lfd_geometry.hpp; IEEE
  * division / square root where the device uses the 1-ulp v_rcp / v_sqrt), spread over n_threads std::threads
  * (<= 0: all hardware threads).  A host context accepts lfd_upload_cameras, lfd_last_error, lfd_destroy and the
- * *_host calls (the three below, lfd_local_corr_host and lfd_cycle_gate_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
+ * *_host calls (the three below, lfd_local_corr_host, lfd_cycle_gate_host and lfd_support_filter_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
  * context: neither side ever stands in for the other.  Semantics (orders, counts, optional outputs, LFD_ERR_CAPACITY
  * with valid counts) are those of lfd_aggregate / lfd_triangulate_dense / lfd_triangulate_indexed. */
 int lfd_create_host(int32_t n_threads, lfd_context** out);

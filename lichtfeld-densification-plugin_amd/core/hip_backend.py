@@ -177,6 +177,9 @@ def load_library() -> C.CDLL:
     lib.lfd_cycle_gate.argtypes = ([ctxp, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                    C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p])
     lib.lfd_cycle_gate_host.argtypes = list(lib.lfd_cycle_gate.argtypes)
+    lib.lfd_support_filter.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_points), C.c_void_p, C.c_int32, C.c_float, C.POINTER(lfd_points),
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lfd_support_filter_host.argtypes = list(lib.lfd_support_filter.argtypes)
     lib.lfd_copy_segments.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.lfd_launch_status.argtypes = [ctxp, C.POINTER(C.c_int32)]
     lib.lfd_get_pair_fundamental.argtypes = [ctxp, C.c_int32, C.POINTER(C.c_double)]
@@ -211,7 +214,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -395,6 +398,7 @@ class TriangulationOutput:
     n_selected: Optional[int] = None         # sampled call: cells the selection stage picked
     launch_status: int = 0                   # sampled call: look-back status of the launch (0 = ok)
     sel_status: Optional[np.ndarray] = None  # sampled calls: selection status per reference (0 = ok, else what upstream would have raised for)
+    support_in: Optional[int] = None         # buffers lfd_support_filter filled: the points that reached the filter (``count`` of them were kept)
     _packed: Optional[torch.Tensor] = None   # the one float buffer xyz / rgb / err are views of
     _cap: int = 0
 
@@ -566,12 +570,16 @@ class OutputBuffers:
         # the small integer outputs share ONE buffer so that collect() needs a single device-to-host copy:
         # [ref_offsets i64 x (R+1)] [seg_counts i32 x R*k] [seg_order i32 x R*k]
         n_off, n_seg = 2 * (n_refs + 1), n_refs * k
-        self._meta = torch.zeros((n_off + 2 * n_seg + 2 * n_refs + 1,), dtype=torch.int32, device=device)
+        # ... [sel_info i32 x 2R+1] [pad to 8 bytes] [support_in i64]: the points that reached lfd_support_filter, written by HipDensifier.support_filter
+        n_info = 2 * n_refs + 2
+        self._meta = torch.zeros((n_off + 2 * n_seg + n_info + 2,), dtype=torch.int32, device=device)
         self._meta[n_off + n_seg:n_off + 2 * n_seg].fill_(-1)
         self.ref_offsets = self._meta[:n_off].view(torch.int64)
         self.seg_counts = self._meta[n_off:n_off + n_seg].view(n_refs, k)
         self.seg_order = self._meta[n_off + n_seg:n_off + 2 * n_seg].view(n_refs, k)
-        self.sel_info = self._meta[n_off + 2 * n_seg:]           # lfd_triangulate_sampled[_multi]: {cells selected, selection status} per reference, then the launch status
+        self.support_in = self._meta[n_off + 2 * n_seg + n_info:].view(torch.int64)
+        self.filtered = False                                    # True: these buffers are a support filter's destination (collect reports support_in)
+        self.sel_info = self._meta[n_off + 2 * n_seg:n_off + 2 * n_seg + 2 * n_refs + 1]           # lfd_triangulate_sampled[_multi]: {cells selected, selection status} per reference, then the launch status
         self._n_refs, self._k = n_refs, k
         self.c = lfd_points(xyz=self.xyz.data_ptr(), rgb=self.rgb.data_ptr(), err=self.err.data_ptr(),
                             cell=self.cell.data_ptr() if with_cell else None,
@@ -629,7 +637,8 @@ class OutputBuffers:
             seg_order=meta[n_off + n_seg:n_off + 2 * n_seg].reshape(self._n_refs, self._k).copy() if indexed else None,
             n_selected=int(meta[n_off + 2 * n_seg:n_off + 2 * n_seg + 2 * self._n_refs:2].sum()),
             sel_status=meta[n_off + 2 * n_seg + 1:n_off + 2 * n_seg + 2 * self._n_refs:2].copy(),
-            launch_status=int(meta[n_off + 2 * n_seg + 2 * self._n_refs]), _packed=self._f,
+            launch_status=int(meta[n_off + 2 * n_seg + 2 * self._n_refs]),
+            support_in=int(meta[n_off + 2 * n_seg + 2 * self._n_refs + 2:].view(np.int64)[0]) if self.filtered else None, _packed=self._f,
             _cap=max(self.capacity, 1))
 
 
@@ -698,6 +707,55 @@ def _cycle_gate_call(fn, ctx, cert, warp_ab, warp_ba, w_match, h_match, certaint
             ay.data_ptr() if ay is not None else None, int(w_match), int(h_match), float(certainty_thresh), float(cycle_thresh_px), table(outs),
             table(errs) if errs is not None else None, rejected.data_ptr() if rejected is not None else None)
     return rc, outs, errs
+
+
+def _support_filter_call(fn, ctx, batch, src, min_support, support_thresh_px, with_support, into, device):
+    """One lfd_support_filter[_host] call.  ``src``: the OutputBuffers a triangulation launch wrote for ``batch`` (asynchronous: the result is
+    another OutputBuffers - ``into``, or a new one - whose small integer outputs are the source's with the offsets and counts replaced), or a
+    collected TriangulationOutput (the result is collected as well).  Returns (rc, result or None, support or None)."""
+    if not isinstance(min_support, (int, np.integer)) or isinstance(min_support, bool):
+        raise ValueError("support_filter: min_support must be an integer")
+    collected = isinstance(src, TriangulationOutput)
+    if src.cell is None or src.slot is None:
+        raise ValueError("support_filter: the source buffers need the cell / slot outputs (with_cell=True)")
+    if collected:
+        n = int(src.xyz.shape[0])
+        keep = [src.xyz.contiguous(), src.rgb.contiguous(), src.err.contiguous(), src.cell.contiguous(), src.slot.contiguous()]
+        if n == 0:                            # (an empty tensor may have no address at all; the library wants its arrays)
+            keep = [torch.zeros((1, 3) if t.dim() == 2 else (1,), dtype=t.dtype, device=t.device) for t in keep]
+        if any(t.device != device for t in keep):
+            raise ValueError(f"support_filter: the points live on {keep[0].device}, this context computes on {device}")
+        offs_in = torch.from_numpy(np.ascontiguousarray(src.ref_offsets, np.int64)).to(device)
+        pts_in = lfd_points(xyz=keep[0].data_ptr(), rgb=keep[1].data_ptr(), err=keep[2].data_ptr(), cell=keep[3].data_ptr(), slot=keep[4].data_ptr(),
+                            capacity=n)
+        n_refs, k, cap = int(len(src.ref_offsets)) - 1, int(src.seg_counts.shape[1]), n
+    else:
+        if src.xyz.device != device:
+            raise ValueError(f"support_filter: the points live on {src.xyz.device}, this context computes on {device}")
+        keep, offs_in, pts_in, n_refs, k, cap = [], src.ref_offsets, src.c, src._n_refs, src._k, src.capacity
+    if n_refs != batch.n_refs or k != batch.k:
+        raise ValueError(f"support_filter: the points were made for {n_refs} references x {k} slots, the batch has {batch.n_refs} x {batch.k}")
+    dst = into if into is not None else OutputBuffers(cap, n_refs, k, device, True, True if collected else src.with_segments)
+    if dst.capacity < cap or dst._n_refs != n_refs or dst._k != k or dst.xyz.device != device:
+        raise ValueError("support_filter: `into` must have the source's capacity, references and slots, on this context's device")
+    if not collected:
+        dst._meta.copy_(src._meta)            # group order, selection and launch status travel with the points
+        dst.support_in.copy_(src.ref_offsets[-1:])
+        dst.filtered = True
+    support = torch.empty((max(cap, 1),), dtype=torch.uint8, device=device) if with_support else None
+    rc = fn(ctx, C.byref(batch.c), C.byref(pts_in), offs_in.data_ptr(), int(min_support), C.c_float(float(support_thresh_px)), C.byref(dst.c),
+            dst.ref_offsets.data_ptr(), dst.seg_counts.data_ptr() if dst.with_segments else None, support.data_ptr() if with_support else None)
+    if rc != 0:
+        return rc, None, None
+    if with_support:
+        support = support[:cap]
+    if not collected:
+        return rc, dst, support
+    res = dst.collect()
+    res.support_in = n
+    res.seg_order = None
+    res.n_selected, res.sel_status, res.launch_status = src.n_selected, src.sel_status, src.launch_status
+    return rc, res, support
 
 
 class HipDensifier:
@@ -867,6 +925,20 @@ class HipDensifier:
                                           cycle_thresh_px, axes, inplace, with_err, rejected, self.device)
         self._check(rc, "lfd_cycle_gate")
         return outs, errs
+
+    def support_filter(self, batch: PreparedBatch, out_buffers, min_support: int, support_thresh_px: float, with_support: bool = False,
+                       into: Optional[OutputBuffers] = None):
+        """Multi-view support filter behind a triangulation call (lfd_support_filter): of the points ``out_buffers`` holds for
+        ``batch`` (an OutputBuffers a launch wrote, or a collected TriangulationOutput; with_cell=True), those that at least ``min_support``
+        OTHER neighbours of their reference confirm within ``support_thresh_px`` (px of the neighbour's camera image), compacted in order.
+        Returns buffers of the same kind (asynchronous on the context's stream for OutputBuffers; ``into``: the buffers to fill instead of new
+        ones); with ``with_support`` a pair (result, uint8 support count of every INPUT point)."""
+        self._same_device(batch)
+        with torch.cuda.stream(self.stream):
+            rc, res, support = _support_filter_call(self._lib.lfd_support_filter, self._ctx, batch, out_buffers, min_support, support_thresh_px,
+                                                    with_support, into, self.device)
+        self._check(rc, "lfd_support_filter")
+        return (res, support) if with_support else res
 
     def quantise_rgb(self, rgb: torch.Tensor) -> torch.Tensor:
         rgb = self._pts(rgb, 3, "rgb")
@@ -1193,6 +1265,15 @@ class HostDensifier:
                                           cycle_thresh_px, axes, inplace, with_err, rejected, self.device)
         self._check(rc, "lfd_cycle_gate_host")
         return outs, errs
+
+    def support_filter(self, batch: PreparedBatch, out_buffers, min_support: int, support_thresh_px: float, with_support: bool = False,
+                       into: Optional[OutputBuffers] = None):
+        """HipDensifier.support_filter over CPU tensors (lfd_support_filter_host): the same per-(point, slot) routine, the same bits in every output."""
+        self._same_device(batch)
+        rc, res, support = _support_filter_call(self._lib.lfd_support_filter_host, self._ctx, batch, out_buffers, min_support, support_thresh_px,
+                                                with_support, into, self.device)
+        self._check(rc, "lfd_support_filter_host")
+        return (res, support) if with_support else res
 
     def aggregate(self, batch: PreparedBatch, params: lfd_params):
         self._same_device(batch)

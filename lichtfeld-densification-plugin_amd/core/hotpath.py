@@ -70,6 +70,10 @@ class HotPath:
         self._cycle_counter: Optional[torch.Tensor] = None      # int32 [LFD_MAX_SLOTS] where the kernels run: rejected cells per slot, added to
         self._cycle_pending = 0                                 # cells per slot gated since the counter was last read (it must not wrap)
         self.cycle_cells = self.cycle_rejected = 0
+        self.min_support = int(config.exp("min_support_views"))
+        self.support_thresh_px = float(config.support_threshold())
+        self.support_in = self.support_kept = 0                 # points that reached the filter / that it kept, over the results the run used
+        self._support_void = False                              # a grouped call failed as a whole: what is collected until the next launch is dropped
 
     # -- forward-backward consistency filter (lfd_cycle_gate) -------------------------------------------------------------------
     def cycle_gate(self, warps, certs, backs, axes) -> None:
@@ -98,6 +102,41 @@ class HotPath:
         """(cells gated, cells rejected) of the run so far: the one read of the device counters."""
         self._cycle_flush()
         return self.cycle_cells, self.cycle_rejected
+
+    # -- multi-view support filter (lfd_support_filter, DESIGN.md 4.8) --------------------------------------------------------------------------
+    def support_filter_collected(self, batch: hb.PreparedBatch, res: hb.TriangulationOutput) -> hb.TriangulationOutput:
+        """A collected result through the filter (the synchronous schedules, the host backend)."""
+        if self.min_support <= 0 or res is None:
+            return res
+        self._support_void = False
+        with self.clock.stage("kernel"):
+            out = self.dens.support_filter(batch, res, self.min_support, self.support_thresh_px)
+        self._support_count(out)
+        return out
+
+    def _support_count(self, res: hb.TriangulationOutput) -> None:
+        """The run's totals, from the integers a result brings along anyway (no read-back of their own)."""
+        if res is not None and res.support_in is not None and not self._support_void:
+            self.support_in += int(res.support_in)
+            self.support_kept += int(res.count)
+
+    def support_totals(self) -> Tuple[int, int]:
+        """(points that reached the filter, points it dropped) of the run so far."""
+        return self.support_in, self.support_in - self.support_kept
+
+    def _filtered(self, batch: hb.PreparedBatch, out: hb.OutputBuffers) -> hb.OutputBuffers:
+        """``out`` as the launch left it, or - with the filter on - the buffers the filter compacts it into: one launch behind the one that
+        filled ``out``, on the same stream, before anything is read back (``out`` goes back to the pool: whatever uses it next follows in the
+        same stream).  Destination buffers are recycled among themselves: ``collect`` reports the points that went in only for them."""
+        if self.min_support <= 0:
+            return out
+        self._support_void = False             # (a new launch: whatever a failed grouped call left behind has been dealt with)
+        into = self._take_buffers(out.capacity, out._n_refs, out._k, filtered=True)
+        try:
+            self.dens.support_filter(batch, out, self.min_support, self.support_thresh_px, into=into)
+        finally:
+            self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, False), []).append(out)
+        return into
 
     def close(self) -> None:
         self._prepared.clear()
@@ -194,6 +233,7 @@ class HotPath:
             try:
                 with self.clock.stage("kernel"):
                     out = self.dens.triangulate_sampled(batch, self.params, self.config.matches_per_ref, cap=self.sample_cap, border=2, tiles=24)
+                out = self.support_filter_collected(batch, out)
                 return (out if out.count else None), None
             except hb.SelectionInexact:
                 pass         # weights below 2^-29 (certainty_thresh ~ 0): the host stage below, on the device's RNG stream
@@ -204,6 +244,7 @@ class HotPath:
             return None, best[0]
         with self.clock.stage("kernel"):
             out = self.dens.triangulate_indexed(batch, self.params, sel_t, [0, int(sel_t.numel())])
+        out = self.support_filter_collected(batch, out)
         return (out if out.count else None), best[0]
 
     def _select(self, best: torch.Tensor, rng, device_seed: Optional[int], on_device: bool, torch_sum: bool) -> torch.Tensor:
@@ -261,14 +302,15 @@ class HotPath:
         with self.clock.stage("kernel"):
             out = self._take_buffers(int(M) + 24 * 24 + 64, 1, batch.k)
             self.dens.launch_sampled(batch, self.params, M, out, cap=self.sample_cap, border=2, tiles=24, s_override=float(s_override))
+            out = self._filtered(batch, out)
             out.begin_collect(self.dens.stream)
         return batch, out
 
-    def _take_buffers(self, capacity: int, n_refs: int, k: int) -> hb.OutputBuffers:
+    def _take_buffers(self, capacity: int, n_refs: int, k: int, filtered: bool = False) -> hb.OutputBuffers:
         """Survivor buffers of the fused sampled calls, recycled: a fresh OutputBuffers costs two device allocations and - on its first
         read-back - a pinned host allocation (hipHostMalloc: milliseconds), per reference; ``finish_sampled`` hands a buffer back once the
         reference's survivors have been copied out of it."""
-        free = self._buf_pool.setdefault((int(capacity), int(n_refs), int(k)), [])
+        free = self._buf_pool.setdefault((int(capacity), int(n_refs), int(k), bool(filtered)), [])
         return free.pop() if free else hb.OutputBuffers(int(capacity), int(n_refs), int(k), self.dev)
 
     # -- upstream's normaliser without stalling the launch stream ---------------------------------------------------------------
@@ -349,6 +391,7 @@ class HotPath:
         with self.clock.stage("kernel"):
             out = self._take_buffers(len(refs) * (int(M) + 24 * 24 + 64), len(refs), batch.k)
             self.dens.launch_sampled_multi(batch, self.params, M, out, seeds, cap=self.sample_cap, border=2, tiles=24)
+            out = self._filtered(batch, out)
             out.begin_collect(self.dens.stream)
         return batch, out
 
@@ -396,6 +439,7 @@ class HotPath:
         self.dens.checkpoint_rng(place)
 
     def rollback_rng(self, place: int) -> None:
+        self._support_void = False             # (the failed grouped call and what was launched behind it have been collected and dropped)
         self.dens.rollback_rng(place)
 
     def launch_sampled_chain(self, batch: hb.PreparedBatch, s_overrides: Optional[List[float]]):
@@ -403,6 +447,7 @@ class HotPath:
         with self.clock.stage("kernel"):
             out = self._take_buffers(batch.n_refs * (int(M) + 24 * 24 + 64), batch.n_refs, batch.k)
             self.dens.launch_sampled_chain(batch, self.params, M, out, s_overrides=s_overrides, cap=self.sample_cap, border=2, tiles=24)
+            out = self._filtered(batch, out)
             out.begin_collect(self.dens.stream)
         return batch, out
 
@@ -412,17 +457,24 @@ class HotPath:
         reference's error, not the group's)."""
         _batch, out = handle
         try:
-            with self.clock.stage("d2h"):          # the counts: whatever the device still had to do for this reference shows here
-                res = out.collect(indexed=True, check_selection=check_selection)
-            if res.launch_status != 0:
-                self.dens.check_launches()
+            try:
+                with self.clock.stage("d2h"):          # the counts: whatever the device still had to do for this reference shows here
+                    res = out.collect(indexed=True, check_selection=check_selection)
+                if res.launch_status != 0:
+                    self.dens.check_launches()
+            except Exception:
+                self._support_void = True              # (the caller redoes the call, and drops what was launched behind it)
+                raise
+            if not check_selection and any(int(st) in hb.SELECT_VOIDS_STREAM for st in res.sel_status):
+                self._support_void = True              # (a chained call that is void as a whole: core/strategies.py::SampledLoop._recover)
+            self._support_count(res)
             if not res.count and check_selection:
                 return None
             return dataclasses.replace(res, xyz=res.xyz.clone(), rgb=res.rgb.clone(), err=res.err.clone(),
                                        cell=res.cell.clone() if res.cell is not None else None,
                                        slot=res.slot.clone() if res.slot is not None else None, _packed=None)
         finally:
-            self._buf_pool.setdefault((out.capacity, out._n_refs, out._k), []).append(out)
+            self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, bool(out.filtered)), []).append(out)
 
     def pack_ply_tensor(self, xyz: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
         """The same records as a uint8 tensor that stays where the points are (what a sharded run sends to the writer rank)."""
@@ -443,7 +495,19 @@ class HotPath:
             if bool(self.config.exp("dense_tile_segments")):
                 # unordered retirement (no look-back), raster order restored from the tile table: the same result, bit for bit
                 return self.dens.order_segments(self.dens.triangulate_dense_segments(batch, self.params))
-            return self.dens.triangulate_dense(batch, self.params)
+            if self.min_support > 0 and not self.on_host:
+                # the launch, the filter behind it on the same stream, then the one read-back of the offsets
+                cap = batch.n_refs * batch.H * batch.W
+                out = hb.OutputBuffers(cap, batch.n_refs, batch.k, self.dev)
+                self.dens.launch_dense(batch, self.params, out)
+                out = self.dens.support_filter(batch, out, self.min_support, self.support_thresh_px)
+                self.dens.check_launches()
+                res = out.collect()
+                self._support_void = False
+                self._support_count(res)
+                return res
+            res = self.dens.triangulate_dense(batch, self.params)
+        return self.support_filter_collected(batch, res)
 
     def launch_dense_ply(self, refs: List[hb.ReferenceInputs], axes, records: torch.Tensor, ref_offsets: torch.Tensor,
                          table: Optional[torch.Tensor] = None) -> hb.PreparedBatch:

@@ -256,6 +256,10 @@ def run_dense_pipeline(
         if hot.cycle_thresh_px > 0.0:
             cells, rejected = hot.cycle_totals()
             log.info(f"Forward-backward filter: threshold {hot.cycle_thresh_px:g} px, {cells} cells, {100.0 * rejected / max(1, cells):.2f} % rejected")
+        if hot.min_support > 0:
+            n_in, n_dropped = hot.support_totals()
+            log.info(f"Multi-view support filter: threshold {hot.support_thresh_px:g} px, at least {hot.min_support} other view(s), {n_in} points in, "
+                     f"{n_dropped} dropped")
     except BaseException as exc:
         if world == 1:
             raise

@@ -323,8 +323,8 @@ class DenseBatcher:
             self.drain()                  # one launch, one grid
         self.pending.append(m)
         n = int(self.config.refs_per_launch)
-        if self.auto_group:               # 33 bytes per cell: xyz, rgb, err + the cell and slot columns of the C-ABI
-            n = bounded_group(n, m.H * m.W, 33, 0)
+        if self.auto_group:               # 33 bytes per cell: xyz, rgb, err + the cell and slot columns of the C-ABI (twice with the support filter's copy)
+            n = bounded_group(n, m.H * m.W, 66 if int(self.config.exp("min_support_views")) > 0 else 33, 0)
         if len(self.pending) >= n:
             self.drain()
 

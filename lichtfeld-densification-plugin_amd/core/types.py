@@ -49,6 +49,13 @@ EXPERIMENTAL_DEFAULTS = {
     # its start by more than this many pixels of the match image loses the pair (certainty exactly 0, as if mask_b had masked it out).
     # 0.0 = off: the backward warp is not asked for and no new code runs.  Needs a matcher that hands out warp_BA (supports_backward_warp).
     "cycle_thresh_px": 0.0,
+    # multi-view support filter behind triangulation (lfd_support_filter): a triangulated point is kept only if at least this many
+    # OTHER loaded neighbours of its reference - the ones the arg-max did not pick - see it where their own warp says the cell is.
+    # 0 = off: no new code runs.  At most nns_per_ref - 1; a reference that loaded fewer than min_support_views + 1 neighbours keeps no point.
+    "min_support_views": 0,
+    # ... within this many pixels of the neighbour's camera image (the unit of reproj_thresh).  0.0 = 2 * reproj_thresh: the residual in a third
+    # view carries that view's own matching noise plus the depth error of the two-view point.
+    "support_thresh_px": 0.0,
 }
 
 
@@ -126,6 +133,11 @@ class DensePipelineConfig:
         """The value of an experimental knob (EXPERIMENTAL_DEFAULTS lists them)."""
         return self.experimental.get(key, EXPERIMENTAL_DEFAULTS[key])
 
+    def support_threshold(self) -> float:
+        """Threshold of the multi-view support filter in px of the neighbour's camera image (experimental['support_thresh_px'], 0 = 2 * reproj_thresh)."""
+        tau = float(self.exp("support_thresh_px"))
+        return tau if tau > 0.0 else 2.0 * float(self.reproj_thresh)
+
     def exchange_record_format(self) -> str:
         rec = str(self.exp("exchange_records"))
         if rec == "auto":
@@ -179,6 +191,28 @@ class DensePipelineConfig:
         if not (0.0 <= tau < float("inf")):
             return "experimental['cycle_thresh_px'] must be finite and >= 0 (px of the match image; 0 = off)"
         dense = self.triangulation_mode == "dense"
+        m_sup = self.exp("min_support_views")
+        if isinstance(m_sup, bool) or not isinstance(m_sup, (int, np.integer)) or int(m_sup) < 0:
+            return "experimental['min_support_views'] must be a non-negative integer (other neighbours that have to confirm a point; 0 = off)"
+        try:
+            tau_sup = float(self.exp("support_thresh_px"))
+        except (TypeError, ValueError):
+            return "experimental['support_thresh_px'] must be a number (px of the neighbour's camera image; 0 = 2 * reproj_thresh)"
+        if not (0.0 <= tau_sup < float("inf")):
+            return "experimental['support_thresh_px'] must be finite and >= 0 (px of the neighbour's camera image; 0 = 2 * reproj_thresh)"
+        if int(m_sup) > 0:
+            if int(m_sup) > int(self.nns_per_ref) - 1:
+                return (f"experimental['min_support_views'] = {int(m_sup)} asks for more confirming neighbours than a reference has beside the one "
+                        f"that made the point (nns_per_ref - 1 = {int(self.nns_per_ref) - 1})")
+            if not (self.support_threshold() > 0.0):
+                return "experimental['min_support_views'] needs a threshold: experimental['support_thresh_px'] or, for its default, reproj_thresh must be > 0"
+            if dense and self.stream_output:
+                return ("experimental['min_support_views'] filters points held as arrays (xyz, cell, slot); dense mode with stream_output has the "
+                        "kernel write PLY records instead")
+            if self.exp("dense_tile_segments"):
+                return "experimental['min_support_views'] needs the ordered dense result; experimental['dense_tile_segments'] retires tiles unordered"
+            if self.exchange_record_format() == "ply":
+                return "experimental['min_support_views'] filters f32 rows; experimental['exchange_records'] must be 'f32' with it"
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):
                 return "stream_output writes a PLY while the run proceeds: output_path must end in .ply"

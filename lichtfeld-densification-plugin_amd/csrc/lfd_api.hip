@@ -16,6 +16,7 @@
 #include "lfd_context.hpp"
 #include "lfd_corr.hpp"
 #include "lfd_cycle.hpp"
+#include "lfd_support.hpp"
 
 extern "C" __global__ void lfd_aggregate_kernel(LfdLaunch L, float* best_cert, uint8_t* best_slot);
 extern "C" __global__ void lfd_dense_kernel(LfdLaunch L);
@@ -60,6 +61,7 @@ extern "C" __global__ void lfd_voxel_sums_big_kernel(const float* xyz, const flo
                                                      float* rgb_out);
 hipError_t lfd_corr_launch(const LfdCorrArgs& p, hipStream_t stream);     // lfd_corr.hip
 hipError_t lfd_cycle_launch(const LfdCycleArgs& p, hipStream_t stream);   // lfd_cycle.hip
+hipError_t lfd_support_launch(const LfdSupportArgs& p, hipStream_t stream);   // lfd_support.hip
 extern "C" __global__ void lfd_select_topm_kernel(LfdSelectArgs A);
 extern "C" __global__ void lfd_select_filter_mw_kernel(LfdSelectArgs A, LfdSelectNorms norms);
 extern "C" __global__ void lfd_select_begins_kernel(long long* pairs, long long stride, int n);
@@ -534,7 +536,7 @@ void lfd_destroy(lfd_context* ctx) {
     }
     for (hipEvent_t ev : ctx->kt_start) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->kt_stop) (void)hipEventDestroy(ev);
-    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->vox})
+    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->vox, &ctx->support_ws})
         if (b->ptr) (void)hipFree(b->ptr);
     if (ctx->pinned_words) (void)hipHostFree(ctx->pinned_words);
     delete ctx;
@@ -1433,6 +1435,43 @@ int lfd_cycle_gate(lfd_context* ctx, int32_t n_pairs, const float* const* cert, 
         return fail(ctx, LFD_ERR_INVALID, std::string("lfd_cycle_gate: ") + why);
     LFD_HIP(ctx, hipSetDevice(ctx->device));
     LFD_HIP(ctx, lfd_cycle_launch(p, ctx->stream));
+    return LFD_OK;
+}
+
+// ---- multi-view support filter (lfd_support.hip) -------------------------------------------------------------------------------------------
+int lfd_support_filter(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets_in, int32_t min_support,
+                       float support_thresh_px, const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out, uint8_t* support) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    int code = LFD_ERR_INVALID;
+    if (const char* why = lfd_support_check(in, ref_offsets_in, min_support, support_thresh_px, out, ref_offsets_out, &code))
+        return fail(ctx, code, std::string("lfd_support_filter: ") + why);
+    // the batch's tables and per-pair constants, derived again only when the batch differs from the last one seen (no threshold reaches them)
+    lfd_params none;
+    std::memset(&none, 0, sizeof(none));
+    LfdLaunch L;
+    int rc = prepare_launch(ctx, batch, &none, nullptr, 0, L, nullptr);
+    if (rc != LFD_OK) return rc;
+    LfdSupportArgs p;
+    std::memset(&p, 0, sizeof(p));
+    p.n_wg = (int32_t)((in->capacity + 255) / 256);
+    const size_t counts_bytes = ((size_t)p.n_wg * 256 + 255) & ~size_t(255);
+    rc = ensure(ctx, ctx->support_ws, counts_bytes + ((size_t)p.n_wg + 1) * sizeof(unsigned));
+    if (rc != LFD_OK) return rc;
+    p.refs = L.refs; p.slots = L.slots; p.pair_const = L.pair_const;
+    p.offs_in = reinterpret_cast<const long long*>(ref_offsets_in);
+    p.xyz = in->xyz; p.rgb = in->rgb; p.err = in->err; p.cell = in->cell; p.slot = in->slot;
+    p.o_xyz = out->xyz; p.o_rgb = out->rgb; p.o_err = out->err; p.o_cell = out->cell; p.o_slot = out->slot;
+    p.offs_out = reinterpret_cast<long long*>(ref_offsets_out);
+    p.seg_counts = seg_counts_out; p.support = support;
+    p.counts = static_cast<uint8_t*>(ctx->support_ws.ptr);
+    p.wg_kept = reinterpret_cast<unsigned*>(static_cast<unsigned char*>(ctx->support_ws.ptr) + counts_bytes);
+    p.capacity = in->capacity;
+    p.n_refs = batch->n_refs; p.k = batch->k; p.H = batch->H; p.W = batch->W; p.C = batch->warp_channels;
+    p.w_match = batch->w_match; p.h_match = batch->h_match; p.min_support = min_support;
+    p.wm1 = L.kp.wm1; p.hm1 = L.kp.hm1; p.mask_sx = L.mask_sx; p.mask_sy = L.mask_sy; p.tau = support_thresh_px;
+    if (seg_counts_out) LFD_HIP(ctx, hipMemsetAsync(seg_counts_out, 0, sizeof(int32_t) * (size_t)batch->n_refs * batch->k, ctx->stream));
+    LFD_HIP(ctx, lfd_support_launch(p, ctx->stream));
     return LFD_OK;
 }
 

@@ -92,6 +92,7 @@ struct lfd_context {
     DeviceBuffer stamps;           // profiling builds: phase stamps of the dense kernel
     DeviceBuffer seg_scan;         // tile segments: exclusive prefix of the last table handed to lfd_order_segments / lfd_pack_*_segments
     DeviceBuffer vox;              // lfd_voxel_downsample: statistics, digit counts, keys / indices (x 2), voxel starts; grown on demand
+    DeviceBuffer support_ws;       // lfd_support_filter: support count of every input point, kept points per workgroup; grown on demand
     // N3 image preparation: coefficient / index tables of the last size pair
     DeviceBuffer img_tab, msk_tab;
     int img_key[4] = {0, 0, 0, 0}, img_ks[2] = {0, 0};

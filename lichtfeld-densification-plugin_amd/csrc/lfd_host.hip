@@ -19,6 +19,7 @@
 #include "lfd_context.hpp"
 #include "lfd_corr.hpp"
 #include "lfd_cycle.hpp"
+#include "lfd_support.hpp"
 
 void lfd_fill_kernel_params(const lfd_batch* b, const lfd_params* p, LfdKernelParams& kp);   // lfd_api.hip
 
@@ -314,6 +315,73 @@ int lfd_cycle_gate_host(lfd_context* ctx, int32_t n_pairs, const float* const* c
     });
     if (rejected)
         for (int c = 0; c < n_pairs * chunks_per_pair; ++c) rejected[c / chunks_per_pair] += counts[(size_t)c];
+    return LFD_OK;
+}
+
+int lfd_support_filter_host(lfd_context* ctx, const lfd_batch* b, const lfd_points* in, const int64_t* ref_offsets_in, int32_t min_support,
+                            float support_thresh_px, const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out, uint8_t* support) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    int code = LFD_ERR_INVALID;
+    if (const char* why = lfd_support_check(in, ref_offsets_in, min_support, support_thresh_px, out, ref_offsets_out, &code))
+        return lfd_fail(ctx, code, std::string("lfd_support_filter_host: ") + why);
+    lfd_params none;
+    std::memset(&none, 0, sizeof(none));
+    int rc = validate_host(ctx, b, &none);
+    if (rc != LFD_OK) return rc;
+    HostLaunch L;
+    prepare_host(b, &none, L);
+    std::vector<HostRef> refs((size_t)b->n_refs);
+    for (int r = 0; r < b->n_refs; ++r) make_ref(ctx, L, r, refs[(size_t)r]);
+    const long long cap = in->capacity;
+    const long long* offs = reinterpret_cast<const long long*>(ref_offsets_in);
+    const long long total = lfd_support_clamp(offs[b->n_refs], cap);
+    std::vector<uint8_t> counts((size_t)total);
+    parallel_chunks(ctx, (int)((total + kChunk - 1) / kChunk), [&](int c) {
+        const long long i1 = std::min<long long>(total, (long long)(c + 1) * kChunk);
+        for (long long i = (long long)c * kChunk; i < i1; ++i) {
+            const int r = lfd_support_ref_of(offs, b->n_refs, cap, i);
+            const int cell = in->cell[i], s = (int)in->slot[i];
+            int n = 0;
+            if (cell >= 0 && cell < L.HW) {                             // no address is formed from a cell outside the grid
+                const float X0 = in->xyz[3 * i], X1 = in->xyz[3 * i + 1], X2 = in->xyz[3 * i + 2];
+                for (int j = 0; j < b->n_slots[r]; ++j) {
+                    if (j == s) continue;
+                    const size_t sj = (size_t)r * b->k + j;
+                    const float* wv = b->warp[sj] + (size_t)cell * b->warp_channels + (b->warp_channels - 2);
+                    bool live = lfd_support_live(b->cert[sj][cell]);
+                    const uint8_t* mb = b->mask_b ? b->mask_b[sj] : nullptr;
+                    if (live && mb) {
+                        const long long m = lfd_support_mask_index(wv[0], wv[1], b->W, b->H, L.mask_sx, L.mask_sy, b->w_match, b->h_match);
+                        live = m >= 0 && mb[m] != 0;
+                    }
+                    const LfdPairConst& pc = refs[(size_t)r].pc[j];
+                    const bool agree = lfd_support_agree(pc.P, pc.sx, pc.sy, X0, X1, X2, wv[0], wv[1], L.kp.wm1, L.kp.hm1, support_thresh_px);
+                    n += (live && agree) ? 1 : 0;
+                }
+            }
+            counts[(size_t)i] = (uint8_t)n;
+            if (support) support[i] = (uint8_t)n;
+        }
+    });
+    // stable compaction: the input order inside and across references
+    if (seg_counts_out) std::memset(seg_counts_out, 0, sizeof(int32_t) * (size_t)b->n_refs * b->k);
+    long long o = 0;
+    int r_next = 0;
+    for (long long i = 0; i <= total; ++i) {
+        while (r_next <= b->n_refs && std::min(lfd_support_clamp(offs[r_next], cap), total) <= i) ref_offsets_out[r_next++] = o;
+        if (i == total || (int)counts[(size_t)i] < min_support) continue;
+        for (int e = 0; e < 3; ++e) { out->xyz[3 * o + e] = in->xyz[3 * i + e]; out->rgb[3 * o + e] = in->rgb[3 * i + e]; }
+        out->err[o] = in->err[i];
+        if (out->cell) out->cell[o] = in->cell[i];
+        if (out->slot) out->slot[o] = in->slot[i];
+        if (seg_counts_out) {
+            const int r = lfd_support_ref_of(offs, b->n_refs, cap, i), s = (int)in->slot[i];
+            if (s < b->n_slots[r]) seg_counts_out[(size_t)r * b->k + s] += 1;
+        }
+        ++o;
+    }
+    while (r_next <= b->n_refs) ref_offsets_out[r_next++] = o;       // (offsets that do not ascend: whatever is left counts from the end)
     return LFD_OK;
 }
 

@@ -1,0 +1,210 @@
+// Multi-view support filter on the device (lfd_support_filter): every triangulated point is checked against the OTHER neighbours of
+// its reference and the points that at least min_support of them confirm are compacted in order.
+//
+// Gather-bound: per input point 17 B of its own fields and 12 B (certainty 4, warp pair 8) per other neighbour, 28-33 B per survivor moved.
+// Three launches, nothing waits for another workgroup:
+//
+//   lfd_support_count_kernel<KMAX>   a lane per input point: support count (one byte per point) and the kept points of the workgroup;
+//                                    per (reference, winning slot) counters through LDS, then one integer atomic per workgroup and slot
+//   lfd_support_scan_kernel          one workgroup: exclusive prefix of the workgroups' counts, then ref_offsets_out from it
+//   lfd_support_scatter_kernel       a lane per input point: rank inside the wave by ballot / mbcnt, inside the workgroup by wave sums, copy
+//
+// A point's reference comes from ref_offsets_in (device data: the host does not know the totals); the grid covers in->capacity and the
+// workgroups past the total retire at once.  The constants of the reference a workgroup works on (other neighbours' plane pointers, projection
+// rows, pixel scales) are staged in LDS; a workgroup whose points straddle references takes them one after the other.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "lfd_device.hpp"
+#include "lfd_support.hpp"
+
+namespace {
+
+struct SupportSlot {             // one other neighbour of the reference at work, in LDS
+    const float* cert;
+    const float* warp;
+    const uint8_t* mask_b;
+    float P[12];
+    float sx, sy;
+};
+
+}  // namespace
+
+template <int KMAX>
+__global__ void __launch_bounds__(256) lfd_support_count_kernel(const LfdSupportArgs p) {
+    __shared__ SupportSlot sh[KMAX];
+    __shared__ unsigned sh_seg[KMAX];
+    __shared__ int sh_ref[2];
+    __shared__ unsigned sh_kept;
+    const int tid = (int)threadIdx.x;
+    const long long total = lfd_support_clamp(p.offs_in[p.n_refs], p.capacity);
+    const long long base = (long long)blockIdx.x * 256;
+    if (base >= total) {                                               // the whole workgroup lies past the last point
+        if (tid == 0) p.wg_kept[blockIdx.x] = 0u;
+        return;
+    }
+    const long long i = base + tid;
+    const bool mine = i < total;
+    const long long last = (base + 256 < total ? base + 256 : total) - 1;
+    const long long ii = mine ? i : last;                              // idle lanes read the last point and store nothing
+    const int cell = p.cell[ii];
+    const int s = (int)p.slot[ii];
+    const float X0 = p.xyz[3 * ii], X1 = p.xyz[3 * ii + 1], X2 = p.xyz[3 * ii + 2];
+    const int r = lfd_support_ref_of(p.offs_in, p.n_refs, p.capacity, ii);
+    if (tid == 0) { sh_ref[0] = r; sh_kept = 0u; }
+    if (i == last) sh_ref[1] = r;
+    __syncthreads();
+    const int r_first = sh_ref[0], r_last = sh_ref[1];
+    const long long HW = (long long)p.H * p.W;
+    const bool cell_ok = cell >= 0 && (long long)cell < HW;            // no address is formed from a cell outside the grid
+    const LfdRefDesc* refs = static_cast<const LfdRefDesc*>(p.refs);
+    const LfdSlotDesc* slots = static_cast<const LfdSlotDesc*>(p.slots);
+    int support = 0;
+    for (int rr = r_first; rr <= r_last; ++rr) {
+        if (lfd_support_clamp(p.offs_in[rr + 1], p.capacity) <= lfd_support_clamp(p.offs_in[rr], p.capacity)) continue;   // uniform: no points
+        int ns = refs[rr].n_slots;
+        ns = ns < KMAX ? ns : KMAX;
+        if (tid < KMAX) {
+            sh_seg[tid] = 0u;
+            if (tid < ns) {
+                const LfdSlotDesc& d = slots[(size_t)rr * p.k + tid];
+                const LfdPairConst& c = p.pair_const[(size_t)rr * p.k + tid];
+                SupportSlot& o = sh[tid];
+                o.cert = d.cert; o.warp = d.warp; o.mask_b = d.mask_b;
+#pragma unroll
+                for (int e = 0; e < 12; ++e) o.P[e] = c.P[e];
+                o.sx = c.sx; o.sy = c.sy;
+            }
+        }
+        __syncthreads();
+        const bool here = mine && r == rr;
+        if (here && cell_ok) {
+            // all gathers of the point first, then the arithmetic
+            float c[KMAX];
+            float2 w[KMAX];
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j) {
+                c[j] = 0.0f; w[j] = make_float2(0.0f, 0.0f);
+                if (j < ns && j != s) {
+                    c[j] = sh[j].cert[cell];
+                    w[j] = *reinterpret_cast<const float2*>(sh[j].warp + (size_t)cell * p.C + (p.C - 2));
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j) {
+                if (j < ns && j != s) {
+                    bool live = lfd_support_live(c[j]);
+                    const uint8_t* mb = sh[j].mask_b;
+                    if (live && mb) {
+                        const long long m = lfd_support_mask_index(w[j].x, w[j].y, p.W, p.H, p.mask_sx, p.mask_sy, p.w_match, p.h_match);
+                        live = m >= 0 && mb[m] != 0;
+                    }
+                    const bool agree = lfd_support_agree(sh[j].P, sh[j].sx, sh[j].sy, X0, X1, X2, w[j].x, w[j].y, p.wm1, p.hm1, p.tau);
+                    support += (live && agree) ? 1 : 0;
+                }
+            }
+        }
+        if (p.seg_counts) {
+            const bool kept_here = here && support >= p.min_support;
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j) {
+                const unsigned long long m = __ballot(kept_here && s == j);
+                if (m && (tid & 63) == 0) atomicAdd(&sh_seg[j], (unsigned)__popcll(m));
+            }
+        }
+        __syncthreads();
+        if (p.seg_counts && tid < ns && sh_seg[tid]) atomicAdd(p.seg_counts + (size_t)rr * p.k + tid, (int)sh_seg[tid]);
+    }
+    const bool keep = mine && support >= p.min_support;
+    if (mine) {
+        p.counts[i] = (uint8_t)support;
+        if (p.support) p.support[i] = (uint8_t)support;
+    }
+    const unsigned long long km = __ballot(keep);
+    if ((tid & 63) == 0 && km) atomicAdd(&sh_kept, (unsigned)__popcll(km));
+    __syncthreads();
+    if (tid == 0) p.wg_kept[blockIdx.x] = sh_kept;
+}
+
+// exclusive prefix of wg_kept[0 .. n_wg) in place (the total goes to wg_kept[n_wg]), then ref_offsets_out[r] = kept points before
+// ref_offsets_in[r]: the prefix of that point's workgroup plus the kept points in front of it inside the workgroup.  One workgroup.
+__global__ void __launch_bounds__(1024) lfd_support_scan_kernel(const LfdSupportArgs p) {
+    __shared__ unsigned wave_sum[16];
+    unsigned* v = p.wg_kept;
+    const int m = p.n_wg;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int per = (m + 1023) / 1024;
+    const int a = (long long)tid * per < m ? tid * per : m;
+    const int b = a + per < m ? a + per : m;
+    unsigned sum = 0u;
+    for (int i = a; i < b; ++i) sum += v[i];
+    unsigned incl = sum;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned up = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += up;
+    }
+    if (lane == 63) wave_sum[wave] = incl;
+    __syncthreads();
+    unsigned run = incl - sum;
+    for (int w = 0; w < wave; ++w) run += wave_sum[w];
+    if (tid == 1023) v[m] = run + sum;
+    for (int i = a; i < b; ++i) {
+        const unsigned c = v[i];
+        v[i] = run;
+        run += c;
+    }
+    __threadfence_block();
+    __syncthreads();
+    const long long total = lfd_support_clamp(p.offs_in[p.n_refs], p.capacity);
+    for (int r = tid; r <= p.n_refs; r += 1024) {
+        long long at = lfd_support_clamp(p.offs_in[r], p.capacity);
+        at = at > total ? total : at;
+        const long long wg = at >> 8;                                  // <= n_wg; == n_wg only with nothing to walk
+        long long acc = v[wg];
+        for (long long q = wg << 8; q < at; ++q) acc += ((int)p.counts[q] >= p.min_support) ? 1 : 0;
+        p.offs_out[r] = acc;
+    }
+}
+
+__global__ void __launch_bounds__(256) lfd_support_scatter_kernel(const LfdSupportArgs p) {
+    __shared__ unsigned wc[4];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long total = lfd_support_clamp(p.offs_in[p.n_refs], p.capacity);
+    const long long base = (long long)blockIdx.x * 256;
+    if (base >= total) return;
+    const long long i = base + tid;
+    const bool keep = i < total && (int)p.counts[i] >= p.min_support;
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) wc[wave] = (unsigned)__popcll(m);
+    __syncthreads();
+    if (!keep) return;
+    unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+    for (int w = 0; w < wave; ++w) rank += wc[w];
+    const long long o = (long long)p.wg_kept[blockIdx.x] + rank;       // < total <= in->capacity <= out->capacity
+    p.o_xyz[3 * o] = p.xyz[3 * i]; p.o_xyz[3 * o + 1] = p.xyz[3 * i + 1]; p.o_xyz[3 * o + 2] = p.xyz[3 * i + 2];
+    p.o_rgb[3 * o] = p.rgb[3 * i]; p.o_rgb[3 * o + 1] = p.rgb[3 * i + 1]; p.o_rgb[3 * o + 2] = p.rgb[3 * i + 2];
+    p.o_err[o] = p.err[i];
+    if (p.o_cell) p.o_cell[o] = p.cell[i];
+    if (p.o_slot) p.o_slot[o] = p.slot[i];
+}
+
+// lfd_api.hip's lfd_support_filter: the arguments were validated there (capacity <= 2^31 - 1: at most 2^23 workgroups)
+hipError_t lfd_support_launch(const LfdSupportArgs& p, hipStream_t stream) {
+    if (p.n_wg > 0) {
+        const dim3 grid((unsigned)p.n_wg);
+        if (p.k <= 4) hipLaunchKernelGGL(lfd_support_count_kernel<4>, grid, dim3(256), 0, stream, p);
+        else if (p.k <= 8) hipLaunchKernelGGL(lfd_support_count_kernel<8>, grid, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL(lfd_support_count_kernel<LFD_MAX_SLOTS>, grid, dim3(256), 0, stream, p);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(lfd_support_scan_kernel, dim3(1), dim3(1024), 0, stream, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (p.n_wg > 0) {
+        hipLaunchKernelGGL(lfd_support_scatter_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, stream, p);
+        e = hipGetLastError();
+    }
+    return e;
+}

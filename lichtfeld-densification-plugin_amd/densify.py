@@ -273,7 +273,7 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
         triangulation_mode=getattr(args, "triangulation_mode", "sampled"),
         refs_per_launch=getattr(args, "refs_per_launch", 0), backend=getattr(args, "backend", "device"),
         stream_output=bool(getattr(args, "stream_output", False)), device_image_prep=bool(getattr(args, "device_image_prep", False)),
-        experimental={"cycle_thresh_px": float(args.cycle_thresh_px)} if float(getattr(args, "cycle_thresh_px", 0.0)) != 0.0 else {})
+        experimental=_experimental_from_args(args))
     try:
         result = run_dense_pipeline(records, refs_local, nn_table, config, progress_callback=progress_callback,
                                     on_sequential_viz=None, debug_state=debug_state, cancel_requested=cancel_requested, **pipeline_kwargs)
@@ -394,6 +394,18 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
     return 0, config.output_path
 
 
+def _experimental_from_args(args) -> dict:
+    """The experimental knobs the command line reaches; a flag left at its default adds nothing."""
+    exp = {}
+    if float(getattr(args, "cycle_thresh_px", 0.0)) != 0.0:
+        exp["cycle_thresh_px"] = float(args.cycle_thresh_px)
+    if int(getattr(args, "min_support_views", 0)) != 0:
+        exp["min_support_views"] = int(args.min_support_views)
+    if float(getattr(args, "support_thresh_px", 0.0)) != 0.0:
+        exp["support_thresh_px"] = float(args.support_thresh_px)
+    return exp
+
+
 def build_argparser() -> argparse.ArgumentParser:
     """Upstream's CLI flags and defaults (densify.py:318-415) plus the two launch-shape extensions."""
     ap = argparse.ArgumentParser("Dense COLMAP initializer (RoMa v2 matching + fused HIP filter/triangulate on MI355X)")
@@ -428,6 +440,11 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--cycle_thresh_px", type=float, default=0.0,
                     help="forward-backward consistency filter: drop a match whose round trip A -> B -> A misses its start by more than this many "
                          "pixels of the match image (uses RoMa's backward warp; 0 = off)")
+    ap.add_argument("--min_support_views", type=int, default=0,
+                    help="multi-view support filter: keep a triangulated point only if at least this many OTHER loaded neighbours of its reference "
+                         "confirm it (at most nns_per_ref - 1; 0 = off)")
+    ap.add_argument("--support_thresh_px", type=float, default=0.0,
+                    help="... within this many pixels of the neighbour's camera image (0 = 2 * reproj_thresh)")
     ap.add_argument("--keep_threads", action="store_true",
                     help="leave torch's intra-op thread count alone (by default it is lowered to the container's CPU quota; the count decides the last "
                          "bits of upstream's sampling normaliser, so a run compared bit for bit with upstream keeps upstream's setting)")
