@@ -382,6 +382,33 @@ int lfd_support_filter(lfd_context* ctx, const lfd_batch* batch, const lfd_point
 int lfd_support_filter_host(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets_in, int32_t min_support,
                             float support_thresh_px, const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out, uint8_t* support);
 
+/* Multi-view re-triangulation of supported points (no upstream counterpart).  lfd_support_filter uses the other neighbours that agree
+ * with a two-view point for a vote only; here their observations place the point.  `in` / ref_offsets: what a triangulation call (or
+ * lfd_support_filter) wrote for `batch` (in->cell and in->slot required, in->rgb unused; offsets beyond in->capacity count as in->capacity).  Per
+ * input point of reference r with s = slot[i], cell = cell[i], X = xyz[i] (csrc/lfd_refine.hpp, every rounding written out):
+ *   candidates   every slot j != s, j < n_slots[r], that lfd_support_filter would count for X at support_thresh_px (live and agree, the same
+ *                routines: the same set bit for bit); n_extra their number.  n_extra == 0, a cell outside the grid or s >= n_slots[r]: the point is
+ *                copied bit for bit
+ *   rows         per view the DLT rows u p2 - p0, v p2 - p1 in f32 as the triangulation kernels form them; the reference's observation is warp
+ *                channels 0, 1 of slot s (four channels) or the A-grid axes (two), every other view's the last two channels of its own warp
+ *   solve        M = sum row row^T in f64 (one fma chain; reference, slot s, candidates by ascending j), smallest eigenvector by the kernels'
+ *                scheme (LDL^T, inverse iteration, Rayleigh-shifted passes), X' = c[0..2] / c[3] rounded to f32
+ *   acceptance   X' replaces X iff it is finite, the two-view test of the triangulation kernels holds in the reference and in slot s (depth > 0,
+ *                max reprojection error <= reproj_thresh) and every candidate still agrees with X' at support_thresh_px; err' = that max
+ *                reprojection error.  Otherwise (a NaN anywhere included) the two-view point and its err are emitted bit for bit.  The parallax
+ *                test is not repeated.
+ * xyz_out / err_out: exactly in->xyz and in->err (in place: every point is independent) or arrays [3 * capacity] / [capacity] that overlap nothing
+ * of `in`; points beyond the last offset are not touched.  status: NULL, or u8 [capacity]: n_extra | (accepted ? 0x80 : 0) per input point.
+ * counters: NULL, or device i64 [2] that is ADDED to: points refined, points with a candidate that kept their two-view position.  One launch on the
+ * context's stream, asynchronous, deterministic; the batch is prepared as lfd_support_filter prepares it.  LFD_ERR_INVALID: a null required
+ * pointer, missing cell / slot, a threshold that is <= 0 or not finite, partial overlap, in->capacity > 2^31 - 1.  lfd_refine_multiview_host: the
+ * same routine over host pointers on a host context's threads; the candidate sets are the device's bit for bit, X' agrees to the last bits (the
+ * host divides where the device refines a reciprocal). */
+int lfd_refine_multiview(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets, float support_thresh_px,
+                         float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status, int64_t* counters);
+int lfd_refine_multiview_host(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets, float support_thresh_px,
+                              float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status, int64_t* counters);
+
 /* (e) multi-GPU exchange, placement step (no upstream counterpart - upstream has no multi-GPU code): n copies
  * dst[dst_offset .. +nbytes) = src[src_offset .. +nbytes) in ONE launch on `hip_stream` of device `device_index` (offsets and lengths in
  * bytes, no alignment required: 15-byte PLY records).  The overlapped exchange receives every rank's records of a round as one padded block
@@ -447,7 +474,7 @@ int lfd_host_eval_correspondence(const float* cam1, const float* cam2, float xa_
  * The per-cell arithmetic is the host build of the very source the kernels compile (csrc/lfd_geometry.hpp; IEEE
  * division / square root where the device uses the 1-ulp v_rcp / v_sqrt), spread over n_threads std::threads
  * (<= 0: all hardware threads).  A host context accepts lfd_upload_cameras, lfd_last_error, lfd_destroy and the
- * *_host calls (the three below, lfd_local_corr_host, lfd_cycle_gate_host and lfd_support_filter_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
+ * *_host calls (the three below, lfd_local_corr_host, lfd_cycle_gate_host, lfd_support_filter_host and lfd_refine_multiview_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
  * context: neither side ever stands in for the other.  Semantics (orders, counts, optional outputs, LFD_ERR_CAPACITY
  * with valid counts) are those of lfd_aggregate / lfd_triangulate_dense / lfd_triangulate_indexed. */
 int lfd_create_host(int32_t n_threads, lfd_context** out);

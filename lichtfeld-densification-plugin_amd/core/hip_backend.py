@@ -180,6 +180,9 @@ def load_library() -> C.CDLL:
     lib.lfd_support_filter.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_points), C.c_void_p, C.c_int32, C.c_float, C.POINTER(lfd_points),
                                        C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lfd_support_filter_host.argtypes = list(lib.lfd_support_filter.argtypes)
+    lib.lfd_refine_multiview.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_points), C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]
+    lib.lfd_refine_multiview_host.argtypes = list(lib.lfd_refine_multiview.argtypes)
     lib.lfd_copy_segments.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.lfd_launch_status.argtypes = [ctxp, C.POINTER(C.c_int32)]
     lib.lfd_get_pair_fundamental.argtypes = [ctxp, C.c_int32, C.POINTER(C.c_double)]
@@ -214,7 +217,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -758,6 +761,46 @@ def _support_filter_call(fn, ctx, batch, src, min_support, support_thresh_px, wi
     return rc, res, support
 
 
+def _refine_call(fn, ctx, batch, src, support_thresh_px, reproj_thresh, with_status, counters, device):
+    """One lfd_refine_multiview[_host] call.  ``src``: the OutputBuffers a triangulation launch (or the support filter) wrote for ``batch`` -
+    refined IN PLACE, asynchronously, and returned - or a collected TriangulationOutput (the result is a copy with new xyz / err tensors).
+    ``counters``: None, or an int64 [2] tensor on the context's device that is added to.  Returns (rc, result or None, status or None)."""
+    collected = isinstance(src, TriangulationOutput)
+    if src.cell is None or src.slot is None:
+        raise ValueError("refine_multiview: the source buffers need the cell / slot outputs (with_cell=True)")
+    if counters is not None and (counters.dtype != torch.int64 or counters.numel() != 2 or counters.device != device or not counters.is_contiguous()):
+        raise ValueError(f"refine_multiview: counters must be a contiguous int64 tensor of two elements on {device}")
+    if collected:
+        n = int(src.xyz.shape[0])
+        keep = [src.xyz.contiguous(), src.err.contiguous(), src.cell.contiguous(), src.slot.contiguous()]
+        if n == 0:                            # (an empty tensor may have no address at all; the library wants its arrays)
+            keep = [torch.zeros((1, 3) if t.dim() == 2 else (1,), dtype=t.dtype, device=t.device) for t in keep]
+        if any(t.device != device for t in keep):
+            raise ValueError(f"refine_multiview: the points live on {keep[0].device}, this context computes on {device}")
+        offs = torch.from_numpy(np.ascontiguousarray(src.ref_offsets, np.int64)).to(device)
+        pts = lfd_points(xyz=keep[0].data_ptr(), rgb=None, err=keep[1].data_ptr(), cell=keep[2].data_ptr(), slot=keep[3].data_ptr(), capacity=n)
+        n_refs, k, cap = int(len(src.ref_offsets)) - 1, int(src.seg_counts.shape[1]), n
+        xyz_out = torch.empty((max(n, 1), 3), dtype=torch.float32, device=device)
+        err_out = torch.empty((max(n, 1),), dtype=torch.float32, device=device)
+    else:
+        if src.xyz.device != device:
+            raise ValueError(f"refine_multiview: the points live on {src.xyz.device}, this context computes on {device}")
+        keep, offs, pts, n_refs, k, cap = [], src.ref_offsets, src.c, src._n_refs, src._k, src.capacity
+        xyz_out, err_out = src.xyz, src.err
+    if n_refs != batch.n_refs or k != batch.k:
+        raise ValueError(f"refine_multiview: the points were made for {n_refs} references x {k} slots, the batch has {batch.n_refs} x {batch.k}")
+    status = torch.zeros((max(cap, 1),), dtype=torch.uint8, device=device) if with_status else None
+    rc = fn(ctx, C.byref(batch.c), C.byref(pts), offs.data_ptr(), C.c_float(float(support_thresh_px)), C.c_float(float(reproj_thresh)),
+            xyz_out.data_ptr(), err_out.data_ptr(), status.data_ptr() if with_status else None, counters.data_ptr() if counters is not None else None)
+    if rc != 0:
+        return rc, None, None
+    if with_status:
+        status = status[:cap]
+    if not collected:
+        return rc, src, status
+    return rc, dataclasses.replace(src, xyz=xyz_out[:cap], err=err_out[:cap], _packed=None), status
+
+
 class HipDensifier:
     """One context = one GPU + one stream (``torch.cuda.current_stream`` of the device at creation,
     unless a stream is given).  Not thread-safe: use one per thread, as the C-ABI requires."""
@@ -939,6 +982,21 @@ class HipDensifier:
                                                     with_support, into, self.device)
         self._check(rc, "lfd_support_filter")
         return (res, support) if with_support else res
+
+    def refine_multiview(self, batch: PreparedBatch, out_buffers, support_thresh_px: float, reproj_thresh: float, with_status: bool = False,
+                         counters: Optional[torch.Tensor] = None):
+        """Multi-view re-triangulation of supported points (lfd_refine_multiview): every point ``out_buffers`` holds for ``batch``
+        (an OutputBuffers a launch wrote - refined in place, asynchronously on the context's stream - or a collected TriangulationOutput, which
+        is copied) that OTHER neighbours of its reference confirm within ``support_thresh_px`` is triangulated again from all those views and
+        replaced when the result passes the two-view tests at ``reproj_thresh`` and every confirming view still agrees.  Order, counts, rgb,
+        cell and slot never change.  ``counters``: int64 [2] on the device, added to (refined, kept their two-view position although confirmed).
+        With ``with_status`` a pair (result, uint8 per point: confirming views | 0x80 if replaced)."""
+        self._same_device(batch)
+        with torch.cuda.stream(self.stream):
+            rc, res, status = _refine_call(self._lib.lfd_refine_multiview, self._ctx, batch, out_buffers, support_thresh_px, reproj_thresh,
+                                           with_status, counters, self.device)
+        self._check(rc, "lfd_refine_multiview")
+        return (res, status) if with_status else res
 
     def quantise_rgb(self, rgb: torch.Tensor) -> torch.Tensor:
         rgb = self._pts(rgb, 3, "rgb")
@@ -1274,6 +1332,15 @@ class HostDensifier:
                                                 with_support, into, self.device)
         self._check(rc, "lfd_support_filter_host")
         return (res, support) if with_support else res
+
+    def refine_multiview(self, batch: PreparedBatch, out_buffers, support_thresh_px: float, reproj_thresh: float, with_status: bool = False,
+                         counters: Optional[torch.Tensor] = None):
+        """HipDensifier.refine_multiview over CPU tensors (lfd_refine_multiview_host): the same per-point routine, host build."""
+        self._same_device(batch)
+        rc, res, status = _refine_call(self._lib.lfd_refine_multiview_host, self._ctx, batch, out_buffers, support_thresh_px, reproj_thresh,
+                                       with_status, counters, self.device)
+        self._check(rc, "lfd_refine_multiview_host")
+        return (res, status) if with_status else res
 
     def aggregate(self, batch: PreparedBatch, params: lfd_params):
         self._same_device(batch)

@@ -74,6 +74,8 @@ class HotPath:
         self.support_thresh_px = float(config.support_threshold())
         self.support_in = self.support_kept = 0                 # points that reached the filter / that it kept, over the results the run used
         self._support_void = False                              # a grouped call failed as a whole: what is collected until the next launch is dropped
+        self.refine = bool(config.exp("multiview_refine"))
+        self._refine_counter: Optional[torch.Tensor] = None     # int64 [2] where the kernels run: points refined / confirmed but left alone, added to
 
     # -- forward-backward consistency filter (lfd_cycle_gate) -------------------------------------------------------------------
     def cycle_gate(self, warps, certs, backs, axes) -> None:
@@ -106,13 +108,18 @@ class HotPath:
     # -- multi-view support filter (lfd_support_filter) --------------------------------------------------------------------------
     def support_filter_collected(self, batch: hb.PreparedBatch, res: hb.TriangulationOutput) -> hb.TriangulationOutput:
         """A collected result through the filter (the synchronous schedules, the host backend)."""
-        if self.min_support <= 0 or res is None:
+        if res is None:
             return res
-        self._support_void = False
-        with self.clock.stage("kernel"):
-            out = self.dens.support_filter(batch, res, self.min_support, self.support_thresh_px)
-        self._support_count(out)
-        return out
+        if self.min_support > 0:
+            self._support_void = False
+            with self.clock.stage("kernel"):
+                out = self.dens.support_filter(batch, res, self.min_support, self.support_thresh_px)
+            self._support_count(out)
+            res = out
+        if self.refine:
+            with self.clock.stage("kernel"):
+                res = self._refined(batch, res)
+        return res
 
     def _support_count(self, res: hb.TriangulationOutput) -> None:
         """The run's totals, from the integers a result brings along anyway (no read-back of their own)."""
@@ -128,15 +135,31 @@ class HotPath:
         """``out`` as the launch left it, or - with the filter on - the buffers the filter compacts it into: one launch behind the one that
         filled ``out``, on the same stream, before anything is read back (``out`` goes back to the pool: whatever uses it next follows in the
         same stream).  Destination buffers are recycled among themselves: ``collect`` reports the points that went in only for them."""
-        if self.min_support <= 0:
-            return out
-        self._support_void = False             # (a new launch: whatever a failed grouped call left behind has been dealt with)
-        into = self._take_buffers(out.capacity, out._n_refs, out._k, filtered=True)
-        try:
-            self.dens.support_filter(batch, out, self.min_support, self.support_thresh_px, into=into)
-        finally:
-            self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, False), []).append(out)
-        return into
+        if self.min_support > 0:
+            self._support_void = False             # (a new launch: whatever a failed grouped call left behind has been dealt with)
+            into = self._take_buffers(out.capacity, out._n_refs, out._k, filtered=True)
+            try:
+                self.dens.support_filter(batch, out, self.min_support, self.support_thresh_px, into=into)
+            finally:
+                self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, False), []).append(out)
+            out = into
+        return self._refined(batch, out) if self.refine else out
+
+    # -- multi-view re-triangulation of supported points (lfd_refine_multiview, DESIGN.md 4.9) ---------------------------------------------------
+    def _refined(self, batch: hb.PreparedBatch, out):
+        """The points of ``out`` (buffers a launch or the support filter just filled: in place; or a collected result: a copy) through
+        lfd_refine_multiview: one launch on the stream that made them, before anything reads them.  The counters stay where the kernels run
+        until ``refine_totals``; they count every launch issued (a grouped call that is redone is counted twice)."""
+        if self._refine_counter is None:
+            self._refine_counter = torch.zeros(2, dtype=torch.int64, device=self.dev)
+        return self.dens.refine_multiview(batch, out, self.support_thresh_px, float(self.config.reproj_thresh), counters=self._refine_counter)
+
+    def refine_totals(self) -> Tuple[int, int]:
+        """(points refined, points other views confirmed that kept their two-view position) of the run: the one read of the device counters."""
+        if self._refine_counter is None:
+            return 0, 0
+        n = self._refine_counter.cpu()
+        return int(n[0]), int(n[1])
 
     def close(self) -> None:
         self._prepared.clear()
@@ -495,12 +518,15 @@ class HotPath:
             if bool(self.config.exp("dense_tile_segments")):
                 # unordered retirement (no look-back), raster order restored from the tile table: the same result, bit for bit
                 return self.dens.order_segments(self.dens.triangulate_dense_segments(batch, self.params))
-            if self.min_support > 0 and not self.on_host:
-                # the launch, the filter behind it on the same stream, then the one read-back of the offsets
+            if (self.min_support > 0 or self.refine) and not self.on_host:
+                # the launch, the filter and / or the re-triangulation behind it on the same stream, then the one read-back of the offsets
                 cap = batch.n_refs * batch.H * batch.W
                 out = hb.OutputBuffers(cap, batch.n_refs, batch.k, self.dev)
                 self.dens.launch_dense(batch, self.params, out)
-                out = self.dens.support_filter(batch, out, self.min_support, self.support_thresh_px)
+                if self.min_support > 0:
+                    out = self.dens.support_filter(batch, out, self.min_support, self.support_thresh_px)
+                if self.refine:
+                    out = self._refined(batch, out)
                 self.dens.check_launches()
                 res = out.collect()
                 self._support_void = False

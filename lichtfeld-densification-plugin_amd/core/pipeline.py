@@ -260,6 +260,10 @@ def run_dense_pipeline(
             n_in, n_dropped = hot.support_totals()
             log.info(f"Multi-view support filter: threshold {hot.support_thresh_px:g} px, at least {hot.min_support} other view(s), {n_in} points in, "
                      f"{n_dropped} dropped")
+        if hot.refine:
+            n_refined, n_fallback = hot.refine_totals()
+            log.info(f"Multi-view re-triangulation: threshold {hot.support_thresh_px:g} px, {n_refined} points refined, {n_fallback} confirmed points "
+                     f"kept their two-view position")
     except BaseException as exc:
         if world == 1:
             raise

@@ -56,6 +56,10 @@ EXPERIMENTAL_DEFAULTS = {
     # ... within this many pixels of the neighbour's camera image (the unit of reproj_thresh).  0.0 = 2 * reproj_thresh: the residual in a third
     # view carries that view's own matching noise plus the depth error of the two-view point.
     "support_thresh_px": 0.0,
+    # multi-view re-triangulation of supported points (lfd_refine_multiview): a two-view point that OTHER loaded neighbours of its
+    # reference confirm within support_threshold() is triangulated again from all the views that see it and moved there when the result still
+    # passes the two-view tests and every confirming view still agrees.  Nothing is added or dropped.  False = off: no new code runs.
+    "multiview_refine": False,
 }
 
 
@@ -213,6 +217,23 @@ class DensePipelineConfig:
                 return "experimental['min_support_views'] needs the ordered dense result; experimental['dense_tile_segments'] retires tiles unordered"
             if self.exchange_record_format() == "ply":
                 return "experimental['min_support_views'] filters f32 rows; experimental['exchange_records'] must be 'f32' with it"
+        refine = self.exp("multiview_refine")
+        if not isinstance(refine, (bool, np.bool_)):
+            return "experimental['multiview_refine'] must be True or False"
+        if refine:
+            if self.no_filter:
+                return "experimental['multiview_refine'] accepts a point by the two-view tests; no_filter switches them off"
+            if not (float(self.reproj_thresh) > 0.0) or not (self.support_threshold() > 0.0):
+                return "experimental['multiview_refine'] needs its thresholds: reproj_thresh must be > 0 (and experimental['support_thresh_px'] or its default)"
+            if int(self.nns_per_ref) < 2:
+                return "experimental['multiview_refine'] uses the neighbours beside the one that made a point: nns_per_ref must be at least 2"
+            if dense and self.stream_output:
+                return ("experimental['multiview_refine'] moves points held as arrays (xyz, cell, slot); dense mode with stream_output has the "
+                        "kernel write PLY records instead")
+            if self.exp("dense_tile_segments"):
+                return "experimental['multiview_refine'] needs the ordered dense result; experimental['dense_tile_segments'] retires tiles unordered"
+            if self.exchange_record_format() == "ply":
+                return "experimental['multiview_refine'] moves f32 rows; experimental['exchange_records'] must be 'f32' with it"
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):
                 return "stream_output writes a PLY while the run proceeds: output_path must end in .ply"

@@ -17,6 +17,7 @@
 #include "lfd_corr.hpp"
 #include "lfd_cycle.hpp"
 #include "lfd_support.hpp"
+#include "lfd_refine.hpp"
 
 extern "C" __global__ void lfd_aggregate_kernel(LfdLaunch L, float* best_cert, uint8_t* best_slot);
 extern "C" __global__ void lfd_dense_kernel(LfdLaunch L);
@@ -62,6 +63,7 @@ extern "C" __global__ void lfd_voxel_sums_big_kernel(const float* xyz, const flo
 hipError_t lfd_corr_launch(const LfdCorrArgs& p, hipStream_t stream);     // lfd_corr.hip
 hipError_t lfd_cycle_launch(const LfdCycleArgs& p, hipStream_t stream);   // lfd_cycle.hip
 hipError_t lfd_support_launch(const LfdSupportArgs& p, hipStream_t stream);   // lfd_support.hip
+hipError_t lfd_refine_launch(const LfdRefineArgs& p, hipStream_t stream);     // lfd_refine.hip
 extern "C" __global__ void lfd_select_topm_kernel(LfdSelectArgs A);
 extern "C" __global__ void lfd_select_filter_mw_kernel(LfdSelectArgs A, LfdSelectNorms norms);
 extern "C" __global__ void lfd_select_begins_kernel(long long* pairs, long long stride, int n);
@@ -1472,6 +1474,37 @@ int lfd_support_filter(lfd_context* ctx, const lfd_batch* batch, const lfd_point
     p.wm1 = L.kp.wm1; p.hm1 = L.kp.hm1; p.mask_sx = L.mask_sx; p.mask_sy = L.mask_sy; p.tau = support_thresh_px;
     if (seg_counts_out) LFD_HIP(ctx, hipMemsetAsync(seg_counts_out, 0, sizeof(int32_t) * (size_t)batch->n_refs * batch->k, ctx->stream));
     LFD_HIP(ctx, lfd_support_launch(p, ctx->stream));
+    return LFD_OK;
+}
+
+// ---- multi-view re-triangulation of supported points (lfd_refine.hip) ------------------------------------------------------------------------
+int lfd_refine_multiview(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets, float support_thresh_px,
+                         float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status, int64_t* counters) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_refine_check(in, ref_offsets, support_thresh_px, reproj_thresh, xyz_out, err_out, status))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_refine_multiview: ") + why);
+    // the batch's tables and per-pair constants, derived again only when the batch differs from the last one seen (no threshold reaches them)
+    lfd_params none;
+    std::memset(&none, 0, sizeof(none));
+    LfdLaunch L;
+    int rc = prepare_launch(ctx, batch, &none, nullptr, 0, L, nullptr);
+    if (rc != LFD_OK) return rc;
+    LfdRefineArgs p;
+    std::memset(&p, 0, sizeof(p));
+    p.n_wg = (int32_t)((in->capacity + 255) / 256);
+    p.refs = L.refs; p.slots = L.slots; p.ref_const = L.ref_const; p.pair_const = L.pair_const;
+    p.axis_x = L.axis_x; p.axis_y = L.axis_y;
+    p.offs = reinterpret_cast<const long long*>(ref_offsets);
+    p.xyz = in->xyz; p.err = in->err; p.cell = in->cell; p.slot = in->slot;
+    p.o_xyz = xyz_out; p.o_err = err_out; p.status = status;
+    p.counters = reinterpret_cast<unsigned long long*>(counters);
+    p.capacity = in->capacity;
+    p.n_refs = batch->n_refs; p.k = batch->k;
+    p.g.H = batch->H; p.g.W = batch->W; p.g.C = batch->warp_channels; p.g.w_match = batch->w_match; p.g.h_match = batch->h_match;
+    p.g.wm1 = L.kp.wm1; p.g.hm1 = L.kp.hm1; p.g.mask_sx = L.mask_sx; p.g.mask_sy = L.mask_sy;
+    p.g.tau = support_thresh_px; p.g.reproj_thresh = reproj_thresh;
+    LFD_HIP(ctx, lfd_refine_launch(p, ctx->stream));
     return LFD_OK;
 }
 

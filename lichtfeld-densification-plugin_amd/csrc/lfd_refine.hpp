@@ -1,0 +1,263 @@
+// Multi-view re-triangulation of supported points (lfd_refine_multiview): the per-point routine, compiled for the device
+// (lfd_refine.hip) and for the host (lfd_host.hip's twin).  The support filter (lfd_support.hpp) finds, per two-view point, the OTHER neighbours of
+// its reference whose own warp agrees with it; here their observations join the two that made the point in one N-view DLT, and the result
+// replaces the point when it still passes the two-view tests and every view that agreed before agrees with it.
+//
+// Every rounding is written out (the build uses -ffp-contract=off).  The candidate set uses lfd_support_live / lfd_support_mask_index /
+// lfd_support_agree unchanged, so it is the support filter's set bit for bit on both builds; the rows are lfd_eval_correspondence's f32 rows;
+// M = sum row row^T is one f64 fma chain in the fixed view order (reference, winning slot, candidates by ascending slot).  The two builds differ
+// only where lfd_geometry.hpp's do: lfd_recip_refined (IEEE division / Newton-refined v_rcp_f64), lfd_sqrt_rare, lfd_rcp_f32, lfd_sqrt_f32.
+#pragma once
+
+#include <stdint.h>
+
+#include "../../include/lfd_densify.h"
+#include "lfd_geometry.hpp"
+#include "lfd_support.hpp"
+
+#define LFD_REFINE_ACCEPTED 0x80       /* status: n_extra | (accepted ? 0x80 : 0) */
+
+struct LfdRefineSlot {           // one neighbour of the reference at work (LDS on the device, a table on the host)
+    const float* cert;
+    const float* warp;
+    const uint8_t* mask_b;
+    float P[12];                 // interleaved (LfdPairConst)
+    float sx, sy;
+};
+
+struct LfdRefineRef {            // the reference itself
+    float P[12];                 // interleaved (LfdRefConst)
+    float sx, sy;
+};
+
+struct LfdRefineGeom {
+    int32_t H, W, C, w_match, h_match;
+    float wm1, hm1, mask_sx, mask_sy, tau, reproj_thresh;
+};
+
+// M (upper triangle: m00 m01 m02 m03 m11 m12 m13 m22 m23 m33) += the two DLT rows of one view, u p2 - p0 and v p2 - p1, formed in f32 exactly as
+// lfd_eval_correspondence forms them (multiply, then subtract); the products of f32 values are exact in f64.  `first`: M is set, not added to
+// (the products themselves, as lfd_null_vector_rows starts).
+LFD_HD void lfd_refine_add_view(double* M, const float* Pi, float u, float v, bool first) {
+    float ru[4], rv[4];
+    for (int c = 0; c < 4; ++c) {
+        ru[c] = u * Pi[8 + c] - Pi[2 * c];
+        rv[c] = v * Pi[8 + c] - Pi[2 * c + 1];
+    }
+    {
+        const double a0 = (double)ru[0], a1 = (double)ru[1], a2 = (double)ru[2], a3 = (double)ru[3];
+        if (first) {
+            M[0] = a0 * a0; M[1] = a0 * a1; M[2] = a0 * a2; M[3] = a0 * a3;
+            M[4] = a1 * a1; M[5] = a1 * a2; M[6] = a1 * a3; M[7] = a2 * a2; M[8] = a2 * a3; M[9] = a3 * a3;
+        } else {
+            M[0] = fma(a0, a0, M[0]); M[1] = fma(a0, a1, M[1]); M[2] = fma(a0, a2, M[2]); M[3] = fma(a0, a3, M[3]);
+            M[4] = fma(a1, a1, M[4]); M[5] = fma(a1, a2, M[5]); M[6] = fma(a1, a3, M[6]);
+            M[7] = fma(a2, a2, M[7]); M[8] = fma(a2, a3, M[8]); M[9] = fma(a3, a3, M[9]);
+        }
+    }
+    {
+        const double a0 = (double)rv[0], a1 = (double)rv[1], a2 = (double)rv[2], a3 = (double)rv[3];
+        M[0] = fma(a0, a0, M[0]); M[1] = fma(a0, a1, M[1]); M[2] = fma(a0, a2, M[2]); M[3] = fma(a0, a3, M[3]);
+        M[4] = fma(a1, a1, M[4]); M[5] = fma(a1, a2, M[5]); M[6] = fma(a1, a3, M[6]);
+        M[7] = fma(a2, a2, M[7]); M[8] = fma(a2, a3, M[8]); M[9] = fma(a3, a3, M[9]);
+    }
+}
+
+// Smallest eigenvector of the symmetric positive semi-definite 4x4 matrix M (upper triangle as above) by the scheme of lfd_null_vector_rows
+// (DESIGN 4.1): LDL^T without pivoting, Newton-refined pivot reciprocals, inverse iteration from e4 (its first solve is the last column of
+// L^-T), lfd_nullvec_settled from the second solve on, at most LFD_NULLVEC_MAXIT solves per pass and LFD_NULLVEC_PASSES passes, every pass after
+// the first shifted by the Rayleigh quotient of the iterate backed off by its residual.  M stays where it is (ten values): this routine runs once
+// per supported point behind the dense kernel, not inside its geometry loop.  c[4]: an un-normalised multiple; returns the number of solves.
+LFD_HD int lfd_null_vector_sym(const double* M, double* c) {
+    const double m00 = M[0], m01 = M[1], m02 = M[2], m03 = M[3], m11 = M[4], m12 = M[5], m13 = M[6], m22 = M[7], m23 = M[8], m33 = M[9];
+    double x0 = 0.0, x1 = 0.0, x2 = 0.0, x3 = 1.0;
+    int it = 0;
+    bool settled = false;
+    for (int pass = 0; !settled && pass < LFD_NULLVEC_PASSES; ++pass) {
+        double sh = 0.0;
+        if (pass > 0) {
+            const double sc = lfd_pow2_inv_scale(fabs(x0) + fabs(x1) + fabs(x2) + fabs(x3));
+            x0 *= sc; x1 *= sc; x2 *= sc; x3 *= sc;
+            const double t0 = fma(m03, x3, fma(m02, x2, fma(m01, x1, m00 * x0)));
+            const double t1 = fma(m13, x3, fma(m12, x2, fma(m11, x1, m01 * x0)));
+            const double t2 = fma(m23, x3, fma(m22, x2, fma(m12, x1, m02 * x0)));
+            const double t3 = fma(m33, x3, fma(m23, x2, fma(m13, x1, m03 * x0)));
+            const double num = fma(x3, t3, fma(x2, t2, fma(x1, t1, x0 * t0)));
+            const double den = fma(x3, x3, fma(x2, x2, fma(x1, x1, x0 * x0)));
+            const double rden = lfd_recip_refined(den);
+            const double rho = num * rden;
+            const double e0 = fma(-rho, x0, t0), e1 = fma(-rho, x1, t1), e2 = fma(-rho, x2, t2), e3 = fma(-rho, x3, t3);
+            const double rr = fma(e3, e3, fma(e2, e2, fma(e1, e1, e0 * e0)));
+            sh = rho - lfd_sqrt_rare(rr * rden);
+        }
+        // M - sh I = L D L^T (pass 0: M itself); s_i = d3 / d_i
+        const double q00 = pass ? m00 - sh : m00, q11 = pass ? m11 - sh : m11, q22 = pass ? m22 - sh : m22, q33 = pass ? m33 - sh : m33;
+        const double r0 = lfd_recip_refined(q00);
+        const double l10 = m01 * r0, l20 = m02 * r0, l30 = m03 * r0;
+        const double d1 = fma(-l10, m01, q11);
+        const double n12 = fma(-l10, m02, m12), n13 = fma(-l10, m03, m13);
+        const double n22 = fma(-l20, m02, q22), n23 = fma(-l20, m03, m23), n33 = fma(-l30, m03, q33);
+        const double r1 = lfd_recip_refined(d1);
+        const double l21 = n12 * r1, l31 = n13 * r1;
+        const double d2 = fma(-l21, n12, n22);
+        const double p23 = fma(-l21, n13, n23), p33 = fma(-l31, n13, n33);
+        const double r2 = lfd_recip_refined(d2);
+        const double l32 = p23 * r2;
+        const double d3 = fma(-l32, p23, p33);
+        const double s0 = d3 * r0, s1 = d3 * r1, s2 = d3 * r2;
+        if (pass == 0) {         // first solve from e4: the last column of L^-T
+            x3 = 1.0;
+            x2 = -l32;
+            x1 = fma(-l21, x2, -l31);
+            x0 = fma(-l10, x1, fma(-l20, x2, -l30));
+        }
+        for (int k = 1; k <= LFD_NULLVEC_MAXIT; ++k) {
+            const double o0 = x0, o1 = x1, o2 = x2, o3 = x3;
+            // x <- d3 (M - sh I)^-1 x : forward (L), diagonal, backward (L^T)
+            const double y1 = fma(-l10, o0, o1);
+            const double y2 = fma(-l21, y1, fma(-l20, o0, o2));
+            const double y3 = fma(-l32, y2, fma(-l31, y1, fma(-l30, o0, o3)));
+            const double z0 = o0 * s0, z1 = y1 * s1, z2 = y2 * s2;
+            x3 = y3;
+            x2 = fma(-l32, x3, z2);
+            x1 = fma(-l21, x2, fma(-l31, x3, z1));
+            x0 = fma(-l10, x1, fma(-l20, x2, fma(-l30, x3, z0)));
+            ++it;
+            if (k >= 2 && lfd_nullvec_settled(x0, x1, x2, x3, o0, o1, o2, o3)) { settled = true; break; }
+        }
+    }
+    c[0] = x0; c[1] = x1; c[2] = x2; c[3] = x3;
+    return it;
+}
+
+// X' = c[0..2] / c[3] rounded to f32 as the two-view path rounds it.  False where that path's w guard would act (|c3| / |c| < 1e-12: a point
+// at infinity has no place in the candidates' test, which takes the homogeneous coordinate as 1) or a coordinate is not finite.
+LFD_HD bool lfd_refine_dehomogenise(const double* c, float& X0, float& X1, float& X2) {
+    const double c33 = c[3] * c[3];
+    const double n2 = fma(c[0], c[0], fma(c[1], c[1], fma(c[2], c[2], c33)));
+    const double r = lfd_recip_refined(c[3]);
+    X0 = (float)(c[0] * r);
+    X1 = (float)(c[1] * r);
+    X2 = (float)(c[2] * r);
+    const bool guard = c33 < 1e-24 * n2;
+    return !guard && (n2 == n2) && lfd_finite(X0) && lfd_finite(X1) && lfd_finite(X2);
+}
+
+// The two-view test of lfd_eval_correspondence at X (reference, winning slot): pz > 0 in both and err = sqrt(max of the squared reprojection
+// distances) <= reproj_thresh, the same operations and the same comparison.  A NaN rejects.
+LFD_HD bool lfd_refine_two_view(const float* Pa, const float* Pb, float X0, float X1, float X2, float ua, float va, float ub, float vb,
+                                float reproj_thresh, float& err) {
+    float z1, z2;
+    const float q1 = lfd_reproj_sq(Pa, X0, X1, X2, 1.0f, ua, va, z1);
+    const float q2 = lfd_reproj_sq(Pb, X0, X1, X2, 1.0f, ub, vb, z2);
+    const float qm = (q1 > q2 || q1 != q1) ? q1 : q2;
+    err = lfd_sqrt_f32(qm);
+    return (err <= reproj_thresh) && (z1 > 0.0f) && (z2 > 0.0f);
+}
+
+// One point.  sl[0 .. ns): the reference's neighbours; s: the winning slot (s < ns); (xan, yan) / (xbn, ybn): the reference's and the winner's
+// normalised observations of the cell; cert[j], wx[j], wy[j] (j < ns, j != s): what the other neighbours hold at the cell, gathered by the
+// caller (KMAX >= ns).  Returns the status byte; X0, X1, X2, err are replaced iff it has LFD_REFINE_ACCEPTED.
+template <int KMAX>
+LFD_HD unsigned lfd_refine_point(const LfdRefineRef& ref, const LfdRefineSlot* sl, int ns, int s, const LfdRefineGeom& g, float xan, float yan,
+                                 float xbn, float ybn, const float* cert, const float* wx, const float* wy, float& X0, float& X1, float& X2,
+                                 float& err) {
+    unsigned cand = 0u;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = 0; j < KMAX; ++j) {
+        if (j < ns && j != s) {
+            bool live = lfd_support_live(cert[j]);
+            const uint8_t* mb = sl[j].mask_b;
+            if (live && mb) {
+                const long long m = lfd_support_mask_index(wx[j], wy[j], g.W, g.H, g.mask_sx, g.mask_sy, g.w_match, g.h_match);
+                live = m >= 0 && mb[m] != 0;
+            }
+            const bool agree = lfd_support_agree(sl[j].P, sl[j].sx, sl[j].sy, X0, X1, X2, wx[j], wy[j], g.wm1, g.hm1, g.tau);
+            cand |= (live && agree) ? (1u << j) : 0u;
+        }
+    }
+    if (cand == 0u) return 0u;
+    unsigned n_extra = 0u;
+    for (unsigned m = cand; m; m &= m - 1u) ++n_extra;
+
+    const float ua = lfd_match_px(xan, g.wm1) * ref.sx, va = lfd_match_px(yan, g.hm1) * ref.sy;
+    const float ub = lfd_match_px(xbn, g.wm1) * sl[s].sx, vb = lfd_match_px(ybn, g.hm1) * sl[s].sy;
+    double M[10];
+    lfd_refine_add_view(M, ref.P, ua, va, true);
+    lfd_refine_add_view(M, sl[s].P, ub, vb, false);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = 0; j < KMAX; ++j) {
+        if ((cand >> j) & 1u) {
+            const float uj = lfd_match_px(wx[j], g.wm1) * sl[j].sx, vj = lfd_match_px(wy[j], g.hm1) * sl[j].sy;
+            lfd_refine_add_view(M, sl[j].P, uj, vj, false);
+        }
+    }
+    double c[4];
+    lfd_null_vector_sym(M, c);
+    float Y0, Y1, Y2, e;
+    bool ok = lfd_refine_dehomogenise(c, Y0, Y1, Y2);
+    ok = lfd_refine_two_view(ref.P, sl[s].P, Y0, Y1, Y2, ua, va, ub, vb, g.reproj_thresh, e) && ok;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = 0; j < KMAX; ++j) {
+        if ((cand >> j) & 1u)
+            ok = lfd_support_agree(sl[j].P, sl[j].sx, sl[j].sy, Y0, Y1, Y2, wx[j], wy[j], g.wm1, g.hm1, g.tau) && ok;
+    }
+    if (!ok) return n_extra;
+    X0 = Y0; X1 = Y1; X2 = Y2; err = e;
+    return n_extra | LFD_REFINE_ACCEPTED;
+}
+
+// What a launch works on (device), by value in the kernel arguments.
+struct LfdRefineArgs {
+    const void* refs;                  // LfdRefDesc [n_refs]
+    const void* slots;                 // LfdSlotDesc [n_refs * k]
+    const LfdRefConst* ref_const;      // [n_refs]
+    const LfdPairConst* pair_const;    // [n_refs * k]
+    const float* axis_x;               // [W], [H]: the A-grid axes (two-channel warps)
+    const float* axis_y;
+    const long long* offs;             // [n_refs + 1]
+    const float* xyz; const float* err; const int32_t* cell; const uint8_t* slot;
+    float* o_xyz; float* o_err;
+    uint8_t* status;                   // [capacity] or null
+    unsigned long long* counters;      // [2] or null: points refined, points with a candidate that kept their two-view position; added to
+    long long capacity;
+    int32_t n_refs, k, n_wg;
+    LfdRefineGeom g;
+};
+
+// Arguments of lfd_refine_multiview / lfd_refine_multiview_host that do not depend on the batch; what is wrong with them, or null.
+inline const char* lfd_refine_check(const lfd_points* in, const int64_t* ref_offsets, float support_thresh_px, float reproj_thresh,
+                                    const float* xyz_out, const float* err_out, const uint8_t* status) {
+    if (!in || !ref_offsets) return "null in / ref_offsets";
+    if (!in->xyz || !in->err || !xyz_out || !err_out) return "null point arrays";
+    if (!in->cell || !in->slot) return "in->cell and in->slot are required";
+    if (in->capacity < 0 || in->capacity > 0x7fffffffLL) return "capacity must be in [0, 2^31 - 1]";
+    if (!(support_thresh_px > 0.0f) || !(support_thresh_px <= 3.4028234e38f)) return "support_thresh_px must be finite and > 0";
+    if (!(reproj_thresh > 0.0f) || !(reproj_thresh <= 3.4028234e38f)) return "reproj_thresh must be finite and > 0";
+    const bool in_place = xyz_out == in->xyz && err_out == in->err;
+    const long long cap = in->capacity;
+    const struct { const void* p; long long elem; } a[5] = {{in->xyz, 12}, {in->rgb, 12}, {in->err, 4}, {in->cell, 4}, {in->slot, 1}},
+                                                    b[3] = {{xyz_out, 12}, {err_out, 4}, {status, 1}};
+    for (int j = 0; j < 3; ++j) {
+        if (!b[j].p) continue;
+        const uintptr_t b0 = reinterpret_cast<uintptr_t>(b[j].p), b1 = b0 + (uintptr_t)(b[j].elem * cap);
+        for (int i = 0; i < 5; ++i) {
+            if (!a[i].p) continue;
+            if (in_place && ((j == 0 && i == 0) || (j == 1 && i == 2))) continue;
+            const uintptr_t a0 = reinterpret_cast<uintptr_t>(a[i].p), a1 = a0 + (uintptr_t)(a[i].elem * cap);
+            if (a0 < b1 && b0 < a1) return "xyz_out / err_out / status must be in->xyz and in->err themselves or overlap nothing of in";
+        }
+        for (int i = 0; i < j; ++i) {
+            if (!b[i].p) continue;
+            const uintptr_t a0 = reinterpret_cast<uintptr_t>(b[i].p), a1 = a0 + (uintptr_t)(b[i].elem * cap);
+            if (a0 < b1 && b0 < a1) return "xyz_out, err_out and status overlap each other";
+        }
+    }
+    return nullptr;
+}

@@ -403,6 +403,8 @@ def _experimental_from_args(args) -> dict:
         exp["min_support_views"] = int(args.min_support_views)
     if float(getattr(args, "support_thresh_px", 0.0)) != 0.0:
         exp["support_thresh_px"] = float(args.support_thresh_px)
+    if bool(getattr(args, "multiview_refine", False)):
+        exp["multiview_refine"] = True
     return exp
 
 
@@ -445,6 +447,9 @@ def build_argparser() -> argparse.ArgumentParser:
                          "confirm it (at most nns_per_ref - 1; 0 = off)")
     ap.add_argument("--support_thresh_px", type=float, default=0.0,
                     help="... within this many pixels of the neighbour's camera image (0 = 2 * reproj_thresh)")
+    ap.add_argument("--multiview_refine", action="store_true",
+                    help="multi-view re-triangulation: a point that other loaded neighbours of its reference confirm (within --support_thresh_px) is "
+                         "triangulated again from all the views that see it; nothing is added or dropped")
     ap.add_argument("--keep_threads", action="store_true",
                     help="leave torch's intra-op thread count alone (by default it is lowered to the container's CPU quota; the count decides the last "
                          "bits of upstream's sampling normaliser, so a run compared bit for bit with upstream keeps upstream's setting)")
