@@ -409,6 +409,30 @@ int lfd_refine_multiview(lfd_context* ctx, const lfd_batch* batch, const lfd_poi
 int lfd_refine_multiview_host(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets, float support_thresh_px,
                               float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status, int64_t* counters);
 
+/* Precision-weighted multi-view re-triangulation (no upstream counterpart).  RoMa-v2 predicts a 2x2 precision matrix (inverse error
+ * covariance, px^-2) per match in every preset and nothing uses it; lfd_refine_multiview gives every view's two algebraic rows the same weight, so a
+ * blurry, oblique neighbour pulls a point as hard as a sharp one.  The arguments, the candidates, the rows, the solver, the acceptance, the fallback,
+ * the refusals and the launch are lfd_refine_multiview's; what differs (csrc/lfd_refine.hpp, every rounding written out):
+ *   precision    HOST array [n_refs * k] of DEVICE planes [H*W*3] f32 (host planes for the twin), (q00, q01, q11) per cell: the neighbour's
+ *                precision in px^-2 of its MATCH image, in the pixel convention of the warps.  Entries at j >= n_slots[r] are ignored
+ *   valid(j)     all three values finite, q00 > 0, q11 > 0, q00 q11 - q01 q01 > 0 (f64: exact products, one rounding)
+ *   weights      per participating neighbour j (slot s, the candidates): p = (q00 / (sx sx), q01 / (sx sy), q11 / (sy sy)) in camera px^-2 and
+ *                w2 = 1 / (pz pz), pz the f32 depth of the two-view X in view j, both in f64; the view adds w2 (p00 ru ru^T + p01 (ru rv^T +
+ *                rv ru^T) + p11 rv rv^T) to M, order slot s, candidates by ascending j.  The reference - a cell centre, no matching noise - is
+ *                added last as lamA w2_A (ru ru^T + rv rv^T), lamA = sum_j (p00_j + p11_j) / 2: the result does not depend on a common scale
+ *                of the planes.  ANY participating view invalid: the point is solved with lfd_refine_multiview's unweighted rows, bit for bit
+ * status: n_extra | (weighted rows used ? 0x40 : 0) | (accepted ? 0x80 : 0).  counters: NULL, or device i64 [3] that is ADDED to: points refined,
+ * points with a candidate that kept their two-view position, points solved with weighted rows.  The table of plane pointers reaches the device
+ * as the batch's descriptor tables do: compared with what the device holds, uploaded on the context's stream when it differs, no synchronisation.
+ * One launch, asynchronous, deterministic.  LFD_ERR_INVALID: what lfd_refine_multiview refuses, a null `precision`, a null plane in a valid slot.
+ * lfd_refine_multiview_weighted_host: the same routine over host pointers on a host context's threads. */
+int lfd_refine_multiview_weighted(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets,
+                                  float support_thresh_px, float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status, int64_t* counters,
+                                  const float* const* precision);
+int lfd_refine_multiview_weighted_host(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets,
+                                       float support_thresh_px, float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status,
+                                       int64_t* counters, const float* const* precision);
+
 /* (e) multi-GPU exchange, placement step (no upstream counterpart - upstream has no multi-GPU code): n copies
  * dst[dst_offset .. +nbytes) = src[src_offset .. +nbytes) in ONE launch on `hip_stream` of device `device_index` (offsets and lengths in
  * bytes, no alignment required: 15-byte PLY records).  The overlapped exchange receives every rank's records of a round as one padded block
@@ -474,7 +498,7 @@ int lfd_host_eval_correspondence(const float* cam1, const float* cam2, float xa_
  * The per-cell arithmetic is the host build of the very source the kernels compile (csrc/lfd_geometry.hpp; IEEE
  * division / square root where the device uses the 1-ulp v_rcp / v_sqrt), spread over n_threads std::threads
  * (<= 0: all hardware threads).  A host context accepts lfd_upload_cameras, lfd_last_error, lfd_destroy and the
- * *_host calls (the three below, lfd_local_corr_host, lfd_cycle_gate_host, lfd_support_filter_host and lfd_refine_multiview_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
+ * *_host calls (the three below, lfd_local_corr_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host and lfd_refine_multiview_weighted_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
  * context: neither side ever stands in for the other.  Semantics (orders, counts, optional outputs, LFD_ERR_CAPACITY
  * with valid counts) are those of lfd_aggregate / lfd_triangulate_dense / lfd_triangulate_indexed. */
 int lfd_create_host(int32_t n_threads, lfd_context** out);

@@ -183,6 +183,8 @@ def load_library() -> C.CDLL:
     lib.lfd_refine_multiview.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_points), C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]
     lib.lfd_refine_multiview_host.argtypes = list(lib.lfd_refine_multiview.argtypes)
+    lib.lfd_refine_multiview_weighted.argtypes = list(lib.lfd_refine_multiview.argtypes) + [C.c_void_p]
+    lib.lfd_refine_multiview_weighted_host.argtypes = list(lib.lfd_refine_multiview_weighted.argtypes)
     lib.lfd_copy_segments.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.lfd_launch_status.argtypes = [ctxp, C.POINTER(C.c_int32)]
     lib.lfd_get_pair_fundamental.argtypes = [ctxp, C.c_int32, C.POINTER(C.c_double)]
@@ -217,7 +219,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -386,6 +388,7 @@ class ReferenceInputs:
     mask_a: Optional[torch.Tensor] = None     # (h_match,w_match) u8 {0,1}
     mask_b: Optional[List[Optional[torch.Tensor]]] = None
     fundamental: Optional[Sequence[np.ndarray]] = None   # per slot (3,3) f32: upstream's F for the pair (see PreparedBatch)
+    precision: Optional[List[torch.Tensor]] = None   # per slot (H,W,3) f32: RoMa-v2's precision (q00, q01, q11), match px^-2
 
 
 @dataclasses.dataclass
@@ -478,6 +481,17 @@ class PreparedBatch:
                 self.warp[s] = self._chk(r.warp[j], torch.float32, (H, W, ch), "warp").data_ptr()
                 if r.mask_b is not None and r.mask_b[j] is not None:
                     self.mask_b[s] = self._chk(r.mask_b[j], torch.uint8, (h_match, w_match), "mask_b").data_ptr()
+        # the precision planes of lfd_refine_multiview_weighted: a table of its own (lfd_batch is pinned), present when EVERY reference has them
+        self.precision = None
+        if all(r.precision is not None for r in self.refs):
+            self.precision = (C.c_void_p * (n * k))()
+            for i, r in enumerate(self.refs):
+                if len(r.precision) != len(r.cert):
+                    raise ValueError("precision / cert length mismatch")
+                for j in range(len(r.cert)):
+                    self.precision[i * k + j] = self._chk(r.precision[j], torch.float32, (H, W, 3), "precision").data_ptr()
+        elif any(r.precision is not None for r in self.refs):
+            raise ValueError("precision planes must be given for every reference of a batch or for none")
         self.fundamental = None
         if cameras is not None or any(r.fundamental is not None for r in self.refs):
             fund = np.zeros((n * k, 9), np.float32)
@@ -761,15 +775,19 @@ def _support_filter_call(fn, ctx, batch, src, min_support, support_thresh_px, wi
     return rc, res, support
 
 
-def _refine_call(fn, ctx, batch, src, support_thresh_px, reproj_thresh, with_status, counters, device):
+def _refine_call(fn, ctx, batch, src, support_thresh_px, reproj_thresh, with_status, counters, device, precision=False):
     """One lfd_refine_multiview[_host] call.  ``src``: the OutputBuffers a triangulation launch (or the support filter) wrote for ``batch`` -
     refined IN PLACE, asynchronously, and returned - or a collected TriangulationOutput (the result is a copy with new xyz / err tensors).
-    ``counters``: None, or an int64 [2] tensor on the context's device that is added to.  Returns (rc, result or None, status or None)."""
+    ``counters``: None, or an int64 [2] tensor on the context's device that is added to ([3] with ``precision``: fn is then
+    lfd_refine_multiview_weighted[_host] and the batch's precision table its last argument).  Returns (rc, result or None, status or None)."""
     collected = isinstance(src, TriangulationOutput)
+    n_counters = 3 if precision else 2
+    if precision and batch.precision is None:
+        raise ValueError("refine_multiview: precision=True needs a batch whose references carry precision planes (ReferenceInputs.precision)")
     if src.cell is None or src.slot is None:
         raise ValueError("refine_multiview: the source buffers need the cell / slot outputs (with_cell=True)")
-    if counters is not None and (counters.dtype != torch.int64 or counters.numel() != 2 or counters.device != device or not counters.is_contiguous()):
-        raise ValueError(f"refine_multiview: counters must be a contiguous int64 tensor of two elements on {device}")
+    if counters is not None and (counters.dtype != torch.int64 or counters.numel() != n_counters or counters.device != device or not counters.is_contiguous()):
+        raise ValueError(f"refine_multiview: counters must be a contiguous int64 tensor of {'three' if precision else 'two'} elements on {device}")
     if collected:
         n = int(src.xyz.shape[0])
         keep = [src.xyz.contiguous(), src.err.contiguous(), src.cell.contiguous(), src.slot.contiguous()]
@@ -791,7 +809,8 @@ def _refine_call(fn, ctx, batch, src, support_thresh_px, reproj_thresh, with_sta
         raise ValueError(f"refine_multiview: the points were made for {n_refs} references x {k} slots, the batch has {batch.n_refs} x {batch.k}")
     status = torch.zeros((max(cap, 1),), dtype=torch.uint8, device=device) if with_status else None
     rc = fn(ctx, C.byref(batch.c), C.byref(pts), offs.data_ptr(), C.c_float(float(support_thresh_px)), C.c_float(float(reproj_thresh)),
-            xyz_out.data_ptr(), err_out.data_ptr(), status.data_ptr() if with_status else None, counters.data_ptr() if counters is not None else None)
+            xyz_out.data_ptr(), err_out.data_ptr(), status.data_ptr() if with_status else None, counters.data_ptr() if counters is not None else None,
+            *((C.cast(batch.precision, C.c_void_p),) if precision else ()))
     if rc != 0:
         return rc, None, None
     if with_status:
@@ -984,18 +1003,21 @@ class HipDensifier:
         return (res, support) if with_support else res
 
     def refine_multiview(self, batch: PreparedBatch, out_buffers, support_thresh_px: float, reproj_thresh: float, with_status: bool = False,
-                         counters: Optional[torch.Tensor] = None):
+                         counters: Optional[torch.Tensor] = None, precision: bool = False):
         """Multi-view re-triangulation of supported points (lfd_refine_multiview): every point ``out_buffers`` holds for ``batch``
         (an OutputBuffers a launch wrote - refined in place, asynchronously on the context's stream - or a collected TriangulationOutput, which
         is copied) that OTHER neighbours of its reference confirm within ``support_thresh_px`` is triangulated again from all those views and
         replaced when the result passes the two-view tests at ``reproj_thresh`` and every confirming view still agrees.  Order, counts, rgb,
         cell and slot never change.  ``counters``: int64 [2] on the device, added to (refined, kept their two-view position although confirmed).
-        With ``with_status`` a pair (result, uint8 per point: confirming views | 0x80 if replaced)."""
+        With ``with_status`` a pair (result, uint8 per point: confirming views | 0x80 if replaced).  ``precision``: the rows are weighted by
+        the batch's precision planes (lfd_refine_multiview_weighted); ``counters`` is then int64 [3] (+ points solved with
+        weighted rows) and the status carries 0x40 where they were."""
         self._same_device(batch)
+        name = "lfd_refine_multiview_weighted" if precision else "lfd_refine_multiview"
         with torch.cuda.stream(self.stream):
-            rc, res, status = _refine_call(self._lib.lfd_refine_multiview, self._ctx, batch, out_buffers, support_thresh_px, reproj_thresh,
-                                           with_status, counters, self.device)
-        self._check(rc, "lfd_refine_multiview")
+            rc, res, status = _refine_call(getattr(self._lib, name), self._ctx, batch, out_buffers, support_thresh_px, reproj_thresh,
+                                           with_status, counters, self.device, precision)
+        self._check(rc, name)
         return (res, status) if with_status else res
 
     def quantise_rgb(self, rgb: torch.Tensor) -> torch.Tensor:
@@ -1334,12 +1356,13 @@ class HostDensifier:
         return (res, support) if with_support else res
 
     def refine_multiview(self, batch: PreparedBatch, out_buffers, support_thresh_px: float, reproj_thresh: float, with_status: bool = False,
-                         counters: Optional[torch.Tensor] = None):
-        """HipDensifier.refine_multiview over CPU tensors (lfd_refine_multiview_host): the same per-point routine, host build."""
+                         counters: Optional[torch.Tensor] = None, precision: bool = False):
+        """HipDensifier.refine_multiview over CPU tensors (lfd_refine_multiview[_weighted]_host): the same per-point routine, host build."""
         self._same_device(batch)
-        rc, res, status = _refine_call(self._lib.lfd_refine_multiview_host, self._ctx, batch, out_buffers, support_thresh_px, reproj_thresh,
-                                       with_status, counters, self.device)
-        self._check(rc, "lfd_refine_multiview_host")
+        name = "lfd_refine_multiview_weighted_host" if precision else "lfd_refine_multiview_host"
+        rc, res, status = _refine_call(getattr(self._lib, name), self._ctx, batch, out_buffers, support_thresh_px, reproj_thresh,
+                                       with_status, counters, self.device, precision)
+        self._check(rc, name)
         return (res, status) if with_status else res
 
     def aggregate(self, batch: PreparedBatch, params: lfd_params):

@@ -75,7 +75,9 @@ class HotPath:
         self.support_in = self.support_kept = 0                 # points that reached the filter / that it kept, over the results the run used
         self._support_void = False                              # a grouped call failed as a whole: what is collected until the next launch is dropped
         self.refine = bool(config.exp("multiview_refine"))
-        self._refine_counter: Optional[torch.Tensor] = None     # int64 [2] where the kernels run: points refined / confirmed but left alone, added to
+        self.refine_weighted = bool(config.exp("precision_weighted_refine"))     # lfd_refine_multiview_weighted in its place
+        # int64 [2] where the kernels run: points refined / confirmed but left alone ([3] weighted: + solved with weighted rows), added to
+        self._refine_counter: Optional[torch.Tensor] = None
 
     # -- forward-backward consistency filter (lfd_cycle_gate) -------------------------------------------------------------------
     def cycle_gate(self, warps, certs, backs, axes) -> None:
@@ -148,18 +150,22 @@ class HotPath:
     # -- multi-view re-triangulation of supported points (lfd_refine_multiview) ---------------------------------------------------
     def _refined(self, batch: hb.PreparedBatch, out):
         """The points of ``out`` (buffers a launch or the support filter just filled: in place; or a collected result: a copy) through
-        lfd_refine_multiview: one launch on the stream that made them, before anything reads them.  The counters stay where the kernels run
-        until ``refine_totals``; they count every launch issued (a grouped call that is redone is counted twice)."""
+        lfd_refine_multiview - or, with experimental['precision_weighted_refine'], lfd_refine_multiview_weighted on the batch's precision
+        planes: one launch on the stream that made them, before anything reads them.  The counters stay where the kernels run until
+        ``refine_totals``; they count every launch issued (a grouped call that is redone is counted twice)."""
         if self._refine_counter is None:
-            self._refine_counter = torch.zeros(2, dtype=torch.int64, device=self.dev)
+            self._refine_counter = torch.zeros(3 if self.refine_weighted else 2, dtype=torch.int64, device=self.dev)
+        if self.refine_weighted:
+            return self.dens.refine_multiview(batch, out, self.support_thresh_px, float(self.config.reproj_thresh), counters=self._refine_counter,
+                                              precision=True)
         return self.dens.refine_multiview(batch, out, self.support_thresh_px, float(self.config.reproj_thresh), counters=self._refine_counter)
 
-    def refine_totals(self) -> Tuple[int, int]:
-        """(points refined, points other views confirmed that kept their two-view position) of the run: the one read of the device counters."""
+    def refine_totals(self) -> Tuple[int, ...]:
+        """(points refined, points other views confirmed that kept their two-view position[, points solved with weighted rows]) of the run:
+        the one read of the device counters."""
         if self._refine_counter is None:
-            return 0, 0
-        n = self._refine_counter.cpu()
-        return int(n[0]), int(n[1])
+            return (0, 0, 0) if self.refine_weighted else (0, 0)
+        return tuple(int(v) for v in self._refine_counter.cpu())
 
     def close(self) -> None:
         self._prepared.clear()
@@ -221,13 +227,15 @@ class HotPath:
             out.nbr_masks = [True if n[1] is not None else None for n in nbrs]
         return out
 
-    def inputs(self, packed: PackedReference, warps, certs) -> hb.ReferenceInputs:
+    def inputs(self, packed: PackedReference, warps, certs, precision=None) -> hb.ReferenceInputs:
+        """``precision``: the matcher's precision planes of the pairs (experimental['precision_weighted_refine']), or None."""
         dev = self.dev
         if packed.dev is not None:                 # prepared on the device: nothing to upload
             d = packed.dev
             use_masks = d["mask_a"] is not None or any(m is not None for m in d["nbr_masks"])
             return hb.ReferenceInputs(ref_cam=packed.ref_index, nbr_cams=list(packed.nbr_indices), cert=certs, warp=warps,
-                                      image=d["image"], mask_a=d["mask_a"], mask_b=list(d["nbr_masks"]) if use_masks else None)
+                                      image=d["image"], mask_a=d["mask_a"], mask_b=list(d["nbr_masks"]) if use_masks else None,
+                                      precision=precision)
         use_masks = packed.mask_a is not None or any(m is not None for m in packed.nbr_masks)
         mask_b = None
         with self.clock.stage("prepare"):        # the host-prepared image and masks cross to where the kernels run
@@ -236,7 +244,7 @@ class HotPath:
             image = _upload_u8(packed.image, dev)
             mask_a = _upload_u8(packed.mask_a, dev) if packed.mask_a is not None else None
         return hb.ReferenceInputs(ref_cam=packed.ref_index, nbr_cams=list(packed.nbr_indices), cert=certs, warp=warps, image=image,
-                                  mask_a=mask_a, mask_b=mask_b)
+                                  mask_a=mask_a, mask_b=mask_b, precision=precision)
 
     def sampled(self, ref: hb.ReferenceInputs, axes, rng, device_seed: Optional[int], need_best: bool = False
                 ) -> Tuple[Optional[hb.TriangulationOutput], Optional[torch.Tensor]]:

@@ -176,6 +176,7 @@ class RomaMatcher:
     supports_feature_keys = True      # match_grids_batch(..., keys=(ref_key, [nbr_keys])) shares backbone features between references
     supports_fused_local_corr = True  # set_fused_local_corr(True): the refiners' local correlation runs in this package's HIP kernel
     supports_backward_warp = True     # set_backward_warp(True): match_grids_batch returns (warp, cert, warp_BA) triples
+    supports_precision = True         # set_precision(True): ... (warp, cert, warp_BA or None, precision) 4-tuples
 
     def __init__(self, device: str = "cuda", mode: str = "outdoor", setting: str = "fast", two_channel: bool = True,
                  pairs_per_forward: int = 1, fused_local_corr: bool = False):
@@ -202,6 +203,7 @@ class RomaMatcher:
         self.pairs_per_forward = max(1, int(pairs_per_forward))
         self._local_corr = None
         self._backward = False
+        self._precision = False
         self.set_fused_local_corr(fused_local_corr)
         self._axes: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
         log.info(f"RoMaV2 initialized (setting={setting}, H_lr={self.model.H_lr}, W_lr={self.model.W_lr}, device={device})")
@@ -240,6 +242,33 @@ class RomaMatcher:
     @property
     def backward_warp(self) -> bool:
         return self._backward
+
+    def set_precision(self, on: bool) -> None:
+        """``match_grids_batch`` returns (warp, cert, warp_BA or None, precision) 4-tuples: ``precision`` (H, W, 3) f32, contiguous, holds
+        [p00, p01, p11] of the model's own ``preds["precision_AB"]`` - the 2x2 inverse error covariance every preset computes beside the
+        overlap (romav2.py::_map_confidence) and nothing downstream of upstream's plugin reads - converted from the model's pixel unit to this
+        package's (``precision_scale``).  The forward outputs are the same with the flag on or off
+        (tests/golden/g17_precision_contract.json); the precision-weighted re-triangulation consumes the planes."""
+        self._precision = bool(on)
+
+    @property
+    def precision(self) -> bool:
+        return self._precision
+
+    def precision_scale(self) -> Tuple[float, float]:
+        """(rx, ry): pixels of this package's match image per pixel of the model's last refinement stage.  The model's precision is in px^-2 of
+        that stage (W_stage / 2 px per normalised unit: the high-resolution pass where the preset has one, else the low-resolution one);
+        lfd_match_px counts (w_match - 1) / 2 px per normalised unit.  A plane entry is divided by the two ratios of its axes - the rule of
+        RoMaV2.prec_map_coordinates."""
+        m = self.model
+        hr = m.H_hr is not None and m.W_hr is not None
+        w_stage, h_stage = (int(m.W_hr), int(m.H_hr)) if hr else (int(m.W_lr), int(m.H_lr))
+        return (self.w_resized - 1) / float(w_stage), (self.h_resized - 1) / float(h_stage)
+
+    def _precision_plane(self, P: torch.Tensor) -> torch.Tensor:
+        """(H, W, 2, 2) of the model -> (H, W, 3) [p00, p01, p11] in match px^-2."""
+        rx, ry = self.precision_scale()
+        return torch.stack([P[..., 0, 0] / (rx * rx), P[..., 0, 1] / (rx * ry), P[..., 1, 1] / (ry * ry)], dim=-1).to(torch.float32).contiguous()
 
     def set_feature_cache(self, cache) -> None:
         """A core.scheduler.FeatureCache (or None to switch sharing off): backbone features (``model.f`` of the low-resolution
@@ -310,6 +339,8 @@ class RomaMatcher:
                     cert = pred["overlap_AB"][i].squeeze(-1).contiguous()
                     H, W = cert.shape
                     back = (pred["warp_BA"][i].contiguous(),) if self._backward else ()          # one chunk's own pair i: both branches above
+                    if self._precision:
+                        back = (back[0] if back else None, self._precision_plane(pred["precision_AB"][i]))
                     if self.two_channel:
                         out.append((warp_ab.contiguous(), cert) + back)
                     else:

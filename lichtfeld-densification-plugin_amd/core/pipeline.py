@@ -87,6 +87,8 @@ def _make_matcher(config, dev, progress_callback):
                           fused_local_corr=bool(config.exp("fused_local_corr")))
     if float(config.exp("cycle_thresh_px")) > 0.0:       # (a matcher built here starts with the backward warp off)
         matcher.set_backward_warp(True)
+    if bool(config.exp("precision_weighted_refine")):    # (... and hands out no precision planes)
+        matcher.set_precision(True)
     if not cached and progress_callback is not None:
         progress_callback(10.0, "RoMa v2 model installation complete. Starting matching...")
     return matcher
@@ -135,7 +137,14 @@ def _match_reference(local_i: int, packed: PackedReference, matcher, hot: HotPat
         if any(len(r) < 3 for r in results):
             raise RuntimeError(f"experimental['cycle_thresh_px'] is set but {type(matcher).__name__}.match_grids_batch returned no backward warp")
         hot.cycle_gate(warps, certs, [_as_device_map(r[2], dev) for r in results], axes)
-    return Matched(local_i, packed, hot.inputs(packed, warps, certs), axes, int(H), int(W), first_pair, want_debug)
+    precision = None
+    if hot.refine_weighted:
+        # RoMa-v2's precision planes: element 3 of the matcher's tuples, read in place by the weighted re-triangulation
+        if any(len(r) < 4 or r[3] is None for r in results):
+            raise RuntimeError("experimental['precision_weighted_refine'] is set but "
+                               f"{type(matcher).__name__}.match_grids_batch returned no precision plane")
+        precision = [_as_device_map(r[3], dev) for r in results]
+    return Matched(local_i, packed, hot.inputs(packed, warps, certs, precision), axes, int(H), int(W), first_pair, want_debug)
 
 
 def _as_device_map(t, dev) -> torch.Tensor:
@@ -217,6 +226,11 @@ def run_dense_pipeline(
             elif float(config.exp("cycle_thresh_px")) > 0.0:
                 raise ValueError("experimental['cycle_thresh_px'] asks for the forward-backward filter, which needs the matcher's backward warp, but the "
                                  f"injected matcher ({type(matcher).__name__}) does not declare supports_backward_warp")
+            if bool(getattr(matcher, "supports_precision", False)):
+                matcher.set_precision(bool(config.exp("precision_weighted_refine")))
+            elif config.exp("precision_weighted_refine"):
+                raise ValueError("experimental['precision_weighted_refine'] asks for the precision-weighted re-triangulation, which needs the matcher's "
+                                 f"precision planes, but the injected matcher ({type(matcher).__name__}) does not declare supports_precision")
             _announce(progress_callback, True)
         raise_if_cancelled(cancel_requested)
         size_wh = (int(matcher.w_resized), int(matcher.h_resized))
@@ -261,9 +275,13 @@ def run_dense_pipeline(
             log.info(f"Multi-view support filter: threshold {hot.support_thresh_px:g} px, at least {hot.min_support} other view(s), {n_in} points in, "
                      f"{n_dropped} dropped")
         if hot.refine:
-            n_refined, n_fallback = hot.refine_totals()
+            totals = hot.refine_totals()
+            n_refined, n_fallback = totals[:2]
             log.info(f"Multi-view re-triangulation: threshold {hot.support_thresh_px:g} px, {n_refined} points refined, {n_fallback} confirmed points "
                      f"kept their two-view position")
+        if hot.refine and hot.refine_weighted:
+            log.info(f"Precision-weighted re-triangulation: {n_refined} points refined, {n_fallback} confirmed points kept their two-view position, "
+                     f"{totals[2]} points solved with weighted rows")
     except BaseException as exc:
         if world == 1:
             raise

@@ -60,6 +60,10 @@ EXPERIMENTAL_DEFAULTS = {
     # reference confirm within support_threshold() is triangulated again from all the views that see it and moved there when the result still
     # passes the two-view tests and every confirming view still agrees.  Nothing is added or dropped.  False = off: no new code runs.
     "multiview_refine": False,
+    # ... with every view's rows weighted by the 2x2 precision matrix RoMa-v2 predicts for the match (lfd_refine_multiview_weighted, DESIGN.md
+    # 4.10) instead of equally.  Needs multiview_refine and a matcher that hands out the precision planes (supports_precision); a point with an
+    # unusable plane in any of its views is solved unweighted.  Never changes which points are emitted.  False = off: no new code runs.
+    "precision_weighted_refine": False,
 }
 
 
@@ -234,6 +238,11 @@ class DensePipelineConfig:
                 return "experimental['multiview_refine'] needs the ordered dense result; experimental['dense_tile_segments'] retires tiles unordered"
             if self.exchange_record_format() == "ply":
                 return "experimental['multiview_refine'] moves f32 rows; experimental['exchange_records'] must be 'f32' with it"
+        weighted = self.exp("precision_weighted_refine")
+        if not isinstance(weighted, (bool, np.bool_)):
+            return "experimental['precision_weighted_refine'] must be True or False"
+        if weighted and not refine:
+            return "experimental['precision_weighted_refine'] weights the rows of the multi-view re-triangulation: it needs experimental['multiview_refine'] = True"
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):
                 return "stream_output writes a PLY while the run proceeds: output_path must end in .ply"

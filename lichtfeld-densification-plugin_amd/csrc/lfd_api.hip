@@ -64,6 +64,7 @@ hipError_t lfd_corr_launch(const LfdCorrArgs& p, hipStream_t stream);     // lfd
 hipError_t lfd_cycle_launch(const LfdCycleArgs& p, hipStream_t stream);   // lfd_cycle.hip
 hipError_t lfd_support_launch(const LfdSupportArgs& p, hipStream_t stream);   // lfd_support.hip
 hipError_t lfd_refine_launch(const LfdRefineArgs& p, hipStream_t stream);     // lfd_refine.hip
+hipError_t lfd_refine_weighted_launch(const LfdRefineWArgs& p, hipStream_t stream);
 extern "C" __global__ void lfd_select_topm_kernel(LfdSelectArgs A);
 extern "C" __global__ void lfd_select_filter_mw_kernel(LfdSelectArgs A, LfdSelectNorms norms);
 extern "C" __global__ void lfd_select_begins_kernel(long long* pairs, long long stride, int n);
@@ -538,9 +539,11 @@ void lfd_destroy(lfd_context* ctx) {
     }
     for (hipEvent_t ev : ctx->kt_start) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->kt_stop) (void)hipEventDestroy(ev);
-    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->vox, &ctx->support_ws})
+    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->vox, &ctx->support_ws, &ctx->prec_tab})
         if (b->ptr) (void)hipFree(b->ptr);
     if (ctx->pinned_words) (void)hipHostFree(ctx->pinned_words);
+    if (ctx->prec_pinned) (void)hipHostFree(ctx->prec_pinned);
+    if (ctx->prec_free) (void)hipEventDestroy(ctx->prec_free);
     delete ctx;
 }
 
@@ -1505,6 +1508,71 @@ int lfd_refine_multiview(lfd_context* ctx, const lfd_batch* batch, const lfd_poi
     p.g.wm1 = L.kp.wm1; p.g.hm1 = L.kp.hm1; p.g.mask_sx = L.mask_sx; p.g.mask_sy = L.mask_sy;
     p.g.tau = support_thresh_px; p.g.reproj_thresh = reproj_thresh;
     LFD_HIP(ctx, lfd_refine_launch(p, ctx->stream));
+    return LFD_OK;
+}
+
+// The table of precision-plane pointers of a batch, where the kernel reads it: like the batch's descriptor tables it is compared with what the
+// device already holds and uploaded only when it differs, on the launch stream (an earlier launch still reading the old table precedes the
+// copy in it), from a pinned staging buffer that is waited for only while its last upload is still on its way.
+static int upload_precision_table(lfd_context* ctx, const lfd_batch* b, const float* const* precision, const float* const** d_tab) {
+    const size_t n = (size_t)b->n_refs * b->k, bytes = n * sizeof(const float*);
+    std::vector<unsigned char> blob(bytes, 0);
+    const float** tab = reinterpret_cast<const float**>(blob.data());
+    for (int r = 0; r < b->n_refs; ++r)
+        for (int j = 0; j < b->n_slots[r]; ++j) tab[(size_t)r * b->k + j] = precision[(size_t)r * b->k + j];
+    if (!ctx->prec_tab.ptr || ctx->prec_cache != blob) {
+        int rc = ensure(ctx, ctx->prec_tab, bytes);
+        if (rc != LFD_OK) return rc;
+        if (!ctx->prec_free) LFD_HIP(ctx, hipEventCreateWithFlags(&ctx->prec_free, hipEventDisableTiming));
+        if (ctx->prec_in_flight) { LFD_HIP(ctx, hipEventSynchronize(ctx->prec_free)); ctx->prec_in_flight = false; }
+        if (ctx->prec_pinned_bytes < bytes) {
+            if (ctx->prec_pinned) LFD_HIP(ctx, hipHostFree(ctx->prec_pinned));
+            ctx->prec_pinned = nullptr;
+            ctx->prec_pinned_bytes = std::max<size_t>(bytes * 2, 4096);
+            LFD_HIP(ctx, hipHostMalloc(&ctx->prec_pinned, ctx->prec_pinned_bytes, hipHostMallocDefault));
+        }
+        std::memcpy(ctx->prec_pinned, blob.data(), bytes);
+        LFD_HIP(ctx, hipMemcpyAsync(ctx->prec_tab.ptr, ctx->prec_pinned, bytes, hipMemcpyHostToDevice, ctx->stream));
+        LFD_HIP(ctx, hipEventRecord(ctx->prec_free, ctx->stream));
+        ctx->prec_in_flight = true;
+        ctx->prec_cache.swap(blob);
+    }
+    *d_tab = static_cast<const float* const*>(ctx->prec_tab.ptr);
+    return LFD_OK;
+}
+
+int lfd_refine_multiview_weighted(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets,
+                                  float support_thresh_px, float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status, int64_t* counters,
+                                  const float* const* precision) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_refine_check(in, ref_offsets, support_thresh_px, reproj_thresh, xyz_out, err_out, status))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_refine_multiview_weighted: ") + why);
+    lfd_params none;
+    std::memset(&none, 0, sizeof(none));
+    LfdLaunch L;
+    int rc = prepare_launch(ctx, batch, &none, nullptr, 0, L, nullptr);
+    if (rc != LFD_OK) return rc;
+    if (const char* why = lfd_refine_check_precision(batch, precision))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_refine_multiview_weighted: ") + why);
+    LfdRefineWArgs pw;
+    std::memset(&pw, 0, sizeof(pw));
+    rc = upload_precision_table(ctx, batch, precision, &pw.prec);
+    if (rc != LFD_OK) return rc;
+    LfdRefineArgs& p = pw.a;
+    p.n_wg = (int32_t)((in->capacity + 255) / 256);
+    p.refs = L.refs; p.slots = L.slots; p.ref_const = L.ref_const; p.pair_const = L.pair_const;
+    p.axis_x = L.axis_x; p.axis_y = L.axis_y;
+    p.offs = reinterpret_cast<const long long*>(ref_offsets);
+    p.xyz = in->xyz; p.err = in->err; p.cell = in->cell; p.slot = in->slot;
+    p.o_xyz = xyz_out; p.o_err = err_out; p.status = status;
+    p.counters = reinterpret_cast<unsigned long long*>(counters);
+    p.capacity = in->capacity;
+    p.n_refs = batch->n_refs; p.k = batch->k;
+    p.g.H = batch->H; p.g.W = batch->W; p.g.C = batch->warp_channels; p.g.w_match = batch->w_match; p.g.h_match = batch->h_match;
+    p.g.wm1 = L.kp.wm1; p.g.hm1 = L.kp.hm1; p.g.mask_sx = L.mask_sx; p.g.mask_sy = L.mask_sy;
+    p.g.tau = support_thresh_px; p.g.reproj_thresh = reproj_thresh;
+    LFD_HIP(ctx, lfd_refine_weighted_launch(pw, ctx->stream));
     return LFD_OK;
 }
 

@@ -93,6 +93,13 @@ struct lfd_context {
     DeviceBuffer seg_scan;         // tile segments: exclusive prefix of the last table handed to lfd_order_segments / lfd_pack_*_segments
     DeviceBuffer vox;              // lfd_voxel_downsample: statistics, digit counts, keys / indices (x 2), voxel starts; grown on demand
     DeviceBuffer support_ws;       // lfd_support_filter: support count of every input point, kept points per workgroup; grown on demand
+    // lfd_refine_multiview_weighted: the table of precision-plane pointers, uploaded on the launch stream when its content differs from the last
+    DeviceBuffer prec_tab;
+    std::vector<unsigned char> prec_cache;       // what `prec_tab` holds (or will hold once the stream has caught up)
+    void* prec_pinned = nullptr;                 // host staging of that upload
+    size_t prec_pinned_bytes = 0;
+    hipEvent_t prec_free = nullptr;              // behind the upload that last read `prec_pinned`
+    bool prec_in_flight = false;
     // N3 image preparation: coefficient / index tables of the last size pair
     DeviceBuffer img_tab, msk_tab;
     int img_key[4] = {0, 0, 0, 0}, img_ks[2] = {0, 0};

@@ -213,6 +213,145 @@ LFD_HD unsigned lfd_refine_point(const LfdRefineRef& ref, const LfdRefineSlot* s
     return n_extra | LFD_REFINE_ACCEPTED;
 }
 
+// ---- precision-weighted variant (lfd_refine_multiview_weighted) -------------------------------------------------------------------
+#define LFD_REFINE_WEIGHTED 0x40       /* status: the weighted rows were used (every participating view's precision was valid) */
+
+struct LfdRefineWSlot {          // beside LfdRefineSlot: the neighbour's precision plane and what turns its entries into camera px^-2
+    const float* prec;           // [H*W*3]: (q00, q01, q11) per cell, px^-2 of the neighbour's MATCH image
+    double rxx, rxy, ryy;        // 1 / (sx sx), 1 / (sx sy), 1 / (sy sy) through lfd_recip_refined (the products of f32 values are exact)
+};
+
+LFD_HD void lfd_refine_wslot_scale(float sx, float sy, LfdRefineWSlot& o) {
+    const double x = (double)sx, y = (double)sy;
+    o.rxx = lfd_recip_refined(x * x);
+    o.rxy = lfd_recip_refined(x * y);
+    o.ryy = lfd_recip_refined(y * y);
+}
+
+// valid(j): the three values finite and the matrix positive definite; the determinant in f64 (two exact products, one rounding)
+LFD_HD bool lfd_refine_prec_valid(float q00, float q01, float q11) {
+    const double a = (double)q00 * (double)q11, b = (double)q01 * (double)q01;
+    const double det = a - b;
+    return lfd_finite(q00) && lfd_finite(q01) && lfd_finite(q11) && q00 > 0.0f && q11 > 0.0f && det > 0.0;
+}
+
+// M (ten entries, as above) += ru^T (a ru + b rv) + rv^T (b ru + c rv): the view's two f32 rows weighted by the symmetric 2x2 (a b; b c).
+// Per column c: tu_c = fma(b, rv_c, a ru_c), tv_c = fma(c, rv_c, b ru_c); per entry (i <= j): M_ij = fma(rv_i, tv_j, fma(ru_i, tu_j, M_ij)).
+LFD_HD void lfd_refine_add_view_weighted(double* M, const float* Pi, float u, float v, double a, double b, double c) {
+    double ru[4], rv[4], tu[4], tv[4];
+    for (int e = 0; e < 4; ++e) {
+        const float fu = u * Pi[8 + e] - Pi[2 * e];
+        const float fv = v * Pi[8 + e] - Pi[2 * e + 1];
+        ru[e] = (double)fu; rv[e] = (double)fv;
+        tu[e] = fma(b, rv[e], a * ru[e]);
+        tv[e] = fma(c, rv[e], b * ru[e]);
+    }
+    M[0] = fma(rv[0], tv[0], fma(ru[0], tu[0], M[0])); M[1] = fma(rv[0], tv[1], fma(ru[0], tu[1], M[1]));
+    M[2] = fma(rv[0], tv[2], fma(ru[0], tu[2], M[2])); M[3] = fma(rv[0], tv[3], fma(ru[0], tu[3], M[3]));
+    M[4] = fma(rv[1], tv[1], fma(ru[1], tu[1], M[4])); M[5] = fma(rv[1], tv[2], fma(ru[1], tu[2], M[5]));
+    M[6] = fma(rv[1], tv[3], fma(ru[1], tu[3], M[6])); M[7] = fma(rv[2], tv[2], fma(ru[2], tu[2], M[7]));
+    M[8] = fma(rv[2], tv[3], fma(ru[2], tu[3], M[8])); M[9] = fma(rv[3], tv[3], fma(ru[3], tu[3], M[9]));
+}
+
+// One neighbour view into M: its precision in camera px^-2 (q / (s s)) times w2 = 1 / (pz pz), pz the f32 depth of the two-view X in that view
+// (what turns the algebraic rows into first-order pixel residuals).  lam += (p00 + p11) / 2.
+LFD_HD void lfd_refine_add_neighbour_weighted(double* M, double& lam, const LfdRefineSlot& sl, const LfdRefineWSlot& ws, float q00, float q01,
+                                              float q11, float X0, float X1, float X2, float u, float v) {
+    const double p00 = (double)q00 * ws.rxx, p01 = (double)q01 * ws.rxy, p11 = (double)q11 * ws.ryy;
+    const double z = (double)lfd_proj_row(sl.P, 2, X0, X1, X2, 1.0f);
+    const double w2 = lfd_recip_refined(z * z);
+    lam = lam + (p00 + p11) * 0.5;
+    lfd_refine_add_view_weighted(M, sl.P, u, v, w2 * p00, w2 * p01, w2 * p11);
+}
+
+// lfd_refine_point with precision-weighted rows.  q00 / q01 / q11 [j] (j < ns, j != s): the other neighbours' precision at the cell; qs[3]: the
+// winning slot's.  The candidates are lfd_refine_point's, by the same code.  Every participating view (slot s, the candidates) valid: M is
+// built in the order slot s, candidates by ascending j, reference LAST - it has no matching noise (a cell centre), so it enters isotropically
+// with lamA = the sum of the neighbours' mean precisions: as precise as everything that looked at it, which also makes the solution invariant
+// to a common scale of the planes.  Any of them invalid: today's unweighted M, in today's order - lfd_refine_point's bits.  Solve, acceptance
+// and fallback are lfd_refine_point's.  Status: n_extra | LFD_REFINE_WEIGHTED | LFD_REFINE_ACCEPTED.
+template <int KMAX>
+LFD_HD unsigned lfd_refine_point_weighted(const LfdRefineRef& ref, const LfdRefineSlot* sl, const LfdRefineWSlot* ws, int ns, int s,
+                                          const LfdRefineGeom& g, float xan, float yan, float xbn, float ybn, const float* cert, const float* wx,
+                                          const float* wy, const float* q00, const float* q01, const float* q11, const float* qs, float& X0,
+                                          float& X1, float& X2, float& err) {
+    unsigned cand = 0u;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = 0; j < KMAX; ++j) {
+        if (j < ns && j != s) {
+            bool live = lfd_support_live(cert[j]);
+            const uint8_t* mb = sl[j].mask_b;
+            if (live && mb) {
+                const long long m = lfd_support_mask_index(wx[j], wy[j], g.W, g.H, g.mask_sx, g.mask_sy, g.w_match, g.h_match);
+                live = m >= 0 && mb[m] != 0;
+            }
+            const bool agree = lfd_support_agree(sl[j].P, sl[j].sx, sl[j].sy, X0, X1, X2, wx[j], wy[j], g.wm1, g.hm1, g.tau);
+            cand |= (live && agree) ? (1u << j) : 0u;
+        }
+    }
+    if (cand == 0u) return 0u;
+    unsigned n_extra = 0u;
+    for (unsigned m = cand; m; m &= m - 1u) ++n_extra;
+    bool weighted = lfd_refine_prec_valid(qs[0], qs[1], qs[2]);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = 0; j < KMAX; ++j) {
+        if ((cand >> j) & 1u) weighted = lfd_refine_prec_valid(q00[j], q01[j], q11[j]) && weighted;
+    }
+
+    const float ua = lfd_match_px(xan, g.wm1) * ref.sx, va = lfd_match_px(yan, g.hm1) * ref.sy;
+    const float ub = lfd_match_px(xbn, g.wm1) * sl[s].sx, vb = lfd_match_px(ybn, g.hm1) * sl[s].sy;
+    double M[10];
+    if (weighted) {
+        for (int e = 0; e < 10; ++e) M[e] = 0.0;
+        double lam = 0.0;
+        lfd_refine_add_neighbour_weighted(M, lam, sl[s], ws[s], qs[0], qs[1], qs[2], X0, X1, X2, ub, vb);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int j = 0; j < KMAX; ++j) {
+            if ((cand >> j) & 1u) {
+                const float uj = lfd_match_px(wx[j], g.wm1) * sl[j].sx, vj = lfd_match_px(wy[j], g.hm1) * sl[j].sy;
+                lfd_refine_add_neighbour_weighted(M, lam, sl[j], ws[j], q00[j], q01[j], q11[j], X0, X1, X2, uj, vj);
+            }
+        }
+        const double z = (double)lfd_proj_row(ref.P, 2, X0, X1, X2, 1.0f);
+        const double wa = lam * lfd_recip_refined(z * z);
+        lfd_refine_add_view_weighted(M, ref.P, ua, va, wa, 0.0, wa);
+    } else {
+        lfd_refine_add_view(M, ref.P, ua, va, true);
+        lfd_refine_add_view(M, sl[s].P, ub, vb, false);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int j = 0; j < KMAX; ++j) {
+            if ((cand >> j) & 1u) {
+                const float uj = lfd_match_px(wx[j], g.wm1) * sl[j].sx, vj = lfd_match_px(wy[j], g.hm1) * sl[j].sy;
+                lfd_refine_add_view(M, sl[j].P, uj, vj, false);
+            }
+        }
+    }
+    const unsigned base = n_extra | (weighted ? (unsigned)LFD_REFINE_WEIGHTED : 0u);
+    double c[4];
+    lfd_null_vector_sym(M, c);
+    float Y0, Y1, Y2, e;
+    bool ok = lfd_refine_dehomogenise(c, Y0, Y1, Y2);
+    ok = lfd_refine_two_view(ref.P, sl[s].P, Y0, Y1, Y2, ua, va, ub, vb, g.reproj_thresh, e) && ok;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = 0; j < KMAX; ++j) {
+        if ((cand >> j) & 1u)
+            ok = lfd_support_agree(sl[j].P, sl[j].sx, sl[j].sy, Y0, Y1, Y2, wx[j], wy[j], g.wm1, g.hm1, g.tau) && ok;
+    }
+    if (!ok) return base;
+    X0 = Y0; X1 = Y1; X2 = Y2; err = e;
+    return base | LFD_REFINE_ACCEPTED;
+}
+
 // What a launch works on (device), by value in the kernel arguments.
 struct LfdRefineArgs {
     const void* refs;                  // LfdRefDesc [n_refs]
@@ -229,6 +368,11 @@ struct LfdRefineArgs {
     long long capacity;
     int32_t n_refs, k, n_wg;
     LfdRefineGeom g;
+};
+
+struct LfdRefineWArgs {                // lfd_refine_multiview_weighted: the same, counters [3] (+ points solved with weighted rows), and
+    LfdRefineArgs a;
+    const float* const* prec;          // [n_refs * k] precision planes (device table; entries at j >= n_slots[r] are not read)
 };
 
 // Arguments of lfd_refine_multiview / lfd_refine_multiview_host that do not depend on the batch; what is wrong with them, or null.
@@ -259,5 +403,14 @@ inline const char* lfd_refine_check(const lfd_points* in, const int64_t* ref_off
             if (a0 < b1 && b0 < a1) return "xyz_out, err_out and status overlap each other";
         }
     }
+    return nullptr;
+}
+
+// The one argument lfd_refine_multiview_weighted[_host] adds, checked behind the batch's own validation; what is wrong with it, or null.
+inline const char* lfd_refine_check_precision(const lfd_batch* b, const float* const* precision) {
+    if (!precision) return "null precision";
+    for (int r = 0; r < b->n_refs; ++r)
+        for (int j = 0; j < b->n_slots[r]; ++j)
+            if (!precision[(size_t)r * b->k + j]) return "null precision plane in a valid slot";
     return nullptr;
 }

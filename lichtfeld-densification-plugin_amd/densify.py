@@ -405,6 +405,8 @@ def _experimental_from_args(args) -> dict:
         exp["support_thresh_px"] = float(args.support_thresh_px)
     if bool(getattr(args, "multiview_refine", False)):
         exp["multiview_refine"] = True
+    if bool(getattr(args, "precision_weighted_refine", False)):
+        exp["precision_weighted_refine"] = True
     return exp
 
 
@@ -450,6 +452,9 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--multiview_refine", action="store_true",
                     help="multi-view re-triangulation: a point that other loaded neighbours of its reference confirm (within --support_thresh_px) is "
                          "triangulated again from all the views that see it; nothing is added or dropped")
+    ap.add_argument("--precision_weighted_refine", action="store_true",
+                    help="... with every view weighted by the precision matrix RoMa-v2 predicts for its match instead of equally (needs "
+                         "--multiview_refine)")
     ap.add_argument("--keep_threads", action="store_true",
                     help="leave torch's intra-op thread count alone (by default it is lowered to the container's CPU quota; the count decides the last "
                          "bits of upstream's sampling normaliser, so a run compared bit for bit with upstream keeps upstream's setting)")

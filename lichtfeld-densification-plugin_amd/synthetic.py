@@ -68,6 +68,28 @@ class SyntheticReference:
     image: torch.Tensor       # (h_match,w_match,3) u8
     w_match: int
     h_match: int
+    precision: Optional[torch.Tensor] = None   # noise_model="hetero": (k,H,W,3) f32, the TRUE precision (q00, q01, q11) of the matching noise, match px^-2
+
+
+HETERO_SIGMA_PX = (0.25, 2.0)     # noise_model="hetero": range of the two standard deviations, camera px of the neighbour
+
+
+def _triangle(phase: torch.Tensor) -> torch.Tensor:
+    """asin(sin(phase)) / pi + 0.5: a smooth-phase wave in [0, 1] that is UNIFORMLY spread over it (a plain sine piles up at the ends)."""
+    return torch.asin(torch.sin(phase).clamp(-1.0, 1.0)) / math.pi + 0.5
+
+
+def hetero_noise_fields(H: int, W: int, slot: int, ref_index: int, device="cpu"):
+    """(sigma1, sigma2, angle) (H, W) f64 of noise_model="hetero": analytic fields with slot- and reference-dependent phases (like the certainty
+    field of cert_mode="smooth"); the standard deviations are log-uniformly spread over HETERO_SIGMA_PX."""
+    gy = torch.linspace(0, 1, H, dtype=torch.float64, device=device).view(H, 1)
+    gx = torch.linspace(0, 1, W, dtype=torch.float64, device=device).view(1, W)
+    ph = 2.399963 * (slot + 1) + 0.37 * ref_index
+    lo, hi = math.log(HETERO_SIGMA_PX[0]), math.log(HETERO_SIGMA_PX[1])
+    s1 = torch.exp(lo + (hi - lo) * _triangle(7.0 * gx + 3.0 * gy + ph))
+    s2 = torch.exp(lo + (hi - lo) * _triangle(4.0 * gy - 5.0 * gx + 1.7 * ph))
+    ang = math.pi * torch.sin(2.0 * gx + 1.3 * ph) * torch.sin(3.0 * gy + 0.7 * ph)
+    return s1, s2, ang
 
 
 def _cam_t(cam: CameraRecord, device):
@@ -93,7 +115,7 @@ def synth_reference(cams: Sequence[CameraRecord], ref_index: int, nbr_indices: S
                     cert_mode: str = "smooth", device="cpu", far_depth: float = 25.0,
                     low_parallax_patch: Optional[Sequence[float]] = None,
                     patch_depths: Sequence[float] = (6.0, 60.0), out_of_range: float = 0.0,
-                    occlusion_steps: bool = False) -> SyntheticReference:
+                    occlusion_steps: bool = False, noise_model: str = "iid") -> SyntheticReference:
     """Dense warp + certainty of ``ref_index`` into each neighbour.
 
     low_parallax_patch: (y0, y1, x0, x1) as fractions of the grid.  Inside it the surface is replaced by a ramp of
@@ -111,7 +133,14 @@ def synth_reference(cams: Sequence[CameraRecord], ref_index: int, nbr_indices: S
                of the neighbour - x (y) beyond [-1, 1], through the border and on to 2.5 image half-widths outside - as the real matcher does for
                content the neighbour does not see; upstream does not reject such coordinates (core/pipeline.py:697-703), the reprojection test does.
     occlusion_steps: the surface gets depth discontinuities (a checker of foreground slabs at 0.65 of the depth): the warp jumps at their edges.
+    noise_model: "iid"    - the matching noise is noise_px times a standard-normal draw, the same everywhere
+                 "hetero" - the SAME standard-normal draw shaped per cell and slot by the Cholesky factor of a covariance whose two standard
+                            deviations (log-uniform over HETERO_SIGMA_PX camera px, whatever noise_px > 0 is) and angle are the analytic fields of
+                            ``hetero_noise_fields``; the result carries the TRUE precision planes of that noise, in match px^-2, as RoMa-v2
+                            predicts them
     """
+    if noise_model not in ("iid", "hetero"):
+        raise ValueError(f"noise_model must be 'iid' or 'hetero', got {noise_model!r}")
     dev = torch.device(device)
     gen = torch.Generator(device="cpu").manual_seed(int(seed) * 7919 + int(ref_index) * 104729 + 13)
     camA = cams[ref_index]
@@ -146,7 +175,7 @@ def synth_reference(cams: Sequence[CameraRecord], ref_index: int, nbr_indices: S
         s[iy0:iy1, ix0:ix1] = ramp.view(1, -1).expand(iy1 - iy0, ix1 - ix0) / dirs_w[iy0:iy1, ix0:ix1].norm(dim=-1)
     Xw = CA.view(1, 1, 3) + s.unsqueeze(-1) * dirs_w
 
-    warps, certs = [], []
+    warps, certs, precs = [], [], []
     for slot, nb in enumerate(nbr_indices):
         camB = cams[nb]
         KB, RB, tB, _ = _cam_t(camB, dev)
@@ -154,10 +183,26 @@ def synth_reference(cams: Sequence[CameraRecord], ref_index: int, nbr_indices: S
         z = Xc[..., 2]
         uB = KB[0, 0] * Xc[..., 0] / z + KB[0, 2]
         vB = KB[1, 1] * Xc[..., 1] / z + KB[1, 2]
-        if noise_px > 0:      # matching noise, in full-resolution camera pixels of the neighbour
+        if noise_px > 0 and noise_model == "iid":      # matching noise, in full-resolution camera pixels of the neighbour
             nz = torch.randn((2, H, W), generator=gen, dtype=torch.float64).to(dev) * noise_px
             uB = uB + nz[0]
             vB = vB + nz[1]
+        elif noise_px > 0:
+            nz = torch.randn((2, H, W), generator=gen, dtype=torch.float64).to(dev)        # the same use of the generator
+            s1, s2, ang = hetero_noise_fields(H, W, slot, ref_index, dev)
+            ca, sa = torch.cos(ang), torch.sin(ang)
+            c00 = ca * ca * s1 * s1 + sa * sa * s2 * s2                # covariance R diag(s1^2, s2^2) R^T
+            c01 = ca * sa * (s1 * s1 - s2 * s2)
+            c11 = sa * sa * s1 * s1 + ca * ca * s2 * s2
+            l00 = torch.sqrt(c00)
+            l10 = c01 / l00
+            l11 = torch.sqrt(c11 - l10 * l10)
+            uB = uB + l00 * nz[0]
+            vB = vB + l10 * nz[0] + l11 * nz[1]
+            i1, i2 = 1.0 / (s1 * s1), 1.0 / (s2 * s2)                   # precision R diag(1/s1^2, 1/s2^2) R^T, camera px^-2 ...
+            sx, sy = camB.width / float(w_match), camB.height / float(h_match)
+            precs.append(torch.stack([(ca * ca * i1 + sa * sa * i2) * (sx * sx), (ca * sa * (i1 - i2)) * (sx * sy),
+                                      (sa * sa * i1 + ca * ca * i2) * (sy * sy)], dim=-1).to(torch.float32))      # ... to match px^-2
         xB = uB / (camB.width / float(w_match))
         yB = vB / (camB.height / float(h_match))
         xBn = xB / (0.5 * (w_match - 1)) - 1.0
@@ -204,7 +249,8 @@ def synth_reference(cams: Sequence[CameraRecord], ref_index: int, nbr_indices: S
     return SyntheticReference(
         ref_index=int(ref_index), nbr_indices=[int(n) for n in nbr_indices],
         warp=torch.stack(warps, 0).contiguous(), cert=torch.stack(certs, 0).contiguous(),
-        image=synth_image(h_match, w_match, seed * 1000 + ref_index, dev), w_match=int(w_match), h_match=int(h_match))
+        image=synth_image(h_match, w_match, seed * 1000 + ref_index, dev), w_match=int(w_match), h_match=int(h_match),
+        precision=torch.stack(precs, 0).contiguous() if precs else None)
 
 
 def ring_neighbours(n_cams: int, ref_index: int, k: int) -> List[int]:
@@ -283,16 +329,21 @@ class SyntheticMatcher:
     accepts_device_images = True
     supports_feature_keys = True
     supports_backward_warp = True     # set_backward_warp(True): match_grids_batch returns (warp, cert, warp_BA) triples
+    supports_precision = True         # set_precision(True): ... (warp, cert, warp_BA or None, precision) 4-tuples
 
     def __init__(self, cams: Sequence[CameraRecord], setting: str = "fast", device="cpu", *, noise_px: float = 0.5, outlier_frac: float = 0.05,
                  channels: int = 2, seed: int = 0, latency_s_per_pair: float = 0.0, cert_mode: str = "smooth", occlusion_steps: bool = False,
-                 out_of_range: float = 0.0):
+                 out_of_range: float = 0.0, noise_model: str = "iid"):
         self.cams, self.device = list(cams), torch.device(device)
         h_lr, w_lr, self.H, self.W = ROMA_PRESETS[setting]
         self.w_resized, self.h_resized = int(w_lr), int(h_lr)
         self.kw = dict(noise_px=noise_px, outlier_frac=outlier_frac, channels=int(channels), seed=int(seed), cert_mode=cert_mode)
         if occlusion_steps or out_of_range:
             self.kw.update(occlusion_steps=bool(occlusion_steps), out_of_range=float(out_of_range))
+        if noise_model != "iid":
+            self.kw.update(noise_model=str(noise_model))
+        self.precision = False
+        self.prec_table: dict = {}
         self.backward = False
         self.back_table: dict = {}
         self.latency = float(latency_s_per_pair)
@@ -327,20 +378,42 @@ class SyntheticMatcher:
         reference - ``synth_reference(cams, nbr, [ref])`` with the matcher's noise and outliers - i.e. normalised A-coordinates on B's grid."""
         self.backward = bool(on)
 
+    def set_precision(self, on: bool) -> None:
+        """``match_grids_batch`` hands out (warp, cert, warp_BA or None, precision) 4-tuples: precision (H, W, 3) f32 is the TRUE precision of the
+        matching noise in match px^-2 - the planes of ``noise_model="hetero"``, or I / noise_px^2 under "iid"."""
+        self.precision = bool(on)
+
+    def _planes(self, key, s):
+        if s.precision is not None:
+            return [s.precision[j].contiguous() for j in range(len(key[1]))]
+        out = []
+        inv = 1.0 / max(float(self.kw["noise_px"]), 1e-3) ** 2
+        for n in key[1]:
+            sx, sy = self.cams[n].width / float(self.w_resized), self.cams[n].height / float(self.h_resized)
+            out.append(torch.tensor([inv * sx * sx, 0.0, inv * sy * sy], dtype=torch.float32, device=self.device).expand(self.H, self.W, 3).contiguous())
+        return out
+
     def fields(self, ref: int, nbrs: Sequence[int]):
         key = (int(ref), tuple(int(n) for n in nbrs))
         hit = self.table.get(key)
-        if hit is None:
+        prec = self.prec_table.get(key) if self.precision else None
+        if hit is None or (self.precision and prec is None):
             s = synth_reference(self.cams, key[0], list(key[1]), self.H, self.W, self.w_resized, self.h_resized, device=self.device, **self.kw)
-            hit = [(s.warp[j].contiguous(), s.cert[j].contiguous()) for j in range(len(key[1]))]
-        if not self.backward:
+            hit = [(s.warp[j].contiguous(), s.cert[j].contiguous()) for j in range(len(key[1]))] if hit is None else hit
+            if self.precision:
+                prec = self._planes(key, s)
+        if not self.backward and not self.precision:
             return key, hit
-        back = self.back_table.get(key)
-        if back is None:
-            back = [synth_reference(self.cams, n, [key[0]], self.H, self.W, self.w_resized, self.h_resized, device=self.device,
-                                    **self.kw).warp[0][..., -2:].contiguous() for n in key[1]]
+        back = [None] * len(hit)
+        if self.backward:
+            back = self.back_table.get(key)
+            if back is None:
+                back = [synth_reference(self.cams, n, [key[0]], self.H, self.W, self.w_resized, self.h_resized, device=self.device,
+                                        **self.kw).warp[0][..., -2:].contiguous() for n in key[1]]
         # (the driver gates the certainty plane it is handed in place: the table keeps its own)
-        return key, [(w, c.clone(), b) for (w, c), b in zip(hit, back)]
+        if not self.precision:
+            return key, [(w, c.clone(), b) for (w, c), b in zip(hit, back)]
+        return key, [(w, c.clone(), b, q) for (w, c), b, q in zip(hit, back, prec)]
 
     def precompute(self, refs: Sequence[int], nn_table, nns_per_ref: int) -> int:
         """The fields of these references with the neighbours the driver will load (``nn_table[r][:nns_per_ref]`` without r itself)."""
@@ -351,6 +424,8 @@ class SyntheticMatcher:
                 self.table[key] = [v[:2] for v in val]
                 if self.backward:
                     self.back_table[key] = [v[2] for v in val]
+                if self.precision:
+                    self.prec_table[key] = [v[3] for v in val]
         return len(self.table)
 
     def match_grids_batch(self, imA, imB_list, keys=None):
