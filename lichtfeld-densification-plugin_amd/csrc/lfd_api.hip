@@ -64,7 +64,6 @@ hipError_t lfd_corr_launch(const LfdCorrArgs& p, hipStream_t stream);     // lfd
 hipError_t lfd_cycle_launch(const LfdCycleArgs& p, hipStream_t stream);   // lfd_cycle.hip
 hipError_t lfd_support_launch(const LfdSupportArgs& p, hipStream_t stream);   // lfd_support.hip
 hipError_t lfd_refine_launch(const LfdRefineArgs& p, hipStream_t stream);     // lfd_refine.hip
-hipError_t lfd_refine_weighted_launch(const LfdRefineWArgs& p, hipStream_t stream);
 extern "C" __global__ void lfd_select_topm_kernel(LfdSelectArgs A);
 extern "C" __global__ void lfd_select_filter_mw_kernel(LfdSelectArgs A, LfdSelectNorms norms);
 extern "C" __global__ void lfd_select_begins_kernel(long long* pairs, long long stride, int n);
@@ -1444,6 +1443,14 @@ int lfd_cycle_gate(lfd_context* ctx, int32_t n_pairs, const float* const* cert, 
 }
 
 // ---- multi-view support filter (lfd_support.hip) -------------------------------------------------------------------------------------------
+static LfdSupportGeom launch_geom(const lfd_batch* batch, const LfdLaunch& L, float support_thresh_px, float reproj_thresh) {
+    LfdSupportGeom g;
+    g.H = batch->H; g.W = batch->W; g.C = batch->warp_channels; g.w_match = batch->w_match; g.h_match = batch->h_match;
+    g.wm1 = L.kp.wm1; g.hm1 = L.kp.hm1; g.mask_sx = L.mask_sx; g.mask_sy = L.mask_sy;
+    g.tau = support_thresh_px; g.reproj_thresh = reproj_thresh;
+    return g;
+}
+
 int lfd_support_filter(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets_in, int32_t min_support,
                        float support_thresh_px, const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out, uint8_t* support) {
     if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
@@ -1472,45 +1479,14 @@ int lfd_support_filter(lfd_context* ctx, const lfd_batch* batch, const lfd_point
     p.counts = static_cast<uint8_t*>(ctx->support_ws.ptr);
     p.wg_kept = reinterpret_cast<unsigned*>(static_cast<unsigned char*>(ctx->support_ws.ptr) + counts_bytes);
     p.capacity = in->capacity;
-    p.n_refs = batch->n_refs; p.k = batch->k; p.H = batch->H; p.W = batch->W; p.C = batch->warp_channels;
-    p.w_match = batch->w_match; p.h_match = batch->h_match; p.min_support = min_support;
-    p.wm1 = L.kp.wm1; p.hm1 = L.kp.hm1; p.mask_sx = L.mask_sx; p.mask_sy = L.mask_sy; p.tau = support_thresh_px;
+    p.n_refs = batch->n_refs; p.k = batch->k; p.min_support = min_support;
+    p.g = launch_geom(batch, L, support_thresh_px, 0.0f);
     if (seg_counts_out) LFD_HIP(ctx, hipMemsetAsync(seg_counts_out, 0, sizeof(int32_t) * (size_t)batch->n_refs * batch->k, ctx->stream));
     LFD_HIP(ctx, lfd_support_launch(p, ctx->stream));
     return LFD_OK;
 }
 
 // ---- multi-view re-triangulation of supported points (lfd_refine.hip) ------------------------------------------------------------------------
-int lfd_refine_multiview(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets, float support_thresh_px,
-                         float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status, int64_t* counters) {
-    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
-    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
-    if (const char* why = lfd_refine_check(in, ref_offsets, support_thresh_px, reproj_thresh, xyz_out, err_out, status))
-        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_refine_multiview: ") + why);
-    // the batch's tables and per-pair constants, derived again only when the batch differs from the last one seen (no threshold reaches them)
-    lfd_params none;
-    std::memset(&none, 0, sizeof(none));
-    LfdLaunch L;
-    int rc = prepare_launch(ctx, batch, &none, nullptr, 0, L, nullptr);
-    if (rc != LFD_OK) return rc;
-    LfdRefineArgs p;
-    std::memset(&p, 0, sizeof(p));
-    p.n_wg = (int32_t)((in->capacity + 255) / 256);
-    p.refs = L.refs; p.slots = L.slots; p.ref_const = L.ref_const; p.pair_const = L.pair_const;
-    p.axis_x = L.axis_x; p.axis_y = L.axis_y;
-    p.offs = reinterpret_cast<const long long*>(ref_offsets);
-    p.xyz = in->xyz; p.err = in->err; p.cell = in->cell; p.slot = in->slot;
-    p.o_xyz = xyz_out; p.o_err = err_out; p.status = status;
-    p.counters = reinterpret_cast<unsigned long long*>(counters);
-    p.capacity = in->capacity;
-    p.n_refs = batch->n_refs; p.k = batch->k;
-    p.g.H = batch->H; p.g.W = batch->W; p.g.C = batch->warp_channels; p.g.w_match = batch->w_match; p.g.h_match = batch->h_match;
-    p.g.wm1 = L.kp.wm1; p.g.hm1 = L.kp.hm1; p.g.mask_sx = L.mask_sx; p.g.mask_sy = L.mask_sy;
-    p.g.tau = support_thresh_px; p.g.reproj_thresh = reproj_thresh;
-    LFD_HIP(ctx, lfd_refine_launch(p, ctx->stream));
-    return LFD_OK;
-}
-
 // The table of precision-plane pointers of a batch, where the kernel reads it: like the batch's descriptor tables it is compared with what the
 // device already holds and uploaded only when it differs, on the launch stream (an earlier launch still reading the old table precedes the
 // copy in it), from a pinned staging buffer that is waited for only while its last upload is still on its way.
@@ -1541,25 +1517,28 @@ static int upload_precision_table(lfd_context* ctx, const lfd_batch* b, const fl
     return LFD_OK;
 }
 
-int lfd_refine_multiview_weighted(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets,
-                                  float support_thresh_px, float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status, int64_t* counters,
-                                  const float* const* precision) {
+// Both re-triangulation calls.  weighted: lfd_refine_multiview_weighted (precision checked behind the batch, its table uploaded, three
+// counters); otherwise lfd_refine_multiview (two).  name: the entry point, for the messages.
+static int refine_impl(lfd_context* ctx, const char* name, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets,
+                       float support_thresh_px, float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status, int64_t* counters,
+                       const float* const* precision, bool weighted) {
     if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
     if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
     if (const char* why = lfd_refine_check(in, ref_offsets, support_thresh_px, reproj_thresh, xyz_out, err_out, status))
-        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_refine_multiview_weighted: ") + why);
+        return fail(ctx, LFD_ERR_INVALID, std::string(name) + ": " + why);
+    // the batch's tables and per-pair constants, derived again only when the batch differs from the last one seen (no threshold reaches them)
     lfd_params none;
     std::memset(&none, 0, sizeof(none));
     LfdLaunch L;
     int rc = prepare_launch(ctx, batch, &none, nullptr, 0, L, nullptr);
     if (rc != LFD_OK) return rc;
-    if (const char* why = lfd_refine_check_precision(batch, precision))
-        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_refine_multiview_weighted: ") + why);
-    LfdRefineWArgs pw;
-    std::memset(&pw, 0, sizeof(pw));
-    rc = upload_precision_table(ctx, batch, precision, &pw.prec);
-    if (rc != LFD_OK) return rc;
-    LfdRefineArgs& p = pw.a;
+    LfdRefineArgs p;
+    std::memset(&p, 0, sizeof(p));
+    if (weighted) {
+        if (const char* why = lfd_refine_check_precision(batch, precision)) return fail(ctx, LFD_ERR_INVALID, std::string(name) + ": " + why);
+        rc = upload_precision_table(ctx, batch, precision, &p.prec);
+        if (rc != LFD_OK) return rc;
+    }
     p.n_wg = (int32_t)((in->capacity + 255) / 256);
     p.refs = L.refs; p.slots = L.slots; p.ref_const = L.ref_const; p.pair_const = L.pair_const;
     p.axis_x = L.axis_x; p.axis_y = L.axis_y;
@@ -1569,11 +1548,22 @@ int lfd_refine_multiview_weighted(lfd_context* ctx, const lfd_batch* batch, cons
     p.counters = reinterpret_cast<unsigned long long*>(counters);
     p.capacity = in->capacity;
     p.n_refs = batch->n_refs; p.k = batch->k;
-    p.g.H = batch->H; p.g.W = batch->W; p.g.C = batch->warp_channels; p.g.w_match = batch->w_match; p.g.h_match = batch->h_match;
-    p.g.wm1 = L.kp.wm1; p.g.hm1 = L.kp.hm1; p.g.mask_sx = L.mask_sx; p.g.mask_sy = L.mask_sy;
-    p.g.tau = support_thresh_px; p.g.reproj_thresh = reproj_thresh;
-    LFD_HIP(ctx, lfd_refine_weighted_launch(pw, ctx->stream));
+    p.g = launch_geom(batch, L, support_thresh_px, reproj_thresh);
+    LFD_HIP(ctx, lfd_refine_launch(p, ctx->stream));
     return LFD_OK;
+}
+
+int lfd_refine_multiview(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets, float support_thresh_px,
+                         float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status, int64_t* counters) {
+    return refine_impl(ctx, "lfd_refine_multiview", batch, in, ref_offsets, support_thresh_px, reproj_thresh, xyz_out, err_out, status, counters,
+                       nullptr, false);
+}
+
+int lfd_refine_multiview_weighted(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets,
+                                  float support_thresh_px, float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status, int64_t* counters,
+                                  const float* const* precision) {
+    return refine_impl(ctx, "lfd_refine_multiview_weighted", batch, in, ref_offsets, support_thresh_px, reproj_thresh, xyz_out, err_out, status,
+                       counters, precision, true);
 }
 
 int lfd_copy_segments(void* hip_stream, int32_t device_index, const void* src, void* dst, const lfd_copy_segment* segs, int32_t n) {

@@ -245,3 +245,35 @@ struct LfdSelectNorms {
 #define LFD_CHAIN_TENT 656            // [LFD_SELECT_BATCH_MAX + 1]: 1 + where reference y starts IF its predecessor's second round is its last (published when the predecessor's first round is counted)
 #define LFD_CHAIN_BYTES 1024
 struct LfdSeedBatch { unsigned seed[LFD_SELECT_BATCH_MAX]; };
+
+// ---- what the per-point kernels behind triangulation share (lfd_support.hip, lfd_refine.hip) ------------------------------------------------
+#if defined(__HIPCC__)
+#include "lfd_support.hpp"
+
+struct LfdPointSpan {           // the input points of a 256-lane workgroup: lane tid has point i (ii: the point it reads)
+    long long total, i, last, ii;
+    bool any, mine;             // any: the workgroup has points at all (uniform); mine: this lane has one
+};
+
+__device__ __forceinline__ LfdPointSpan lfd_point_span(const long long* offs, int n_refs, long long capacity) {
+    LfdPointSpan w;
+    w.total = lfd_support_clamp(offs[n_refs], capacity);
+    const long long base = (long long)blockIdx.x * 256;
+    w.any = base < w.total;
+    w.i = base + (int)threadIdx.x;
+    w.mine = w.i < w.total;
+    w.last = (base + 256 < w.total ? base + 256 : w.total) - 1;
+    w.ii = w.mine ? w.i : w.last;                                      // idle lanes read the last point and store nothing
+    return w;
+}
+
+// Lanes tid < ns copy the descriptors and pair constants of reference rr's neighbours into sh[0 .. ns).  Every lane of the workgroup calls it;
+// the barriers on either side are the caller's.
+__device__ __forceinline__ void lfd_stage_slots(LfdSlot* sh, const void* slots, const LfdPairConst* pair_const, int rr, int k, int ns) {
+    const int tid = (int)threadIdx.x;
+    if (tid < ns) {
+        const LfdSlotDesc& d = static_cast<const LfdSlotDesc*>(slots)[(size_t)rr * k + tid];
+        lfd_slot_fill(sh[tid], d.cert, d.warp, d.mask_b, pair_const[(size_t)rr * k + tid]);
+    }
+}
+#endif

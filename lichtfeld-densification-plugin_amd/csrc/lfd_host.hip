@@ -319,6 +319,39 @@ int lfd_cycle_gate_host(lfd_context* ctx, int32_t n_pairs, const float* const* c
     return LFD_OK;
 }
 
+namespace {
+
+// The slot table of the twins behind triangulation: what lfd_stage_slots stages per reference on the device, for every reference at once.
+// slot[r * LFD_MAX_SLOTS + j], j < n_slots[r]; rref[r] (when asked for): the reference's own constants.
+void make_slot_table(const lfd_context* ctx, const HostLaunch& L, std::vector<LfdSlot>& slot, std::vector<LfdRefineRef>* rref) {
+    const lfd_batch* b = L.b;
+    slot.resize((size_t)b->n_refs * LFD_MAX_SLOTS);
+    if (rref) rref->resize((size_t)b->n_refs);
+    for (int r = 0; r < b->n_refs; ++r) {
+        HostRef R;
+        make_ref(ctx, L, r, R);
+        if (rref) {
+            LfdRefineRef& o = (*rref)[(size_t)r];
+            for (int e = 0; e < 12; ++e) o.P[e] = R.rc.P[e];
+            o.sx = R.rc.sx; o.sy = R.rc.sy;
+        }
+        for (int j = 0; j < b->n_slots[r]; ++j) {
+            const size_t sj = (size_t)r * b->k + j;
+            lfd_slot_fill(slot[(size_t)r * LFD_MAX_SLOTS + j], b->cert[sj], b->warp[sj], b->mask_b ? b->mask_b[sj] : nullptr, R.pc[j]);
+        }
+    }
+}
+
+LfdSupportGeom make_geom(const HostLaunch& L, float support_thresh_px, float reproj_thresh) {
+    const lfd_batch* b = L.b;
+    LfdSupportGeom g;
+    g.H = b->H; g.W = b->W; g.C = b->warp_channels; g.w_match = b->w_match; g.h_match = b->h_match;
+    g.wm1 = L.kp.wm1; g.hm1 = L.kp.hm1; g.mask_sx = L.mask_sx; g.mask_sy = L.mask_sy; g.tau = support_thresh_px; g.reproj_thresh = reproj_thresh;
+    return g;
+}
+
+}  // namespace
+
 int lfd_support_filter_host(lfd_context* ctx, const lfd_batch* b, const lfd_points* in, const int64_t* ref_offsets_in, int32_t min_support,
                             float support_thresh_px, const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out, uint8_t* support) {
     if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
@@ -332,8 +365,9 @@ int lfd_support_filter_host(lfd_context* ctx, const lfd_batch* b, const lfd_poin
     if (rc != LFD_OK) return rc;
     HostLaunch L;
     prepare_host(b, &none, L);
-    std::vector<HostRef> refs((size_t)b->n_refs);
-    for (int r = 0; r < b->n_refs; ++r) make_ref(ctx, L, r, refs[(size_t)r]);
+    std::vector<LfdSlot> slot;
+    make_slot_table(ctx, L, slot, nullptr);
+    const LfdSupportGeom g = make_geom(L, support_thresh_px, 0.0f);
     const long long cap = in->capacity;
     const long long* offs = reinterpret_cast<const long long*>(ref_offsets_in);
     const long long total = lfd_support_clamp(offs[b->n_refs], cap);
@@ -346,19 +380,11 @@ int lfd_support_filter_host(lfd_context* ctx, const lfd_batch* b, const lfd_poin
             int n = 0;
             if (cell >= 0 && cell < L.HW) {                             // no address is formed from a cell outside the grid
                 const float X0 = in->xyz[3 * i], X1 = in->xyz[3 * i + 1], X2 = in->xyz[3 * i + 2];
+                const LfdSlot* sl = &slot[(size_t)r * LFD_MAX_SLOTS];
                 for (int j = 0; j < b->n_slots[r]; ++j) {
                     if (j == s) continue;
-                    const size_t sj = (size_t)r * b->k + j;
-                    const float* wv = b->warp[sj] + (size_t)cell * b->warp_channels + (b->warp_channels - 2);
-                    bool live = lfd_support_live(b->cert[sj][cell]);
-                    const uint8_t* mb = b->mask_b ? b->mask_b[sj] : nullptr;
-                    if (live && mb) {
-                        const long long m = lfd_support_mask_index(wv[0], wv[1], b->W, b->H, L.mask_sx, L.mask_sy, b->w_match, b->h_match);
-                        live = m >= 0 && mb[m] != 0;
-                    }
-                    const LfdPairConst& pc = refs[(size_t)r].pc[j];
-                    const bool agree = lfd_support_agree(pc.P, pc.sx, pc.sy, X0, X1, X2, wv[0], wv[1], L.kp.wm1, L.kp.hm1, support_thresh_px);
-                    n += (live && agree) ? 1 : 0;
+                    const float* wv = sl[j].warp + (size_t)cell * g.C + (g.C - 2);
+                    n += lfd_support_candidate(sl[j], g, sl[j].cert[cell], wv[0], wv[1], X0, X1, X2) ? 1 : 0;
                 }
             }
             counts[(size_t)i] = (uint8_t)n;
@@ -386,120 +412,40 @@ int lfd_support_filter_host(lfd_context* ctx, const lfd_batch* b, const lfd_poin
     return LFD_OK;
 }
 
-int lfd_refine_multiview_host(lfd_context* ctx, const lfd_batch* b, const lfd_points* in, const int64_t* ref_offsets, float support_thresh_px,
-                              float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status, int64_t* counters) {
+// Both re-triangulation twins.  weighted: lfd_refine_multiview_weighted_host (precision checked behind the batch - a null one is refused, not
+// taken for the other call -, three counters); otherwise lfd_refine_multiview_host (two).  name: the entry point, for the messages.
+static int refine_host_impl(lfd_context* ctx, const char* name, const lfd_batch* b, const lfd_points* in, const int64_t* ref_offsets,
+                            float support_thresh_px, float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status, int64_t* counters,
+                            const float* const* precision, bool weighted) {
     if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
     if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
     if (const char* why = lfd_refine_check(in, ref_offsets, support_thresh_px, reproj_thresh, xyz_out, err_out, status))
-        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_refine_multiview_host: ") + why);
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string(name) + ": " + why);
     lfd_params none;
     std::memset(&none, 0, sizeof(none));
     int rc = validate_host(ctx, b, &none);
     if (rc != LFD_OK) return rc;
+    if (weighted)
+        if (const char* why = lfd_refine_check_precision(b, precision)) return lfd_fail(ctx, LFD_ERR_INVALID, std::string(name) + ": " + why);
     HostLaunch L;
     prepare_host(b, &none, L);
-    std::vector<LfdRefineRef> rref((size_t)b->n_refs);
-    std::vector<LfdRefineSlot> rslot((size_t)b->n_refs * LFD_MAX_SLOTS);
-    for (int r = 0; r < b->n_refs; ++r) {
-        HostRef R;
-        make_ref(ctx, L, r, R);
-        for (int e = 0; e < 12; ++e) rref[(size_t)r].P[e] = R.rc.P[e];
-        rref[(size_t)r].sx = R.rc.sx; rref[(size_t)r].sy = R.rc.sy;
-        for (int j = 0; j < b->n_slots[r]; ++j) {
-            const size_t sj = (size_t)r * b->k + j;
-            LfdRefineSlot& o = rslot[(size_t)r * LFD_MAX_SLOTS + j];
-            o.cert = b->cert[sj]; o.warp = b->warp[sj]; o.mask_b = b->mask_b ? b->mask_b[sj] : nullptr;
-            for (int e = 0; e < 12; ++e) o.P[e] = R.pc[j].P[e];
-            o.sx = R.pc[j].sx; o.sy = R.pc[j].sy;
-        }
-    }
-    LfdRefineGeom g;
-    g.H = b->H; g.W = b->W; g.C = b->warp_channels; g.w_match = b->w_match; g.h_match = b->h_match;
-    g.wm1 = L.kp.wm1; g.hm1 = L.kp.hm1; g.mask_sx = L.mask_sx; g.mask_sy = L.mask_sy; g.tau = support_thresh_px; g.reproj_thresh = reproj_thresh;
-    const long long cap = in->capacity;
-    const long long* offs = reinterpret_cast<const long long*>(ref_offsets);
-    const long long total = lfd_support_clamp(offs[b->n_refs], cap);
-    const int n_chunks = (int)((total + kChunk - 1) / kChunk);
-    std::vector<long long> refined((size_t)n_chunks, 0), fallback((size_t)n_chunks, 0);
-    parallel_chunks(ctx, n_chunks, [&](int c) {
-        const long long i1 = std::min<long long>(total, (long long)(c + 1) * kChunk);
-        for (long long i = (long long)c * kChunk; i < i1; ++i) {
-            const int r = lfd_support_ref_of(offs, b->n_refs, cap, i);
-            const int cell = in->cell[i], s = (int)in->slot[i], ns = b->n_slots[r];
-            float X0 = in->xyz[3 * i], X1 = in->xyz[3 * i + 1], X2 = in->xyz[3 * i + 2], err = in->err[i];
-            unsigned st = 0u;
-            if (cell >= 0 && cell < L.HW && s < ns) {                   // no address is formed from a cell outside the grid
-                const LfdRefineSlot* sl = &rslot[(size_t)r * LFD_MAX_SLOTS];
-                float cj[LFD_MAX_SLOTS], wx[LFD_MAX_SLOTS], wy[LFD_MAX_SLOTS];
-                const float* wp = sl[s].warp + (size_t)cell * g.C;
-                const float xbn = wp[g.C - 2], ybn = wp[g.C - 1];
-                float xan, yan;
-                if (g.C == 4) { xan = wp[0]; yan = wp[1]; }
-                else { const int y = cell / g.W, x = cell - y * g.W; xan = L.ax[x]; yan = L.ay[y]; }
-                for (int j = 0; j < LFD_MAX_SLOTS; ++j) {
-                    cj[j] = 0.0f; wx[j] = 0.0f; wy[j] = 0.0f;
-                    if (j < ns && j != s) {
-                        cj[j] = sl[j].cert[cell];
-                        const float* wv = sl[j].warp + (size_t)cell * g.C + (g.C - 2);
-                        wx[j] = wv[0]; wy[j] = wv[1];
-                    }
-                }
-                st = lfd_refine_point<LFD_MAX_SLOTS>(rref[(size_t)r], sl, ns, s, g, xan, yan, xbn, ybn, cj, wx, wy, X0, X1, X2, err);
+    std::vector<LfdRefineRef> rref;
+    std::vector<LfdSlot> rslot;
+    make_slot_table(ctx, L, rslot, &rref);
+    std::vector<LfdSlotPrec> wslot(weighted ? rslot.size() : 0);
+    if (weighted)
+        for (int r = 0; r < b->n_refs; ++r)
+            for (int j = 0; j < b->n_slots[r]; ++j) {
+                LfdSlotPrec& w = wslot[(size_t)r * LFD_MAX_SLOTS + j];
+                w.prec = precision[(size_t)r * b->k + j];
+                lfd_slot_prec_scale(rslot[(size_t)r * LFD_MAX_SLOTS + j].sx, rslot[(size_t)r * LFD_MAX_SLOTS + j].sy, w);
             }
-            xyz_out[3 * i] = X0; xyz_out[3 * i + 1] = X1; xyz_out[3 * i + 2] = X2;
-            err_out[i] = err;
-            if (status) status[i] = (uint8_t)st;
-            if (st & LFD_REFINE_ACCEPTED) ++refined[(size_t)c];
-            else if (st) ++fallback[(size_t)c];
-        }
-    });
-    if (counters)
-        for (int c = 0; c < n_chunks; ++c) { counters[0] += refined[(size_t)c]; counters[1] += fallback[(size_t)c]; }
-    return LFD_OK;
-}
-
-int lfd_refine_multiview_weighted_host(lfd_context* ctx, const lfd_batch* b, const lfd_points* in, const int64_t* ref_offsets,
-                                       float support_thresh_px, float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status,
-                                       int64_t* counters, const float* const* precision) {
-    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
-    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
-    if (const char* why = lfd_refine_check(in, ref_offsets, support_thresh_px, reproj_thresh, xyz_out, err_out, status))
-        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_refine_multiview_weighted_host: ") + why);
-    lfd_params none;
-    std::memset(&none, 0, sizeof(none));
-    int rc = validate_host(ctx, b, &none);
-    if (rc != LFD_OK) return rc;
-    if (const char* why = lfd_refine_check_precision(b, precision))
-        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_refine_multiview_weighted_host: ") + why);
-    HostLaunch L;
-    prepare_host(b, &none, L);
-    std::vector<LfdRefineRef> rref((size_t)b->n_refs);
-    std::vector<LfdRefineSlot> rslot((size_t)b->n_refs * LFD_MAX_SLOTS);
-    std::vector<LfdRefineWSlot> wslot((size_t)b->n_refs * LFD_MAX_SLOTS);
-    for (int r = 0; r < b->n_refs; ++r) {
-        HostRef R;
-        make_ref(ctx, L, r, R);
-        for (int e = 0; e < 12; ++e) rref[(size_t)r].P[e] = R.rc.P[e];
-        rref[(size_t)r].sx = R.rc.sx; rref[(size_t)r].sy = R.rc.sy;
-        for (int j = 0; j < b->n_slots[r]; ++j) {
-            const size_t sj = (size_t)r * b->k + j;
-            LfdRefineSlot& o = rslot[(size_t)r * LFD_MAX_SLOTS + j];
-            o.cert = b->cert[sj]; o.warp = b->warp[sj]; o.mask_b = b->mask_b ? b->mask_b[sj] : nullptr;
-            for (int e = 0; e < 12; ++e) o.P[e] = R.pc[j].P[e];
-            o.sx = R.pc[j].sx; o.sy = R.pc[j].sy;
-            LfdRefineWSlot& w = wslot[(size_t)r * LFD_MAX_SLOTS + j];
-            w.prec = precision[sj];
-            lfd_refine_wslot_scale(o.sx, o.sy, w);
-        }
-    }
-    LfdRefineGeom g;
-    g.H = b->H; g.W = b->W; g.C = b->warp_channels; g.w_match = b->w_match; g.h_match = b->h_match;
-    g.wm1 = L.kp.wm1; g.hm1 = L.kp.hm1; g.mask_sx = L.mask_sx; g.mask_sy = L.mask_sy; g.tau = support_thresh_px; g.reproj_thresh = reproj_thresh;
+    const LfdSupportGeom g = make_geom(L, support_thresh_px, reproj_thresh);
     const long long cap = in->capacity;
     const long long* offs = reinterpret_cast<const long long*>(ref_offsets);
     const long long total = lfd_support_clamp(offs[b->n_refs], cap);
     const int n_chunks = (int)((total + kChunk - 1) / kChunk);
-    std::vector<long long> refined((size_t)n_chunks, 0), fallback((size_t)n_chunks, 0), weighted((size_t)n_chunks, 0);
+    std::vector<long long> count((size_t)n_chunks * 3, 0);             // per chunk: refined, fallen back, solved with weighted rows
     parallel_chunks(ctx, n_chunks, [&](int c) {
         const long long i1 = std::min<long long>(total, (long long)(c + 1) * kChunk);
         for (long long i = (long long)c * kChunk; i < i1; ++i) {
@@ -508,41 +454,57 @@ int lfd_refine_multiview_weighted_host(lfd_context* ctx, const lfd_batch* b, con
             float X0 = in->xyz[3 * i], X1 = in->xyz[3 * i + 1], X2 = in->xyz[3 * i + 2], err = in->err[i];
             unsigned st = 0u;
             if (cell >= 0 && cell < L.HW && s < ns) {                   // no address is formed from a cell outside the grid
-                const LfdRefineSlot* sl = &rslot[(size_t)r * LFD_MAX_SLOTS];
-                const LfdRefineWSlot* ws = &wslot[(size_t)r * LFD_MAX_SLOTS];
+                const LfdSlot* sl = &rslot[(size_t)r * LFD_MAX_SLOTS];
+                const LfdSlotPrec* ws = weighted ? &wslot[(size_t)r * LFD_MAX_SLOTS] : nullptr;
                 float cj[LFD_MAX_SLOTS], wx[LFD_MAX_SLOTS], wy[LFD_MAX_SLOTS], q00[LFD_MAX_SLOTS], q01[LFD_MAX_SLOTS], q11[LFD_MAX_SLOTS], qs[3];
                 const float* wp = sl[s].warp + (size_t)cell * g.C;
                 const float xbn = wp[g.C - 2], ybn = wp[g.C - 1];
                 float xan, yan;
                 if (g.C == 4) { xan = wp[0]; yan = wp[1]; }
                 else { const int y = cell / g.W, x = cell - y * g.W; xan = L.ax[x]; yan = L.ay[y]; }
-                for (int e = 0; e < 3; ++e) qs[e] = ws[s].prec[(size_t)cell * 3 + e];
+                if (weighted)
+                    for (int e = 0; e < 3; ++e) qs[e] = ws[s].prec[(size_t)cell * 3 + e];
                 for (int j = 0; j < LFD_MAX_SLOTS; ++j) {
                     cj[j] = 0.0f; wx[j] = 0.0f; wy[j] = 0.0f; q00[j] = 0.0f; q01[j] = 0.0f; q11[j] = 0.0f;
                     if (j < ns && j != s) {
                         cj[j] = sl[j].cert[cell];
                         const float* wv = sl[j].warp + (size_t)cell * g.C + (g.C - 2);
                         wx[j] = wv[0]; wy[j] = wv[1];
-                        const float* qp = ws[j].prec + (size_t)cell * 3;
-                        q00[j] = qp[0]; q01[j] = qp[1]; q11[j] = qp[2];
+                        if (weighted) {
+                            const float* qp = ws[j].prec + (size_t)cell * 3;
+                            q00[j] = qp[0]; q01[j] = qp[1]; q11[j] = qp[2];
+                        }
                     }
                 }
-                st = lfd_refine_point_weighted<LFD_MAX_SLOTS>(rref[(size_t)r], sl, ws, ns, s, g, xan, yan, xbn, ybn, cj, wx, wy, q00, q01, q11, qs,
-                                                              X0, X1, X2, err);
+                const LfdRefineGather o = {cj, wx, wy, q00, q01, q11, qs};
+                st = weighted ? lfd_refine_point<LFD_MAX_SLOTS, true>(rref[(size_t)r], sl, ws, ns, s, g, xan, yan, xbn, ybn, o, X0, X1, X2, err)
+                              : lfd_refine_point<LFD_MAX_SLOTS, false>(rref[(size_t)r], sl, ws, ns, s, g, xan, yan, xbn, ybn, o, X0, X1, X2, err);
             }
             xyz_out[3 * i] = X0; xyz_out[3 * i + 1] = X1; xyz_out[3 * i + 2] = X2;
             err_out[i] = err;
             if (status) status[i] = (uint8_t)st;
-            if (st & LFD_REFINE_ACCEPTED) ++refined[(size_t)c];
-            else if (st) ++fallback[(size_t)c];
-            if (st & LFD_REFINE_WEIGHTED) ++weighted[(size_t)c];
+            if (st & LFD_REFINE_ACCEPTED) ++count[(size_t)c * 3];
+            else if (st) ++count[(size_t)c * 3 + 1];
+            if (st & LFD_REFINE_WEIGHTED) ++count[(size_t)c * 3 + 2];
         }
     });
     if (counters)
-        for (int c = 0; c < n_chunks; ++c) {
-            counters[0] += refined[(size_t)c]; counters[1] += fallback[(size_t)c]; counters[2] += weighted[(size_t)c];
-        }
+        for (int c = 0; c < n_chunks; ++c)
+            for (int e = 0; e < (weighted ? 3 : 2); ++e) counters[e] += count[(size_t)c * 3 + e];
     return LFD_OK;
+}
+
+int lfd_refine_multiview_host(lfd_context* ctx, const lfd_batch* b, const lfd_points* in, const int64_t* ref_offsets, float support_thresh_px,
+                              float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status, int64_t* counters) {
+    return refine_host_impl(ctx, "lfd_refine_multiview_host", b, in, ref_offsets, support_thresh_px, reproj_thresh, xyz_out, err_out, status,
+                            counters, nullptr, false);
+}
+
+int lfd_refine_multiview_weighted_host(lfd_context* ctx, const lfd_batch* b, const lfd_points* in, const int64_t* ref_offsets,
+                                       float support_thresh_px, float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status,
+                                       int64_t* counters, const float* const* precision) {
+    return refine_host_impl(ctx, "lfd_refine_multiview_weighted_host", b, in, ref_offsets, support_thresh_px, reproj_thresh, xyz_out, err_out,
+                            status, counters, precision, true);
 }
 
 int lfd_aggregate_host(lfd_context* ctx, const lfd_batch* b, const lfd_params* p, float* best_cert, uint8_t* best_slot) {

@@ -3,10 +3,15 @@
 // its reference whose own warp agrees with it; here their observations join the two that made the point in one N-view DLT, and the result
 // replaces the point when it still passes the two-view tests and every view that agreed before agrees with it.
 //
-// Every rounding is written out (the build uses -ffp-contract=off).  The candidate set uses lfd_support_live / lfd_support_mask_index /
-// lfd_support_agree unchanged, so it is the support filter's set bit for bit on both builds; the rows are lfd_eval_correspondence's f32 rows;
-// M = sum row row^T is one f64 fma chain in the fixed view order (reference, winning slot, candidates by ascending slot).  The two builds differ
-// only where lfd_geometry.hpp's do: lfd_recip_refined (IEEE division / Newton-refined v_rcp_f64), lfd_sqrt_rare, lfd_rcp_f32, lfd_sqrt_f32.
+// Every rounding is written out (the build uses -ffp-contract=off).  The candidate set is lfd_support_candidate's (lfd_support.hpp), the one
+// function the support filter counts with, so it is the filter's set bit for bit on both builds; the rows are lfd_eval_correspondence's f32
+// rows; M = sum row row^T is one f64 fma chain in the fixed view order (reference, winning slot, candidates by ascending slot).  The two builds
+// differ only where lfd_geometry.hpp's do: lfd_recip_refined (IEEE division / Newton-refined v_rcp_f64), lfd_sqrt_rare, lfd_rcp_f32,
+// lfd_sqrt_f32.
+//
+// One routine, lfd_refine_point<KMAX, WEIGHTED>, serves lfd_refine_multiview and its precision-weighted variant: WEIGHTED adds the
+// validity test of the participating planes and the weighted M; where a plane is invalid it runs lfd_refine_build_unweighted, the very code of
+// the other instantiation.
 #pragma once
 
 #include <stdint.h>
@@ -16,23 +21,26 @@
 #include "lfd_support.hpp"
 
 #define LFD_REFINE_ACCEPTED 0x80       /* status: n_extra | (accepted ? 0x80 : 0) */
-
-struct LfdRefineSlot {           // one neighbour of the reference at work (LDS on the device, a table on the host)
-    const float* cert;
-    const float* warp;
-    const uint8_t* mask_b;
-    float P[12];                 // interleaved (LfdPairConst)
-    float sx, sy;
-};
+#define LFD_REFINE_WEIGHTED 0x40       /* status: the weighted rows were used (every participating view's precision was valid) */
 
 struct LfdRefineRef {            // the reference itself
     float P[12];                 // interleaved (LfdRefConst)
     float sx, sy;
 };
 
-struct LfdRefineGeom {
-    int32_t H, W, C, w_match, h_match;
-    float wm1, hm1, mask_sx, mask_sy, tau, reproj_thresh;
+struct LfdSlotPrec {             // beside LfdSlot (weighted only): the neighbour's precision plane and what turns its entries into camera px^-2
+    const float* prec;           // [H*W*3]: (q00, q01, q11) per cell, px^-2 of the neighbour's MATCH image
+    double rxx, rxy, ryy;        // 1 / (sx sx), 1 / (sx sy), 1 / (sy sy) through lfd_recip_refined (the products of f32 values are exact)
+};
+
+struct LfdRefineGather {         // what the caller gathered at the point's cell, [KMAX] each, entries j < ns, j != s (the rest is not read)
+    const float* cert;           // certainty of the other neighbours
+    const float* wx;             // their warps' B side
+    const float* wy;
+    const float* q00;            // weighted only (null otherwise): their precision, and qs[3] the winning slot's
+    const float* q01;
+    const float* q11;
+    const float* qs;
 };
 
 // M (upper triangle: m00 m01 m02 m03 m11 m12 m13 m22 m23 m33) += the two DLT rows of one view, u p2 - p0 and v p2 - p1, formed in f32 exactly as
@@ -155,73 +163,8 @@ LFD_HD bool lfd_refine_two_view(const float* Pa, const float* Pb, float X0, floa
     return (err <= reproj_thresh) && (z1 > 0.0f) && (z2 > 0.0f);
 }
 
-// One point.  sl[0 .. ns): the reference's neighbours; s: the winning slot (s < ns); (xan, yan) / (xbn, ybn): the reference's and the winner's
-// normalised observations of the cell; cert[j], wx[j], wy[j] (j < ns, j != s): what the other neighbours hold at the cell, gathered by the
-// caller (KMAX >= ns).  Returns the status byte; X0, X1, X2, err are replaced iff it has LFD_REFINE_ACCEPTED.
-template <int KMAX>
-LFD_HD unsigned lfd_refine_point(const LfdRefineRef& ref, const LfdRefineSlot* sl, int ns, int s, const LfdRefineGeom& g, float xan, float yan,
-                                 float xbn, float ybn, const float* cert, const float* wx, const float* wy, float& X0, float& X1, float& X2,
-                                 float& err) {
-    unsigned cand = 0u;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (int j = 0; j < KMAX; ++j) {
-        if (j < ns && j != s) {
-            bool live = lfd_support_live(cert[j]);
-            const uint8_t* mb = sl[j].mask_b;
-            if (live && mb) {
-                const long long m = lfd_support_mask_index(wx[j], wy[j], g.W, g.H, g.mask_sx, g.mask_sy, g.w_match, g.h_match);
-                live = m >= 0 && mb[m] != 0;
-            }
-            const bool agree = lfd_support_agree(sl[j].P, sl[j].sx, sl[j].sy, X0, X1, X2, wx[j], wy[j], g.wm1, g.hm1, g.tau);
-            cand |= (live && agree) ? (1u << j) : 0u;
-        }
-    }
-    if (cand == 0u) return 0u;
-    unsigned n_extra = 0u;
-    for (unsigned m = cand; m; m &= m - 1u) ++n_extra;
-
-    const float ua = lfd_match_px(xan, g.wm1) * ref.sx, va = lfd_match_px(yan, g.hm1) * ref.sy;
-    const float ub = lfd_match_px(xbn, g.wm1) * sl[s].sx, vb = lfd_match_px(ybn, g.hm1) * sl[s].sy;
-    double M[10];
-    lfd_refine_add_view(M, ref.P, ua, va, true);
-    lfd_refine_add_view(M, sl[s].P, ub, vb, false);
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (int j = 0; j < KMAX; ++j) {
-        if ((cand >> j) & 1u) {
-            const float uj = lfd_match_px(wx[j], g.wm1) * sl[j].sx, vj = lfd_match_px(wy[j], g.hm1) * sl[j].sy;
-            lfd_refine_add_view(M, sl[j].P, uj, vj, false);
-        }
-    }
-    double c[4];
-    lfd_null_vector_sym(M, c);
-    float Y0, Y1, Y2, e;
-    bool ok = lfd_refine_dehomogenise(c, Y0, Y1, Y2);
-    ok = lfd_refine_two_view(ref.P, sl[s].P, Y0, Y1, Y2, ua, va, ub, vb, g.reproj_thresh, e) && ok;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (int j = 0; j < KMAX; ++j) {
-        if ((cand >> j) & 1u)
-            ok = lfd_support_agree(sl[j].P, sl[j].sx, sl[j].sy, Y0, Y1, Y2, wx[j], wy[j], g.wm1, g.hm1, g.tau) && ok;
-    }
-    if (!ok) return n_extra;
-    X0 = Y0; X1 = Y1; X2 = Y2; err = e;
-    return n_extra | LFD_REFINE_ACCEPTED;
-}
-
-// ---- precision-weighted variant (lfd_refine_multiview_weighted) -------------------------------------------------------------------
-#define LFD_REFINE_WEIGHTED 0x40       /* status: the weighted rows were used (every participating view's precision was valid) */
-
-struct LfdRefineWSlot {          // beside LfdRefineSlot: the neighbour's precision plane and what turns its entries into camera px^-2
-    const float* prec;           // [H*W*3]: (q00, q01, q11) per cell, px^-2 of the neighbour's MATCH image
-    double rxx, rxy, ryy;        // 1 / (sx sx), 1 / (sx sy), 1 / (sy sy) through lfd_recip_refined (the products of f32 values are exact)
-};
-
-LFD_HD void lfd_refine_wslot_scale(float sx, float sy, LfdRefineWSlot& o) {
+// ---- precision-weighted rows (lfd_refine_multiview_weighted) ------------------------------------------------------------------------
+LFD_HD void lfd_slot_prec_scale(float sx, float sy, LfdSlotPrec& o) {
     const double x = (double)sx, y = (double)sy;
     o.rxx = lfd_recip_refined(x * x);
     o.rxy = lfd_recip_refined(x * y);
@@ -255,7 +198,7 @@ LFD_HD void lfd_refine_add_view_weighted(double* M, const float* Pi, float u, fl
 
 // One neighbour view into M: its precision in camera px^-2 (q / (s s)) times w2 = 1 / (pz pz), pz the f32 depth of the two-view X in that view
 // (what turns the algebraic rows into first-order pixel residuals).  lam += (p00 + p11) / 2.
-LFD_HD void lfd_refine_add_neighbour_weighted(double* M, double& lam, const LfdRefineSlot& sl, const LfdRefineWSlot& ws, float q00, float q01,
+LFD_HD void lfd_refine_add_neighbour_weighted(double* M, double& lam, const LfdSlot& sl, const LfdSlotPrec& ws, float q00, float q01,
                                               float q11, float X0, float X1, float X2, float u, float v) {
     const double p00 = (double)q00 * ws.rxx, p01 = (double)q01 * ws.rxy, p11 = (double)q11 * ws.ryy;
     const double z = (double)lfd_proj_row(sl.P, 2, X0, X1, X2, 1.0f);
@@ -264,75 +207,83 @@ LFD_HD void lfd_refine_add_neighbour_weighted(double* M, double& lam, const LfdR
     lfd_refine_add_view_weighted(M, sl.P, u, v, w2 * p00, w2 * p01, w2 * p11);
 }
 
-// lfd_refine_point with precision-weighted rows.  q00 / q01 / q11 [j] (j < ns, j != s): the other neighbours' precision at the cell; qs[3]: the
-// winning slot's.  The candidates are lfd_refine_point's, by the same code.  Every participating view (slot s, the candidates) valid: M is
-// built in the order slot s, candidates by ascending j, reference LAST - it has no matching noise (a cell centre), so it enters isotropically
-// with lamA = the sum of the neighbours' mean precisions: as precise as everything that looked at it, which also makes the solution invariant
-// to a common scale of the planes.  Any of them invalid: today's unweighted M, in today's order - lfd_refine_point's bits.  Solve, acceptance
-// and fallback are lfd_refine_point's.  Status: n_extra | LFD_REFINE_WEIGHTED | LFD_REFINE_ACCEPTED.
-template <int KMAX>
-LFD_HD unsigned lfd_refine_point_weighted(const LfdRefineRef& ref, const LfdRefineSlot* sl, const LfdRefineWSlot* ws, int ns, int s,
-                                          const LfdRefineGeom& g, float xan, float yan, float xbn, float ybn, const float* cert, const float* wx,
-                                          const float* wy, const float* q00, const float* q01, const float* q11, const float* qs, float& X0,
-                                          float& X1, float& X2, float& err) {
-    unsigned cand = 0u;
+// ---- one point ---------------------------------------------------------------------------------------------------------------------------------
 #if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
+#define LFD_REFINE_UNROLL _Pragma("unroll")
+#else
+#define LFD_REFINE_UNROLL
 #endif
+
+// Today's M: reference, winning slot, candidates by ascending slot, every view with weight one.
+template <int KMAX>
+LFD_HD void lfd_refine_build_unweighted(double* M, const LfdRefineRef& ref, const LfdSlot* sl, int s, unsigned cand, const LfdSupportGeom& g,
+                                        const LfdRefineGather& o, float ua, float va, float ub, float vb) {
+    lfd_refine_add_view(M, ref.P, ua, va, true);
+    lfd_refine_add_view(M, sl[s].P, ub, vb, false);
+    LFD_REFINE_UNROLL
     for (int j = 0; j < KMAX; ++j) {
-        if (j < ns && j != s) {
-            bool live = lfd_support_live(cert[j]);
-            const uint8_t* mb = sl[j].mask_b;
-            if (live && mb) {
-                const long long m = lfd_support_mask_index(wx[j], wy[j], g.W, g.H, g.mask_sx, g.mask_sy, g.w_match, g.h_match);
-                live = m >= 0 && mb[m] != 0;
-            }
-            const bool agree = lfd_support_agree(sl[j].P, sl[j].sx, sl[j].sy, X0, X1, X2, wx[j], wy[j], g.wm1, g.hm1, g.tau);
-            cand |= (live && agree) ? (1u << j) : 0u;
+        if ((cand >> j) & 1u) {
+            const float uj = lfd_match_px(o.wx[j], g.wm1) * sl[j].sx, vj = lfd_match_px(o.wy[j], g.hm1) * sl[j].sy;
+            lfd_refine_add_view(M, sl[j].P, uj, vj, false);
         }
+    }
+}
+
+// The weighted M: winning slot, candidates by ascending slot, reference LAST - it has no matching noise (a cell centre), so it enters
+// isotropically with lamA = the sum of the neighbours' mean precisions: as precise as everything that looked at it, which also makes the
+// solution invariant to a common scale of the planes.  (X0, X1, X2): the two-view point, whose depths scale the rows.
+template <int KMAX>
+LFD_HD void lfd_refine_build_weighted(double* M, const LfdRefineRef& ref, const LfdSlot* sl, const LfdSlotPrec* ws, int s, unsigned cand,
+                                      const LfdSupportGeom& g, const LfdRefineGather& o, float ua, float va, float ub, float vb, float X0, float X1,
+                                      float X2) {
+    for (int e = 0; e < 10; ++e) M[e] = 0.0;
+    double lam = 0.0;
+    lfd_refine_add_neighbour_weighted(M, lam, sl[s], ws[s], o.qs[0], o.qs[1], o.qs[2], X0, X1, X2, ub, vb);
+    LFD_REFINE_UNROLL
+    for (int j = 0; j < KMAX; ++j) {
+        if ((cand >> j) & 1u) {
+            const float uj = lfd_match_px(o.wx[j], g.wm1) * sl[j].sx, vj = lfd_match_px(o.wy[j], g.hm1) * sl[j].sy;
+            lfd_refine_add_neighbour_weighted(M, lam, sl[j], ws[j], o.q00[j], o.q01[j], o.q11[j], X0, X1, X2, uj, vj);
+        }
+    }
+    const double z = (double)lfd_proj_row(ref.P, 2, X0, X1, X2, 1.0f);
+    const double wa = lam * lfd_recip_refined(z * z);
+    lfd_refine_add_view_weighted(M, ref.P, ua, va, wa, 0.0, wa);
+}
+
+// One point.  sl[0 .. ns): the reference's neighbours (ws[0 .. ns) beside them when WEIGHTED, else not read); s: the winning slot (s < ns);
+// (xan, yan) / (xbn, ybn): the reference's and the winner's normalised observations of the cell; o: what the other neighbours hold at the cell
+// (KMAX >= ns).  The candidates are lfd_support_candidate's.  WEIGHTED and every participating view (slot s, the candidates) has a valid
+// precision: the weighted M; otherwise the unweighted one - with WEIGHTED false nothing else is compiled.  Solve and acceptance are the same.
+// Returns the status byte n_extra | LFD_REFINE_WEIGHTED | LFD_REFINE_ACCEPTED; X0, X1, X2, err are replaced iff it has LFD_REFINE_ACCEPTED.
+template <int KMAX, bool WEIGHTED>
+LFD_HD unsigned lfd_refine_point(const LfdRefineRef& ref, const LfdSlot* sl, const LfdSlotPrec* ws, int ns, int s, const LfdSupportGeom& g,
+                                 float xan, float yan, float xbn, float ybn, const LfdRefineGather& o, float& X0, float& X1, float& X2,
+                                 float& err) {
+    unsigned cand = 0u;
+    LFD_REFINE_UNROLL
+    for (int j = 0; j < KMAX; ++j) {
+        if (j < ns && j != s) cand |= lfd_support_candidate(sl[j], g, o.cert[j], o.wx[j], o.wy[j], X0, X1, X2) ? (1u << j) : 0u;
     }
     if (cand == 0u) return 0u;
     unsigned n_extra = 0u;
     for (unsigned m = cand; m; m &= m - 1u) ++n_extra;
-    bool weighted = lfd_refine_prec_valid(qs[0], qs[1], qs[2]);
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (int j = 0; j < KMAX; ++j) {
-        if ((cand >> j) & 1u) weighted = lfd_refine_prec_valid(q00[j], q01[j], q11[j]) && weighted;
+    bool weighted = false;
+    if constexpr (WEIGHTED) {
+        weighted = lfd_refine_prec_valid(o.qs[0], o.qs[1], o.qs[2]);
+        LFD_REFINE_UNROLL
+        for (int j = 0; j < KMAX; ++j) {
+            if ((cand >> j) & 1u) weighted = lfd_refine_prec_valid(o.q00[j], o.q01[j], o.q11[j]) && weighted;
+        }
     }
 
     const float ua = lfd_match_px(xan, g.wm1) * ref.sx, va = lfd_match_px(yan, g.hm1) * ref.sy;
     const float ub = lfd_match_px(xbn, g.wm1) * sl[s].sx, vb = lfd_match_px(ybn, g.hm1) * sl[s].sy;
     double M[10];
     if (weighted) {
-        for (int e = 0; e < 10; ++e) M[e] = 0.0;
-        double lam = 0.0;
-        lfd_refine_add_neighbour_weighted(M, lam, sl[s], ws[s], qs[0], qs[1], qs[2], X0, X1, X2, ub, vb);
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-        for (int j = 0; j < KMAX; ++j) {
-            if ((cand >> j) & 1u) {
-                const float uj = lfd_match_px(wx[j], g.wm1) * sl[j].sx, vj = lfd_match_px(wy[j], g.hm1) * sl[j].sy;
-                lfd_refine_add_neighbour_weighted(M, lam, sl[j], ws[j], q00[j], q01[j], q11[j], X0, X1, X2, uj, vj);
-            }
-        }
-        const double z = (double)lfd_proj_row(ref.P, 2, X0, X1, X2, 1.0f);
-        const double wa = lam * lfd_recip_refined(z * z);
-        lfd_refine_add_view_weighted(M, ref.P, ua, va, wa, 0.0, wa);
+        if constexpr (WEIGHTED) lfd_refine_build_weighted<KMAX>(M, ref, sl, ws, s, cand, g, o, ua, va, ub, vb, X0, X1, X2);
     } else {
-        lfd_refine_add_view(M, ref.P, ua, va, true);
-        lfd_refine_add_view(M, sl[s].P, ub, vb, false);
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-        for (int j = 0; j < KMAX; ++j) {
-            if ((cand >> j) & 1u) {
-                const float uj = lfd_match_px(wx[j], g.wm1) * sl[j].sx, vj = lfd_match_px(wy[j], g.hm1) * sl[j].sy;
-                lfd_refine_add_view(M, sl[j].P, uj, vj, false);
-            }
-        }
+        lfd_refine_build_unweighted<KMAX>(M, ref, sl, s, cand, g, o, ua, va, ub, vb);
     }
     const unsigned base = n_extra | (weighted ? (unsigned)LFD_REFINE_WEIGHTED : 0u);
     double c[4];
@@ -340,12 +291,10 @@ LFD_HD unsigned lfd_refine_point_weighted(const LfdRefineRef& ref, const LfdRefi
     float Y0, Y1, Y2, e;
     bool ok = lfd_refine_dehomogenise(c, Y0, Y1, Y2);
     ok = lfd_refine_two_view(ref.P, sl[s].P, Y0, Y1, Y2, ua, va, ub, vb, g.reproj_thresh, e) && ok;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
+    LFD_REFINE_UNROLL
     for (int j = 0; j < KMAX; ++j) {
         if ((cand >> j) & 1u)
-            ok = lfd_support_agree(sl[j].P, sl[j].sx, sl[j].sy, Y0, Y1, Y2, wx[j], wy[j], g.wm1, g.hm1, g.tau) && ok;
+            ok = lfd_support_agree(sl[j].P, sl[j].sx, sl[j].sy, Y0, Y1, Y2, o.wx[j], o.wy[j], g.wm1, g.hm1, g.tau) && ok;
     }
     if (!ok) return base;
     X0 = Y0; X1 = Y1; X2 = Y2; err = e;
@@ -365,14 +314,12 @@ struct LfdRefineArgs {
     float* o_xyz; float* o_err;
     uint8_t* status;                   // [capacity] or null
     unsigned long long* counters;      // [2] or null: points refined, points with a candidate that kept their two-view position; added to
+                                       // ([3] when prec is set: + points solved with weighted rows; without prec element 2 is never touched)
     long long capacity;
     int32_t n_refs, k, n_wg;
-    LfdRefineGeom g;
-};
-
-struct LfdRefineWArgs {                // lfd_refine_multiview_weighted: the same, counters [3] (+ points solved with weighted rows), and
-    LfdRefineArgs a;
-    const float* const* prec;          // [n_refs * k] precision planes (device table; entries at j >= n_slots[r] are not read)
+    LfdSupportGeom g;
+    const float* const* prec;          // lfd_refine_multiview_weighted: [n_refs * k] precision planes (device table; entries at j >= n_slots[r]
+                                       // are not read); null: lfd_refine_multiview
 };
 
 // Arguments of lfd_refine_multiview / lfd_refine_multiview_host that do not depend on the batch; what is wrong with them, or null.

@@ -18,64 +18,39 @@
 #include "lfd_device.hpp"
 #include "lfd_support.hpp"
 
-namespace {
-
-struct SupportSlot {             // one other neighbour of the reference at work, in LDS
-    const float* cert;
-    const float* warp;
-    const uint8_t* mask_b;
-    float P[12];
-    float sx, sy;
-};
-
-}  // namespace
-
 template <int KMAX>
 __global__ void __launch_bounds__(256) lfd_support_count_kernel(const LfdSupportArgs p) {
-    __shared__ SupportSlot sh[KMAX];
+    __shared__ LfdSlot sh[KMAX];
     __shared__ unsigned sh_seg[KMAX];
     __shared__ int sh_ref[2];
     __shared__ unsigned sh_kept;
     const int tid = (int)threadIdx.x;
-    const long long total = lfd_support_clamp(p.offs_in[p.n_refs], p.capacity);
-    const long long base = (long long)blockIdx.x * 256;
-    if (base >= total) {                                               // the whole workgroup lies past the last point
+    const LfdPointSpan sp = lfd_point_span(p.offs_in, p.n_refs, p.capacity);
+    if (!sp.any) {                                                      // the whole workgroup lies past the last point
         if (tid == 0) p.wg_kept[blockIdx.x] = 0u;
         return;
     }
-    const long long i = base + tid;
-    const bool mine = i < total;
-    const long long last = (base + 256 < total ? base + 256 : total) - 1;
-    const long long ii = mine ? i : last;                              // idle lanes read the last point and store nothing
+    const long long i = sp.i, ii = sp.ii;
+    const bool mine = sp.mine;
     const int cell = p.cell[ii];
     const int s = (int)p.slot[ii];
     const float X0 = p.xyz[3 * ii], X1 = p.xyz[3 * ii + 1], X2 = p.xyz[3 * ii + 2];
     const int r = lfd_support_ref_of(p.offs_in, p.n_refs, p.capacity, ii);
     if (tid == 0) { sh_ref[0] = r; sh_kept = 0u; }
-    if (i == last) sh_ref[1] = r;
+    if (i == sp.last) sh_ref[1] = r;
     __syncthreads();
     const int r_first = sh_ref[0], r_last = sh_ref[1];
-    const long long HW = (long long)p.H * p.W;
+    const LfdSupportGeom g = p.g;
+    const long long HW = (long long)g.H * g.W;
     const bool cell_ok = cell >= 0 && (long long)cell < HW;            // no address is formed from a cell outside the grid
     const LfdRefDesc* refs = static_cast<const LfdRefDesc*>(p.refs);
-    const LfdSlotDesc* slots = static_cast<const LfdSlotDesc*>(p.slots);
     int support = 0;
     for (int rr = r_first; rr <= r_last; ++rr) {
         if (lfd_support_clamp(p.offs_in[rr + 1], p.capacity) <= lfd_support_clamp(p.offs_in[rr], p.capacity)) continue;   // uniform: no points
         int ns = refs[rr].n_slots;
         ns = ns < KMAX ? ns : KMAX;
-        if (tid < KMAX) {
-            sh_seg[tid] = 0u;
-            if (tid < ns) {
-                const LfdSlotDesc& d = slots[(size_t)rr * p.k + tid];
-                const LfdPairConst& c = p.pair_const[(size_t)rr * p.k + tid];
-                SupportSlot& o = sh[tid];
-                o.cert = d.cert; o.warp = d.warp; o.mask_b = d.mask_b;
-#pragma unroll
-                for (int e = 0; e < 12; ++e) o.P[e] = c.P[e];
-                o.sx = c.sx; o.sy = c.sy;
-            }
-        }
+        if (tid < KMAX) sh_seg[tid] = 0u;
+        lfd_stage_slots(sh, p.slots, p.pair_const, rr, p.k, ns);
         __syncthreads();
         const bool here = mine && r == rr;
         if (here && cell_ok) {
@@ -87,21 +62,12 @@ __global__ void __launch_bounds__(256) lfd_support_count_kernel(const LfdSupport
                 c[j] = 0.0f; w[j] = make_float2(0.0f, 0.0f);
                 if (j < ns && j != s) {
                     c[j] = sh[j].cert[cell];
-                    w[j] = *reinterpret_cast<const float2*>(sh[j].warp + (size_t)cell * p.C + (p.C - 2));
+                    w[j] = *reinterpret_cast<const float2*>(sh[j].warp + (size_t)cell * g.C + (g.C - 2));
                 }
             }
 #pragma unroll
             for (int j = 0; j < KMAX; ++j) {
-                if (j < ns && j != s) {
-                    bool live = lfd_support_live(c[j]);
-                    const uint8_t* mb = sh[j].mask_b;
-                    if (live && mb) {
-                        const long long m = lfd_support_mask_index(w[j].x, w[j].y, p.W, p.H, p.mask_sx, p.mask_sy, p.w_match, p.h_match);
-                        live = m >= 0 && mb[m] != 0;
-                    }
-                    const bool agree = lfd_support_agree(sh[j].P, sh[j].sx, sh[j].sy, X0, X1, X2, w[j].x, w[j].y, p.wm1, p.hm1, p.tau);
-                    support += (live && agree) ? 1 : 0;
-                }
+                if (j < ns && j != s) support += lfd_support_candidate(sh[j], g, c[j], w[j].x, w[j].y, X0, X1, X2) ? 1 : 0;
             }
         }
         if (p.seg_counts) {

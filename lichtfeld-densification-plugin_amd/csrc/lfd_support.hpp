@@ -4,6 +4,9 @@
 //
 // Every rounding is written out (the build uses -ffp-contract=off) and nothing is divided, inverted or rooted: the twin and the kernels execute
 // the same f32 multiplies, adds, subtracts and fmaf in the same order, so the support counts and the decisions agree bit for bit.
+//
+// LfdSlot, LfdSupportGeom and lfd_support_candidate - the candidate test - are also what the multi-view re-triangulation (lfd_refine.hpp,
+// DESIGN 4.9) works with: the test exists once, so its candidates are this filter's set by construction.
 #pragma once
 
 #include <stdint.h>
@@ -53,6 +56,41 @@ LFD_HD int lfd_support_ref_of(const long long* offs, int n_refs, long long cap, 
 
 LFD_HD long long lfd_support_clamp(long long v, long long cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
 
+struct LfdSlot {                 // one neighbour of the reference at work (LDS on the device, a table on the host)
+    const float* cert;
+    const float* warp;
+    const uint8_t* mask_b;
+    float P[12];                 // interleaved (LfdPairConst)
+    float sx, sy;
+};
+
+struct LfdSupportGeom {          // the grid and the thresholds of a launch (reproj_thresh: the re-triangulation's acceptance test only)
+    int32_t H, W, C, w_match, h_match;
+    float wm1, hm1, mask_sx, mask_sy, tau, reproj_thresh;
+};
+
+LFD_HD void lfd_slot_fill(LfdSlot& o, const float* cert, const float* warp, const uint8_t* mask_b, const LfdPairConst& c) {
+    o.cert = cert; o.warp = warp; o.mask_b = mask_b;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int e = 0; e < 12; ++e) o.P[e] = c.P[e];
+    o.sx = c.sx; o.sy = c.sy;
+}
+
+// The candidate test, the one copy the support filter and the re-triangulation share on both builds: neighbour `sl`, whose certainty and warp
+// at the point's cell are cert and (wx, wy), is live (the mask is looked at only behind a live certainty) and agrees with X.
+LFD_HD bool lfd_support_candidate(const LfdSlot& sl, const LfdSupportGeom& g, float cert, float wx, float wy, float X0, float X1, float X2) {
+    bool live = lfd_support_live(cert);
+    const uint8_t* mb = sl.mask_b;
+    if (live && mb) {
+        const long long m = lfd_support_mask_index(wx, wy, g.W, g.H, g.mask_sx, g.mask_sy, g.w_match, g.h_match);
+        live = m >= 0 && mb[m] != 0;
+    }
+    const bool agree = lfd_support_agree(sl.P, sl.sx, sl.sy, X0, X1, X2, wx, wy, g.wm1, g.hm1, g.tau);
+    return live && agree;
+}
+
 // What a launch works on (device), by value in the kernel arguments.
 struct LfdSupportArgs {
     const void* refs;                  // LfdRefDesc [n_refs]            (lfd_device.hpp; the twin reads the lfd_batch itself)
@@ -67,8 +105,8 @@ struct LfdSupportArgs {
     uint8_t* counts;                   // workspace [n_wg * 256]: support count of every input point
     unsigned* wg_kept;                 // workspace [n_wg + 1]: kept points per workgroup, then their exclusive prefix and the total
     long long capacity;                // in->capacity
-    int32_t n_refs, k, H, W, C, w_match, h_match, min_support, n_wg;
-    float wm1, hm1, mask_sx, mask_sy, tau;
+    int32_t n_refs, k, min_support, n_wg;
+    LfdSupportGeom g;
 };
 
 // Arguments of lfd_support_filter / lfd_support_filter_host that do not depend on the batch; what is wrong with them (and the status), or null.
