@@ -433,6 +433,36 @@ int lfd_refine_multiview_weighted_host(lfd_context* ctx, const lfd_batch* batch,
                                        float support_thresh_px, float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status,
                                        int64_t* counters, const float* const* precision);
 
+/* Depth-uncertainty gate on triangulated points (no upstream counterpart - upstream's only depth-conditioning test is the fixed
+ * parallax angle).  Per point X of reference r made by winning slot s: X(l) = C_A + l D, D = X - C_A; sigma_rel is the 1-sigma Cramer-Rao
+ * bound on l, the relative depth error, from the views that placed the point (csrc/lfd_sigma.hpp, every rounding written out, f64 from the f32
+ * inputs, rounded to f32 once):
+ *   view j       (px, py, pz) = P_j (X, 1), h = P_j[:, :3] D, g = (hx / pz - px hz / pz^2, hy / pz - py hz / pz^2) camera px per unit l,
+ *                I_j = p00 gx^2 + 2 p01 gx gy + p11 gy^2 with the view's precision p in camera px^-2; sigma_rel = 1 / sqrt(sum_j I_j).
+ *                A view with pz <= 0 or a non-finite I_j is skipped.  +inf: sum not finite or <= 0, no view, X not finite, a cell outside the
+ *                grid, a slot the reference does not have (no address is formed from either)
+ *   views        the winning slot; with refine_status non-null (the status of lfd_refine_multiview[_weighted]) and 0x80 set for the point
+ *                also every slot j != s that lfd_support_filter's candidate test accepts at X and support_thresh_px, by ascending j.  With
+ *                refine_status NULL no other slot's certainty, warp or precision is read and support_thresh_px is ignored
+ *   precision    exactly one of: `precision` (the table of lfd_refine_multiview_weighted: p = q / (s s), a view whose entry is not valid
+ *                there is skipped) or iso_sigma_px > 0 (every view p00 = p11 = 1 / iso_sigma_px^2, p01 = 0; camera px, reproj_thresh's unit)
+ *   gate         max_rel_sigma > 0: kept iff sigma_rel <= max_rel_sigma (NaN and +inf drop); 0: every point is kept (annotate only)
+ * Compaction, `out`, ref_offsets_out (always written, stays on the device), seg_counts_out (optional), the batch preparation and the three
+ * launches are lfd_support_filter's.  sigma_rel: NULL, or f32 [in->capacity], one value per INPUT point; sigma_rel_out: NULL, or f32
+ * [out->capacity], compacted with the points.  LFD_ERR_INVALID: a null required pointer, missing cell / slot, both or neither of precision and
+ * iso_sigma_px > 0, a null plane in a valid slot, max_rel_sigma negative or not finite, refine_status with support_thresh_px not finite or
+ * <= 0, in and out overlapping, a capacity beyond 2^31 - 1; LFD_ERR_CAPACITY: out->capacity < in->capacity.  lfd_depth_sigma_filter_host: the
+ * same routine over host pointers on a host context's threads; the participating sets are the device's bit for bit, sigma_rel agrees within
+ * one f32 ulp (the host divides and takes an IEEE root where the device refines v_rcp_f64 / v_rsq_f64). */
+int lfd_depth_sigma_filter(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets_in,
+                           const float* const* precision, float iso_sigma_px, const uint8_t* refine_status, float support_thresh_px,
+                           float max_rel_sigma, const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out, float* sigma_rel,
+                           float* sigma_rel_out);
+int lfd_depth_sigma_filter_host(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets_in,
+                                const float* const* precision, float iso_sigma_px, const uint8_t* refine_status, float support_thresh_px,
+                                float max_rel_sigma, const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out,
+                                float* sigma_rel, float* sigma_rel_out);
+
 /* (e) multi-GPU exchange, placement step (no upstream counterpart - upstream has no multi-GPU code): n copies
  * dst[dst_offset .. +nbytes) = src[src_offset .. +nbytes) in ONE launch on `hip_stream` of device `device_index` (offsets and lengths in
  * bytes, no alignment required: 15-byte PLY records).  The overlapped exchange receives every rank's records of a round as one padded block

@@ -185,6 +185,9 @@ def load_library() -> C.CDLL:
     lib.lfd_refine_multiview_host.argtypes = list(lib.lfd_refine_multiview.argtypes)
     lib.lfd_refine_multiview_weighted.argtypes = list(lib.lfd_refine_multiview.argtypes) + [C.c_void_p]
     lib.lfd_refine_multiview_weighted_host.argtypes = list(lib.lfd_refine_multiview_weighted.argtypes)
+    lib.lfd_depth_sigma_filter.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_points), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float,
+                                           C.c_float, C.POINTER(lfd_points), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lfd_depth_sigma_filter_host.argtypes = list(lib.lfd_depth_sigma_filter.argtypes)
     lib.lfd_copy_segments.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.lfd_launch_status.argtypes = [ctxp, C.POINTER(C.c_int32)]
     lib.lfd_get_pair_fundamental.argtypes = [ctxp, C.c_int32, C.POINTER(C.c_double)]
@@ -405,6 +408,8 @@ class TriangulationOutput:
     launch_status: int = 0                   # sampled call: look-back status of the launch (0 = ok)
     sel_status: Optional[np.ndarray] = None  # sampled calls: selection status per reference (0 = ok, else what upstream would have raised for)
     support_in: Optional[int] = None         # buffers lfd_support_filter filled: the points that reached the filter (``count`` of them were kept)
+    sigma_in: Optional[int] = None           # buffers lfd_depth_sigma_filter filled: the points that reached the gate (``count`` of them were kept;
+                                             # with both, the support filter kept ``sigma_in``)
     _packed: Optional[torch.Tensor] = None   # the one float buffer xyz / rgb / err are views of
     _cap: int = 0
 
@@ -589,13 +594,16 @@ class OutputBuffers:
         n_off, n_seg = 2 * (n_refs + 1), n_refs * k
         # ... [sel_info i32 x 2R+1] [pad to 8 bytes] [support_in i64]: the points that reached lfd_support_filter, written by HipDensifier.support_filter
         n_info = 2 * n_refs + 2
-        self._meta = torch.zeros((n_off + 2 * n_seg + n_info + 2,), dtype=torch.int32, device=device)
+        # ... [sigma_in i64]: the points that reached lfd_depth_sigma_filter, written by HipDensifier.depth_sigma_filter
+        self._meta = torch.zeros((n_off + 2 * n_seg + n_info + 4,), dtype=torch.int32, device=device)
         self._meta[n_off + n_seg:n_off + 2 * n_seg].fill_(-1)
         self.ref_offsets = self._meta[:n_off].view(torch.int64)
         self.seg_counts = self._meta[n_off:n_off + n_seg].view(n_refs, k)
         self.seg_order = self._meta[n_off + n_seg:n_off + 2 * n_seg].view(n_refs, k)
-        self.support_in = self._meta[n_off + 2 * n_seg + n_info:].view(torch.int64)
+        self.support_in = self._meta[n_off + 2 * n_seg + n_info:n_off + 2 * n_seg + n_info + 2].view(torch.int64)
+        self.sigma_in = self._meta[n_off + 2 * n_seg + n_info + 2:].view(torch.int64)
         self.filtered = False                                    # True: these buffers are a support filter's destination (collect reports support_in)
+        self.sigma_filtered = False                              # True: ... a depth-uncertainty gate's (collect reports sigma_in)
         self.sel_info = self._meta[n_off + 2 * n_seg:n_off + 2 * n_seg + 2 * n_refs + 1]           # lfd_triangulate_sampled[_multi]: {cells selected, selection status} per reference, then the launch status
         self._n_refs, self._k = n_refs, k
         self.c = lfd_points(xyz=self.xyz.data_ptr(), rgb=self.rgb.data_ptr(), err=self.err.data_ptr(),
@@ -655,7 +663,8 @@ class OutputBuffers:
             n_selected=int(meta[n_off + 2 * n_seg:n_off + 2 * n_seg + 2 * self._n_refs:2].sum()),
             sel_status=meta[n_off + 2 * n_seg + 1:n_off + 2 * n_seg + 2 * self._n_refs:2].copy(),
             launch_status=int(meta[n_off + 2 * n_seg + 2 * self._n_refs]),
-            support_in=int(meta[n_off + 2 * n_seg + 2 * self._n_refs + 2:].view(np.int64)[0]) if self.filtered else None, _packed=self._f,
+            support_in=int(meta[n_off + 2 * n_seg + 2 * self._n_refs + 2:].view(np.int64)[0]) if self.filtered else None,
+            sigma_in=int(meta[n_off + 2 * n_seg + 2 * self._n_refs + 2:].view(np.int64)[1]) if self.sigma_filtered else None, _packed=self._f,
             _cap=max(self.capacity, 1))
 
 
@@ -818,6 +827,63 @@ def _refine_call(fn, ctx, batch, src, support_thresh_px, reproj_thresh, with_sta
     if not collected:
         return rc, src, status
     return rc, dataclasses.replace(src, xyz=xyz_out[:cap], err=err_out[:cap], _packed=None), status
+
+
+def _depth_sigma_call(fn, ctx, batch, src, max_rel_sigma, iso_sigma_px, refine_status, support_thresh_px, with_sigma, into, device):
+    """One lfd_depth_sigma_filter[_host] call.  ``src``, ``into`` and the result: as in ``_support_filter_call``.  ``iso_sigma_px`` > 0: the
+    isotropic form; 0: the batch's precision planes.  ``refine_status``: None (the winner alone places a point) or the uint8 status tensor of
+    the re-triangulation that just ran over ``src``.  Returns (rc, result or None, sigma_rel of the input points or None, compacted sigma_rel
+    or None)."""
+    collected = isinstance(src, TriangulationOutput)
+    iso_sigma_px = float(iso_sigma_px)
+    if iso_sigma_px == 0.0 and batch.precision is None:
+        raise ValueError("depth_sigma_filter: iso_sigma_px=0 needs a batch whose references carry precision planes (ReferenceInputs.precision)")
+    if src.cell is None or src.slot is None:
+        raise ValueError("depth_sigma_filter: the source buffers need the cell / slot outputs (with_cell=True)")
+    if collected:
+        n = int(src.xyz.shape[0])
+        keep = [src.xyz.contiguous(), src.rgb.contiguous(), src.err.contiguous(), src.cell.contiguous(), src.slot.contiguous()]
+        if n == 0:                            # (an empty tensor may have no address at all; the library wants its arrays)
+            keep = [torch.zeros((1, 3) if t.dim() == 2 else (1,), dtype=t.dtype, device=t.device) for t in keep]
+        if any(t.device != device for t in keep):
+            raise ValueError(f"depth_sigma_filter: the points live on {keep[0].device}, this context computes on {device}")
+        offs_in = torch.from_numpy(np.ascontiguousarray(src.ref_offsets, np.int64)).to(device)
+        pts_in = lfd_points(xyz=keep[0].data_ptr(), rgb=keep[1].data_ptr(), err=keep[2].data_ptr(), cell=keep[3].data_ptr(), slot=keep[4].data_ptr(),
+                            capacity=n)
+        n_refs, k, cap = int(len(src.ref_offsets)) - 1, int(src.seg_counts.shape[1]), n
+    else:
+        if src.xyz.device != device:
+            raise ValueError(f"depth_sigma_filter: the points live on {src.xyz.device}, this context computes on {device}")
+        keep, offs_in, pts_in, n_refs, k, cap = [], src.ref_offsets, src.c, src._n_refs, src._k, src.capacity
+    if n_refs != batch.n_refs or k != batch.k:
+        raise ValueError(f"depth_sigma_filter: the points were made for {n_refs} references x {k} slots, the batch has {batch.n_refs} x {batch.k}")
+    if refine_status is not None and (refine_status.dtype != torch.uint8 or refine_status.device != device or not refine_status.is_contiguous()
+                                      or int(refine_status.numel()) < cap):
+        raise ValueError(f"depth_sigma_filter: refine_status must be a contiguous uint8 tensor of at least {cap} elements on {device}")
+    dst = into if into is not None else OutputBuffers(cap, n_refs, k, device, True, True if collected else src.with_segments)
+    if dst.capacity < cap or dst._n_refs != n_refs or dst._k != k or dst.xyz.device != device:
+        raise ValueError("depth_sigma_filter: `into` must have the source's capacity, references and slots, on this context's device")
+    if not collected:
+        dst._meta.copy_(src._meta)            # group order, selection and launch status (and the support filter's count) travel with the points
+        dst.sigma_in.copy_(src.ref_offsets[-1:])
+        dst.filtered, dst.sigma_filtered = bool(src.filtered), True
+    sigma = torch.empty((max(cap, 1),), dtype=torch.float32, device=device) if with_sigma else None
+    sigma_out = torch.empty((max(dst.capacity, 1),), dtype=torch.float32, device=device) if with_sigma else None
+    rc = fn(ctx, C.byref(batch.c), C.byref(pts_in), offs_in.data_ptr(), C.cast(batch.precision, C.c_void_p) if iso_sigma_px == 0.0 else None,
+            C.c_float(iso_sigma_px), refine_status.data_ptr() if refine_status is not None else None, C.c_float(float(support_thresh_px)),
+            C.c_float(float(max_rel_sigma)), C.byref(dst.c), dst.ref_offsets.data_ptr(), dst.seg_counts.data_ptr() if dst.with_segments else None,
+            sigma.data_ptr() if with_sigma else None, sigma_out.data_ptr() if with_sigma else None)
+    if rc != 0:
+        return rc, None, None, None
+    if with_sigma:
+        sigma = sigma[:cap]
+    if not collected:
+        return rc, dst, sigma, sigma_out
+    res = dst.collect()
+    res.sigma_in = n
+    res.seg_order = None
+    res.n_selected, res.sel_status, res.launch_status = src.n_selected, src.sel_status, src.launch_status
+    return rc, res, sigma, (sigma_out[:res.count] if with_sigma else None)
 
 
 class HipDensifier:
@@ -1019,6 +1085,24 @@ class HipDensifier:
                                            with_status, counters, self.device, precision)
         self._check(rc, name)
         return (res, status) if with_status else res
+
+    def depth_sigma_filter(self, batch: PreparedBatch, out_buffers, max_rel_sigma: float, iso_sigma_px: float = 0.0,
+                           refine_status: Optional[torch.Tensor] = None, support_thresh_px: float = 0.0, with_sigma: bool = False,
+                           into: Optional[OutputBuffers] = None):
+        """Depth-uncertainty gate behind a triangulation call (lfd_depth_sigma_filter): of the points ``out_buffers`` holds for
+        ``batch`` (an OutputBuffers a launch wrote, or a collected TriangulationOutput; with_cell=True), those whose sigma_rel - the 1-sigma
+        Cramer-Rao bound on the relative depth error along the reference's ray, from the views that placed the point - is at most
+        ``max_rel_sigma`` (0: all of them), compacted in order.  ``iso_sigma_px`` > 0: every match has that isotropic noise (camera px); 0: the
+        batch's precision planes.  ``refine_status``: the status tensor of the ``refine_multiview`` call that just ran over the points (its
+        candidates at ``support_thresh_px`` then count for the points it replaced), or None: the winning slot alone.  Returns buffers of the
+        same kind (asynchronous on the context's stream for OutputBuffers; ``into``: the buffers to fill instead of new ones); with
+        ``with_sigma`` a triple (result, f32 sigma_rel of every INPUT point, f32 sigma_rel compacted with the points)."""
+        self._same_device(batch)
+        with torch.cuda.stream(self.stream):
+            rc, res, sigma, sigma_out = _depth_sigma_call(self._lib.lfd_depth_sigma_filter, self._ctx, batch, out_buffers, max_rel_sigma,
+                                                          iso_sigma_px, refine_status, support_thresh_px, with_sigma, into, self.device)
+        self._check(rc, "lfd_depth_sigma_filter")
+        return (res, sigma, sigma_out) if with_sigma else res
 
     def quantise_rgb(self, rgb: torch.Tensor) -> torch.Tensor:
         rgb = self._pts(rgb, 3, "rgb")
@@ -1364,6 +1448,16 @@ class HostDensifier:
                                        with_status, counters, self.device, precision)
         self._check(rc, name)
         return (res, status) if with_status else res
+
+    def depth_sigma_filter(self, batch: PreparedBatch, out_buffers, max_rel_sigma: float, iso_sigma_px: float = 0.0,
+                           refine_status: Optional[torch.Tensor] = None, support_thresh_px: float = 0.0, with_sigma: bool = False,
+                           into: Optional[OutputBuffers] = None):
+        """HipDensifier.depth_sigma_filter over CPU tensors (lfd_depth_sigma_filter_host): the same per-point routine, host build."""
+        self._same_device(batch)
+        rc, res, sigma, sigma_out = _depth_sigma_call(self._lib.lfd_depth_sigma_filter_host, self._ctx, batch, out_buffers, max_rel_sigma,
+                                                      iso_sigma_px, refine_status, support_thresh_px, with_sigma, into, self.device)
+        self._check(rc, "lfd_depth_sigma_filter_host")
+        return (res, sigma, sigma_out) if with_sigma else res
 
     def aggregate(self, batch: PreparedBatch, params: lfd_params):
         self._same_device(batch)

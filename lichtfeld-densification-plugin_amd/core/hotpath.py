@@ -36,6 +36,12 @@ def _upload_u8(a, dev) -> torch.Tensor:
     return t if torch.device(dev).type == "cpu" else t.to(dev)
 
 
+def _pool_kind(out: hb.OutputBuffers) -> int:
+    """Which of the recycled buffers ``out`` belongs to: 0 a launch's own, 1 a support filter's destination, 2 / 3 a depth-uncertainty gate's
+    (behind no / a support filter) - ``collect`` reports the points that went into a stage only for that stage's destinations."""
+    return int(bool(out.filtered)) | (2 if getattr(out, "sigma_filtered", False) else 0)
+
+
 class HotPath:
     """Per-run state of the hot path: context, camera table, and the ways of triangulating a reference."""
 
@@ -78,6 +84,11 @@ class HotPath:
         self.refine_weighted = bool(config.exp("precision_weighted_refine"))     # lfd_refine_multiview_weighted in its place
         # int64 [2] where the kernels run: points refined / confirmed but left alone ([3] weighted: + solved with weighted rows), added to
         self._refine_counter: Optional[torch.Tensor] = None
+        # depth-uncertainty gate (lfd_depth_sigma_filter): the last stage behind support filter and re-triangulation
+        self.max_sigma = float(config.exp("max_depth_sigma_rel"))
+        self.iso_sigma_px = float(config.exp("match_sigma_px"))
+        self.sigma_planes = self.max_sigma > 0.0 and self.iso_sigma_px == 0.0     # the gate reads the matcher's precision planes
+        self.sigma_in = self.sigma_kept = 0                     # points that reached the gate / that it kept, over the results the run used
 
     # -- forward-backward consistency filter (lfd_cycle_gate) -------------------------------------------------------------------
     def cycle_gate(self, warps, certs, backs, axes) -> None:
@@ -118,16 +129,36 @@ class HotPath:
                 out = self.dens.support_filter(batch, res, self.min_support, self.support_thresh_px)
             self._support_count(out)
             res = out
+        status = None
         if self.refine:
             with self.clock.stage("kernel"):
-                res = self._refined(batch, res)
+                res, status = self._refined(batch, res, self.max_sigma > 0.0)
+        if self.max_sigma > 0.0:
+            with self.clock.stage("kernel"):
+                res = self._sigma_gated(batch, res, status)
+            self._support_count(res)
         return res
 
     def _support_count(self, res: hb.TriangulationOutput) -> None:
         """The run's totals, from the integers a result brings along anyway (no read-back of their own)."""
-        if res is not None and res.support_in is not None and not self._support_void:
+        if res is None or self._support_void:
+            return
+        if res.support_in is not None:             # (with the gate behind the filter, what the filter kept is what reached the gate)
             self.support_in += int(res.support_in)
-            self.support_kept += int(res.count)
+            self.support_kept += int(res.count if res.sigma_in is None else res.sigma_in)
+        if res.sigma_in is not None:
+            self.sigma_in += int(res.sigma_in)
+            self.sigma_kept += int(res.count)
+
+    def sigma_totals(self) -> Tuple[int, int]:
+        """(points that reached the depth-uncertainty gate, points it kept) of the run so far."""
+        return self.sigma_in, self.sigma_kept
+
+    def _sigma_gated(self, batch: hb.PreparedBatch, out, status, into=None):
+        """``out`` (buffers on the stream, or a collected result) through lfd_depth_sigma_filter.  ``status``: the status of the re-triangulation
+        that just ran over ``out`` on the same stream, or None: the winning slot alone placed every point."""
+        return self.dens.depth_sigma_filter(batch, out, self.max_sigma, iso_sigma_px=self.iso_sigma_px, refine_status=status,
+                                            support_thresh_px=self.support_thresh_px if status is not None else 0.0, into=into)
 
     def support_totals(self) -> Tuple[int, int]:
         """(points that reached the filter, points it dropped) of the run so far."""
@@ -145,20 +176,32 @@ class HotPath:
             finally:
                 self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, False), []).append(out)
             out = into
-        return self._refined(batch, out) if self.refine else out
+        status = None
+        if self.refine:
+            out, status = self._refined(batch, out, self.max_sigma > 0.0)
+        if self.max_sigma > 0.0:
+            into = self._take_buffers(out.capacity, out._n_refs, out._k, filtered=_pool_kind(out) | 2)
+            try:
+                self._sigma_gated(batch, out, status, into=into)
+            finally:
+                self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, _pool_kind(out)), []).append(out)
+            out = into
+        return out
 
     # -- multi-view re-triangulation of supported points (lfd_refine_multiview) ---------------------------------------------------
-    def _refined(self, batch: hb.PreparedBatch, out):
+    def _refined(self, batch: hb.PreparedBatch, out, with_status: bool = False):
         """The points of ``out`` (buffers a launch or the support filter just filled: in place; or a collected result: a copy) through
         lfd_refine_multiview - or, with experimental['precision_weighted_refine'], lfd_refine_multiview_weighted on the batch's precision
         planes: one launch on the stream that made them, before anything reads them.  The counters stay where the kernels run until
-        ``refine_totals``; they count every launch issued (a grouped call that is redone is counted twice)."""
+        ``refine_totals``; they count every launch issued (a grouped call that is redone is counted twice).  Returns (result, status): the
+        per-point status tensor, where the kernels run, when ``with_status`` (the depth-uncertainty gate behind it reads it), else None."""
         if self._refine_counter is None:
             self._refine_counter = torch.zeros(3 if self.refine_weighted else 2, dtype=torch.int64, device=self.dev)
-        if self.refine_weighted:
-            return self.dens.refine_multiview(batch, out, self.support_thresh_px, float(self.config.reproj_thresh), counters=self._refine_counter,
-                                              precision=True)
-        return self.dens.refine_multiview(batch, out, self.support_thresh_px, float(self.config.reproj_thresh), counters=self._refine_counter)
+        kw = {"precision": True} if self.refine_weighted else {}
+        if with_status:
+            return self.dens.refine_multiview(batch, out, self.support_thresh_px, float(self.config.reproj_thresh), with_status=True,
+                                              counters=self._refine_counter, **kw)
+        return self.dens.refine_multiview(batch, out, self.support_thresh_px, float(self.config.reproj_thresh), counters=self._refine_counter, **kw), None
 
     def refine_totals(self) -> Tuple[int, ...]:
         """(points refined, points other views confirmed that kept their two-view position[, points solved with weighted rows]) of the run:
@@ -228,7 +271,8 @@ class HotPath:
         return out
 
     def inputs(self, packed: PackedReference, warps, certs, precision=None) -> hb.ReferenceInputs:
-        """``precision``: the matcher's precision planes of the pairs (experimental['precision_weighted_refine']), or None."""
+        """``precision``: the matcher's precision planes of the pairs (experimental['precision_weighted_refine'], the depth-uncertainty gate
+        without experimental['match_sigma_px']), or None."""
         dev = self.dev
         if packed.dev is not None:                 # prepared on the device: nothing to upload
             d = packed.dev
@@ -337,11 +381,11 @@ class HotPath:
             out.begin_collect(self.dens.stream)
         return batch, out
 
-    def _take_buffers(self, capacity: int, n_refs: int, k: int, filtered: bool = False) -> hb.OutputBuffers:
+    def _take_buffers(self, capacity: int, n_refs: int, k: int, filtered: int = 0) -> hb.OutputBuffers:
         """Survivor buffers of the fused sampled calls, recycled: a fresh OutputBuffers costs two device allocations and - on its first
         read-back - a pinned host allocation (hipHostMalloc: milliseconds), per reference; ``finish_sampled`` hands a buffer back once the
         reference's survivors have been copied out of it."""
-        free = self._buf_pool.setdefault((int(capacity), int(n_refs), int(k), bool(filtered)), [])
+        free = self._buf_pool.setdefault((int(capacity), int(n_refs), int(k), int(filtered)), [])
         return free.pop() if free else hb.OutputBuffers(int(capacity), int(n_refs), int(k), self.dev)
 
     # -- upstream's normaliser without stalling the launch stream ---------------------------------------------------------------
@@ -505,7 +549,7 @@ class HotPath:
                                        cell=res.cell.clone() if res.cell is not None else None,
                                        slot=res.slot.clone() if res.slot is not None else None, _packed=None)
         finally:
-            self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, bool(out.filtered)), []).append(out)
+            self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, _pool_kind(out)), []).append(out)
 
     def pack_ply_tensor(self, xyz: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
         """The same records as a uint8 tensor that stays where the points are (what a sharded run sends to the writer rank)."""
@@ -526,15 +570,18 @@ class HotPath:
             if bool(self.config.exp("dense_tile_segments")):
                 # unordered retirement (no look-back), raster order restored from the tile table: the same result, bit for bit
                 return self.dens.order_segments(self.dens.triangulate_dense_segments(batch, self.params))
-            if (self.min_support > 0 or self.refine) and not self.on_host:
-                # the launch, the filter and / or the re-triangulation behind it on the same stream, then the one read-back of the offsets
+            if (self.min_support > 0 or self.refine or self.max_sigma > 0.0) and not self.on_host:
+                # the launch, the filter, the re-triangulation and / or the gate behind it on the same stream, then the one read-back of the offsets
                 cap = batch.n_refs * batch.H * batch.W
                 out = hb.OutputBuffers(cap, batch.n_refs, batch.k, self.dev)
                 self.dens.launch_dense(batch, self.params, out)
                 if self.min_support > 0:
                     out = self.dens.support_filter(batch, out, self.min_support, self.support_thresh_px)
+                status = None
                 if self.refine:
-                    out = self._refined(batch, out)
+                    out, status = self._refined(batch, out, self.max_sigma > 0.0)
+                if self.max_sigma > 0.0:
+                    out = self._sigma_gated(batch, out, status)
                 self.dens.check_launches()
                 res = out.collect()
                 self._support_void = False

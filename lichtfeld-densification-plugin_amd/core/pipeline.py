@@ -87,11 +87,18 @@ def _make_matcher(config, dev, progress_callback):
                           fused_local_corr=bool(config.exp("fused_local_corr")))
     if float(config.exp("cycle_thresh_px")) > 0.0:       # (a matcher built here starts with the backward warp off)
         matcher.set_backward_warp(True)
-    if bool(config.exp("precision_weighted_refine")):    # (... and hands out no precision planes)
+    if _wants_precision(config):                         # (... and hands out no precision planes)
         matcher.set_precision(True)
     if not cached and progress_callback is not None:
         progress_callback(10.0, "RoMa v2 model installation complete. Starting matching...")
     return matcher
+
+
+def _wants_precision(config) -> bool:
+    """Does the run read RoMa-v2's precision planes?  The weighted re-triangulation does, and the depth-uncertainty gate unless
+    it is given an isotropic match noise."""
+    return bool(config.exp("precision_weighted_refine")) or (float(config.exp("max_depth_sigma_rel")) > 0.0
+                                                             and float(config.exp("match_sigma_px")) == 0.0)
 
 
 def _announce(progress_callback, cached: bool) -> None:
@@ -138,10 +145,12 @@ def _match_reference(local_i: int, packed: PackedReference, matcher, hot: HotPat
             raise RuntimeError(f"experimental['cycle_thresh_px'] is set but {type(matcher).__name__}.match_grids_batch returned no backward warp")
         hot.cycle_gate(warps, certs, [_as_device_map(r[2], dev) for r in results], axes)
     precision = None
-    if hot.refine_weighted:
-        # RoMa-v2's precision planes: element 3 of the matcher's tuples, read in place by the weighted re-triangulation
+    if hot.refine_weighted or hot.sigma_planes:
+        # RoMa-v2's precision planes: element 3 of the matcher's tuples, read in place by the weighted re-triangulation and by
+        # the depth-uncertainty gate
         if any(len(r) < 4 or r[3] is None for r in results):
-            raise RuntimeError("experimental['precision_weighted_refine'] is set but "
+            knob = "precision_weighted_refine" if hot.refine_weighted else "max_depth_sigma_rel"
+            raise RuntimeError(f"experimental['{knob}'] is set but "
                                f"{type(matcher).__name__}.match_grids_batch returned no precision plane")
         precision = [_as_device_map(r[3], dev) for r in results]
     return Matched(local_i, packed, hot.inputs(packed, warps, certs, precision), axes, int(H), int(W), first_pair, want_debug)
@@ -227,9 +236,12 @@ def run_dense_pipeline(
                 raise ValueError("experimental['cycle_thresh_px'] asks for the forward-backward filter, which needs the matcher's backward warp, but the "
                                  f"injected matcher ({type(matcher).__name__}) does not declare supports_backward_warp")
             if bool(getattr(matcher, "supports_precision", False)):
-                matcher.set_precision(bool(config.exp("precision_weighted_refine")))
+                matcher.set_precision(_wants_precision(config))
             elif config.exp("precision_weighted_refine"):
                 raise ValueError("experimental['precision_weighted_refine'] asks for the precision-weighted re-triangulation, which needs the matcher's "
+                                 f"precision planes, but the injected matcher ({type(matcher).__name__}) does not declare supports_precision")
+            elif _wants_precision(config):
+                raise ValueError("experimental['max_depth_sigma_rel'] without experimental['match_sigma_px'] takes the match noise from the matcher's "
                                  f"precision planes, but the injected matcher ({type(matcher).__name__}) does not declare supports_precision")
             _announce(progress_callback, True)
         raise_if_cancelled(cancel_requested)
@@ -282,6 +294,10 @@ def run_dense_pipeline(
         if hot.refine and hot.refine_weighted:
             log.info(f"Precision-weighted re-triangulation: {n_refined} points refined, {n_fallback} confirmed points kept their two-view position, "
                      f"{totals[2]} points solved with weighted rows")
+        if hot.max_sigma > 0.0:
+            n_in, n_kept = hot.sigma_totals()
+            noise = f"isotropic match noise {hot.iso_sigma_px:g} px" if hot.iso_sigma_px > 0.0 else "the matcher's precision planes"
+            log.info(f"Depth-uncertainty gate: relative depth sigma at most {hot.max_sigma:g} ({noise}), {n_in} points in, {n_kept} kept")
     except BaseException as exc:
         if world == 1:
             raise

@@ -64,6 +64,13 @@ EXPERIMENTAL_DEFAULTS = {
     # 4.10) instead of equally.  Needs multiview_refine and a matcher that hands out the precision planes (supports_precision); a point with an
     # unusable plane in any of its views is solved unweighted.  Never changes which points are emitted.  False = off: no new code runs.
     "precision_weighted_refine": False,
+    # depth-uncertainty gate behind triangulation (lfd_depth_sigma_filter): a point is kept only if the 1-sigma bound on its
+    # relative depth error along the reference's ray - from the views that placed it, their geometry and their match precision - is at most
+    # this.  The last stage behind support filter and re-triangulation.  0.0 = off: no new code runs.
+    "max_depth_sigma_rel": 0.0,
+    # ... with every match taken to have this isotropic 1-sigma noise in px of the camera image (the unit of reproj_thresh).  0.0 = RoMa-v2's
+    # own 2x2 precision per match instead: needs a matcher that hands out the precision planes (supports_precision).
+    "match_sigma_px": 0.0,
 }
 
 
@@ -243,6 +250,28 @@ class DensePipelineConfig:
             return "experimental['precision_weighted_refine'] must be True or False"
         if weighted and not refine:
             return "experimental['precision_weighted_refine'] weights the rows of the multi-view re-triangulation: it needs experimental['multiview_refine'] = True"
+        try:
+            max_sigma = float(self.exp("max_depth_sigma_rel"))
+        except (TypeError, ValueError):
+            return "experimental['max_depth_sigma_rel'] must be a number (1-sigma relative depth error a point may have; 0 = off)"
+        if not (0.0 <= max_sigma < float("inf")):
+            return "experimental['max_depth_sigma_rel'] must be finite and >= 0 (1-sigma relative depth error a point may have; 0 = off)"
+        try:
+            iso_sigma = float(self.exp("match_sigma_px"))
+        except (TypeError, ValueError):
+            return "experimental['match_sigma_px'] must be a number (px of the camera image; 0 = the matcher's precision planes)"
+        if not (0.0 <= iso_sigma < float("inf")):
+            return "experimental['match_sigma_px'] must be finite and >= 0 (px of the camera image; 0 = the matcher's precision planes)"
+        if iso_sigma > 0.0 and not max_sigma > 0.0:
+            return "experimental['match_sigma_px'] is the match noise of the depth-uncertainty gate: it needs experimental['max_depth_sigma_rel'] > 0"
+        if max_sigma > 0.0:
+            if dense and self.stream_output:
+                return ("experimental['max_depth_sigma_rel'] filters points held as arrays (xyz, cell, slot); dense mode with stream_output has the "
+                        "kernel write PLY records instead")
+            if self.exp("dense_tile_segments"):
+                return "experimental['max_depth_sigma_rel'] needs the ordered dense result; experimental['dense_tile_segments'] retires tiles unordered"
+            if self.exchange_record_format() == "ply":
+                return "experimental['max_depth_sigma_rel'] filters f32 rows; experimental['exchange_records'] must be 'f32' with it"
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):
                 return "stream_output writes a PLY while the run proceeds: output_path must end in .ply"

@@ -18,6 +18,7 @@
 #include "lfd_cycle.hpp"
 #include "lfd_support.hpp"
 #include "lfd_refine.hpp"
+#include "lfd_sigma.hpp"
 
 extern "C" __global__ void lfd_aggregate_kernel(LfdLaunch L, float* best_cert, uint8_t* best_slot);
 extern "C" __global__ void lfd_dense_kernel(LfdLaunch L);
@@ -64,6 +65,7 @@ hipError_t lfd_corr_launch(const LfdCorrArgs& p, hipStream_t stream);     // lfd
 hipError_t lfd_cycle_launch(const LfdCycleArgs& p, hipStream_t stream);   // lfd_cycle.hip
 hipError_t lfd_support_launch(const LfdSupportArgs& p, hipStream_t stream);   // lfd_support.hip
 hipError_t lfd_refine_launch(const LfdRefineArgs& p, hipStream_t stream);     // lfd_refine.hip
+hipError_t lfd_sigma_launch(const LfdSigmaArgs& p, hipStream_t stream);       // lfd_sigma.hip
 extern "C" __global__ void lfd_select_topm_kernel(LfdSelectArgs A);
 extern "C" __global__ void lfd_select_filter_mw_kernel(LfdSelectArgs A, LfdSelectNorms norms);
 extern "C" __global__ void lfd_select_begins_kernel(long long* pairs, long long stride, int n);
@@ -1564,6 +1566,55 @@ int lfd_refine_multiview_weighted(lfd_context* ctx, const lfd_batch* batch, cons
                                   const float* const* precision) {
     return refine_impl(ctx, "lfd_refine_multiview_weighted", batch, in, ref_offsets, support_thresh_px, reproj_thresh, xyz_out, err_out, status,
                        counters, precision, true);
+}
+
+// ---- depth-uncertainty gate (lfd_sigma.hip) ---------------------------------------------------------------------------------------------------
+int lfd_depth_sigma_filter(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets_in,
+                           const float* const* precision, float iso_sigma_px, const uint8_t* refine_status, float support_thresh_px,
+                           float max_rel_sigma, const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out, float* sigma_rel,
+                           float* sigma_rel_out) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    int code = LFD_ERR_INVALID;
+    if (const char* why = lfd_sigma_check(in, ref_offsets_in, precision, iso_sigma_px, refine_status, support_thresh_px, max_rel_sigma, out,
+                                          ref_offsets_out, sigma_rel, sigma_rel_out, &code))
+        return fail(ctx, code, std::string("lfd_depth_sigma_filter: ") + why);
+    // the batch's tables and per-pair constants, derived again only when the batch differs from the last one seen (no threshold reaches them)
+    lfd_params none;
+    std::memset(&none, 0, sizeof(none));
+    LfdLaunch L;
+    int rc = prepare_launch(ctx, batch, &none, nullptr, 0, L, nullptr);
+    if (rc != LFD_OK) return rc;
+    LfdSigmaArgs p;
+    std::memset(&p, 0, sizeof(p));
+    if (precision) {
+        if (const char* why = lfd_refine_check_precision(batch, precision)) return fail(ctx, LFD_ERR_INVALID, std::string("lfd_depth_sigma_filter: ") + why);
+        rc = upload_precision_table(ctx, batch, precision, &p.prec);
+        if (rc != LFD_OK) return rc;
+    } else {
+        p.iso = lfd_recip_refined((double)iso_sigma_px * (double)iso_sigma_px);     // (host build: the IEEE quotient, as in the twin)
+    }
+    p.n_wg = (int32_t)((in->capacity + 255) / 256);
+    const size_t n_pad = (size_t)p.n_wg * 256;                          // sigma f32, keep bytes, then the workgroups' counts
+    rc = ensure(ctx, ctx->support_ws, n_pad * 5 + ((size_t)p.n_wg + 1) * sizeof(unsigned));
+    if (rc != LFD_OK) return rc;
+    p.refs = L.refs; p.slots = L.slots; p.ref_const = L.ref_const; p.pair_const = L.pair_const;
+    p.offs_in = reinterpret_cast<const long long*>(ref_offsets_in);
+    p.xyz = in->xyz; p.rgb = in->rgb; p.err = in->err; p.cell = in->cell; p.slot = in->slot;
+    p.o_xyz = out->xyz; p.o_rgb = out->rgb; p.o_err = out->err; p.o_cell = out->cell; p.o_slot = out->slot;
+    p.offs_out = reinterpret_cast<long long*>(ref_offsets_out);
+    p.seg_counts = seg_counts_out; p.sigma = sigma_rel; p.o_sigma = sigma_rel_out; p.status = refine_status;
+    unsigned char* ws = static_cast<unsigned char*>(ctx->support_ws.ptr);
+    p.ws_sigma = reinterpret_cast<float*>(ws);
+    p.keep = ws + n_pad * 4;
+    p.wg_kept = reinterpret_cast<unsigned*>(ws + n_pad * 5);
+    p.capacity = in->capacity;
+    p.max_rel_sigma = max_rel_sigma;
+    p.n_refs = batch->n_refs; p.k = batch->k;
+    p.g = launch_geom(batch, L, refine_status ? support_thresh_px : 0.0f, 0.0f);
+    if (seg_counts_out) LFD_HIP(ctx, hipMemsetAsync(seg_counts_out, 0, sizeof(int32_t) * (size_t)batch->n_refs * batch->k, ctx->stream));
+    LFD_HIP(ctx, lfd_sigma_launch(p, ctx->stream));
+    return LFD_OK;
 }
 
 int lfd_copy_segments(void* hip_stream, int32_t device_index, const void* src, void* dst, const lfd_copy_segment* segs, int32_t n) {

@@ -21,6 +21,7 @@
 #include "lfd_cycle.hpp"
 #include "lfd_support.hpp"
 #include "lfd_refine.hpp"
+#include "lfd_sigma.hpp"
 
 void lfd_fill_kernel_params(const lfd_batch* b, const lfd_params* p, LfdKernelParams& kp);   // lfd_api.hip
 
@@ -505,6 +506,105 @@ int lfd_refine_multiview_weighted_host(lfd_context* ctx, const lfd_batch* b, con
                                        int64_t* counters, const float* const* precision) {
     return refine_host_impl(ctx, "lfd_refine_multiview_weighted_host", b, in, ref_offsets, support_thresh_px, reproj_thresh, xyz_out, err_out,
                             status, counters, precision, true);
+}
+
+// The twin of lfd_depth_sigma_filter: lfd_sigma_point per point on the context's threads, then the stable compaction.
+int lfd_depth_sigma_filter_host(lfd_context* ctx, const lfd_batch* b, const lfd_points* in, const int64_t* ref_offsets_in,
+                                const float* const* precision, float iso_sigma_px, const uint8_t* refine_status, float support_thresh_px,
+                                float max_rel_sigma, const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out, float* sigma_rel,
+                                float* sigma_rel_out) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    int code = LFD_ERR_INVALID;
+    if (const char* why = lfd_sigma_check(in, ref_offsets_in, precision, iso_sigma_px, refine_status, support_thresh_px, max_rel_sigma, out,
+                                          ref_offsets_out, sigma_rel, sigma_rel_out, &code))
+        return lfd_fail(ctx, code, std::string("lfd_depth_sigma_filter_host: ") + why);
+    lfd_params none;
+    std::memset(&none, 0, sizeof(none));
+    int rc = validate_host(ctx, b, &none);
+    if (rc != LFD_OK) return rc;
+    const bool planes = precision != nullptr;
+    if (planes)
+        if (const char* why = lfd_refine_check_precision(b, precision))
+            return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_depth_sigma_filter_host: ") + why);
+    HostLaunch L;
+    prepare_host(b, &none, L);
+    std::vector<LfdSlot> rslot;
+    make_slot_table(ctx, L, rslot, nullptr);
+    std::vector<LfdSigmaRef> rref((size_t)b->n_refs);
+    for (int r = 0; r < b->n_refs; ++r) {
+        const LfdCam& ca = ctx->host_cams[(size_t)b->ref_cam[r]];
+        for (int e = 0; e < 3; ++e) rref[(size_t)r].C[e] = ca.C[e];    // LfdRefConst::C (lfd_make_ref_const)
+    }
+    std::vector<LfdSlotPrec> wslot(rslot.size());
+    if (planes)
+        for (int r = 0; r < b->n_refs; ++r)
+            for (int j = 0; j < b->n_slots[r]; ++j) {
+                LfdSlotPrec& w = wslot[(size_t)r * LFD_MAX_SLOTS + j];
+                w.prec = precision[(size_t)r * b->k + j];
+                lfd_slot_prec_scale(rslot[(size_t)r * LFD_MAX_SLOTS + j].sx, rslot[(size_t)r * LFD_MAX_SLOTS + j].sy, w);
+            }
+    const double iso = planes ? 0.0 : lfd_recip_refined((double)iso_sigma_px * (double)iso_sigma_px);
+    const LfdSupportGeom g = make_geom(L, refine_status ? support_thresh_px : 0.0f, 0.0f);
+    const long long cap = in->capacity;
+    const long long* offs = reinterpret_cast<const long long*>(ref_offsets_in);
+    const long long total = lfd_support_clamp(offs[b->n_refs], cap);
+    std::vector<float> sig((size_t)total);
+    parallel_chunks(ctx, (int)((total + kChunk - 1) / kChunk), [&](int c) {
+        const long long i1 = std::min<long long>(total, (long long)(c + 1) * kChunk);
+        for (long long i = (long long)c * kChunk; i < i1; ++i) {
+            const int r = lfd_support_ref_of(offs, b->n_refs, cap, i);
+            const int cell = in->cell[i], s = (int)in->slot[i], ns = b->n_slots[r];
+            float sigma = LFD_SIGMA_INF;
+            if (cell >= 0 && cell < L.HW && s < ns) {                   // no address is formed from a cell outside the grid
+                const float X0 = in->xyz[3 * i], X1 = in->xyz[3 * i + 1], X2 = in->xyz[3 * i + 2];
+                const LfdSlot* sl = &rslot[(size_t)r * LFD_MAX_SLOTS];
+                const LfdSlotPrec* ws = &wslot[(size_t)r * LFD_MAX_SLOTS];
+                const bool accepted = refine_status && (refine_status[i] & LFD_REFINE_ACCEPTED) != 0;
+                float cj[LFD_MAX_SLOTS], wx[LFD_MAX_SLOTS], wy[LFD_MAX_SLOTS], q00[LFD_MAX_SLOTS], q01[LFD_MAX_SLOTS], q11[LFD_MAX_SLOTS];
+                float qs[3] = {0.0f, 0.0f, 0.0f};
+                if (planes)
+                    for (int e = 0; e < 3; ++e) qs[e] = ws[s].prec[(size_t)cell * 3 + e];
+                for (int j = 0; j < LFD_MAX_SLOTS; ++j) {
+                    cj[j] = 0.0f; wx[j] = 0.0f; wy[j] = 0.0f; q00[j] = 0.0f; q01[j] = 0.0f; q11[j] = 0.0f;
+                    if (accepted && j < ns && j != s) {                 // (no other slot is touched for a point the winner alone placed)
+                        cj[j] = sl[j].cert[cell];
+                        const float* wv = sl[j].warp + (size_t)cell * g.C + (g.C - 2);
+                        wx[j] = wv[0]; wy[j] = wv[1];
+                        if (planes) {
+                            const float* qp = ws[j].prec + (size_t)cell * 3;
+                            q00[j] = qp[0]; q01[j] = qp[1]; q11[j] = qp[2];
+                        }
+                    }
+                }
+                const LfdRefineGather o = {cj, wx, wy, q00, q01, q11, qs};
+                sigma = accepted ? lfd_sigma_point<LFD_MAX_SLOTS, true>(rref[(size_t)r], sl, ws, ns, s, g, planes, iso, true, o, X0, X1, X2)
+                                 : lfd_sigma_point<LFD_MAX_SLOTS, false>(rref[(size_t)r], sl, ws, ns, s, g, planes, iso, false, o, X0, X1, X2);
+            }
+            sig[(size_t)i] = sigma;
+            if (sigma_rel) sigma_rel[i] = sigma;
+        }
+    });
+    // stable compaction: the input order inside and across references
+    if (seg_counts_out) std::memset(seg_counts_out, 0, sizeof(int32_t) * (size_t)b->n_refs * b->k);
+    long long o = 0;
+    int r_next = 0;
+    for (long long i = 0; i <= total; ++i) {
+        while (r_next <= b->n_refs && std::min(lfd_support_clamp(offs[r_next], cap), total) <= i) ref_offsets_out[r_next++] = o;
+        if (i == total || !lfd_sigma_keep(sig[(size_t)i], max_rel_sigma)) continue;
+        for (int e = 0; e < 3; ++e) { out->xyz[3 * o + e] = in->xyz[3 * i + e]; out->rgb[3 * o + e] = in->rgb[3 * i + e]; }
+        out->err[o] = in->err[i];
+        if (out->cell) out->cell[o] = in->cell[i];
+        if (out->slot) out->slot[o] = in->slot[i];
+        if (sigma_rel_out) sigma_rel_out[o] = sig[(size_t)i];
+        if (seg_counts_out) {
+            const int r = lfd_support_ref_of(offs, b->n_refs, cap, i), s = (int)in->slot[i];
+            if (s < b->n_slots[r]) seg_counts_out[(size_t)r * b->k + s] += 1;
+        }
+        ++o;
+    }
+    while (r_next <= b->n_refs) ref_offsets_out[r_next++] = o;       // (offsets that do not ascend: whatever is left counts from the end)
+    return LFD_OK;
 }
 
 int lfd_aggregate_host(lfd_context* ctx, const lfd_batch* b, const lfd_params* p, float* best_cert, uint8_t* best_slot) {

@@ -407,6 +407,10 @@ def _experimental_from_args(args) -> dict:
         exp["multiview_refine"] = True
     if bool(getattr(args, "precision_weighted_refine", False)):
         exp["precision_weighted_refine"] = True
+    if float(getattr(args, "max_depth_sigma_rel", 0.0)) != 0.0:
+        exp["max_depth_sigma_rel"] = float(args.max_depth_sigma_rel)
+    if float(getattr(args, "match_sigma_px", 0.0)) != 0.0:
+        exp["match_sigma_px"] = float(args.match_sigma_px)
     return exp
 
 
@@ -455,6 +459,11 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--precision_weighted_refine", action="store_true",
                     help="... with every view weighted by the precision matrix RoMa-v2 predicts for its match instead of equally (needs "
                          "--multiview_refine)")
+    ap.add_argument("--max_depth_sigma_rel", type=float, default=0.0,
+                    help="depth-uncertainty gate: keep a triangulated point only if the 1-sigma bound on its relative depth error, from the views "
+                         "that placed it, is at most this (e.g. 0.05; 0 = off)")
+    ap.add_argument("--match_sigma_px", type=float, default=0.0,
+                    help="... with this isotropic match noise in pixels of the camera image (0 = the precision matrix RoMa-v2 predicts per match)")
     ap.add_argument("--keep_threads", action="store_true",
                     help="leave torch's intra-op thread count alone (by default it is lowered to the container's CPU quota; the count decides the last "
                          "bits of upstream's sampling normaliser, so a run compared bit for bit with upstream keeps upstream's setting)")
