@@ -463,6 +463,34 @@ int lfd_depth_sigma_filter_host(lfd_context* ctx, const lfd_batch* batch, const 
                                 float max_rel_sigma, const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out,
                                 float* sigma_rel, float* sigma_rel_out);
 
+/* Cross-reference consensus filter on the final cloud (no upstream counterpart - the cloud upstream writes is the plain union of what
+ * every reference triangulated on its own).  The cloud is the concatenation of n_refs references' points; a point is kept iff at least min_refs
+ * OTHER references own a point within `radius` of it - the fusion rule of multi-view stereo, one level above lfd_support_filter, which only sees
+ * the neighbours one reference loaded (csrc/lfd_consensus.hpp, every rounding written out, no FMA):
+ *   agree(i, j)  f32: dx = x_i - x_j, dy, dz likewise; d2 = (dx dx + dy dy) + dz dz; r2 = radius radius; d2 <= r2.  Symmetric bit for bit; a NaN
+ *                never agrees
+ *   c_i          the number of DISTINCT references g != ref(i) that own at least one point agreeing with i, capped at LFD_CONSENSUS_CAP.  A point
+ *                with a non-finite coordinate agrees with nothing and vouches for nothing: c = 0, dropped; it takes no part in the min / max and
+ *                forms no address
+ *   kept         iff c_i >= min_refs.  Neighbours are found through a sorted grid of cells of side 1.000001 radius; neither the kept set nor the
+ *                counts depend on it
+ * xyz: f32 [n][3]; rgb (f32 [n][3]) and err (f32 [n]) travel along when given (NULL together with their output: not copied).  ref_offsets_host:
+ * HOST i64 [n_refs + 1], starts at 0, does not decrease, ends at n; reference g owns the points [off[g], off[g + 1]).  min_refs in
+ * 1 .. LFD_CONSENSUS_CAP.  The compaction is stable and copies bit for bit; xyz_out / rgb_out / err_out hold n points.  ref_offsets_out_host
+ * (HOST i64 [n_refs + 1]) and *n_out_host are always written; consensus: NULL, or u8 [n], c_i per INPUT point (without it the count stops at
+ * min_refs).  Synchronous, deterministic; the workspace belongs to the context and is reused.  LFD_ERR_INVALID: a null required pointer, n < 0 or
+ * > 2^31 - 1, n_refs < 1, malformed offsets, a radius that is <= 0 or not finite (or whose f32 square is below 2^-102 or overflows), min_refs out
+ * of range, in and out arrays that overlap, and - decided before anything is sorted, message "... key range ..." - a cloud so wide for the radius
+ * that an axis has more than 2^30 cells or the linear cell key leaves 63 bits.  n == 0 is valid.  lfd_consensus_filter_host: the same over host
+ * pointers on a host context's threads; every output equals the device's bit for bit. */
+#define LFD_CONSENSUS_CAP 8
+int lfd_consensus_filter(lfd_context* ctx, const float* xyz, const float* rgb, const float* err, int64_t n, const int64_t* ref_offsets_host,
+                         int32_t n_refs, float radius, int32_t min_refs, float* xyz_out, float* rgb_out, float* err_out,
+                         int64_t* ref_offsets_out_host, uint8_t* consensus, int64_t* n_out_host);
+int lfd_consensus_filter_host(lfd_context* ctx, const float* xyz, const float* rgb, const float* err, int64_t n, const int64_t* ref_offsets_host,
+                              int32_t n_refs, float radius, int32_t min_refs, float* xyz_out, float* rgb_out, float* err_out,
+                              int64_t* ref_offsets_out_host, uint8_t* consensus, int64_t* n_out_host);
+
 /* (e) multi-GPU exchange, placement step (no upstream counterpart - upstream has no multi-GPU code): n copies
  * dst[dst_offset .. +nbytes) = src[src_offset .. +nbytes) in ONE launch on `hip_stream` of device `device_index` (offsets and lengths in
  * bytes, no alignment required: 15-byte PLY records).  The overlapped exchange receives every rank's records of a round as one padded block
@@ -528,7 +556,7 @@ int lfd_host_eval_correspondence(const float* cam1, const float* cam2, float xa_
  * The per-cell arithmetic is the host build of the very source the kernels compile (csrc/lfd_geometry.hpp; IEEE
  * division / square root where the device uses the 1-ulp v_rcp / v_sqrt), spread over n_threads std::threads
  * (<= 0: all hardware threads).  A host context accepts lfd_upload_cameras, lfd_last_error, lfd_destroy and the
- * *_host calls (the three below, lfd_local_corr_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host and lfd_refine_multiview_weighted_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
+ * *_host calls (the three below, lfd_local_corr_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host and lfd_consensus_filter_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
  * context: neither side ever stands in for the other.  Semantics (orders, counts, optional outputs, LFD_ERR_CAPACITY
  * with valid counts) are those of lfd_aggregate / lfd_triangulate_dense / lfd_triangulate_indexed. */
 int lfd_create_host(int32_t n_threads, lfd_context** out);

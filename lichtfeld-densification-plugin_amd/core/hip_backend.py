@@ -19,6 +19,7 @@ from .types import CameraRecord, DensePipelineConfig
 
 LFD_MAX_SLOTS = 16
 LFD_ABI_VERSION = 9
+LFD_CONSENSUS_CAP = 8        # lfd_consensus_filter: min_refs is in 1 .. this, and the counts stop there
 LFD_FLAG_EXACT_COLOUR = 1     # lfd_params.flags: dense mode blends colours with upstream's f64 arithmetic (bit-identical rgb)
 LFD_FLAG_TILE_SEGMENTS = 2    # informational: the caller takes the unordered-retirement route (lfd_triangulate_dense_segments)
 _LIB_NAME = "liblfd_densify.so"
@@ -38,6 +39,11 @@ class SelectionInexact(HipBackendError):
 class VoxelInputRefused(HipBackendError):
     """lfd_voxel_downsample refused its input - a non-finite coordinate, or a linear voxel key beyond 63 bits - before sorting anything.
     The caller filters on the host instead (densify.dense_init_from_lfs does)."""
+
+
+class ConsensusInputRefused(HipBackendError):
+    """lfd_consensus_filter refused the cloud for its key range - so wide for the radius that an axis has more than 2^30 cells or the linear
+    cell key leaves 63 bits - before sorting anything.  Nothing stands in for it: the caller reports the radius (densify.py does)."""
 
 
 class lfd_params(C.Structure):
@@ -188,6 +194,9 @@ def load_library() -> C.CDLL:
     lib.lfd_depth_sigma_filter.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_points), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float,
                                            C.c_float, C.POINTER(lfd_points), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lfd_depth_sigma_filter_host.argtypes = list(lib.lfd_depth_sigma_filter.argtypes)
+    lib.lfd_consensus_filter.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_float, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)]
+    lib.lfd_consensus_filter_host.argtypes = list(lib.lfd_consensus_filter.argtypes)
     lib.lfd_copy_segments.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.lfd_launch_status.argtypes = [ctxp, C.POINTER(C.c_int32)]
     lib.lfd_get_pair_fundamental.argtypes = [ctxp, C.c_int32, C.POINTER(C.c_double)]
@@ -222,7 +231,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -886,6 +895,44 @@ def _depth_sigma_call(fn, ctx, batch, src, max_rel_sigma, iso_sigma_px, refine_s
     return rc, res, sigma, (sigma_out[:res.count] if with_sigma else None)
 
 
+def _consensus_call(fn, ctx, what, xyz, rgb, err, ref_counts, radius, min_refs, with_consensus, device, last_error):
+    """One lfd_consensus_filter[_host] call.  ``xyz`` (n, 3), ``rgb`` (n, 3) or None, ``err`` (n,) or None: float32 tensors on ``device``;
+    ``ref_counts``: points per reference, in the order of the cloud.  Returns ``(xyz, rgb, err, counts, consensus)``: the kept points in input
+    order (views of n-row tensors; rgb / err None when not given), the kept points per reference (int64 array) and - ``with_consensus`` - the
+    uint8 count of every INPUT point, else None.  Raises ``ConsensusInputRefused`` for the key-range refusal."""
+    counts = np.ascontiguousarray(np.asarray(ref_counts, np.int64).reshape(-1))
+    n = int(xyz.shape[0])
+    if counts.size < 1 or (counts < 0).any() or int(counts.sum()) != n:
+        raise ValueError(f"{what}: ref_counts must be non-negative counts, one per reference, that add up to the {n} points")
+    tensors = []
+    for t, cols, name in ((xyz, 3, "xyz"), (rgb, 3, "rgb"), (err, 0, "err")):
+        if t is None:
+            tensors.append(None)
+            continue
+        if t.dtype != torch.float32 or t.device != device or int(t.shape[0]) != n or (cols and (t.dim() != 2 or t.shape[1] != cols)) or (not cols and t.dim() != 1):
+            raise ValueError(f"{what}: {name} must be a float32 tensor of {n} rows{' x 3' if cols else ''} on {device}")
+        tensors.append(t.contiguous())
+    xyz, rgb, err = tensors
+    offs = np.zeros(counts.size + 1, np.int64)
+    np.cumsum(counts, out=offs[1:])
+    offs_out = np.zeros_like(offs)
+    outs = [torch.empty((max(n, 1),) + tuple(t.shape[1:]), dtype=torch.float32, device=device) if t is not None else None for t in tensors]
+    cons = torch.empty((max(n, 1),), dtype=torch.uint8, device=device) if with_consensus else None
+    n_out = C.c_int64(0)
+    ptr = lambda t: t.data_ptr() if t is not None and n > 0 else None       # noqa: E731  (an empty tensor may have no address at all)
+    i64p = C.POINTER(C.c_int64)
+    rc = fn(ctx, ptr(xyz), ptr(rgb), ptr(err), n, offs.ctypes.data_as(i64p), int(counts.size), C.c_float(float(radius)), int(min_refs),
+            ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), offs_out.ctypes.data_as(i64p), ptr(cons), C.byref(n_out))
+    if rc != 0:
+        msg = last_error()
+        if "key range" in msg:
+            raise ConsensusInputRefused(f"{what} refused its input ({rc}): {msg}")
+        raise HipBackendError(f"{what} failed ({rc}): {msg}")
+    k = int(n_out.value)
+    kept = [o[:k] if o is not None else None for o in outs]
+    return kept[0], kept[1], kept[2], np.diff(offs_out), (cons[:n] if with_consensus else None)
+
+
 class HipDensifier:
     """One context = one GPU + one stream (``torch.cuda.current_stream`` of the device at creation,
     unless a stream is given).  Not thread-safe: use one per thread, as the C-ABI requires."""
@@ -1019,6 +1066,14 @@ class HipDensifier:
                 raise VoxelInputRefused(f"lfd_voxel_downsample refused its input ({rc}): {msg}")
             self._check(rc, "lfd_voxel_downsample")
         return xo[:nv.value], ro[:nv.value]
+
+    def consensus_filter(self, xyz: torch.Tensor, rgb: Optional[torch.Tensor], err: Optional[torch.Tensor], ref_counts, radius: float, min_refs: int,
+                         with_consensus: bool = False):
+        """Cross-reference consensus filter on the device (lfd_consensus_filter): a point of the cloud - the concatenation of the
+        references' points, ``ref_counts`` each - is kept iff at least ``min_refs`` OTHER references own a point within ``radius`` of it.
+        Returns ``(xyz, rgb, err, counts, consensus)`` as ``_consensus_call`` describes.  Synchronous."""
+        return _consensus_call(self._lib.lfd_consensus_filter, self._ctx, "lfd_consensus_filter", xyz, rgb, err, ref_counts, radius, min_refs,
+                               with_consensus, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
 
     def set_stream(self, stream: "torch.cuda.Stream") -> None:
         """Later calls are issued on ``stream`` (lfd_set_stream: what was issued on the previous one is waited for first).  A call with the
@@ -1458,6 +1513,12 @@ class HostDensifier:
                                                       iso_sigma_px, refine_status, support_thresh_px, with_sigma, into, self.device)
         self._check(rc, "lfd_depth_sigma_filter_host")
         return (res, sigma, sigma_out) if with_sigma else res
+
+    def consensus_filter(self, xyz: torch.Tensor, rgb: Optional[torch.Tensor], err: Optional[torch.Tensor], ref_counts, radius: float, min_refs: int,
+                         with_consensus: bool = False):
+        """HipDensifier.consensus_filter over CPU tensors (lfd_consensus_filter_host): the same per-point routine, the same bits in every output."""
+        return _consensus_call(self._lib.lfd_consensus_filter_host, self._ctx, "lfd_consensus_filter_host", xyz, rgb, err, ref_counts, radius,
+                               min_refs, with_consensus, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
 
     def aggregate(self, batch: PreparedBatch, params: lfd_params):
         self._same_device(batch)

@@ -71,7 +71,14 @@ EXPERIMENTAL_DEFAULTS = {
     # ... with every match taken to have this isotropic 1-sigma noise in px of the camera image (the unit of reproj_thresh).  0.0 = RoMa-v2's
     # own 2x2 precision per match instead: needs a matcher that hands out the precision planes (supports_precision).
     "match_sigma_px": 0.0,
+    # cross-reference consensus filter on the final cloud (lfd_consensus_filter): a point is kept only if at least this many
+    # OTHER references put a point within consensus_radius of it - the one test that compares what different references say about the same
+    # surface.  Runs once, behind the run and in front of the point cap and the voxel filter.  1 .. 8; 0 = off: no new code runs.
+    "min_consensus_refs": 0,
+    # ... within this distance, in scene units (the unit of voxel_size).  Required > 0 with the filter on, 0 with it off.
+    "consensus_radius": 0.0,
 }
+CONSENSUS_CAP = 8            # LFD_CONSENSUS_CAP of include/lfd_densify.h
 
 
 @dataclasses.dataclass
@@ -272,6 +279,30 @@ class DensePipelineConfig:
                 return "experimental['max_depth_sigma_rel'] needs the ordered dense result; experimental['dense_tile_segments'] retires tiles unordered"
             if self.exchange_record_format() == "ply":
                 return "experimental['max_depth_sigma_rel'] filters f32 rows; experimental['exchange_records'] must be 'f32' with it"
+        m_con = self.exp("min_consensus_refs")
+        if isinstance(m_con, bool) or not isinstance(m_con, (int, np.integer)) or int(m_con) < 0:
+            return "experimental['min_consensus_refs'] must be a non-negative integer (other references that have to put a point next to a point; 0 = off)"
+        if int(m_con) > CONSENSUS_CAP:
+            return f"experimental['min_consensus_refs'] = {int(m_con)} is more than the {CONSENSUS_CAP} references the filter counts (LFD_CONSENSUS_CAP)"
+        try:
+            r_con = float(self.exp("consensus_radius"))
+        except (TypeError, ValueError):
+            return "experimental['consensus_radius'] must be a number (scene units, the unit of voxel_size)"
+        if not (0.0 <= r_con < float("inf")):
+            return "experimental['consensus_radius'] must be finite and >= 0 (scene units, the unit of voxel_size)"
+        if int(m_con) > 0 and not r_con > 0.0:
+            return "experimental['min_consensus_refs'] needs a distance: experimental['consensus_radius'] must be > 0 (scene units, the unit of voxel_size)"
+        if r_con > 0.0 and int(m_con) == 0:
+            return "experimental['consensus_radius'] is the distance of the consensus filter: it needs experimental['min_consensus_refs'] >= 1"
+        if int(m_con) > 0:
+            if self.stream_output:
+                return ("experimental['min_consensus_refs'] has to see the whole cloud before anything is written; stream_output writes the file "
+                        "while the run proceeds")
+            if self.exchange_record_format() == "ply":
+                return "experimental['min_consensus_refs'] filters f32 rows; experimental['exchange_records'] must be 'f32' with it"
+            if dense and self.exp("dense_tile_segments"):
+                return ("experimental['min_consensus_refs'] needs the cloud as arrays with per-reference counts; dense mode with "
+                        "experimental['dense_tile_segments'] retires tiles unordered")
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):
                 return "stream_output writes a PLY while the run proceeds: output_path must end in .ply"

@@ -19,6 +19,7 @@
 #include "lfd_support.hpp"
 #include "lfd_refine.hpp"
 #include "lfd_sigma.hpp"
+#include "lfd_consensus.hpp"
 
 extern "C" __global__ void lfd_aggregate_kernel(LfdLaunch L, float* best_cert, uint8_t* best_slot);
 extern "C" __global__ void lfd_dense_kernel(LfdLaunch L);
@@ -61,6 +62,18 @@ extern "C" __global__ void lfd_voxel_sums_kernel(const float* xyz, const float* 
 extern "C" __global__ void lfd_voxel_sums_big_kernel(const float* xyz, const float* rgb, long long n, const unsigned* sorted_idx, const unsigned* vstart,
                                                      const unsigned* nv_p, double cscale, const unsigned* big, const unsigned* n_big, float* xyz_out,
                                                      float* rgb_out);
+extern "C" __global__ void lfd_consensus_minmax_kernel(const float* xyz, long long n, LfdVoxStats* part);
+extern "C" __global__ void lfd_consensus_keys_kernel(const float* xyz, long long n, double o0, double o1, double o2, double h, unsigned long long e1,
+                                                     unsigned long long e2, unsigned long long sentinel, unsigned long long* keys, unsigned* idx);
+extern "C" __global__ void lfd_consensus_gather_kernel(const float* xyz, const unsigned* sorted_idx, const long long* offs, int n_refs, long long n,
+                                                       LfdConsensusPt* spt);
+extern "C" __global__ void lfd_consensus_count_kernel(const unsigned long long* skey, const LfdConsensusPt* spt, const unsigned* sorted_idx, long long n,
+                                                      unsigned long long e1, unsigned long long e2, unsigned long long sentinel, float r2, int min_refs,
+                                                      int bound, uint8_t* keep, uint8_t* consensus);
+extern "C" __global__ void lfd_consensus_wgcount_kernel(const uint8_t* keep, long long n, unsigned* wg_kept);
+extern "C" __global__ void lfd_consensus_offsets_kernel(const long long* offs, int n_refs, const uint8_t* keep, const unsigned* wg_kept, long long* offs_out);
+extern "C" __global__ void lfd_consensus_scatter_kernel(const float* xyz, const float* rgb, const float* err, long long n, const uint8_t* keep,
+                                                        const unsigned* wg_kept, float* o_xyz, float* o_rgb, float* o_err);
 hipError_t lfd_corr_launch(const LfdCorrArgs& p, hipStream_t stream);     // lfd_corr.hip
 hipError_t lfd_cycle_launch(const LfdCycleArgs& p, hipStream_t stream);   // lfd_cycle.hip
 hipError_t lfd_support_launch(const LfdSupportArgs& p, hipStream_t stream);   // lfd_support.hip
@@ -540,7 +553,7 @@ void lfd_destroy(lfd_context* ctx) {
     }
     for (hipEvent_t ev : ctx->kt_start) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->kt_stop) (void)hipEventDestroy(ev);
-    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->vox, &ctx->support_ws, &ctx->prec_tab})
+    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->vox, &ctx->support_ws, &ctx->prec_tab, &ctx->consensus_ws})
         if (b->ptr) (void)hipFree(b->ptr);
     if (ctx->pinned_words) (void)hipHostFree(ctx->pinned_words);
     if (ctx->prec_pinned) (void)hipHostFree(ctx->prec_pinned);
@@ -1411,6 +1424,91 @@ int lfd_voxel_downsample(lfd_context* ctx, const float* xyz, const float* rgb, i
     LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, nv_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     LFD_HIP(ctx, hipStreamSynchronize(st));
     *n_out_host = (int64_t)(unsigned)ctx->pinned_words[0];
+    return LFD_OK;
+}
+
+// ---- cross-reference consensus filter on the final cloud (lfd_consensus.hip) --------------------------------------------------------------------
+int lfd_consensus_filter(lfd_context* ctx, const float* xyz, const float* rgb, const float* err, int64_t n, const int64_t* ref_offsets_host,
+                         int32_t n_refs, float radius, int32_t min_refs, float* xyz_out, float* rgb_out, float* err_out,
+                         int64_t* ref_offsets_out_host, uint8_t* consensus, int64_t* n_out_host) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_consensus_check(xyz, rgb, err, n, ref_offsets_host, n_refs, radius, min_refs, xyz_out, rgb_out, err_out,
+                                              ref_offsets_out_host, consensus, n_out_host))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_consensus_filter: ") + why);
+    for (int32_t r = 0; r <= n_refs; ++r) ref_offsets_out_host[r] = 0;
+    *n_out_host = 0;
+    if (n == 0) return LFD_OK;
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // radix passes: workgroup b of G owns the items [b * chunk, (b + 1) * chunk); chunk is a multiple of the scatter's 512-item round
+    long long G = std::min<long long>(1024, (n + 4095) / 4096);
+    const long long chunk = (((n + G - 1) / G) + 511) / 512 * 512;
+    G = (n + chunk - 1) / chunk;
+    const int n_part = (int)std::min<long long>(1024, (n + 255) / 256);
+    const long long n_wg = (n + 255) / 256;
+    // workspace: partials | stats | digit counts | keys x 2 | indices x 2 | sorted points | offsets in, out | keep bytes | kept per workgroup
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t offs_bytes = ((size_t)n_refs + 1) * sizeof(long long);
+    const size_t o_part = 0, o_small = al(o_part + 1024 * sizeof(LfdVoxStats)), o_counts = al(o_small + sizeof(LfdVoxStats));
+    const size_t o_ka = al(o_counts + 256 * 1024 * sizeof(unsigned)), o_kb = al(o_ka + 8 * (size_t)n), o_ia = al(o_kb + 8 * (size_t)n);
+    const size_t o_ib = al(o_ia + 4 * (size_t)n), o_pt = al(o_ib + 4 * (size_t)n), o_off = al(o_pt + sizeof(LfdConsensusPt) * (size_t)n);
+    const size_t o_offo = al(o_off + offs_bytes), o_keep = al(o_offo + offs_bytes), o_wg = al(o_keep + (size_t)n_wg * 256);
+    const size_t total = al(o_wg + ((size_t)n_wg + 1) * sizeof(unsigned));
+    if (int rc = ensure(ctx, ctx->consensus_ws, total)) return rc;
+    unsigned char* w = static_cast<unsigned char*>(ctx->consensus_ws.ptr);
+    LfdVoxStats* part = reinterpret_cast<LfdVoxStats*>(w + o_part);
+    LfdVoxStats* stats = reinterpret_cast<LfdVoxStats*>(w + o_small);
+    unsigned* counts = reinterpret_cast<unsigned*>(w + o_counts);
+    unsigned long long* keys[2] = {reinterpret_cast<unsigned long long*>(w + o_ka), reinterpret_cast<unsigned long long*>(w + o_kb)};
+    unsigned* idx[2] = {reinterpret_cast<unsigned*>(w + o_ia), reinterpret_cast<unsigned*>(w + o_ib)};
+    LfdConsensusPt* spt = reinterpret_cast<LfdConsensusPt*>(w + o_pt);
+    long long* offs = reinterpret_cast<long long*>(w + o_off);
+    long long* offs_out = reinterpret_cast<long long*>(w + o_offo);
+    uint8_t* keep = w + o_keep;
+    unsigned* wg_kept = reinterpret_cast<unsigned*>(w + o_wg);
+
+    // min / max pass over the finite points; the key-range refusal is decided before anything is sorted
+    LFD_HIP(ctx, hipMemcpyAsync(offs, ref_offsets_host, offs_bytes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(lfd_consensus_minmax_kernel, dim3(n_part), dim3(256), 0, st, xyz, (long long)n, part);
+    hipLaunchKernelGGL(lfd_voxel_final_kernel, dim3(1), dim3(256), 0, st, part, n_part, stats);
+    LFD_HIP(ctx, hipGetLastError());
+    LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, stats, sizeof(LfdVoxStats), hipMemcpyDeviceToHost, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));
+    LfdVoxStats s;
+    std::memcpy(&s, ctx->pinned_words, sizeof(s));
+    if (!(s.lo[0] <= s.hi[0])) {                                   // no finite point: nothing agrees with anything
+        if (consensus) LFD_HIP(ctx, hipMemsetAsync(consensus, 0, (size_t)n, st));
+        LFD_HIP(ctx, hipStreamSynchronize(st));
+        return LFD_OK;
+    }
+    LfdConsensusGrid g;
+    if (!lfd_consensus_grid(s.lo, s.hi, radius, g))
+        return fail(ctx, LFD_ERR_INVALID, "lfd_consensus_filter: key range: more than 2^30 cells along an axis or a linear cell key beyond 63 bits");
+
+    const unsigned grid = (unsigned)std::min<long long>(n_wg, 4096);
+    hipLaunchKernelGGL(lfd_consensus_keys_kernel, dim3(grid), dim3(256), 0, st, xyz, (long long)n, g.origin[0], g.origin[1], g.origin[2], g.h, g.e[1],
+                       g.e[2], g.sentinel, keys[0], idx[0]);
+    int cur = 0;
+    for (int shift = 0; shift < g.bits; shift += 8, cur ^= 1) {
+        hipLaunchKernelGGL(lfd_voxel_hist_kernel, dim3((unsigned)G), dim3(256), 0, st, keys[cur], (long long)n, chunk, shift, counts);
+        hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, counts, (int)(256 * G), (unsigned*)nullptr);
+        hipLaunchKernelGGL(lfd_voxel_scatter_kernel, dim3((unsigned)G), dim3(512), 0, st, keys[cur], idx[cur], (long long)n, chunk, shift, counts,
+                           keys[cur ^ 1], idx[cur ^ 1]);
+    }
+    hipLaunchKernelGGL(lfd_consensus_gather_kernel, dim3(grid), dim3(256), 0, st, xyz, idx[cur], offs, (int)n_refs, (long long)n, spt);
+    hipLaunchKernelGGL(lfd_consensus_count_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, keys[cur], spt, idx[cur], (long long)n, g.e[1], g.e[2],
+                       g.sentinel, lfd_consensus_r2(radius), (int)min_refs, consensus ? LFD_CONSENSUS_CAP : (int)min_refs, keep, consensus);
+    hipLaunchKernelGGL(lfd_consensus_wgcount_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, keep, (long long)n, wg_kept);
+    hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, wg_kept, (int)n_wg, wg_kept + n_wg);
+    hipLaunchKernelGGL(lfd_consensus_offsets_kernel, dim3((unsigned)std::min<long long>(((long long)n_refs + 256) / 256, 1024)), dim3(256), 0, st, offs,
+                       (int)n_refs, keep, wg_kept, offs_out);
+    hipLaunchKernelGGL(lfd_consensus_scatter_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, xyz, rgb, err, (long long)n, keep, wg_kept, xyz_out, rgb_out,
+                       err_out);
+    LFD_HIP(ctx, hipGetLastError());
+    LFD_HIP(ctx, hipMemcpyAsync(ref_offsets_out_host, offs_out, offs_bytes, hipMemcpyDeviceToHost, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));
+    *n_out_host = ref_offsets_out_host[n_refs];
     return LFD_OK;
 }
 

@@ -22,6 +22,7 @@
 #include "lfd_support.hpp"
 #include "lfd_refine.hpp"
 #include "lfd_sigma.hpp"
+#include "lfd_consensus.hpp"
 
 void lfd_fill_kernel_params(const lfd_batch* b, const lfd_params* p, LfdKernelParams& kp);   // lfd_api.hip
 
@@ -604,6 +605,80 @@ int lfd_depth_sigma_filter_host(lfd_context* ctx, const lfd_batch* b, const lfd_
         ++o;
     }
     while (r_next <= b->n_refs) ref_offsets_out[r_next++] = o;       // (offsets that do not ascend: whatever is left counts from the end)
+    return LFD_OK;
+}
+
+// The twin of lfd_consensus_filter: the same keys, a stable sort, lfd_consensus_count_point per sorted point on the context's
+// threads, then the stable compaction.
+int lfd_consensus_filter_host(lfd_context* ctx, const float* xyz, const float* rgb, const float* err, int64_t n, const int64_t* ref_offsets_host,
+                              int32_t n_refs, float radius, int32_t min_refs, float* xyz_out, float* rgb_out, float* err_out,
+                              int64_t* ref_offsets_out_host, uint8_t* consensus, int64_t* n_out_host) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    if (const char* why = lfd_consensus_check(xyz, rgb, err, n, ref_offsets_host, n_refs, radius, min_refs, xyz_out, rgb_out, err_out,
+                                              ref_offsets_out_host, consensus, n_out_host))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_consensus_filter_host: ") + why);
+    for (int32_t r = 0; r <= n_refs; ++r) ref_offsets_out_host[r] = 0;
+    *n_out_host = 0;
+    if (n == 0) return LFD_OK;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (long long i = 0; i < n; ++i) {
+        if (!lfd_consensus_finite(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2])) continue;
+        for (int c = 0; c < 3; ++c) { lo[c] = std::min(lo[c], xyz[3 * i + c]); hi[c] = std::max(hi[c], xyz[3 * i + c]); }
+    }
+    if (!(lo[0] <= hi[0])) {                                           // no finite point: nothing agrees with anything
+        if (consensus) std::memset(consensus, 0, (size_t)n);
+        return LFD_OK;
+    }
+    LfdConsensusGrid g;
+    if (!lfd_consensus_grid(lo, hi, radius, g))
+        return lfd_fail(ctx, LFD_ERR_INVALID, "lfd_consensus_filter_host: key range: more than 2^30 cells along an axis or a linear cell key beyond 63 bits");
+    const long long* offs = reinterpret_cast<const long long*>(ref_offsets_host);
+    const int n_chunks = (int)((n + kChunk - 1) / kChunk);
+    std::vector<std::pair<unsigned long long, unsigned>> order((size_t)n);
+    parallel_chunks(ctx, n_chunks, [&](int c) {
+        const long long i1 = std::min<long long>(n, (long long)(c + 1) * kChunk);
+        for (long long i = (long long)c * kChunk; i < i1; ++i)
+            order[(size_t)i] = {lfd_consensus_key(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], g.origin[0], g.origin[1], g.origin[2], g.h, g.e[1], g.e[2],
+                                                  g.sentinel), (unsigned)i};
+    });
+    std::sort(order.begin(), order.end());                             // (key, original index): the order of a stable sort by key
+    std::vector<unsigned long long> skey((size_t)n);
+    std::vector<LfdConsensusPt> spt((size_t)n);
+    parallel_chunks(ctx, n_chunks, [&](int c) {
+        const long long j1 = std::min<long long>(n, (long long)(c + 1) * kChunk);
+        for (long long j = (long long)c * kChunk; j < j1; ++j) {
+            const long long i = order[(size_t)j].second;
+            skey[(size_t)j] = order[(size_t)j].first;
+            spt[(size_t)j] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], lfd_support_ref_of(offs, n_refs, n, i)};
+        }
+    });
+    const float r2 = lfd_consensus_r2(radius);
+    const int bound = consensus ? LFD_CONSENSUS_CAP : (int)min_refs;
+    std::vector<uint8_t> cnt((size_t)n);
+    parallel_chunks(ctx, n_chunks, [&](int c) {
+        const long long j1 = std::min<long long>(n, (long long)(c + 1) * kChunk);
+        for (long long j = (long long)c * kChunk; j < j1; ++j) {
+            int v = 0;
+            if (skey[(size_t)j] != g.sentinel)
+                v = lfd_consensus_count_point<LFD_CONSENSUS_CAP>(skey.data(), spt.data(), (long long)n, j, g.e[1], g.e[2], r2, bound);
+            cnt[(size_t)order[(size_t)j].second] = (uint8_t)v;
+        }
+    });
+    // stable compaction: the input order inside and across references, every value copied as bytes
+    long long o = 0;
+    int r_next = 0;
+    for (long long i = 0; i <= n; ++i) {
+        while (r_next <= n_refs && offs[r_next] <= i) ref_offsets_out_host[r_next++] = o;
+        if (i == n) break;
+        if (consensus) consensus[i] = cnt[(size_t)i];
+        if ((int)cnt[(size_t)i] < (int)min_refs) continue;
+        std::memcpy(xyz_out + 3 * o, xyz + 3 * i, 12);
+        if (rgb) std::memcpy(rgb_out + 3 * o, rgb + 3 * i, 12);
+        if (err) std::memcpy(err_out + o, err + i, 4);
+        ++o;
+    }
+    *n_out_host = o;
     return LFD_OK;
 }
 

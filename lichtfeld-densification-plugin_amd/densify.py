@@ -175,6 +175,55 @@ def _voxel_filter_on_device(device_points, voxel_size: float):
         dens.close()
 
 
+def _apply_consensus_filter(result, config: DensePipelineConfig, progress_callback=None):
+    """The cross-reference consensus filter on the finished cloud (lfd_consensus_filter), where the points are: the device
+    tensors of a GPU run through the device call, the host arrays of ``backend='host'`` through the twin.  Returns the result with the kept
+    points (input order, same bits) and their per-reference counts in place of the cloud; everything downstream - cap, voxel filter, packing,
+    writers - sees an ordinary result.  Off (experimental['min_consensus_refs'] = 0): the result itself, nothing runs."""
+    min_refs = int(config.exp("min_consensus_refs"))
+    if min_refs <= 0 or result.streamed_path is not None:
+        return result
+    from .core import hip_backend as hb
+    from .core.sinks import PipelineResult
+    import torch
+    radius = float(config.exp("consensus_radius"))
+    pts = result.device_points
+    if pts is None:
+        pts = tuple(torch.from_numpy(np.ascontiguousarray(a)) for a in (result.xyz, result.rgb, result.err))
+    counts = np.asarray(result.points_per_reference, np.int64)
+    n_in = int(pts[0].shape[0])
+    if int(counts.sum()) != n_in:
+        raise RuntimeError(f"experimental['min_consensus_refs'] needs the whole cloud with its per-reference counts: this result holds {n_in:,} "
+                           f"points, the counts add up to {int(counts.sum()):,} (a rank of a gather_to_root run that is not the root)")
+    if progress_callback:
+        progress_callback(92.0, "Applying consensus filter...")
+    on_gpu = bool(pts[0].is_cuda)
+    dens = hb.HipDensifier(pts[0].device) if on_gpu else hb.HostDensifier(int(config.exp("host_threads")))
+    try:
+        xyz, rgb, err, kept, _ = dens.consensus_filter(pts[0], pts[1], pts[2], counts, radius, min_refs)
+    except hb.ConsensusInputRefused as exc:
+        raise RuntimeError(f"experimental['consensus_radius'] = {radius:g} is too small for the extent of this cloud: {exc}") from exc
+    finally:
+        dens.close()
+    n_kept = int(xyz.shape[0])
+    log.info(f"Consensus filter (radius {radius:.4f}, {min_refs} other reference{'s' if min_refs != 1 else ''}): {n_in:,} points in, {n_kept:,} kept")
+    new_pts = (xyz, rgb, err)
+    if on_gpu:
+        clock = result._clock
+
+        def loader(p=new_pts, clk=clock):
+            if hasattr(clk, "stage"):
+                with clk.stage("d2h"):
+                    return tuple(t.cpu().numpy() for t in p)
+            return tuple(t.cpu().numpy() for t in p)
+        arrays = (None, None, None)
+    else:
+        loader, arrays = None, tuple(t.numpy() for t in new_pts)
+    return PipelineResult(xyz=arrays[0], rgb=arrays[1], err=arrays[2], elapsed_seconds=result.elapsed_seconds, pairs_processed=result.pairs_processed,
+                          pairs_matched=result.pairs_matched, points_per_reference=kept, device_points=new_pts, streamed_path=None,
+                          clock=result._clock, loader=loader)
+
+
 def _is_writer_rank() -> bool:
     """True unless this process is a non-zero rank of an initialised torch.distributed job."""
     try:
@@ -285,6 +334,7 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
         if progress_callback:
             progress_callback(0.0, "Cancelled")
         return 2
+    result = _apply_consensus_filter(result, config, progress_callback)      # (in front of the point cap: it has to see the whole cloud)
     if progress_callback:
         progress_callback(95.0, "Writing output...")
     if result.streamed_path == config.output_path:      # config.stream_output: the file is already complete (and no cap applies to it)
@@ -334,6 +384,10 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
         return 1, str(exc)
     if _was_cancelled(cancel_requested):
         return 2, "Cancelled"
+    try:
+        result = _apply_consensus_filter(result, config, progress_callback)  # (in front of the point cap and the voxel filter: it has to see the whole cloud)
+    except RuntimeError as exc:
+        return 1, str(exc)
     if result.streamed_path == config.output_path:      # config.stream_output: the PLY is complete; neither a cap nor a voxel filter applies to it
         if progress_callback:
             progress_callback(95.0, "Writing output PLY...")
@@ -411,6 +465,10 @@ def _experimental_from_args(args) -> dict:
         exp["max_depth_sigma_rel"] = float(args.max_depth_sigma_rel)
     if float(getattr(args, "match_sigma_px", 0.0)) != 0.0:
         exp["match_sigma_px"] = float(args.match_sigma_px)
+    if int(getattr(args, "min_consensus_refs", 0)) != 0:
+        exp["min_consensus_refs"] = int(args.min_consensus_refs)
+    if float(getattr(args, "consensus_radius", 0.0)) != 0.0:
+        exp["consensus_radius"] = float(args.consensus_radius)
     return exp
 
 
@@ -464,6 +522,11 @@ def build_argparser() -> argparse.ArgumentParser:
                          "that placed it, is at most this (e.g. 0.05; 0 = off)")
     ap.add_argument("--match_sigma_px", type=float, default=0.0,
                     help="... with this isotropic match noise in pixels of the camera image (0 = the precision matrix RoMa-v2 predicts per match)")
+    ap.add_argument("--min_consensus_refs", type=int, default=0,
+                    help="cross-reference consensus filter on the final cloud: keep a point only if at least this many OTHER references put a point "
+                         "within --consensus_radius of it (1 .. 8; runs in front of --max_points; 0 = off)")
+    ap.add_argument("--consensus_radius", type=float, default=0.0,
+                    help="... within this distance in scene units (required > 0 with --min_consensus_refs)")
     ap.add_argument("--keep_threads", action="store_true",
                     help="leave torch's intra-op thread count alone (by default it is lowered to the container's CPU quota; the count decides the last "
                          "bits of upstream's sampling normaliser, so a run compared bit for bit with upstream keeps upstream's setting)")
