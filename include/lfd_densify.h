@@ -519,7 +519,29 @@ int lfd_prepare_image(lfd_context* ctx, const uint8_t* src_rgb, int32_t w_in, in
                       const uint8_t* mask01, uint8_t* dst_rgb);
 int lfd_prepare_mask(lfd_context* ctx, const uint8_t* src_l, int32_t w_in, int32_t h_in, int32_t w_out, int32_t h_out,
                      float threshold, int32_t invert, uint8_t* dst01);
-/* host helpers (CPU tests): the resampling tables exactly as the kernels use them.  bounds: [out_size*2] = {first, count};
+/* Image undistortion in front of everything else (no upstream counterpart - upstream reads (fx, fy, cx, cy) of a COLMAP camera and
+ * ignores the rest).  dst is the pinhole image of the same (fx, fy, cx, cy), width and height: output pixel (i, j) is sent through the camera
+ * model and sampled from the photograph src.  COLMAP's SIMPLE_RADIAL, RADIAL, OPENCV and FULL_OPENCV are one formula with the eight
+ * coefficients dist = (k1, k2, p1, p2, k3, k4, k5, k6); all in f64, every rounding written out, no FMA (csrc/lfd_undistort.hpp), pixel
+ * centres at +0.5:
+ *   x = ((j + 0.5) - cx) / fx, y likewise;  r2 = x x + y y;  rad = (((1 + k1 r2) + k2 r4) + k3 r6) / (((1 + k4 r2) + k5 r4) + k6 r6)
+ *   xd = (x rad + (2 p1) x y) + p2 (r2 + 2 x x), yd = (y rad + (2 p2) x y) + p1 (r2 + 2 y y);  su = (fx xd + cx) - 0.5, sv likewise
+ *   valid  iff -0.5 <= su <= w - 0.5 and -0.5 <= sv <= h - 0.5 (a NaN or an infinity, a zero denominator included, is not)
+ *   valid pixels: bilinear blend of the four u8 taps around (su, sv), indices clamped to the image (edge replication inside the half-pixel
+ *   border), top = p00 + ax (p01 - p00), bot likewise, val = top + ay (bot - top), out = floor(val + 0.5); with `nearest` (mask planes) the
+ *   one tap at floor(su + 0.5), floor(sv + 0.5), clamped.  Invalid pixels: every channel 0.
+ * With all-zero coefficients dst equals src byte for byte.  src, dst: u8 [h][w][channels], channels 1 or 3; valid255: NULL, or u8 [h*w],
+ * 255 where valid and 0 elsewhere (an "L" mask as it stands); intr = (fx, fy, cx, cy) and dist: HOST f64.  Asynchronous on the context's
+ * stream unless n_invalid_host is given: the call then synchronises and reports the number of invalid pixels (counted per wave, one atomic
+ * add per workgroup into a counter of the context).  LFD_ERR_INVALID: a null required pointer, w or h < 1 or w*h beyond 2^31 - 1, channels
+ * not 1 or 3, fx or fy not finite or <= 0, any other parameter not finite, src / dst / valid255 overlapping; LFD_ERR_STATE: a host context.
+ * lfd_host_undistort_image: the same routine over host pointers on the caller's thread; no context, no global state (callable from several
+ * threads at once; an error is its return code alone); every output equals the device's byte for byte. */
+int lfd_undistort_image(lfd_context* ctx, const uint8_t* src, int32_t w, int32_t h, int32_t channels, int32_t nearest, const double intr[4],
+                        const double dist[8], uint8_t* dst, uint8_t* valid255, int64_t* n_invalid_host);
+int lfd_host_undistort_image(const uint8_t* src, int32_t w, int32_t h, int32_t channels, int32_t nearest, const double intr[4],
+                             const double dist[8], uint8_t* dst, uint8_t* valid255, int64_t* n_invalid_host);
+/* host helpers (CPU tests): the resampling tables exactly as the kernels use them. bounds: [out_size*2] = {first, count};
  * kk: [out_size * *ksize_out] 22-bit fixed-point coefficients (LFD_ERR_CAPACITY if kk_capacity is too small, *ksize_out is
  * still set); idx: [out_size] NEAREST source indices. */
 int lfd_host_resize_tables(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* kk, int32_t kk_capacity, int32_t* ksize_out);

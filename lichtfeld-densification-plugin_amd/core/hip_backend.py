@@ -217,6 +217,9 @@ def load_library() -> C.CDLL:
                                                  C.POINTER(C.c_int64), C.POINTER(lfd_points), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lfd_prepare_image.argtypes = [ctxp, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.lfd_prepare_mask.argtypes = [ctxp, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]
+    dptr = C.POINTER(C.c_double)
+    lib.lfd_undistort_image.argtypes = [ctxp, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dptr, dptr, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.lfd_host_undistort_image.argtypes = list(lib.lfd_undistort_image.argtypes[1:])
     lib.lfd_host_resize_tables.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]
     lib.lfd_host_nearest_indices.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
     lib.lfd_identity_axis.argtypes = [C.c_int32, fptr]
@@ -326,6 +329,33 @@ def host_nearest_indices(in_size: int, out_size: int) -> np.ndarray:
     if load_library().lfd_host_nearest_indices(in_size, out_size, idx.ctypes.data_as(C.POINTER(C.c_int32))) != 0:
         raise HipBackendError("lfd_host_nearest_indices failed")
     return idx
+
+
+def _undistort_parameters(distortion):
+    """(intr, dist) as the C arrays of lfd_undistort_image from the twelve f64 values (fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6)."""
+    d = [float(v) for v in distortion]
+    if len(d) != 12:
+        raise ValueError("distortion must hold twelve values: fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6")
+    return (C.c_double * 4)(*d[:4]), (C.c_double * 8)(*d[4:])
+
+
+def host_undistort_image(src, distortion, nearest: bool = False, with_valid: bool = False):
+    """The context-free CPU twin of ``HipDensifier.undistort_image`` (lfd_host_undistort_image): ``src`` a (h, w) or
+    (h, w, 3) u8 array, ``distortion`` the twelve f64 parameters.  Returns ``(dst, valid255 or None, n_invalid)``; ``valid255`` (h, w) u8 is
+    255 where the photograph covers the pixel and 0 elsewhere.  Callable from several threads at once."""
+    a = np.ascontiguousarray(src, dtype=np.uint8)
+    if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
+        raise ValueError("src must be a (h, w) or (h, w, 3) uint8 array")
+    h, w = int(a.shape[0]), int(a.shape[1])
+    intr, dist = _undistort_parameters(distortion)
+    dst = np.empty_like(a)
+    valid = np.empty((h, w), np.uint8) if with_valid else None
+    n_bad = C.c_int64(-1)
+    rc = load_library().lfd_host_undistort_image(a.ctypes.data, w, h, 1 if a.ndim == 2 else 3, 1 if nearest else 0, intr, dist, dst.ctypes.data,
+                                                 valid.ctypes.data if with_valid else None, C.byref(n_bad))
+    if rc != 0:
+        raise HipBackendError(f"lfd_host_undistort_image refused its arguments ({rc}): {w} x {h}, parameters {tuple(float(v) for v in distortion)}")
+    return dst, valid, int(n_bad.value)
 
 
 def fundamental_from_world2cam(K1, R1, t1, K2, R2, t2) -> np.ndarray:
@@ -940,6 +970,7 @@ class HipDensifier:
     def __init__(self, device: Optional[torch.device] = None, stream: Optional[torch.cuda.Stream] = None):
         self._lib = load_library()
         self._ctx = C.c_void_p()
+        self._undistort_ws: dict = {}           # undistort_image's named workspaces: (name, part) -> u8 buffer
         if not torch.cuda.is_available():
             raise HipBackendError("no GPU visible: the dense-initialisation hot path has no CPU fallback")
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -957,6 +988,7 @@ class HipDensifier:
         if getattr(self, "_ctx", None) is not None and self._ctx.value:
             self._lib.lfd_destroy(self._ctx)
             self._ctx = C.c_void_p()
+        self._undistort_ws = {}
 
     def __del__(self):
         try:
@@ -1192,6 +1224,35 @@ class HipDensifier:
         self._check(self._lib.lfd_prepare_mask(self._ctx, mask_l.data_ptr(), int(mask_l.shape[1]), int(mask_l.shape[0]), w_out, h_out,
                                                C.c_float(threshold), 1 if invert else 0, out.data_ptr()), "lfd_prepare_mask")
         return out
+
+    def undistort_image(self, src: torch.Tensor, distortion, nearest: bool = False, with_valid: bool = False, count: bool = False,
+                        workspace: Optional[str] = None):
+        """A decoded (h, w, 3) or (h, w) u8 device image resampled through the camera's distortion model into the pinhole image of the same
+        intrinsics (lfd_undistort_image, DESIGN.md 4.13); ``distortion``: the twelve f64 parameters of ``CameraRecord.distortion``;
+        ``nearest``: one tap per pixel (mask planes).  Returns ``(dst, valid255 or None, n_invalid or None)``: ``valid255`` (h, w) u8, 255
+        where the photograph covers the pixel; ``count``: the call synchronises and reports the invalid pixels, else it is asynchronous on
+        the context's stream.  ``workspace``: a name - the outputs are then views of buffers this context owns under that name and reuses
+        (valid until the next call with the same name: everything runs in stream order) instead of fresh tensors."""
+        if src.dtype != torch.uint8 or src.device != self.device or src.dim() not in (2, 3) or (src.dim() == 3 and src.shape[2] != 3):
+            raise ValueError("src must be a (h, w) or (h, w, 3) uint8 tensor on this context's device")
+        src = src.contiguous()
+        h, w = int(src.shape[0]), int(src.shape[1])
+        intr, dist = _undistort_parameters(distortion)
+        dst = self._undistort_buffer(workspace, "dst", src.numel()).view(src.shape)
+        valid = self._undistort_buffer(workspace, "valid", h * w).view(h, w) if with_valid else None
+        n_bad = C.c_int64(-1)
+        self._check(self._lib.lfd_undistort_image(self._ctx, src.data_ptr(), w, h, 1 if src.dim() == 2 else 3, 1 if nearest else 0, intr, dist,
+                                                  dst.data_ptr(), valid.data_ptr() if with_valid else None, C.byref(n_bad) if count else None),
+                    "lfd_undistort_image")
+        return dst, valid, (int(n_bad.value) if count else None)
+
+    def _undistort_buffer(self, workspace: Optional[str], part: str, nbytes: int) -> torch.Tensor:
+        if workspace is None:
+            return torch.empty((int(nbytes),), dtype=torch.uint8, device=self.device)
+        buf = self._undistort_ws.get((workspace, part))
+        if buf is None or buf.numel() < nbytes:
+            buf = self._undistort_ws[(workspace, part)] = torch.empty((int(nbytes),), dtype=torch.uint8, device=self.device)
+        return buf[:int(nbytes)]
 
     # -- S: selection stage on the device ----------------------------------------------------------------
     def seed_rng(self, seed: int) -> None:

@@ -89,6 +89,10 @@ class HotPath:
         self.iso_sigma_px = float(config.exp("match_sigma_px"))
         self.sigma_planes = self.max_sigma > 0.0 and self.iso_sigma_px == 0.0     # the gate reads the matcher's precision planes
         self.sigma_in = self.sigma_kept = 0                     # points that reached the gate / that it kept, over the results the run used
+        # experimental['undistort_images']: per camera, the twelve parameters its decoded image is undistorted with in
+        # prepare_on_device, or None (knob off, or a camera without distortion coefficients: no new code runs for it)
+        on = bool(config.exp("undistort_images"))
+        self._distortion = [c.active_distortion() if on else None for c in cams]
 
     # -- forward-backward consistency filter (lfd_cycle_gate) -------------------------------------------------------------------
     def cycle_gate(self, warps, certs, backs, axes) -> None:
@@ -244,8 +248,13 @@ class HotPath:
             if hit is not None:
                 self._prepared.move_to_end(key)
                 return hit
-            m01 = self.dens.prepare_mask(up(mask_l), size_wh) if mask_l is not None else None
-            entry = (self.dens.prepare_image(up(img), size_wh, m01), m01)
+            dist = self._distortion[int(cam_index)]
+            if dist is None:
+                m01 = self.dens.prepare_mask(up(mask_l), size_wh) if mask_l is not None else None
+                entry = (self.dens.prepare_image(up(img), size_wh, m01), m01)
+            else:
+                entry = undistorted(up(img), up(mask_l) if mask_l is not None else None, dist)
+                m01 = entry[1]
             nbytes = entry[0].numel() + (m01.numel() if m01 is not None else 0)
             if nbytes <= PREPARED_CACHE_BYTES:
                 self._prepared[key] = entry
@@ -254,6 +263,23 @@ class HotPath:
                     _k, old = self._prepared.popitem(last=False)
                     self._prepared_bytes -= old[0].numel() + (old[1].numel() if old[1] is not None else 0)
             return entry
+
+        def undistorted(img_t, mask_t, dist):
+            # lfd_undistort_image into the context's full-resolution workspaces, in front of the two preparation kernels, all in stream order.
+            # The one read-back - the number of pixels the photograph does not cover - decides whether the camera gets a mask of its own: with
+            # ordinary barrel distortion there is none, and the dense kernel keeps its no-mask fast path.
+            pin, valid, n_invalid = self.dens.undistort_image(img_t, dist, with_valid=True, count=True, workspace="image")
+            m01 = None
+            if mask_t is not None:
+                m01 = self.dens.prepare_mask(self.dens.undistort_image(mask_t, dist, nearest=True, workspace="mask")[0], size_wh)
+            if n_invalid:
+                v01 = self.dens.prepare_mask(valid, size_wh)
+                if m01 is None:
+                    m01 = v01
+                else:
+                    with torch.cuda.stream(self.dens.stream):
+                        m01 &= v01
+            return self.dens.prepare_image(pin, size_wh, m01), m01
 
         with self.clock.stage("prepare"):
             img_a, mask_a = one(packed.ref_index, packed.image, packed.mask_a)

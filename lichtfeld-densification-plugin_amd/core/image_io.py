@@ -2,14 +2,17 @@
 
 Same decoding rules as upstream so that the colours sampled by the kernel come from the same
 pixels: RGB via PIL, resized to the matcher resolution with ``Image.BILINEAR``; masks converted to
-"L", resized with ``Image.NEAREST`` and thresholded at ``> 0.5`` of full scale (1 = keep)."""
+"L", resized with ``Image.NEAREST`` and thresholded at ``> 0.5`` of full scale (1 = keep).
+
+``distortion`` (experimental['undistort_images']): the twelve f64 parameters of ``CameraRecord.distortion``; the decoded image /
+"L" plane then goes through lfd_host_undistort_image - into the pinhole image of the same intrinsics - in front of the resize."""
 from __future__ import annotations
 
 import os
 import threading
 from collections import OrderedDict
 from functools import lru_cache, wraps
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 
@@ -82,14 +85,24 @@ def to_uint8_rgb(rgb01: np.ndarray) -> np.ndarray:
     return np.clip(np.round(np.asarray(rgb01) * 255.0), 0, 255).astype(np.uint8)
 
 
+def _undistorted(im, distortion, nearest: bool):
+    """A decoded PIL image ("RGB" or "L") through lfd_host_undistort_image, as a PIL image again."""
+    from PIL import Image
+
+    from . import hip_backend as hb
+    return Image.fromarray(hb.host_undistort_image(np.asarray(im, dtype=np.uint8), distortion, nearest=nearest)[0])
+
+
 @lru_cache(maxsize=4096)
-def load_rgb_u8(path: str, size: Tuple[int, int]) -> np.ndarray:
-    """(h, w, 3) u8 array of ``path`` resized to ``size=(w, h)``."""
+def load_rgb_u8(path: str, size: Tuple[int, int], distortion: Optional[Tuple[float, ...]] = None) -> np.ndarray:
+    """(h, w, 3) u8 array of ``path`` - undistorted first when ``distortion`` is given - resized to ``size=(w, h)``."""
     from PIL import Image
     clock = stages.current()
     with clock.stage("decode", sync=False):
         im = Image.open(path).convert("RGB")
     with clock.stage("prepare", sync=False):
+        if distortion is not None:
+            im = _undistorted(im, distortion, nearest=False)
         if im.size != tuple(size):
             im = im.resize(tuple(size), Image.BILINEAR)
         arr = np.asarray(im, dtype=np.uint8)
@@ -98,8 +111,9 @@ def load_rgb_u8(path: str, size: Tuple[int, int]) -> np.ndarray:
 
 
 @lru_cache(maxsize=4096)
-def load_mask01(path: str, size: Tuple[int, int], invert: bool = False, threshold: float = 0.5) -> np.ndarray:
-    """(h, w) u8 {0,1} mask, 1 = keep."""
+def load_mask01(path: str, size: Tuple[int, int], invert: bool = False, threshold: float = 0.5,
+                distortion: Optional[Tuple[float, ...]] = None) -> np.ndarray:
+    """(h, w) u8 {0,1} mask, 1 = keep; with ``distortion`` the "L" plane is undistorted (one tap per pixel) in front of the resize."""
     from PIL import Image
     if not os.path.isfile(path):
         raise FileNotFoundError(path)
@@ -107,12 +121,35 @@ def load_mask01(path: str, size: Tuple[int, int], invert: bool = False, threshol
     with clock.stage("decode", sync=False):
         im = Image.open(path).convert("L")
     with clock.stage("prepare", sync=False):
+        if distortion is not None:
+            im = _undistorted(im, distortion, nearest=True)
         if im.size != tuple(size):
             im = im.resize(tuple(size), Image.NEAREST)
         keep = (np.asarray(im, dtype=np.uint8).astype(np.float32) / 255.0) > float(threshold)
         if invert:
             keep = ~keep
         out = keep.astype(np.uint8)
+    out.setflags(write=False)
+    return out
+
+
+@lru_cache(maxsize=256)
+def undistort_valid01(full_size: Tuple[int, int], size: Tuple[int, int], distortion: Tuple[float, ...], threshold: float = 0.5) -> Optional[np.ndarray]:
+    """(h, w) u8 {0,1} plane at ``size=(w, h)`` of the pixels an undistorted ``full_size=(w, h)`` image of this camera takes from inside the
+    photograph (1) - the validity plane of lfd_host_undistort_image, resized and thresholded like a mask file - or None when every pixel
+    does (ordinary barrel distortion: the camera needs no mask of its own)."""
+    from PIL import Image
+
+    from . import hip_backend as hb
+    with stages.current().stage("prepare", sync=False):
+        blank = np.zeros((int(full_size[1]), int(full_size[0])), np.uint8)
+        _dst, valid, n_invalid = hb.host_undistort_image(blank, distortion, nearest=True, with_valid=True)
+        if n_invalid == 0:
+            return None
+        im = Image.fromarray(valid)
+        if im.size != tuple(size):
+            im = im.resize(tuple(size), Image.NEAREST)
+        out = ((np.asarray(im, dtype=np.uint8).astype(np.float32) / 255.0) > float(threshold)).astype(np.uint8)
     out.setflags(write=False)
     return out
 

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import stages
 from .hostlog import log
-from .image_io import black_out, decode_mask_l, decode_rgb_u8, load_mask01, load_rgb_u8
+from .image_io import black_out, decode_mask_l, decode_rgb_u8, load_mask01, load_rgb_u8, undistort_valid01
 from .types import CameraRecord
 
 
@@ -53,35 +53,48 @@ class PackedReference:
     dev: Optional[dict] = None
 
 
-def _load_view(cam: CameraRecord, size_wh: Tuple[int, int], raw: bool, who: str):
+def _load_view(cam: CameraRecord, size_wh: Tuple[int, int], raw: bool, who: str, undistort: bool = False):
     """(image, mask) of one camera: prepared on the host (resized, masked pixels black, mask as {0,1}) or - ``raw`` - as decoded.  An
-    unreadable image raises; an unreadable mask is a warning and no mask (upstream core/pipeline.py:163-171,196-204)."""
-    img = decode_rgb_u8(cam.image_path) if raw else load_rgb_u8(cam.image_path, size_wh)
+    unreadable image raises; an unreadable mask is a warning and no mask (upstream core/pipeline.py:163-171,196-204).  ``undistort``
+    (experimental['undistort_images']): a camera with distortion coefficients has its image and its mask undistorted in
+    front of the resize, and the pixels its photograph does not cover masked out; ``raw`` leaves that to ``HotPath.prepare_on_device``."""
+    dist = cam.active_distortion() if undistort else None
+    if dist is None or raw:
+        img = decode_rgb_u8(cam.image_path) if raw else load_rgb_u8(cam.image_path, size_wh)
+    else:
+        img = load_rgb_u8(cam.image_path, size_wh, dist)
     mask = None
     if getattr(cam, "mask_path", None):
         try:
             if raw:
                 mask = decode_mask_l(cam.mask_path)
             else:
-                mask = load_mask01(cam.mask_path, size_wh)
-                img = black_out(img, mask)
+                mask = load_mask01(cam.mask_path, size_wh) if dist is None else load_mask01(cam.mask_path, size_wh, False, 0.5, dist)
+                if dist is None:
+                    img = black_out(img, mask)
         except Exception as exc:
             log.warn(f"Failed to load/apply mask for {who} {cam.uid}: {exc}")
             mask = None
+    if dist is not None and not raw:
+        valid = undistort_valid01((int(cam.width), int(cam.height)), tuple(size_wh), dist)
+        if valid is not None:
+            mask = valid if mask is None else (mask & valid)
+        if mask is not None:
+            img = black_out(img, mask)
     return img, mask
 
 
 def pack_reference(position: int, ref_index: int, cams: Sequence[CameraRecord], nn_table, nns_per_ref: int,
-                   size_wh: Tuple[int, int], cancel, raw: bool = False, stage=None) -> Optional[PackedReference]:
+                   size_wh: Tuple[int, int], cancel, raw: bool = False, stage=None, undistort: bool = False) -> Optional[PackedReference]:
     """Load and pre-process one reference and its neighbours (upstream core/pipeline.py:132-227): same skip / warn rules.  ``raw``: decode
     only; the resize / mask / black-out steps then run on the GPU (``HotPath.prepare_on_device``).  ``stage(cam_index, image, mask)``: what a
     pack thread does with a freshly decoded view before it hands the package over (``HotPath.stage_decoded``: the upload, here instead of on the
-    driver's thread)."""
+    driver's thread).  ``undistort``: see ``_load_view``."""
     if cancelled(cancel):
         return None
     cam = cams[ref_index]
     try:
-        img_a, mask_a = _load_view(cam, size_wh, raw, "reference")
+        img_a, mask_a = _load_view(cam, size_wh, raw, "reference", undistort)
         if stage is not None:
             img_a, mask_a = stage(ref_index, img_a, mask_a)
     except Exception as exc:
@@ -99,7 +112,7 @@ def pack_reference(position: int, ref_index: int, cams: Sequence[CameraRecord], 
         if nb.uid == cam.uid:
             continue
         try:
-            img_b, mask_b = _load_view(nb, size_wh, raw, "neighbor")
+            img_b, mask_b = _load_view(nb, size_wh, raw, "neighbor", undistort)
             if stage is not None:
                 img_b, mask_b = stage(n, img_b, mask_b)
         except Exception as exc:

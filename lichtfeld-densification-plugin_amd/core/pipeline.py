@@ -108,6 +108,43 @@ def _announce(progress_callback, cached: bool) -> None:
     log.info(msg)
 
 
+def _plan_undistortion(camera_records, refs_local, nn_table, config) -> bool:
+    """What experimental['undistort_images'] means for this run, decided before anything is matched: True when images are
+    going to be undistorted.  Knob on: a selected camera - a reference or one of the neighbours it loads - whose model the undistortion does
+    not support, or whose image is not of the calibration's size, stops the run by name; no camera with distortion coefficients: one info
+    line, nothing else happens.  Knob off: one warning when any camera's coefficients are being ignored."""
+    distorted = [c for c in camera_records if c.active_distortion() is not None]
+    if not bool(config.exp("undistort_images")):
+        if distorted:
+            log.warn(f"{len(distorted)} of {len(camera_records)} cameras have non-zero distortion coefficients ({distorted[0].distortion_model}): distortion "
+                     "is ignored, the images are matched as they are and triangulated as pinhole images; experimental['undistort_images'] "
+                     "(--undistort_images) undistorts them first")
+        return False
+    selected = sorted({int(r) for r in refs_local} | {int(n) for r in refs_local for n in nn_table[int(r)][:int(config.nns_per_ref)]})
+    for i in selected:
+        cam = camera_records[i]
+        if cam.distortion is None and cam.distortion_model is not None:
+            raise RuntimeError(f"experimental['undistort_images'] supports the camera models SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV and "
+                               f"FULL_OPENCV; image {cam.image_path} has a {cam.distortion_model} camera")
+    if not distorted:
+        log.info("experimental['undistort_images']: no camera carries distortion coefficients; the images are used as they are")
+        return False
+    from PIL import Image
+    for i in selected:
+        cam = camera_records[i]
+        if cam.active_distortion() is None:
+            continue
+        try:
+            with Image.open(cam.image_path) as im:          # (the header alone)
+                size = tuple(im.size)
+        except OSError:
+            continue                                        # (an unreadable image is the loader's warning, as without the knob)
+        if size != (int(cam.width), int(cam.height)):
+            raise RuntimeError(f"experimental['undistort_images'] needs every image at the size its camera was calibrated at: image {cam.image_path} "
+                               f"is {size[0]} x {size[1]}, its {cam.distortion_model} camera {int(cam.width)} x {int(cam.height)}")
+    return True
+
+
 def _match_reference(local_i: int, packed: PackedReference, matcher, hot: HotPath, outputs: RunOutputs, feat_cache, size_wh, want_debug: bool,
                      cancel) -> Optional[Matched]:
     """One package through the matcher (upstream core/pipeline.py:856-872): prepared on the device first when it came decoded; the maps stay
@@ -207,6 +244,7 @@ def run_dense_pipeline(
     if int(config.refs_per_launch) != config.launch_group(world, previews):
         config = dataclasses.replace(config, refs_per_launch=config.launch_group(world, previews))
     clock = stage_clock if stage_clock is not None else NULL_CLOCK
+    undistort = _plan_undistortion(camera_records, refs_local, nn_table, config)
     uids = [c.uid for c in camera_records]
     total_pairs_est = _estimate_total_pairs(refs_local, nn_table, uids, config.nns_per_ref)
     if debug_state:
@@ -256,7 +294,7 @@ def run_dense_pipeline(
             matcher.set_feature_cache(feat_cache)    # always (re)set: an injected, warm matcher may still hold the cache of an earlier run
         stage = (lambda ci, im, mk: hot.stage_decoded(ci, size_wh, im, mk)) if config.device_image_prep else None
         jobs = [(lambda p=p: pack_reference(p, refs_local[p], camera_records, nn_table, config.nns_per_ref, size_wh, cancel_requested,
-                                            raw=bool(config.device_image_prep), stage=stage)) for p in plan.my_positions]
+                                            raw=bool(config.device_image_prep), stage=stage, undistort=undistort)) for p in plan.my_positions]
         # (upstream's `prefetch_packages` bounds the queue of FINISHED packages while all of its workers keep loading: the look-ahead here is at
         # least one package per worker, so that none of them idles)
         prefetch = OrderedPrefetcher(jobs, workers=int(config.pack_workers), window=max(int(config.prefetch_packages), int(config.pack_workers)), clock=clock)

@@ -11,7 +11,7 @@ world-to-camera pose, the projection ``P = K [R|t]`` and the centre ``C = -R^T t
 from __future__ import annotations
 
 import dataclasses
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 
@@ -77,6 +77,11 @@ EXPERIMENTAL_DEFAULTS = {
     "min_consensus_refs": 0,
     # ... within this distance, in scene units (the unit of voxel_size).  Required > 0 with the filter on, 0 with it off.
     "consensus_radius": 0.0,
+    # undistort every image (and its mask) on its way in (lfd_undistort_image): a COLMAP camera with a SIMPLE_RADIAL, RADIAL,
+    # OPENCV or FULL_OPENCV model is resampled into the pinhole image of the same K before anything matches it - every later stage assumes
+    # pinhole cameras.  Pixels the photograph does not cover become masked.  Any other distorted model (the fisheye family, FOV) is refused
+    # by name.  False = off: no new code runs (a camera with non-zero coefficients then draws one warning: its distortion is ignored).
+    "undistort_images": False,
 }
 CONSENSUS_CAP = 8            # LFD_CONSENSUS_CAP of include/lfd_densify.h
 
@@ -303,6 +308,8 @@ class DensePipelineConfig:
             if dense and self.exp("dense_tile_segments"):
                 return ("experimental['min_consensus_refs'] needs the cloud as arrays with per-reference counts; dense mode with "
                         "experimental['dense_tile_segments'] retires tiles unordered")
+        if not isinstance(self.exp("undistort_images"), (bool, np.bool_)):
+            return "experimental['undistort_images'] must be True or False"
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):
                 return "stream_output writes a PLY while the run proceeds: output_path must end in .ply"
@@ -390,6 +397,15 @@ class CameraRecord:
     P: np.ndarray
     C: np.ndarray
     mask_path: Optional[str] = None
+    # (fx, fy, cx, cy) + the eight coefficients (k1, k2, p1, p2, k3, k4, k5, k6) of the camera model in f64, as COLMAP stores them, or None:
+    # what experimental['undistort_images'] resamples the image through.  ``K`` above stays the f32 pinhole part.
+    distortion: Optional[Tuple[float, ...]] = None
+    distortion_model: Optional[str] = None          # COLMAP's name of the model, kept so that an unsupported one can be named
+
+    def active_distortion(self) -> Optional[Tuple[float, ...]]:
+        """``distortion`` when any of its eight coefficients is not zero, else None: a camera without them is a pinhole camera already."""
+        d = self.distortion
+        return tuple(d) if d is not None and any(float(v) != 0.0 for v in d[4:]) else None
 
     def flat_pose(self) -> np.ndarray:
         """Row-major 4x4 world-to-camera matrix as a 16-vector (f64), the feature used for

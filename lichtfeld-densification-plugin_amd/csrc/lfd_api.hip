@@ -20,6 +20,7 @@
 #include "lfd_refine.hpp"
 #include "lfd_sigma.hpp"
 #include "lfd_consensus.hpp"
+#include "lfd_undistort.hpp"
 
 extern "C" __global__ void lfd_aggregate_kernel(LfdLaunch L, float* best_cert, uint8_t* best_slot);
 extern "C" __global__ void lfd_dense_kernel(LfdLaunch L);
@@ -62,6 +63,7 @@ extern "C" __global__ void lfd_voxel_sums_kernel(const float* xyz, const float* 
 extern "C" __global__ void lfd_voxel_sums_big_kernel(const float* xyz, const float* rgb, long long n, const unsigned* sorted_idx, const unsigned* vstart,
                                                      const unsigned* nv_p, double cscale, const unsigned* big, const unsigned* n_big, float* xyz_out,
                                                      float* rgb_out);
+hipError_t lfd_undistort_launch(const LfdUndistortArgs& p, unsigned long long* n_invalid, hipStream_t stream);
 extern "C" __global__ void lfd_consensus_minmax_kernel(const float* xyz, long long n, LfdVoxStats* part);
 extern "C" __global__ void lfd_consensus_keys_kernel(const float* xyz, long long n, double o0, double o1, double o2, double h, unsigned long long e1,
                                                      unsigned long long e2, unsigned long long sentinel, unsigned long long* keys, unsigned* idx);
@@ -553,7 +555,7 @@ void lfd_destroy(lfd_context* ctx) {
     }
     for (hipEvent_t ev : ctx->kt_start) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->kt_stop) (void)hipEventDestroy(ev);
-    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->vox, &ctx->support_ws, &ctx->prec_tab, &ctx->consensus_ws})
+    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->vox, &ctx->support_ws, &ctx->prec_tab, &ctx->consensus_ws, &ctx->undist_cnt})
         if (b->ptr) (void)hipFree(b->ptr);
     if (ctx->pinned_words) (void)hipHostFree(ctx->pinned_words);
     if (ctx->prec_pinned) (void)hipHostFree(ctx->prec_pinned);
@@ -1509,6 +1511,32 @@ int lfd_consensus_filter(lfd_context* ctx, const float* xyz, const float* rgb, c
     LFD_HIP(ctx, hipMemcpyAsync(ref_offsets_out_host, offs_out, offs_bytes, hipMemcpyDeviceToHost, st));
     LFD_HIP(ctx, hipStreamSynchronize(st));
     *n_out_host = ref_offsets_out_host[n_refs];
+    return LFD_OK;
+}
+
+// ---- image undistortion in front of everything else (lfd_undistort.hip) -------------------------------------------------------------------------
+int lfd_undistort_image(lfd_context* ctx, const uint8_t* src, int32_t w, int32_t h, int32_t channels, int32_t nearest, const double intr[4],
+                        const double dist[8], uint8_t* dst, uint8_t* valid255, int64_t* n_invalid_host) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_undistort_check(src, w, h, channels, intr, dist, dst, valid255))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_undistort_image: ") + why);
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    const LfdUndistortArgs p = lfd_undistort_args(src, w, h, channels, nearest, intr, dist, dst, valid255);
+    unsigned long long* counter = nullptr;
+    if (n_invalid_host) {
+        if (int rc = ensure(ctx, ctx->undist_cnt, sizeof(unsigned long long))) return rc;
+        counter = static_cast<unsigned long long*>(ctx->undist_cnt.ptr);
+        LFD_HIP(ctx, hipMemsetAsync(counter, 0, sizeof(unsigned long long), ctx->stream));
+    }
+    LFD_HIP(ctx, lfd_undistort_launch(p, counter, ctx->stream));
+    if (n_invalid_host) {
+        LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, counter, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        LFD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        unsigned long long v;
+        std::memcpy(&v, ctx->pinned_words, sizeof(v));
+        *n_invalid_host = (int64_t)v;
+    }
     return LFD_OK;
 }
 

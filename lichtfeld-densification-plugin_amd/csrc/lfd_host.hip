@@ -23,6 +23,7 @@
 #include "lfd_refine.hpp"
 #include "lfd_sigma.hpp"
 #include "lfd_consensus.hpp"
+#include "lfd_undistort.hpp"
 
 void lfd_fill_kernel_params(const lfd_batch* b, const lfd_params* p, LfdKernelParams& kp);   // lfd_api.hip
 
@@ -679,6 +680,19 @@ int lfd_consensus_filter_host(lfd_context* ctx, const float* xyz, const float* r
         ++o;
     }
     *n_out_host = o;
+    return LFD_OK;
+}
+
+// The twin of lfd_undistort_image: lfd_undistort_pixel over host pointers, on the caller's thread.  No context and no global state: the
+// pack threads call it side by side, each on its own image.
+int lfd_host_undistort_image(const uint8_t* src, int32_t w, int32_t h, int32_t channels, int32_t nearest, const double intr[4], const double dist[8],
+                             uint8_t* dst, uint8_t* valid255, int64_t* n_invalid_host) {
+    if (lfd_undistort_check(src, w, h, channels, intr, dist, dst, valid255)) return LFD_ERR_INVALID;
+    const LfdUndistortArgs p = lfd_undistort_args(src, w, h, channels, nearest, intr, dist, dst, valid255);
+    int64_t bad = 0;
+    for (int i = 0; i < h; ++i)
+        for (int j = 0; j < w; ++j) bad += lfd_undistort_pixel(p, i, j) ? 0 : 1;
+    if (n_invalid_host) *n_invalid_host = bad;
     return LFD_OK;
 }
 

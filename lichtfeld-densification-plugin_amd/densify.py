@@ -46,6 +46,31 @@ def K_from_camera(cam) -> np.ndarray:
     return K
 
 
+def distortion_from_camera(cam) -> Optional[Tuple[float, ...]]:
+    """``(fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6)`` of a COLMAP camera (pycolmap's or core/colmap_io.Camera) in f64, exactly as the
+    model stores them - what experimental['undistort_images'] resamples the image through - or None for a model the
+    undistortion does not support: the fisheye family, FOV, anything unknown.  The name is tested as ``K_from_camera`` tests it, with the
+    fisheye models taken out first: SIMPLE_RADIAL_FISHEYE contains SIMPLE_RADIAL but is a fisheye model."""
+    model = str(cam.model.name).upper()
+    p = [float(v) for v in np.asarray(cam.params, dtype=np.float64).reshape(-1)]
+    zero = [0.0] * 8
+    if "FISHEYE" in model:
+        return None
+    if model == "PINHOLE" and len(p) == 4:
+        return tuple(p + zero)
+    if model == "SIMPLE_PINHOLE" and len(p) == 3:
+        return (p[0], p[0], p[1], p[2], *zero)
+    if model == "SIMPLE_RADIAL" and len(p) == 4:
+        return (p[0], p[0], p[1], p[2], p[3], *zero[1:])
+    if model == "RADIAL" and len(p) == 5:
+        return (p[0], p[0], p[1], p[2], p[3], p[4], *zero[2:])
+    if model == "OPENCV" and len(p) == 8:
+        return tuple(p + zero[4:])
+    if model == "FULL_OPENCV" and len(p) == 12:
+        return tuple(p)
+    return None
+
+
 def pose_world2cam(im) -> Tuple[np.ndarray, np.ndarray]:
     if hasattr(im, "cam_from_world"):
         cfw = im.cam_from_world
@@ -81,6 +106,7 @@ def camera_records_from_colmap(cams: Dict, imgs: Dict, images_dir: str) -> Tuple
         R, t = pose_world2cam(im)
         rec = CameraRecord.from_krt(iid, K_from_camera(cam), R, t, cam.width, cam.height,
                                     image_path=find_image(images_dir, im.name))
+        rec.distortion, rec.distortion_model = distortion_from_camera(cam), str(cam.model.name).upper()
         records.append(rec)
     return records, img_ids
 
@@ -469,6 +495,8 @@ def _experimental_from_args(args) -> dict:
         exp["min_consensus_refs"] = int(args.min_consensus_refs)
     if float(getattr(args, "consensus_radius", 0.0)) != 0.0:
         exp["consensus_radius"] = float(args.consensus_radius)
+    if bool(getattr(args, "undistort_images", False)):
+        exp["undistort_images"] = True
     return exp
 
 
@@ -527,6 +555,9 @@ def build_argparser() -> argparse.ArgumentParser:
                          "within --consensus_radius of it (1 .. 8; runs in front of --max_points; 0 = off)")
     ap.add_argument("--consensus_radius", type=float, default=0.0,
                     help="... within this distance in scene units (required > 0 with --min_consensus_refs)")
+    ap.add_argument("--undistort_images", action="store_true",
+                    help="resample every image (and its mask) through its COLMAP camera's distortion model (SIMPLE_RADIAL, RADIAL, OPENCV, "
+                         "FULL_OPENCV) into the pinhole image of the same intrinsics before it is matched; other distorted models are refused")
     ap.add_argument("--keep_threads", action="store_true",
                     help="leave torch's intra-op thread count alone (by default it is lowered to the container's CPU quota; the count decides the last "
                          "bits of upstream's sampling normaliser, so a run compared bit for bit with upstream keeps upstream's setting)")

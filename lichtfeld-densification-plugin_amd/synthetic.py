@@ -271,10 +271,13 @@ def ring_neighbours(n_cams: int, ref_index: int, k: int) -> List[int]:
 
 # ---- a whole scene on disk + a matcher that knows it (bench.py's pipeline leg, tests/golden/time_reference.py) -------------------------------
 def write_colmap_scene(root: str, n_cams: int = 185, width: int = 1297, height: int = 840, images_subdir: str = "images_4", fmt: str = "jpg",
-                       seed: int = 0, n_points: int = 600, workers: int = 8) -> List[CameraRecord]:
+                       seed: int = 0, n_points: int = 600, workers: int = 8, camera_model: str = "PINHOLE", distortion: Sequence[float] = ()
+                       ) -> List[CameraRecord]:
     """A garden-like scene as upstream's CLI reads it (densify.py:54-88): ``root/sparse/0/{cameras,images,points3D}.bin`` (one PINHOLE camera per
     view, principal point off the centre; ``n_points`` ground points with their tracks, which the visibility-based reference selection needs) and
     ``root/<images_subdir>/view_NNNN.<fmt>`` - ``n_cams`` images of ``width`` x ``height`` (MipNeRF360 garden: 185 views, ``images_4`` 1297 x 840).
+    ``camera_model`` / ``distortion``: COLMAP's name of the cameras' model and the parameters it stores behind the focal length(s) and the
+    principal point (SIMPLE_RADIAL: k; OPENCV: k1, k2, p1, p2; ...) - the images are then taken to be that camera's photographs.
     Returns the cameras with their image paths.  Files that exist already are kept (the images take ~10 s to make)."""
     import os
     from concurrent.futures import ThreadPoolExecutor
@@ -286,6 +289,9 @@ def write_colmap_scene(root: str, n_cams: int = 185, width: int = 1297, height: 
     os.makedirs(sparse, exist_ok=True)
     os.makedirs(img_dir, exist_ok=True)
     cams = ring_cameras(n_cams, width=width, height=height, seed=seed)
+    n_model_params = {name: n for name, n in cio.CAMERA_MODELS.values()}[camera_model]
+    if n_model_params - len(distortion) not in (3, 4):
+        raise ValueError(f"{camera_model} stores {n_model_params} parameters: {len(distortion)} behind the focal length(s) and the principal point do not fit")
     rs = np.random.RandomState(seed + 7)
     pts = {pid: (rs.uniform(-1.0, 1.0, 3) * np.array([1.8, 1.8, 0.15]), rs.randint(0, 255, 3).astype(np.uint8), float(rs.uniform(0.1, 1.0)))
            for pid in range(1, n_points + 1)}
@@ -296,7 +302,8 @@ def write_colmap_scene(root: str, n_cams: int = 185, width: int = 1297, height: 
         name = f"view_{i:04d}.{fmt}"
         c.image_path = os.path.join(img_dir, name)
         K = np.asarray(c.K, np.float64)
-        cameras.append(cio.Camera(i + 1, "PINHOLE", c.width, c.height, [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]))
+        pinhole = [K[0, 0], K[1, 1], K[0, 2], K[1, 2]] if n_model_params - len(distortion) == 4 else [K[0, 0], K[0, 2], K[1, 2]]
+        cameras.append(cio.Camera(i + 1, camera_model, c.width, c.height, pinhole + [float(v) for v in distortion]))
         proj = (np.asarray(c.P, np.float64) @ np.concatenate([xyz, np.ones((xyz.shape[0], 1))], 1).T).T
         uv = proj[:, :2] / proj[:, 2:3]
         seen = (proj[:, 2] > 0) & (uv[:, 0] >= 0) & (uv[:, 0] < c.width) & (uv[:, 1] >= 0) & (uv[:, 1] < c.height) & (rs.rand(xyz.shape[0]) < 0.7)
