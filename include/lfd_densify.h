@@ -285,8 +285,11 @@ int lfd_select_top_m(lfd_context* ctx, const float* best_cert, int32_t H, int32_
  * lfd_pack_ply:      out[n*15] = per point x y z (f32 LE) r g b (u8): the PLY body after upstream's header.
  * lfd_pack_points3d: out[n*43] = per point u64 id (id_base + i + 1), xyz as f64, rgb u8, error f64
  *                    (err may be NULL -> 0.0): upstream's points3D.bin body after the u64 count.
+ * lfd_pack_ply_normals: out[n*27] = per point x y z nx ny nz (f32 LE) r g b (u8): the body of a PLY whose header lists
+ *                    x y z nx ny nz red green blue (normals: lfd_estimate_normals' f32 [3*n]).
  * out must be 4-byte aligned.  Asynchronous on the context's stream. */
 int lfd_pack_ply(lfd_context* ctx, const float* xyz, const float* rgb, int64_t n, uint8_t* out);
+int lfd_pack_ply_normals(lfd_context* ctx, const float* xyz, const float* normals, const float* rgb, int64_t n, uint8_t* out);
 int lfd_pack_points3d(lfd_context* ctx, const float* xyz, const float* rgb, const float* err, int64_t n,
                       uint64_t id_base, uint8_t* out);
 int lfd_quantise_rgb(lfd_context* ctx, const float* rgb, int64_t n, uint8_t* out);
@@ -462,6 +465,35 @@ int lfd_depth_sigma_filter_host(lfd_context* ctx, const lfd_batch* batch, const 
                                 const float* const* precision, float iso_sigma_px, const uint8_t* refine_status, float support_thresh_px,
                                 float max_rel_sigma, const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out,
                                 float* sigma_rel, float* sigma_rel_out);
+
+/* Per-point surface normals from the resident warps (no upstream counterpart - upstream writes x y z r g b).  Per input point X
+ * of reference r made by winning slot s on cell (x, y): the winning slot's warp in the (2 radius_cells + 1)^2 window of grid cells around the
+ * cell gives the neighbouring surface samples, and the normal is the cross product of the two regression slopes of those samples on the cell
+ * offsets, oriented towards the reference's centre C_A (csrc/lfd_normals.hpp, every rounding written out):
+ *   fallback     Vw / |Vw|, Vw = C_A - X in f64, rounded to f32; (0, 0, 0) where |Vw| is zero or not finite
+ *   guard        the fallback with status 0 where X is not finite, the cell lies outside the grid, s >= n_slots[r] or X's depth in the
+ *                reference (row 2 of P_A applied to (X, 1)) is not > 0 (no address is formed from the cell or the slot)
+ *   window       cells q = (x + dx, y + dy) inside the grid, dy outer, dx inner, the centre included.  q takes part iff it is live in slot
+ *                s as lfd_support_filter defines it (raw certainty > 0, the mask_b pixel its warp points at non-zero), the reference's
+ *                mask_a pixel of q is non-zero, its own two-view point Y_q (the routine of lfd_triangulate_dense, Sampson and parallax
+ *                gates off) passes that routine's test at reproj_thresh, and |pz(Y_q) - pz(X)| <= depth_step_rel * pz(X) in f32
+ *   fit          n, sum dx, sum dy, sum dx^2, sum dx dy, sum dy^2 in integers; sum D, sum dx D, sum dy D, D = Y_q - X, in f64 in the visiting
+ *                order; U = n sum dx D - sum dx sum D, V likewise with dy, N = U x V, negated when N . Vw < 0.  The fallback with status n
+ *                where the cells are fewer than three or collinear or N . N is not finite or not > 0; otherwise N / |N| rounded to f32
+ *                and status n | 0x80
+ * `in` and ref_offsets are what a triangulation call or any post-stage wrote (cell and slot required, rgb and err unused); nothing of `in`
+ * is written and points beyond the last offset are not touched.  normals_out: f32 [3 * in->capacity]; status: NULL or u8 [in->capacity];
+ * counters: NULL or device i64 [2], ADDED to: points fitted, points that fell back (integer adds only).  One launch on the context's
+ * stream, asynchronous and deterministic; the batch is prepared as lfd_support_filter prepares it.  LFD_ERR_INVALID: a null required
+ * pointer, missing cell / slot, radius_cells outside 1..4, depth_step_rel or reproj_thresh <= 0 or not finite, normals_out or status
+ * overlapping any array of `in` (or each other), a capacity beyond 2^31 - 1.  lfd_estimate_normals_host: the same routine over host pointers
+ * on a host context's threads (counters: host i64 [2]); the statuses are the device's wherever the window's points are, the components agree
+ * within one f32 ulp (the host divides by an IEEE root where the device refines v_rcp_f64 / v_rsq_f64).  A host context is served by
+ * _host only, a device context refuses _host (LFD_ERR_STATE). */
+int lfd_estimate_normals(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets, int32_t radius_cells,
+                         float depth_step_rel, float reproj_thresh, float* normals_out, uint8_t* status, int64_t* counters);
+int lfd_estimate_normals_host(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets, int32_t radius_cells,
+                              float depth_step_rel, float reproj_thresh, float* normals_out, uint8_t* status, int64_t* counters);
 
 /* Cross-reference consensus filter on the final cloud (no upstream counterpart - the cloud upstream writes is the plain union of what
  * every reference triangulated on its own).  The cloud is the concatenation of n_refs references' points; a point is kept iff at least min_refs

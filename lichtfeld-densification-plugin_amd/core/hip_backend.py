@@ -194,6 +194,10 @@ def load_library() -> C.CDLL:
     lib.lfd_depth_sigma_filter.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_points), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float,
                                            C.c_float, C.POINTER(lfd_points), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lfd_depth_sigma_filter_host.argtypes = list(lib.lfd_depth_sigma_filter.argtypes)
+    lib.lfd_estimate_normals.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_points), C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]
+    lib.lfd_estimate_normals_host.argtypes = list(lib.lfd_estimate_normals.argtypes)
+    lib.lfd_pack_ply_normals.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.lfd_consensus_filter.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_float, C.c_int32,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)]
     lib.lfd_consensus_filter_host.argtypes = list(lib.lfd_consensus_filter.argtypes)
@@ -234,7 +238,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -451,6 +455,7 @@ class TriangulationOutput:
                                              # with both, the support filter kept ``sigma_in``)
     _packed: Optional[torch.Tensor] = None   # the one float buffer xyz / rgb / err are views of
     _cap: int = 0
+    normals: Optional[torch.Tensor] = None   # (n,3) f32 where the points live: what estimate_normals wrote for these points
 
     def host_arrays(self):
         """(xyz, rgb, err) as NumPy arrays.  When the buffers are small (sampled mode) the whole packed buffer crosses in
@@ -641,6 +646,9 @@ class OutputBuffers:
         self.seg_order = self._meta[n_off + n_seg:n_off + 2 * n_seg].view(n_refs, k)
         self.support_in = self._meta[n_off + 2 * n_seg + n_info:n_off + 2 * n_seg + n_info + 2].view(torch.int64)
         self.sigma_in = self._meta[n_off + 2 * n_seg + n_info + 2:].view(torch.int64)
+        self.normals: Optional[torch.Tensor] = None              # (cap,3) f32, allocated by the first estimate_normals over these buffers
+        self.normals_valid = False                               # True: ``normals`` was written for the points the buffers hold NOW (collect
+                                                                 # hands them out); whatever refills the buffers or moves their points clears it
         self.filtered = False                                    # True: these buffers are a support filter's destination (collect reports support_in)
         self.sigma_filtered = False                              # True: ... a depth-uncertainty gate's (collect reports sigma_in)
         self.sel_info = self._meta[n_off + 2 * n_seg:n_off + 2 * n_seg + 2 * n_refs + 1]           # lfd_triangulate_sampled[_multi]: {cells selected, selection status} per reference, then the launch status
@@ -704,7 +712,7 @@ class OutputBuffers:
             launch_status=int(meta[n_off + 2 * n_seg + 2 * self._n_refs]),
             support_in=int(meta[n_off + 2 * n_seg + 2 * self._n_refs + 2:].view(np.int64)[0]) if self.filtered else None,
             sigma_in=int(meta[n_off + 2 * n_seg + 2 * self._n_refs + 2:].view(np.int64)[1]) if self.sigma_filtered else None, _packed=self._f,
-            _cap=max(self.capacity, 1))
+            _cap=max(self.capacity, 1), normals=self.normals[:n] if (self.normals is not None and self.normals_valid) else None)
 
 
 
@@ -803,6 +811,7 @@ def _support_filter_call(fn, ctx, batch, src, min_support, support_thresh_px, wi
     dst = into if into is not None else OutputBuffers(cap, n_refs, k, device, True, True if collected else src.with_segments)
     if dst.capacity < cap or dst._n_refs != n_refs or dst._k != k or dst.xyz.device != device:
         raise ValueError("support_filter: `into` must have the source's capacity, references and slots, on this context's device")
+    dst.normals_valid = False                 # (refilled: normals an earlier estimate wrote there belong to other points)
     if not collected:
         dst._meta.copy_(src._meta)            # group order, selection and launch status travel with the points
         dst.support_in.copy_(src.ref_offsets[-1:])
@@ -853,6 +862,7 @@ def _refine_call(fn, ctx, batch, src, support_thresh_px, reproj_thresh, with_sta
             raise ValueError(f"refine_multiview: the points live on {src.xyz.device}, this context computes on {device}")
         keep, offs, pts, n_refs, k, cap = [], src.ref_offsets, src.c, src._n_refs, src._k, src.capacity
         xyz_out, err_out = src.xyz, src.err
+        src.normals_valid = False             # (the points move: normals estimated before belong to the old positions)
     if n_refs != batch.n_refs or k != batch.k:
         raise ValueError(f"refine_multiview: the points were made for {n_refs} references x {k} slots, the batch has {batch.n_refs} x {batch.k}")
     status = torch.zeros((max(cap, 1),), dtype=torch.uint8, device=device) if with_status else None
@@ -866,6 +876,52 @@ def _refine_call(fn, ctx, batch, src, support_thresh_px, reproj_thresh, with_sta
     if not collected:
         return rc, src, status
     return rc, dataclasses.replace(src, xyz=xyz_out[:cap], err=err_out[:cap], _packed=None), status
+
+
+def _normals_call(fn, ctx, batch, src, radius, depth_step_rel, reproj_thresh, with_status, counters, device):
+    """One lfd_estimate_normals[_host] call.  ``src``: the OutputBuffers a triangulation launch or a post-stage wrote for ``batch`` - their
+    ``normals`` tensor is allocated on first use and written asynchronously, the buffers are returned - or a collected TriangulationOutput (the
+    result is a copy that carries ``normals``).  ``counters``: None, or an int64 [2] tensor on the context's device that is added to (fitted,
+    fell back).  Returns (rc, result or None, status or None)."""
+    if not isinstance(radius, (int, np.integer)) or isinstance(radius, bool):
+        raise ValueError("estimate_normals: radius must be an integer")
+    collected = isinstance(src, TriangulationOutput)
+    if src.cell is None or src.slot is None:
+        raise ValueError("estimate_normals: the source buffers need the cell / slot outputs (with_cell=True)")
+    if counters is not None and (counters.dtype != torch.int64 or counters.numel() != 2 or counters.device != device or not counters.is_contiguous()):
+        raise ValueError(f"estimate_normals: counters must be a contiguous int64 tensor of two elements on {device}")
+    if collected:
+        n = int(src.xyz.shape[0])
+        keep = [src.xyz.contiguous(), src.cell.contiguous(), src.slot.contiguous()]
+        if n == 0:                            # (an empty tensor may have no address at all; the library wants its arrays)
+            keep = [torch.zeros((1, 3) if t.dim() == 2 else (1,), dtype=t.dtype, device=t.device) for t in keep]
+        if any(t.device != device for t in keep):
+            raise ValueError(f"estimate_normals: the points live on {keep[0].device}, this context computes on {device}")
+        offs = torch.from_numpy(np.ascontiguousarray(src.ref_offsets, np.int64)).to(device)
+        pts = lfd_points(xyz=keep[0].data_ptr(), rgb=None, err=None, cell=keep[1].data_ptr(), slot=keep[2].data_ptr(), capacity=n)
+        n_refs, k, cap = int(len(src.ref_offsets)) - 1, int(src.seg_counts.shape[1]), n
+        normals = torch.empty((max(n, 1), 3), dtype=torch.float32, device=device)
+    else:
+        if src.xyz.device != device:
+            raise ValueError(f"estimate_normals: the points live on {src.xyz.device}, this context computes on {device}")
+        keep, offs, pts, n_refs, k, cap = [], src.ref_offsets, src.c, src._n_refs, src._k, src.capacity
+        if src.normals is None:
+            src.normals = torch.empty((max(cap, 1), 3), dtype=torch.float32, device=device)
+        normals = src.normals
+        src.normals_valid = False
+    if n_refs != batch.n_refs or k != batch.k:
+        raise ValueError(f"estimate_normals: the points were made for {n_refs} references x {k} slots, the batch has {batch.n_refs} x {batch.k}")
+    status = torch.zeros((max(cap, 1),), dtype=torch.uint8, device=device) if with_status else None
+    rc = fn(ctx, C.byref(batch.c), C.byref(pts), offs.data_ptr(), int(radius), C.c_float(float(depth_step_rel)), C.c_float(float(reproj_thresh)),
+            normals.data_ptr(), status.data_ptr() if with_status else None, counters.data_ptr() if counters is not None else None)
+    if rc != 0:
+        return rc, None, None
+    if with_status:
+        status = status[:cap]
+    if not collected:
+        src.normals_valid = True
+        return rc, src, status
+    return rc, dataclasses.replace(src, normals=normals[:cap]), status
 
 
 def _depth_sigma_call(fn, ctx, batch, src, max_rel_sigma, iso_sigma_px, refine_status, support_thresh_px, with_sigma, into, device):
@@ -902,6 +958,7 @@ def _depth_sigma_call(fn, ctx, batch, src, max_rel_sigma, iso_sigma_px, refine_s
     dst = into if into is not None else OutputBuffers(cap, n_refs, k, device, True, True if collected else src.with_segments)
     if dst.capacity < cap or dst._n_refs != n_refs or dst._k != k or dst.xyz.device != device:
         raise ValueError("depth_sigma_filter: `into` must have the source's capacity, references and slots, on this context's device")
+    dst.normals_valid = False                 # (refilled: normals an earlier estimate wrote there belong to other points)
     if not collected:
         dst._meta.copy_(src._meta)            # group order, selection and launch status (and the support filter's count) travel with the points
         dst.sigma_in.copy_(src.ref_offsets[-1:])
@@ -1191,6 +1248,32 @@ class HipDensifier:
         self._check(rc, "lfd_depth_sigma_filter")
         return (res, sigma, sigma_out) if with_sigma else res
 
+    def estimate_normals(self, batch: PreparedBatch, out_buffers, radius: int, depth_step_rel: float, reproj_thresh: float,
+                         with_status: bool = False, counters: Optional[torch.Tensor] = None):
+        """Per-point surface normals from the resident warps (lfd_estimate_normals): for every point ``out_buffers`` holds for
+        ``batch`` (an OutputBuffers a launch or a post-stage wrote - their ``normals`` tensor is written asynchronously on the context's
+        stream - or a collected TriangulationOutput, whose copy carries ``normals``) the unit normal of the plane fitted to the winning
+        neighbour's warp in the (2 ``radius`` + 1)^2 window of grid cells around the point's cell, oriented towards the reference's centre;
+        the unit view vector where no plane can be fitted.  The points themselves are not touched.  ``counters``: int64 [2] on the device,
+        added to (fitted, fell back).  With ``with_status`` a pair (result, uint8 per point: window cells that took part | 0x80 if fitted)."""
+        self._same_device(batch)
+        with torch.cuda.stream(self.stream):
+            rc, res, status = _normals_call(self._lib.lfd_estimate_normals, self._ctx, batch, out_buffers, radius, depth_step_rel, reproj_thresh,
+                                            with_status, counters, self.device)
+        self._check(rc, "lfd_estimate_normals")
+        return (res, status) if with_status else res
+
+    def pack_ply_normals(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
+        """(n*27,) u8 device tensor: the body of a PLY whose header lists x y z nx ny nz red green blue."""
+        xyz, normals, rgb = self._pts(xyz, 3, "xyz"), self._pts(normals, 3, "normals"), self._pts(rgb, 3, "rgb")
+        n = int(xyz.shape[0])
+        if int(normals.shape[0]) != n or int(rgb.shape[0]) != n:
+            raise ValueError("pack_ply_normals: xyz, normals and rgb must have the same number of rows")
+        out = torch.empty((max(n * 27, 4),), dtype=torch.uint8, device=xyz.device)
+        self._check(self._lib.lfd_pack_ply_normals(self._ctx, xyz.data_ptr(), normals.data_ptr(), rgb.data_ptr(), n, out.data_ptr()),
+                    "lfd_pack_ply_normals")
+        return out[:n * 27]
+
     def quantise_rgb(self, rgb: torch.Tensor) -> torch.Tensor:
         rgb = self._pts(rgb, 3, "rgb")
         out = torch.empty(rgb.shape, dtype=torch.uint8, device=rgb.device)
@@ -1330,6 +1413,7 @@ class HipDensifier:
 
     def launch_dense(self, batch: PreparedBatch, params: lfd_params, out: OutputBuffers) -> None:
         self._same_device(batch, out)
+        out.normals_valid = False             # (refilled)
         self._check(self._lib.lfd_triangulate_dense(self._ctx, C.byref(batch.c), C.byref(params), C.byref(out.c),
                                                     out.ref_offsets.data_ptr(),
                                                     out.seg_counts.data_ptr() if out.with_segments else None),
@@ -1376,6 +1460,7 @@ class HipDensifier:
     def launch_dense_segments(self, batch: PreparedBatch, params: lfd_params, out: OutputBuffers, table: torch.Tensor,
                               ref_counts: torch.Tensor) -> None:
         self._same_device(batch, out, table, ref_counts)
+        out.normals_valid = False             # (refilled)
         if table.dtype != torch.int32 or ref_counts.dtype != torch.int64 or not table.is_contiguous():
             raise ValueError("table must be a contiguous int32 (n_tiles, 2) tensor, ref_counts int64 (n_refs,)")
         self._check(self._lib.lfd_triangulate_dense_segments(self._ctx, C.byref(batch.c), C.byref(params), C.byref(out.c), ref_counts.data_ptr(),
@@ -1436,6 +1521,7 @@ class HipDensifier:
         """One reference view through aggregate -> selection -> indexed triangulation in one asynchronous call
         (lfd_triangulate_sampled): no read-back in between, the selection count stays on the device."""
         self._same_device(batch, out, sel_cells)
+        out.normals_valid = False             # (refilled)
         self._check(self._lib.lfd_triangulate_sampled(self._ctx, C.byref(batch.c), C.byref(params), int(M), C.c_float(cap), int(border),
                                                       int(tiles), C.c_float(s_override), C.byref(out.c), out.ref_offsets.data_ptr(),
                                                       out.seg_counts.data_ptr(), out.seg_order.data_ptr(), out.sel_info.data_ptr(),
@@ -1449,6 +1535,7 @@ class HipDensifier:
         if len(seeds) != batch.n_refs:
             raise ValueError("one seed per reference")
         self._same_device(batch, out)
+        out.normals_valid = False             # (refilled)
         arr = (C.c_uint32 * batch.n_refs)(*[int(v) & 0xFFFFFFFF for v in seeds])
         self._check(self._lib.lfd_triangulate_sampled_multi(self._ctx, C.byref(batch.c), C.byref(params), int(M), C.c_float(cap), int(border),
                                                             int(tiles), arr, C.byref(out.c), out.ref_offsets.data_ptr(),
@@ -1464,6 +1551,7 @@ class HipDensifier:
         if s_overrides is not None and len(s_overrides) != batch.n_refs:
             raise ValueError("one normaliser per reference")
         self._same_device(batch, out, sel_cells)
+        out.normals_valid = False             # (refilled)
         arr = (C.c_float * batch.n_refs)(*[float(v) for v in s_overrides]) if s_overrides is not None else None
         self._check(self._lib.lfd_triangulate_sampled_chain(self._ctx, C.byref(batch.c), C.byref(params), int(M), C.c_float(cap), int(border),
                                                             int(tiles), arr, C.byref(out.c), out.ref_offsets.data_ptr(),
@@ -1574,6 +1662,22 @@ class HostDensifier:
                                                       iso_sigma_px, refine_status, support_thresh_px, with_sigma, into, self.device)
         self._check(rc, "lfd_depth_sigma_filter_host")
         return (res, sigma, sigma_out) if with_sigma else res
+
+    def estimate_normals(self, batch: PreparedBatch, out_buffers, radius: int, depth_step_rel: float, reproj_thresh: float,
+                         with_status: bool = False, counters: Optional[torch.Tensor] = None):
+        """HipDensifier.estimate_normals over CPU tensors (lfd_estimate_normals_host): the same per-point routine, host build."""
+        self._same_device(batch)
+        rc, res, status = _normals_call(self._lib.lfd_estimate_normals_host, self._ctx, batch, out_buffers, radius, depth_step_rel, reproj_thresh,
+                                        with_status, counters, self.device)
+        self._check(rc, "lfd_estimate_normals_host")
+        return (res, status) if with_status else res
+
+    def pack_ply_normals(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
+        """HipDensifier.pack_ply_normals over CPU tensors: the host writer's records (core/writers.py), the same bytes."""
+        from .image_io import to_uint8_rgb
+        from .writers import ply_records
+        rec = ply_records(xyz.numpy(), to_uint8_rgb(rgb.numpy()), normals=normals.numpy())
+        return torch.from_numpy(rec.view(np.uint8).reshape(-1).copy())
 
     def consensus_filter(self, xyz: torch.Tensor, rgb: Optional[torch.Tensor], err: Optional[torch.Tensor], ref_counts, radius: float, min_refs: int,
                          with_consensus: bool = False):

@@ -91,6 +91,11 @@ class HotPath:
         self.sigma_in = self.sigma_kept = 0                     # points that reached the gate / that it kept, over the results the run used
         # experimental['undistort_images']: per camera, the twelve parameters its decoded image is undistorted with in
         # prepare_on_device, or None (knob off, or a camera without distortion coefficients: no new code runs for it)
+        # per-point normals (lfd_estimate_normals): the last stage, behind everything that moves or drops points
+        self.normals = bool(config.exp("estimate_normals"))
+        self.normal_radius = int(config.exp("normal_radius_cells"))
+        self.normal_depth_step = float(config.exp("normal_depth_step_rel"))
+        self._normal_counter: Optional[torch.Tensor] = None     # int64 [2] where the kernels run: points fitted / fallen back, added to
         on = bool(config.exp("undistort_images"))
         self._distortion = [c.active_distortion() if on else None for c in cams]
 
@@ -141,7 +146,25 @@ class HotPath:
             with self.clock.stage("kernel"):
                 res = self._sigma_gated(batch, res, status)
             self._support_count(res)
+        if self.normals:
+            with self.clock.stage("kernel"):
+                res = self._with_normals(batch, res)
         return res
+
+    def _with_normals(self, batch: hb.PreparedBatch, out):
+        """``out`` (buffers on the stream, or a collected result) with the normals of the points it holds NOW: one launch of
+        lfd_estimate_normals on the stream that made them, behind every stage that moves or drops points and before anything is read back.
+        The counters stay where the kernels run until ``normal_totals``; like the re-triangulation's they count every launch issued."""
+        if self._normal_counter is None:
+            self._normal_counter = torch.zeros(2, dtype=torch.int64, device=self.dev)
+        return self.dens.estimate_normals(batch, out, self.normal_radius, self.normal_depth_step, float(self.config.reproj_thresh),
+                                          counters=self._normal_counter)
+
+    def normal_totals(self) -> Tuple[int, int]:
+        """(points whose normal was fitted, points that got the view vector) over the launches of the run: the one read of the counters."""
+        if self._normal_counter is None:
+            return 0, 0
+        return tuple(int(v) for v in self._normal_counter.cpu())
 
     def _support_count(self, res: hb.TriangulationOutput) -> None:
         """The run's totals, from the integers a result brings along anyway (no read-back of their own)."""
@@ -190,6 +213,8 @@ class HotPath:
             finally:
                 self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, _pool_kind(out)), []).append(out)
             out = into
+        if self.normals:
+            out = self._with_normals(batch, out)
         return out
 
     # -- multi-view re-triangulation of supported points (lfd_refine_multiview) ---------------------------------------------------
@@ -412,7 +437,9 @@ class HotPath:
         read-back - a pinned host allocation (hipHostMalloc: milliseconds), per reference; ``finish_sampled`` hands a buffer back once the
         reference's survivors have been copied out of it."""
         free = self._buf_pool.setdefault((int(capacity), int(n_refs), int(k), int(filtered)), [])
-        return free.pop() if free else hb.OutputBuffers(int(capacity), int(n_refs), int(k), self.dev)
+        out = free.pop() if free else hb.OutputBuffers(int(capacity), int(n_refs), int(k), self.dev)
+        out.normals_valid = False              # (whatever fills them next has not had its normals estimated)
+        return out
 
     # -- upstream's normaliser without stalling the launch stream ---------------------------------------------------------------
     def can_pipeline_normaliser(self, need_best: bool, per_ref_rng: bool, H: int, W: int) -> bool:
@@ -573,7 +600,8 @@ class HotPath:
                 return None
             return dataclasses.replace(res, xyz=res.xyz.clone(), rgb=res.rgb.clone(), err=res.err.clone(),
                                        cell=res.cell.clone() if res.cell is not None else None,
-                                       slot=res.slot.clone() if res.slot is not None else None, _packed=None)
+                                       slot=res.slot.clone() if res.slot is not None else None, _packed=None,
+                                       normals=res.normals.clone() if res.normals is not None else None)
         finally:
             self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, _pool_kind(out)), []).append(out)
 
@@ -596,7 +624,7 @@ class HotPath:
             if bool(self.config.exp("dense_tile_segments")):
                 # unordered retirement (no look-back), raster order restored from the tile table: the same result, bit for bit
                 return self.dens.order_segments(self.dens.triangulate_dense_segments(batch, self.params))
-            if (self.min_support > 0 or self.refine or self.max_sigma > 0.0) and not self.on_host:
+            if (self.min_support > 0 or self.refine or self.max_sigma > 0.0 or self.normals) and not self.on_host:
                 # the launch, the filter, the re-triangulation and / or the gate behind it on the same stream, then the one read-back of the offsets
                 cap = batch.n_refs * batch.H * batch.W
                 out = hb.OutputBuffers(cap, batch.n_refs, batch.k, self.dev)
@@ -608,6 +636,8 @@ class HotPath:
                     out, status = self._refined(batch, out, self.max_sigma > 0.0)
                 if self.max_sigma > 0.0:
                     out = self._sigma_gated(batch, out, status)
+                if self.normals:
+                    out = self._with_normals(batch, out)
                 self.dens.check_launches()
                 res = out.collect()
                 self._support_void = False

@@ -236,6 +236,10 @@ def run_dense_pipeline(
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank() if world > 1 else 0
     config.validate()
+    if world > 1 and bool(config.exp("estimate_normals")):
+        # (a condition of the world, not of the configuration: every rank sees it and stops here, before anything is set up)
+        raise ValueError("experimental['estimate_normals'] cannot run sharded over several GPUs: the exchange of a sharded run does not carry the "
+                         "normals (rows of xyz, rgb, err or 15-byte records)")
     config, dev = _resolve_backend(config, backend, device)
     per_ref_rng = bool(config.per_reference_rng) or world > 1
     # refs_per_launch = 0 (the default): several references per launch where the results do not depend on it and nobody watches the run proceed
@@ -336,6 +340,10 @@ def run_dense_pipeline(
             n_in, n_kept = hot.sigma_totals()
             noise = f"isotropic match noise {hot.iso_sigma_px:g} px" if hot.iso_sigma_px > 0.0 else "the matcher's precision planes"
             log.info(f"Depth-uncertainty gate: relative depth sigma at most {hot.max_sigma:g} ({noise}), {n_in} points in, {n_kept} kept")
+        if hot.normals:
+            n_fit, n_fell = hot.normal_totals()
+            log.info(f"Surface normals: window radius {hot.normal_radius} cell(s), depth step {hot.normal_depth_step:g}, {n_fit} points fitted, "
+                     f"{n_fell} with the view vector instead")
     except BaseException as exc:
         if world == 1:
             raise

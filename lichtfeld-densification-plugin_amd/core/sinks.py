@@ -34,8 +34,10 @@ class PipelineResult:
 
     def __init__(self, xyz=None, rgb=None, err=None, elapsed_seconds: float = 0.0, pairs_processed: int = 0, pairs_matched: int = 0,
                  points_per_reference: Optional[np.ndarray] = None, device_points=None, streamed_path: Optional[str] = None,
-                 clock=None, loader: Optional[Callable[[], Tuple[np.ndarray, np.ndarray, np.ndarray]]] = None):
+                 clock=None, loader: Optional[Callable[[], Tuple[np.ndarray, np.ndarray, np.ndarray]]] = None, device_normals=None):
         self._arrays = (xyz, rgb, err) if loader is None else None
+        self.device_normals = device_normals                  # experimental['estimate_normals']: (N,3) f32 unit normals where the points are, else None
+        self._normals = None
         self._loader = loader
         self.elapsed_seconds = float(elapsed_seconds)
         self.pairs_processed = int(pairs_processed)           # upstream's name; counts REFERENCES that produced points
@@ -59,6 +61,13 @@ class PipelineResult:
     xyz = property(lambda self: self._get(0))      # (N,3) f32
     rgb = property(lambda self: self._get(1))      # (N,3) f32 in [0,1]
     err = property(lambda self: self._get(2))      # (N,)  f32
+
+    @property
+    def normals(self) -> Optional[np.ndarray]:
+        """(N,3) f32 unit normals of the points (experimental['estimate_normals']), made on first access; None with the knob off"""
+        if self._normals is None and self.device_normals is not None:
+            self._normals = self.device_normals.cpu().numpy()
+        return self._normals
 
     @property
     def n_points(self) -> int:
@@ -112,6 +121,7 @@ class Emission:
     dbg: Optional[dict] = None
     _ply: Optional[torch.Tensor] = None
     _body: Optional[bytes] = None
+    normals: Optional[torch.Tensor] = None       # experimental['estimate_normals']: (n,3) f32 beside the points, else None (previews stay 15-byte)
 
     @property
     def count(self) -> int:
@@ -279,6 +289,7 @@ class RunOutputs:
         self.on_sequential_viz, self.debug_state, self.cancel = on_sequential_viz, debug_state, cancel_requested
         self.total_pairs_est = int(total_pairs_est)
         self.dev_parts: List[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = []
+        self.normal_parts: List[torch.Tensor] = []       # experimental['estimate_normals']: in step with dev_parts, else empty
         self.counts_local = [0] * len(plan.my_positions)
         self.refs_with_points = 0
         self.pair_counter = 0
@@ -319,6 +330,10 @@ class RunOutputs:
 
     def emit(self, em: Emission, hot) -> None:
         self.dev_parts.append(em.points)
+        if em.normals is not None:
+            self.normal_parts.append(em.normals)
+        if len(self.normal_parts) not in (0, len(self.dev_parts)) or (em.normals is not None and int(em.normals.shape[0]) != em.count):
+            raise RuntimeError("normals out of step with the points: every reference of a run carries them, one per point, or none does")
         self.count_reference(em.local_i, em.count)
         if self.link is not None:
             self.link.push(em, hot, replicated=em.local_i >= self.plan.n_sharded_mine)
@@ -386,6 +401,7 @@ class RunOutputs:
             device_points, counts, refs_with_points, pairs = self.link.gather(self)
         elif self.dev_parts:
             device_points = tuple(torch.cat([p[i] for p in self.dev_parts], 0) for i in range(3))
+        device_normals = torch.cat(self.normal_parts, 0) if (self.normal_parts and self.link is None) else None
         if int(counts.sum()) == 0:
             raise RuntimeError("No points triangulated. Try adjusting parameters.")
         if self.records_only:
@@ -403,7 +419,7 @@ class RunOutputs:
         xyz, rgb, err = arrays if arrays is not None else (None, None, None)
         return PipelineResult(xyz=xyz, rgb=rgb, err=err, elapsed_seconds=time.time() - t0, pairs_processed=refs_with_points,
                               pairs_matched=pairs, points_per_reference=counts, device_points=device_points, streamed_path=streamed_path,
-                              clock=clock, loader=loader)
+                              clock=clock, loader=loader, device_normals=device_normals)
 
 
 __all__ = ["PipelineResult", "ShardPlan", "Emission", "ShardLink", "RunOutputs", "arrays_from_ply", "build_preview", "cancelled"]

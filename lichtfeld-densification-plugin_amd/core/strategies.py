@@ -66,6 +66,11 @@ def _trimmed(res: hb.TriangulationOutput, lo: int, hi: int):
     return res.xyz[lo:hi].clone(), res.rgb[lo:hi].clone(), res.err[lo:hi].clone()
 
 
+def _normals(res: hb.TriangulationOutput, lo: int = 0, hi: Optional[int] = None):
+    """the normals of the same points (experimental['estimate_normals']), a copy like theirs; None with the knob off"""
+    return res.normals[lo:hi].clone() if res.normals is not None else None
+
+
 class SampledLoop:
     def __init__(self, hot: HotPath, outputs: RunOutputs, config, per_ref_rng: bool, auto_group: bool = False):
         self.hot, self.out, self.config, self.per_ref_rng = hot, outputs, config, bool(per_ref_rng)
@@ -162,7 +167,7 @@ class SampledLoop:
         if m.want_debug:
             dbg = {"matches": self.hot.debug_matches(m.ref, res.cell, res.slot, m.axes, best),
                    "pair_index": {j: m.first_pair + j for j in range(len(m.ref.cert))}}
-        self.out.emit(Emission(m.local_i, m.packed, (res.xyz.clone(), res.rgb.clone(), res.err.clone()), dbg), self.hot)
+        self.out.emit(Emission(m.local_i, m.packed, (res.xyz.clone(), res.rgb.clone(), res.err.clone()), dbg, normals=_normals(res)), self.hot)
 
     def _promote_one(self) -> None:
         """The oldest reference whose aggregated map has reached the host: upstream's normaliser from it, then its fused call."""
@@ -183,7 +188,7 @@ class SampledLoop:
             log.error(f"Triangulation error for ref {m.packed.ref_uid}: {ex}")
             return
         if res is not None:
-            self.out.emit(Emission(m.local_i, m.packed, (res.xyz, res.rgb, res.err)), self.hot)
+            self.out.emit(Emission(m.local_i, m.packed, (res.xyz, res.rgb, res.err), normals=res.normals), self.hot)
 
     def _launch_chain(self) -> None:
         """The group that has filled up.  With upstream's normaliser its weight maps start their way to the host now (one aggregate launch, one
@@ -253,7 +258,7 @@ class SampledLoop:
                 continue
             lo, hi = int(res.ref_offsets[bi]), int(res.ref_offsets[bi + 1])
             if hi > lo:
-                self.out.emit(Emission(m.local_i, m.packed, _trimmed(res, lo, hi)), self.hot)
+                self.out.emit(Emission(m.local_i, m.packed, _trimmed(res, lo, hi), normals=_normals(res, lo, hi)), self.hot)
 
     def _recover(self, items: List[Matched], place, why) -> None:
         """A fused call of several references failed as a whole.  Nothing of it has been emitted; whatever was launched behind it drew from a
@@ -303,14 +308,14 @@ class SampledLoop:
                     log.error(f"Triangulation error for ref {m.packed.ref_uid}: {ex1}")
                     continue
                 if one is not None:
-                    self.out.emit(Emission(m.local_i, m.packed, (one.xyz, one.rgb, one.err)), self.hot)
+                    self.out.emit(Emission(m.local_i, m.packed, (one.xyz, one.rgb, one.err), normals=one.normals), self.hot)
             return
         if res is None:
             return
         for bi, (m, _sd) in enumerate(items):
             lo, hi = int(res.ref_offsets[bi]), int(res.ref_offsets[bi + 1])
             if hi > lo:
-                self.out.emit(Emission(m.local_i, m.packed, _trimmed(res, lo, hi)), self.hot)
+                self.out.emit(Emission(m.local_i, m.packed, _trimmed(res, lo, hi), normals=_normals(res, lo, hi)), self.hot)
 
 
 class DenseBatcher:
@@ -342,7 +347,7 @@ class DenseBatcher:
         for bi, m in enumerate(items):
             lo, hi = int(offs[bi]), int(offs[bi + 1])
             if hi > lo:
-                self.out.emit(Emission(m.local_i, m.packed, _trimmed(res, lo, hi)), self.hot)
+                self.out.emit(Emission(m.local_i, m.packed, _trimmed(res, lo, hi), normals=_normals(res, lo, hi)), self.hot)
 
     def close(self) -> None:
         pass

@@ -82,6 +82,19 @@ EXPERIMENTAL_DEFAULTS = {
     # pinhole cameras.  Pixels the photograph does not cover become masked.  Any other distorted model (the fisheye family, FOV) is refused
     # by name.  False = off: no new code runs (a camera with non-zero coefficients then draws one warning: its distortion is ignored).
     "undistort_images": False,
+    # per-point surface normals from the resident warps (lfd_estimate_normals): every emitted point gets the unit normal of the
+    # plane fitted to its winning neighbour's warp in a window of grid cells around its own cell, oriented towards its reference's camera; the
+    # output PLY then has 27-byte x y z nx ny nz r g b vertices.  The last stage behind support filter, re-triangulation and depth gate; never
+    # changes which points are emitted or where.  False = off: no new code runs and the output is the 15-byte file, byte for byte.
+    "estimate_normals": False,
+    # ... over the (2 r + 1)^2 window of this radius, 1 .. 4 grid cells.  With iid matching noise a 3 x 3 window is useless (tens of degrees);
+    # the matcher's noise is smoother than iid, so the default is a judgement - DESIGN.md 4.14 records the measured error per radius.
+    "normal_radius_cells": 3,
+    # ... leaving out window cells whose depth in the reference differs from the point's by more than this fraction of it.  On a plane tilted
+    # 80 degrees to the image, cells r apart differ in relative depth by r tan(80 deg) / f_cells (f_cells: the focal length in grid cells,
+    # about 400 at 512^2): under 0.03 up to r = 2, 0.057 at r = 4.  At 0.05 only the outermost cells of the widest windows on the steepest
+    # planes are cut, while a foreground / background step is far over 0.05.
+    "normal_depth_step_rel": 0.05,
 }
 CONSENSUS_CAP = 8            # LFD_CONSENSUS_CAP of include/lfd_densify.h
 
@@ -310,6 +323,40 @@ class DensePipelineConfig:
                         "experimental['dense_tile_segments'] retires tiles unordered")
         if not isinstance(self.exp("undistort_images"), (bool, np.bool_)):
             return "experimental['undistort_images'] must be True or False"
+        normals = self.exp("estimate_normals")
+        if not isinstance(normals, (bool, np.bool_)):
+            return "experimental['estimate_normals'] must be True or False"
+        r_nrm = self.exp("normal_radius_cells")
+        if isinstance(r_nrm, bool) or not isinstance(r_nrm, (int, np.integer)) or not (1 <= int(r_nrm) <= 4):
+            return "experimental['normal_radius_cells'] must be an integer in 1 .. 4 (grid cells around the point's own cell)"
+        try:
+            step_nrm = float(self.exp("normal_depth_step_rel"))
+        except (TypeError, ValueError):
+            return "experimental['normal_depth_step_rel'] must be a number (fraction of the point's depth in its reference)"
+        if not (0.0 < step_nrm < float("inf")):
+            return "experimental['normal_depth_step_rel'] must be finite and > 0 (fraction of the point's depth in its reference)"
+        if not normals:
+            if "normal_radius_cells" in self.experimental:
+                return "experimental['normal_radius_cells'] is the window of the normal estimate: it needs experimental['estimate_normals'] = True"
+            if "normal_depth_step_rel" in self.experimental:
+                return "experimental['normal_depth_step_rel'] is the depth step of the normal estimate: it needs experimental['estimate_normals'] = True"
+        else:
+            if self.no_filter:
+                return "experimental['estimate_normals'] takes a window cell by the two-view tests; no_filter switches them off"
+            if not (float(self.reproj_thresh) > 0.0):
+                return "experimental['estimate_normals'] needs the two-view threshold: reproj_thresh must be > 0"
+            if self.stream_output:
+                return ("experimental['estimate_normals'] writes 27-byte vertices from points held as arrays (xyz, cell, slot); stream_output "
+                        "writes 15-byte records while the run proceeds")
+            if self.exp("dense_tile_segments"):
+                return "experimental['estimate_normals'] needs the ordered dense result; experimental['dense_tile_segments'] retires tiles unordered"
+            if self.exchange_record_format() == "ply":
+                return "experimental['estimate_normals'] adds a column to f32 rows; experimental['exchange_records'] must be 'f32' with it"
+            if float(self.voxel_size) > 0.0:
+                return ("experimental['estimate_normals'] cannot be combined with voxel_size: the voxel filter averages points, and what it should "
+                        "do to their normals is not defined")
+            if not str(self.output_path).lower().endswith(".ply"):
+                return "experimental['estimate_normals'] writes the normals as PLY vertex properties: output_path must end in .ply"
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):
                 return "stream_output writes a PLY while the run proceeds: output_path must end in .ply"

@@ -10,6 +10,7 @@ from typing import Optional
 import numpy as np
 
 _PLY_REC = np.dtype([("xyz", "<f4", 3), ("rgb", "u1", 3)])                       # 15 bytes
+_PLY_NORMAL_REC = np.dtype([("xyz", "<f4", 3), ("normal", "<f4", 3), ("rgb", "u1", 3)])    # 27 bytes: experimental['estimate_normals']
 _BIN_REC = np.dtype([("id", "<u8"), ("xyz", "<f8", 3), ("rgb", "u1", 3), ("err", "<f8")])   # 43 bytes
 
 
@@ -19,27 +20,31 @@ def ensure_dir(path: str) -> None:
         os.makedirs(d, exist_ok=True)
 
 
-def ply_header(n: int) -> bytes:
+def ply_header(n: int, normals: bool = False) -> bytes:
+    """``normals``: the vertex also carries nx ny nz (27-byte records); without it upstream's header, byte for byte."""
     return ("ply\nformat binary_little_endian 1.0\n"
             f"element vertex {int(n)}\n"
             "property float x\nproperty float y\nproperty float z\n"
+            + ("property float nx\nproperty float ny\nproperty float nz\n" if normals else "") +
             "property uchar red\nproperty uchar green\nproperty uchar blue\n"
             "end_header\n").encode("ascii")
 
 
-def ply_records(xyz: np.ndarray, rgb_uint8: np.ndarray) -> np.ndarray:
+def ply_records(xyz: np.ndarray, rgb_uint8: np.ndarray, normals: Optional[np.ndarray] = None) -> np.ndarray:
     n = int(xyz.shape[0])
-    rec = np.empty(n, dtype=_PLY_REC)
+    rec = np.empty(n, dtype=_PLY_REC if normals is None else _PLY_NORMAL_REC)
     rec["xyz"] = np.asarray(xyz, dtype=np.float32).reshape(n, 3)
+    if normals is not None:
+        rec["normal"] = np.asarray(normals, dtype=np.float32).reshape(n, 3)
     rec["rgb"] = np.asarray(rgb_uint8, dtype=np.uint8).reshape(n, 3)
     return rec
 
 
-def write_ply(path_out: str, xyz: np.ndarray, rgb_uint8: np.ndarray) -> None:
-    """Binary little-endian PLY: x y z (f32) + red green blue (u8)."""
+def write_ply(path_out: str, xyz: np.ndarray, rgb_uint8: np.ndarray, normals: Optional[np.ndarray] = None) -> None:
+    """Binary little-endian PLY: x y z (f32) [+ nx ny nz (f32)] + red green blue (u8)."""
     with open(path_out, "wb") as f:
-        f.write(ply_header(xyz.shape[0]))
-        ply_records(xyz, rgb_uint8).tofile(f)
+        f.write(ply_header(xyz.shape[0], normals is not None))
+        ply_records(xyz, rgb_uint8, normals).tofile(f)
 
 
 def write_points3D_bin(path_out: str, xyz: np.ndarray, rgb_uint8: np.ndarray,
@@ -116,12 +121,14 @@ class StreamedPlyWriter:
         self.close()
 
 
-def write_ply_packed(path_out: str, n: int, body: bytes) -> None:
-    """PLY from a body packed on the device (HipDensifier.pack_ply): header + n 15-byte records."""
-    if len(body) != 15 * int(n):
-        raise ValueError("PLY body must be 15 bytes per vertex")
+def write_ply_packed(path_out: str, n: int, body: bytes, normals: bool = False) -> None:
+    """PLY from a body packed on the device: header + n 15-byte records (HipDensifier.pack_ply), or - ``normals`` - n 27-byte records
+    (HipDensifier.pack_ply_normals)."""
+    size = 27 if normals else 15
+    if len(body) != size * int(n):
+        raise ValueError(f"PLY body must be {size} bytes per vertex")
     with open(path_out, "wb") as f:
-        f.write(ply_header(n))
+        f.write(ply_header(n, normals))
         f.write(body)
 
 

@@ -18,6 +18,7 @@
 #include "lfd_cycle.hpp"
 #include "lfd_support.hpp"
 #include "lfd_refine.hpp"
+#include "lfd_normals.hpp"
 #include "lfd_sigma.hpp"
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
@@ -81,6 +82,8 @@ hipError_t lfd_cycle_launch(const LfdCycleArgs& p, hipStream_t stream);   // lfd
 hipError_t lfd_support_launch(const LfdSupportArgs& p, hipStream_t stream);   // lfd_support.hip
 hipError_t lfd_refine_launch(const LfdRefineArgs& p, hipStream_t stream);     // lfd_refine.hip
 hipError_t lfd_sigma_launch(const LfdSigmaArgs& p, hipStream_t stream);       // lfd_sigma.hip
+hipError_t lfd_normals_launch(const LfdNormalArgs& p, hipStream_t stream);    // lfd_normals.hip
+extern "C" __global__ void lfd_pack_ply_normals_kernel(const float* xyz, const float* normals, const float* rgb, long long n, unsigned char* out);
 extern "C" __global__ void lfd_select_topm_kernel(LfdSelectArgs A);
 extern "C" __global__ void lfd_select_filter_mw_kernel(LfdSelectArgs A, LfdSelectNorms norms);
 extern "C" __global__ void lfd_select_begins_kernel(long long* pairs, long long stride, int n);
@@ -1327,6 +1330,19 @@ int lfd_pack_ply(lfd_context* ctx, const float* xyz, const float* rgb, int64_t n
     return LFD_OK;
 }
 
+int lfd_pack_ply_normals(lfd_context* ctx, const float* xyz, const float* normals, const float* rgb, int64_t n, uint8_t* out) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (n < 0 || (n > 0 && (!xyz || !normals || !rgb || !out))) return fail(ctx, LFD_ERR_INVALID, "bad arguments");
+    if (reinterpret_cast<uintptr_t>(out) & 3u) return fail(ctx, LFD_ERR_INVALID, "out must be 4-byte aligned");
+    if (n == 0) return LFD_OK;
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(lfd_pack_ply_normals_kernel, dim3(grid), dim3(256), 0, ctx->stream, xyz, normals, rgb, (long long)n, out);
+    LFD_HIP(ctx, hipGetLastError());
+    return LFD_OK;
+}
+
 int lfd_pack_points3d(lfd_context* ctx, const float* xyz, const float* rgb, const float* err, int64_t n, uint64_t id_base,
                       uint8_t* out) {
     if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
@@ -1692,6 +1708,35 @@ int lfd_refine_multiview_weighted(lfd_context* ctx, const lfd_batch* batch, cons
                                   const float* const* precision) {
     return refine_impl(ctx, "lfd_refine_multiview_weighted", batch, in, ref_offsets, support_thresh_px, reproj_thresh, xyz_out, err_out, status,
                        counters, precision, true);
+}
+
+// ---- per-point surface normals (lfd_normals.hip) ----------------------------------------------------------------------------------------------
+int lfd_estimate_normals(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets, int32_t radius_cells,
+                         float depth_step_rel, float reproj_thresh, float* normals_out, uint8_t* status, int64_t* counters) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_normals_check(in, ref_offsets, radius_cells, depth_step_rel, reproj_thresh, normals_out, status))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_estimate_normals: ") + why);
+    // the batch's tables and per-pair constants, derived again only when the batch differs from the last one seen (no threshold reaches them)
+    lfd_params none;
+    std::memset(&none, 0, sizeof(none));
+    LfdLaunch L;
+    int rc = prepare_launch(ctx, batch, &none, nullptr, 0, L, nullptr);
+    if (rc != LFD_OK) return rc;
+    LfdNormalArgs p;
+    std::memset(&p, 0, sizeof(p));
+    p.n_wg = (int32_t)((in->capacity + 255) / 256);
+    p.refs = L.refs; p.slots = L.slots; p.ref_const = L.ref_const; p.pair_const = L.pair_const;
+    p.axis_x = L.axis_x; p.axis_y = L.axis_y;
+    p.offs = reinterpret_cast<const long long*>(ref_offsets);
+    p.xyz = in->xyz; p.cell = in->cell; p.slot = in->slot;
+    p.normals = normals_out; p.status = status;
+    p.counters = reinterpret_cast<unsigned long long*>(counters);
+    p.capacity = in->capacity;
+    p.n_refs = batch->n_refs; p.k = batch->k; p.radius = radius_cells; p.depth_step_rel = depth_step_rel;
+    p.g = launch_geom(batch, L, 0.0f, reproj_thresh);
+    LFD_HIP(ctx, lfd_normals_launch(p, ctx->stream));
+    return LFD_OK;
 }
 
 // ---- depth-uncertainty gate (lfd_sigma.hip) ---------------------------------------------------------------------------------------------------

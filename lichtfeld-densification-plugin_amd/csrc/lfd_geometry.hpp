@@ -556,8 +556,10 @@ LFD_HD void lfd_eval_correspondence(const LfdRefConst& rc, const LfdPairConst& p
             LFD_OPAQUE4(u1, v1, u2, v2);
             // the two rows of a view together (one packed multiply and one packed subtract per column on the device; element
             // by element the same f32 multiply-then-subtract as upstream)
+#if LFD_PACK_ROWS
             typedef float v2f __attribute__((ext_vector_type(2)));
             const v2f uv1 = {u1, v1}, uv2 = {u2, v2};
+#endif
             for (int c = 0; c < 4; ++c) {
 #if LFD_PACK_ROWS & 1
                 const v2f p1 = {rc.P[2 * c], rc.P[2 * c + 1]};

@@ -22,6 +22,7 @@
 #include "lfd_support.hpp"
 #include "lfd_refine.hpp"
 #include "lfd_sigma.hpp"
+#include "lfd_normals.hpp"
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
 
@@ -508,6 +509,54 @@ int lfd_refine_multiview_weighted_host(lfd_context* ctx, const lfd_batch* b, con
                                        int64_t* counters, const float* const* precision) {
     return refine_host_impl(ctx, "lfd_refine_multiview_weighted_host", b, in, ref_offsets, support_thresh_px, reproj_thresh, xyz_out, err_out,
                             status, counters, precision, true);
+}
+
+// The twin of lfd_estimate_normals: the routine of lfd_normals.hpp per point over host pointers, on the context's threads.
+int lfd_estimate_normals_host(lfd_context* ctx, const lfd_batch* b, const lfd_points* in, const int64_t* ref_offsets, int32_t radius_cells,
+                              float depth_step_rel, float reproj_thresh, float* normals_out, uint8_t* status, int64_t* counters) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    if (const char* why = lfd_normals_check(in, ref_offsets, radius_cells, depth_step_rel, reproj_thresh, normals_out, status))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_estimate_normals_host: ") + why);
+    lfd_params none;
+    std::memset(&none, 0, sizeof(none));
+    int rc = validate_host(ctx, b, &none);
+    if (rc != LFD_OK) return rc;
+    HostLaunch L;
+    prepare_host(b, &none, L);
+    std::vector<HostRef> href((size_t)b->n_refs);
+    std::vector<LfdNormalSlot> slot((size_t)b->n_refs * LFD_MAX_SLOTS);
+    for (int r = 0; r < b->n_refs; ++r) {
+        make_ref(ctx, L, r, href[(size_t)r]);
+        for (int j = 0; j < b->n_slots[r]; ++j) {
+            const size_t sj = (size_t)r * b->k + j;
+            slot[(size_t)r * LFD_MAX_SLOTS + j] = {b->cert[sj], b->warp[sj], b->mask_b ? b->mask_b[sj] : nullptr};
+        }
+    }
+    const LfdSupportGeom g = make_geom(L, 0.0f, reproj_thresh);
+    const LfdKernelParams kp = lfd_normal_params(g);
+    const long long cap = in->capacity;
+    const long long* offs = reinterpret_cast<const long long*>(ref_offsets);
+    const long long total = lfd_support_clamp(offs[b->n_refs], cap);
+    const int n_chunks = (int)((total + kChunk - 1) / kChunk);
+    std::vector<long long> count((size_t)n_chunks * 2, 0);             // per chunk: fitted, fell back
+    parallel_chunks(ctx, n_chunks, [&](int c) {
+        const long long i1 = std::min<long long>(total, (long long)(c + 1) * kChunk);
+        for (long long i = (long long)c * kChunk; i < i1; ++i) {
+            const int r = lfd_support_ref_of(offs, b->n_refs, cap, i);
+            float nrm[3];
+            const unsigned st = lfd_normal_point(href[(size_t)r].rc, href[(size_t)r].pc, &slot[(size_t)r * LFD_MAX_SLOTS], b->n_slots[r],
+                                                 b->mask_a ? b->mask_a[r] : nullptr, L.ax, L.ay, g, kp, radius_cells, depth_step_rel, in->cell[i],
+                                                 (int)in->slot[i], in->xyz[3 * i], in->xyz[3 * i + 1], in->xyz[3 * i + 2], nrm);
+            normals_out[3 * i] = nrm[0]; normals_out[3 * i + 1] = nrm[1]; normals_out[3 * i + 2] = nrm[2];
+            if (status) status[i] = (uint8_t)st;
+            ++count[(size_t)c * 2 + ((st & LFD_NORMAL_FITTED) ? 0 : 1)];
+        }
+    });
+    if (counters)
+        for (int c = 0; c < n_chunks; ++c)
+            for (int e = 0; e < 2; ++e) counters[e] += count[(size_t)c * 2 + e];
+    return LFD_OK;
 }
 
 // The twin of lfd_depth_sigma_filter: lfd_sigma_point per point on the context's threads, then the stable compaction.

@@ -142,11 +142,32 @@ def _effective_neighbor_count(requested: int, camera_count: int) -> int:
     return max(1, min(int(requested), camera_count - 1))
 
 
+def _cap_index(n_before: int, max_points: int, seed: int) -> Optional[np.ndarray]:
+    """The rows the point cap keeps (upstream densify.py's draw), or None when the cap does not act: the ONE place the choice is made - the
+    host arrays, the device tensors and the normals all index with it."""
+    if max_points > 0 and n_before > max_points:
+        return np.random.default_rng(seed).choice(n_before, size=max_points, replace=False)
+    return None
+
+
+def _take_rows(a, keep: Optional[np.ndarray]):
+    """``a`` (a NumPy array, a tensor wherever it lives, or None) under the cap's index."""
+    if a is None or keep is None:
+        return a
+    if isinstance(a, np.ndarray):
+        return a[keep]
+    import torch
+    return a[torch.from_numpy(keep).to(a.device)]
+
+
 def _apply_point_cap(xyz, rgb, err, max_points: int, seed: int):
-    if max_points > 0 and xyz.shape[0] > max_points:
-        keep = np.random.default_rng(seed).choice(xyz.shape[0], size=max_points, replace=False)
-        return xyz[keep], rgb[keep], err[keep]
-    return xyz, rgb, err
+    keep = _cap_index(int(xyz.shape[0]), max_points, seed)
+    return _take_rows(xyz, keep), _take_rows(rgb, keep), _take_rows(err, keep)
+
+
+def _cap_normals(normals, n_before: int, max_points: int, seed: int):
+    """The normals of the points ``_apply_point_cap`` / ``_cap_device_points`` keep (``_cap_index``).  None stays None."""
+    return _take_rows(normals, _cap_index(n_before, max_points, seed))
 
 
 def _finish_on_device(result, path: str, max_points: int, seed: int, clock=None) -> Optional[int]:
@@ -156,9 +177,10 @@ def _finish_on_device(result, path: str, max_points: int, seed: int, clock=None)
     pts = result.device_points
     if pts is None or not pts[0].is_cuda:
         return None
+    normals = _cap_normals(result.device_normals, int(pts[0].shape[0]), max_points, seed)
     pts = _cap_device_points(pts, int(pts[0].shape[0]), max_points, seed)
     n = int(pts[0].shape[0])
-    _write_output(path, np.empty((n, 0), np.float32), None, None, pts, clock=clock)
+    _write_output(path, np.empty((n, 0), np.float32), None, None, pts, clock=clock, normals=normals)
     return n
 
 
@@ -225,8 +247,16 @@ def _apply_consensus_filter(result, config: DensePipelineConfig, progress_callba
         progress_callback(92.0, "Applying consensus filter...")
     on_gpu = bool(pts[0].is_cuda)
     dens = hb.HipDensifier(pts[0].device) if on_gpu else hb.HostDensifier(int(config.exp("host_threads")))
+    normals = result.device_normals                  # experimental['estimate_normals']: the filter's keep decision applies to them as well
     try:
-        xyz, rgb, err, kept, _ = dens.consensus_filter(pts[0], pts[1], pts[2], counts, radius, min_refs)
+        xyz, rgb, err, kept, cons = dens.consensus_filter(pts[0], pts[1], pts[2], counts, radius, min_refs, with_consensus=normals is not None)
+        if normals is not None:
+            # the compaction is the library's; its per-point count gives the rows it kept, and that is CHECKED, not assumed: the input
+            # positions under the mask must be the kept positions bit for bit before the mask is applied to the normals
+            keep = cons >= min_refs
+            if int(keep.sum()) != int(xyz.shape[0]) or not torch.equal(pts[0][keep].view(torch.int32), xyz.view(torch.int32)):
+                raise RuntimeError("consensus filter: the per-point counts do not name the rows the filter kept; the normals cannot follow the points")
+            normals = normals[keep]
     except hb.ConsensusInputRefused as exc:
         raise RuntimeError(f"experimental['consensus_radius'] = {radius:g} is too small for the extent of this cloud: {exc}") from exc
     finally:
@@ -247,7 +277,7 @@ def _apply_consensus_filter(result, config: DensePipelineConfig, progress_callba
         loader, arrays = None, tuple(t.numpy() for t in new_pts)
     return PipelineResult(xyz=arrays[0], rgb=arrays[1], err=arrays[2], elapsed_seconds=result.elapsed_seconds, pairs_processed=result.pairs_processed,
                           pairs_matched=result.pairs_matched, points_per_reference=kept, device_points=new_pts, streamed_path=None,
-                          clock=result._clock, loader=loader)
+                          clock=result._clock, loader=loader, device_normals=normals)
 
 
 def _is_writer_rank() -> bool:
@@ -259,10 +289,11 @@ def _is_writer_rank() -> bool:
         return True
 
 
-def _write_output(path: str, xyz, rgb, err, device_points=None, clock=None, as_ply: Optional[bool] = None) -> None:
+def _write_output(path: str, xyz, rgb, err, device_points=None, clock=None, as_ply: Optional[bool] = None, normals=None) -> None:
     """``.ply`` -> upstream's PLY, anything else -> upstream's points3D.bin (densify.py:129-135); ``as_ply`` overrides the suffix.  When
     the points are still on the GPU the records are quantised and packed there (lfd_pack_*) and only
-    the final bytes are copied to the host; the files are byte-identical either way."""
+    the final bytes are copied to the host; the files are byte-identical either way.  ``normals`` (experimental['estimate_normals'], a PLY
+    only): one per point, where the points are - the vertices then are the 27-byte x y z nx ny nz r g b."""
     if not _is_writer_rank():        # sharded run: every rank holds the gathered cloud, rank 0 alone writes the file
         return
     d = os.path.dirname(path)
@@ -278,28 +309,34 @@ def _write_output(path: str, xyz, rgb, err, device_points=None, clock=None, as_p
         try:
             n = int(xyz.shape[0])
             with clock.stage("d2h"):            # the file payload - 15 / 43 bytes per point - is what crosses PCIe
-                packed = dens.pack_ply(device_points[0], device_points[1]) if as_ply else dens.pack_points3d(*device_points)
+                if normals is not None:
+                    packed = dens.pack_ply_normals(device_points[0], normals, device_points[1])
+                else:
+                    packed = dens.pack_ply(device_points[0], device_points[1]) if as_ply else dens.pack_points3d(*device_points)
                 body = packed.cpu().numpy().tobytes()
             with clock.stage("write", sync=False):
-                (write_ply_packed if as_ply else write_points3D_bin_packed)(path, n, body)
+                if normals is not None:
+                    write_ply_packed(path, n, body, normals=True)
+                else:
+                    (write_ply_packed if as_ply else write_points3D_bin_packed)(path, n, body)
         finally:
             dens.close()
         return
     rgb8 = to_uint8_rgb(rgb)
-    if as_ply:
+    if normals is not None:
+        write_ply(path, xyz, rgb8, normals.cpu().numpy() if hasattr(normals, "cpu") else normals)
+    elif as_ply:
         write_ply(path, xyz, rgb8)
     else:
         write_points3D_bin(path, xyz, rgb8, err)
 
 
 def _cap_device_points(device_points, n_before: int, max_points: int, seed: int):
-    """The same subset _apply_point_cap picks, applied to the GPU copy."""
-    if device_points is None or not (max_points > 0 and n_before > max_points):
+    """The same subset _apply_point_cap picks (``_cap_index``), applied to the GPU copy."""
+    if device_points is None:
         return device_points
-    import torch
-    keep = np.random.default_rng(seed).choice(n_before, size=max_points, replace=False)
-    idx = torch.from_numpy(keep).to(device_points[0].device)
-    return tuple(t[idx] for t in device_points)
+    keep = _cap_index(n_before, max_points, seed)
+    return device_points if keep is None else tuple(_take_rows(t, keep) for t in device_points)
 
 
 def _was_cancelled(cb) -> bool:
@@ -368,8 +405,9 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
     else:
         n_points = _finish_on_device(result, config.output_path, args.max_points, args.seed, clock=pipeline_kwargs.get("stage_clock"))
         if n_points is None:
+            normals = _cap_normals(result.normals, int(result.xyz.shape[0]), args.max_points, args.seed)
             xyz, rgb, err = _apply_point_cap(result.xyz, result.rgb, result.err, args.max_points, args.seed)
-            _write_output(config.output_path, xyz, rgb, err, None)
+            _write_output(config.output_path, xyz, rgb, err, None, normals=normals)
             n_points = int(xyz.shape[0])
     log.info(f"Dense reconstruction finished: {n_points:,} points -> {config.output_path}")
     if progress_callback:
@@ -449,6 +487,7 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
             if progress_callback:
                 progress_callback(100.0, f"Done! {n_vox:,} points")
             return 0, config.output_path
+    normals = _cap_normals(result.normals, int(result.xyz.shape[0]), config.max_points, config.seed)      # (None without experimental['estimate_normals'])
     xyz, rgb, err = _apply_point_cap(result.xyz, result.rgb, result.err, config.max_points, config.seed)
     dev_pts = _cap_device_points(result.device_points, result.xyz.shape[0], config.max_points, config.seed)
     if config.voxel_size > 0.0:
@@ -467,7 +506,7 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
         if _is_writer_rank():
             write_ply(config.output_path, xyz, to_uint8_rgb(rgb))
     else:
-        _write_output(config.output_path, xyz, rgb, err, dev_pts)
+        _write_output(config.output_path, xyz, rgb, err, dev_pts if normals is None else None, normals=normals)
     log.info(f"Dense point cloud saved to {config.output_path} ({xyz.shape[0]:,} points)")
     if progress_callback:
         progress_callback(100.0, f"Done! {xyz.shape[0]:,} points")
@@ -497,6 +536,12 @@ def _experimental_from_args(args) -> dict:
         exp["consensus_radius"] = float(args.consensus_radius)
     if bool(getattr(args, "undistort_images", False)):
         exp["undistort_images"] = True
+    if bool(getattr(args, "estimate_normals", False)):
+        exp["estimate_normals"] = True
+    if getattr(args, "normal_radius_cells", None) is not None:
+        exp["normal_radius_cells"] = int(args.normal_radius_cells)
+    if getattr(args, "normal_depth_step_rel", None) is not None:
+        exp["normal_depth_step_rel"] = float(args.normal_depth_step_rel)
     return exp
 
 
@@ -558,6 +603,14 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--undistort_images", action="store_true",
                     help="resample every image (and its mask) through its COLMAP camera's distortion model (SIMPLE_RADIAL, RADIAL, OPENCV, "
                          "FULL_OPENCV) into the pinhole image of the same intrinsics before it is matched; other distorted models are refused")
+    ap.add_argument("--estimate_normals", action="store_true",
+                    help="give every point a unit surface normal, fitted to its winning neighbour's warp around its grid cell and oriented towards "
+                         "its reference's camera: the PLY then has x y z nx ny nz red green blue vertices (needs a .ply --out_name)")
+    ap.add_argument("--normal_radius_cells", type=int, default=None,
+                    help="... over the (2 r + 1)^2 window of this radius in grid cells (1 .. 4; default 3; needs --estimate_normals)")
+    ap.add_argument("--normal_depth_step_rel", type=float, default=None,
+                    help="... leaving out window cells whose depth differs from the point's by more than this fraction of it (> 0; default 0.05; "
+                         "needs --estimate_normals)")
     ap.add_argument("--keep_threads", action="store_true",
                     help="leave torch's intra-op thread count alone (by default it is lowered to the container's CPU quota; the count decides the last "
                          "bits of upstream's sampling normaliser, so a run compared bit for bit with upstream keeps upstream's setting)")
