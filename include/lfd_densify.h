@@ -523,6 +523,36 @@ int lfd_consensus_filter_host(lfd_context* ctx, const float* xyz, const float* r
                               int32_t n_refs, float radius, int32_t min_refs, float* xyz_out, float* rgb_out, float* err_out,
                               int64_t* ref_offsets_out_host, uint8_t* consensus, int64_t* n_out_host);
 
+/* Free-space filter on the final cloud (no upstream counterpart).  Every reference's own points are a sparse depth map of what it
+ * saw; a point of ANOTHER reference that lies in front of that depth map on the same ray cannot exist - the reference looked through it.  The
+ * cloud is the concatenation of n_refs references' points (ref_offsets_host as for lfd_consensus_filter); cam_P_host: HOST f32 [n_refs][12], the
+ * row-major 3 x 4 projection of each reference (pixels of its image); cam_wh_host: HOST i32 [n_refs][2], its image size w, h; pw x ph: the size of
+ * every reference's z-buffer plane (csrc/lfd_freespace.hpp, every rounding written out, no FMA):
+ *   projection   f64 from the f32 inputs: p_r = ((P[r][0] x + P[r][1] y) + P[r][2] z) + P[r][3]; u = p_0 / p_2, v = p_1 / p_2; d = (float) p_2;
+ *                inside iff p_0, p_1, p_2 finite, p_2 > 0, 0 <= u < w, 0 <= v < h, d finite and > 0;
+ *                cx = min(pw - 1, floor((u pw) / w)), cy = min(ph - 1, floor((v ph) / h))
+ *   Z_r[cy][cx]  the smallest d over reference r's OWN points inside its own camera, +inf where there are none
+ *   test         point i of reference r against every j != r it is inside of, d_i its depth there, over the cells of the 3 x 3 window around its
+ *                cell that lie in the plane; for a finite D = Z_j[cell], f32: t = tol D, lo = D - t, hi = D + t.  j SUPPORTS i iff some cell has
+ *                lo <= d_i <= hi; else j REFUTES i iff the window has a finite cell and d_i < lo(D_min), D_min its smallest; else j says nothing
+ *   dropped      iff v_i >= min_violations and v_i > s_i, the numbers of refuting and supporting references (unsaturated)
+ * rgb (f32 [n][3]) and err (f32 [n]) travel along when given (NULL together with their output).  tol in (0, 1), min_violations in 1 .. 255.  The
+ * compaction is stable and copies bit for bit; xyz_out / rgb_out / err_out hold n points.  ref_offsets_out_host (HOST i64 [n_refs + 1]) and
+ * *n_out_host are always written; violations / supports: each NULL, or u8 [n], min(v_i, 255) / min(s_i, 255) per INPUT point.  Synchronous,
+ * deterministic; the workspace (the z-buffers among it, refilled on every call) belongs to the context and is reused.  LFD_ERR_INVALID: a null
+ * required pointer or half of an optional pair, n < 0 or > 2^31 - 1, n_refs < 1, malformed offsets, pw, ph, w or h below 1,
+ * n_refs pw ph > 2^31 - 1, an entry of P that is not finite, tol outside (0, 1), min_violations out of range, in and out arrays that overlap.
+ * n == 0 is valid.  lfd_freespace_filter_host: the same over host pointers on a host context's threads; every output equals the device's bit for
+ * bit. */
+int lfd_freespace_filter(lfd_context* ctx, const float* xyz, const float* rgb, const float* err, int64_t n, const int64_t* ref_offsets_host,
+                         int32_t n_refs, const float* cam_P_host, const int32_t* cam_wh_host, int32_t pw, int32_t ph, float tol,
+                         int32_t min_violations, float* xyz_out, float* rgb_out, float* err_out, int64_t* ref_offsets_out_host,
+                         uint8_t* violations, uint8_t* supports, int64_t* n_out_host);
+int lfd_freespace_filter_host(lfd_context* ctx, const float* xyz, const float* rgb, const float* err, int64_t n, const int64_t* ref_offsets_host,
+                              int32_t n_refs, const float* cam_P_host, const int32_t* cam_wh_host, int32_t pw, int32_t ph, float tol,
+                              int32_t min_violations, float* xyz_out, float* rgb_out, float* err_out, int64_t* ref_offsets_out_host,
+                              uint8_t* violations, uint8_t* supports, int64_t* n_out_host);
+
 /* (e) multi-GPU exchange, placement step (no upstream counterpart - upstream has no multi-GPU code): n copies
  * dst[dst_offset .. +nbytes) = src[src_offset .. +nbytes) in ONE launch on `hip_stream` of device `device_index` (offsets and lengths in
  * bytes, no alignment required: 15-byte PLY records).  The overlapped exchange receives every rank's records of a round as one padded block
@@ -610,7 +640,7 @@ int lfd_host_eval_correspondence(const float* cam1, const float* cam2, float xa_
  * The per-cell arithmetic is the host build of the very source the kernels compile (csrc/lfd_geometry.hpp; IEEE
  * division / square root where the device uses the 1-ulp v_rcp / v_sqrt), spread over n_threads std::threads
  * (<= 0: all hardware threads).  A host context accepts lfd_upload_cameras, lfd_last_error, lfd_destroy and the
- * *_host calls (the three below, lfd_local_corr_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host and lfd_consensus_filter_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
+ * *_host calls (the three below, lfd_local_corr_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host, lfd_consensus_filter_host and lfd_freespace_filter_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
  * context: neither side ever stands in for the other.  Semantics (orders, counts, optional outputs, LFD_ERR_CAPACITY
  * with valid counts) are those of lfd_aggregate / lfd_triangulate_dense / lfd_triangulate_indexed. */
 int lfd_create_host(int32_t n_threads, lfd_context** out);

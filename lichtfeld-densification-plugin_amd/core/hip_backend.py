@@ -201,6 +201,10 @@ def load_library() -> C.CDLL:
     lib.lfd_consensus_filter.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_float, C.c_int32,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)]
     lib.lfd_consensus_filter_host.argtypes = list(lib.lfd_consensus_filter.argtypes)
+    lib.lfd_freespace_filter.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_float),
+                                         C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.lfd_freespace_filter_host.argtypes = list(lib.lfd_freespace_filter.argtypes)
     lib.lfd_copy_segments.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.lfd_launch_status.argtypes = [ctxp, C.POINTER(C.c_int32)]
     lib.lfd_get_pair_fundamental.argtypes = [ctxp, C.c_int32, C.POINTER(C.c_double)]
@@ -238,7 +242,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -1020,6 +1024,48 @@ def _consensus_call(fn, ctx, what, xyz, rgb, err, ref_counts, radius, min_refs, 
     return kept[0], kept[1], kept[2], np.diff(offs_out), (cons[:n] if with_consensus else None)
 
 
+def _freespace_call(fn, ctx, what, xyz, rgb, err, ref_counts, cam_P, cam_wh, plane, tol, min_violations, with_counts, device, last_error):
+    """One lfd_freespace_filter[_host] call.  ``xyz`` (n, 3), ``rgb`` (n, 3) or None, ``err`` (n,) or None: float32 tensors on ``device``;
+    ``ref_counts``: points per reference, in the order of the cloud; ``cam_P`` (n_refs, 3, 4) or (n_refs, 12) float32 and ``cam_wh`` (n_refs, 2)
+    int32: every reference's projection and image size (host arrays); ``plane`` = (pw, ph), the z-buffer size.  Returns
+    ``(xyz, rgb, err, counts, violations, supports)``: the kept points in input order (views of n-row tensors; rgb / err None when not given), the
+    kept points per reference (int64 array) and - ``with_counts`` - the two uint8 counts of every INPUT point, else None."""
+    counts = np.ascontiguousarray(np.asarray(ref_counts, np.int64).reshape(-1))
+    n = int(xyz.shape[0])
+    if counts.size < 1 or (counts < 0).any() or int(counts.sum()) != n:
+        raise ValueError(f"{what}: ref_counts must be non-negative counts, one per reference, that add up to the {n} points")
+    P = np.ascontiguousarray(np.asarray(cam_P, np.float32).reshape(-1, 12))
+    wh = np.ascontiguousarray(np.asarray(cam_wh, np.int32).reshape(-1, 2))
+    if P.shape[0] != counts.size or wh.shape[0] != counts.size:
+        raise ValueError(f"{what}: cam_P and cam_wh must hold one camera per reference ({counts.size}), not {P.shape[0]} and {wh.shape[0]}")
+    tensors = []
+    for t, cols, name in ((xyz, 3, "xyz"), (rgb, 3, "rgb"), (err, 0, "err")):
+        if t is None:
+            tensors.append(None)
+            continue
+        if t.dtype != torch.float32 or t.device != device or int(t.shape[0]) != n or (cols and (t.dim() != 2 or t.shape[1] != cols)) or (not cols and t.dim() != 1):
+            raise ValueError(f"{what}: {name} must be a float32 tensor of {n} rows{' x 3' if cols else ''} on {device}")
+        tensors.append(t.contiguous())
+    xyz, rgb, err = tensors
+    offs = np.zeros(counts.size + 1, np.int64)
+    np.cumsum(counts, out=offs[1:])
+    offs_out = np.zeros_like(offs)
+    outs = [torch.empty((max(n, 1),) + tuple(t.shape[1:]), dtype=torch.float32, device=device) if t is not None else None for t in tensors]
+    viol = torch.empty((max(n, 1),), dtype=torch.uint8, device=device) if with_counts else None
+    supp = torch.empty((max(n, 1),), dtype=torch.uint8, device=device) if with_counts else None
+    n_out = C.c_int64(0)
+    ptr = lambda t: t.data_ptr() if t is not None and n > 0 else None       # noqa: E731  (an empty tensor may have no address at all)
+    i64p = C.POINTER(C.c_int64)
+    rc = fn(ctx, ptr(xyz), ptr(rgb), ptr(err), n, offs.ctypes.data_as(i64p), int(counts.size), P.ctypes.data_as(C.POINTER(C.c_float)),
+            wh.ctypes.data_as(C.POINTER(C.c_int32)), int(plane[0]), int(plane[1]), C.c_float(float(tol)), int(min_violations),
+            ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), offs_out.ctypes.data_as(i64p), ptr(viol), ptr(supp), C.byref(n_out))
+    if rc != 0:
+        raise HipBackendError(f"{what} failed ({rc}): {last_error()}")
+    k = int(n_out.value)
+    kept = [o[:k] if o is not None else None for o in outs]
+    return kept[0], kept[1], kept[2], np.diff(offs_out), (viol[:n] if with_counts else None), (supp[:n] if with_counts else None)
+
+
 class HipDensifier:
     """One context = one GPU + one stream (``torch.cuda.current_stream`` of the device at creation,
     unless a stream is given).  Not thread-safe: use one per thread, as the C-ABI requires."""
@@ -1163,6 +1209,15 @@ class HipDensifier:
         Returns ``(xyz, rgb, err, counts, consensus)`` as ``_consensus_call`` describes.  Synchronous."""
         return _consensus_call(self._lib.lfd_consensus_filter, self._ctx, "lfd_consensus_filter", xyz, rgb, err, ref_counts, radius, min_refs,
                                with_consensus, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
+
+    def freespace_filter(self, xyz: torch.Tensor, rgb: Optional[torch.Tensor], err: Optional[torch.Tensor], ref_counts, cam_P, cam_wh, plane,
+                         tol: float, min_violations: int, with_counts: bool = False):
+        """Free-space filter on the device (lfd_freespace_filter): a point of the cloud - the concatenation of the references'
+        points, ``ref_counts`` each - is dropped when at least ``min_violations`` OTHER references triangulated a surface behind it on the same
+        ray (they looked through it) and more refute than support it.  Returns ``(xyz, rgb, err, counts, violations, supports)`` as
+        ``_freespace_call`` describes.  Synchronous."""
+        return _freespace_call(self._lib.lfd_freespace_filter, self._ctx, "lfd_freespace_filter", xyz, rgb, err, ref_counts, cam_P, cam_wh, plane, tol,
+                               min_violations, with_counts, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
 
     def set_stream(self, stream: "torch.cuda.Stream") -> None:
         """Later calls are issued on ``stream`` (lfd_set_stream: what was issued on the previous one is waited for first).  A call with the
@@ -1684,6 +1739,12 @@ class HostDensifier:
         """HipDensifier.consensus_filter over CPU tensors (lfd_consensus_filter_host): the same per-point routine, the same bits in every output."""
         return _consensus_call(self._lib.lfd_consensus_filter_host, self._ctx, "lfd_consensus_filter_host", xyz, rgb, err, ref_counts, radius,
                                min_refs, with_consensus, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
+
+    def freespace_filter(self, xyz: torch.Tensor, rgb: Optional[torch.Tensor], err: Optional[torch.Tensor], ref_counts, cam_P, cam_wh, plane,
+                         tol: float, min_violations: int, with_counts: bool = False):
+        """HipDensifier.freespace_filter over CPU tensors (lfd_freespace_filter_host): the same per-point routine, the same bits in every output."""
+        return _freespace_call(self._lib.lfd_freespace_filter_host, self._ctx, "lfd_freespace_filter_host", xyz, rgb, err, ref_counts, cam_P, cam_wh,
+                               plane, tol, min_violations, with_counts, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
 
     def aggregate(self, batch: PreparedBatch, params: lfd_params):
         self._same_device(batch)

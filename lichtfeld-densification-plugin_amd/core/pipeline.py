@@ -170,6 +170,7 @@ def _match_reference(local_i: int, packed: PackedReference, matcher, hot: HotPat
         warps = [_as_device_map(r[0], dev) for r in results]
         certs = [_as_device_map(r[1], dev) for r in results]
     H, W = certs[0].shape
+    outputs.match_grid = (int(H), int(W))
     axes = None
     ax = getattr(matcher, "reference_axes", None)
     if warps[0].shape[-1] == 2 and callable(ax):

@@ -34,10 +34,11 @@ class PipelineResult:
 
     def __init__(self, xyz=None, rgb=None, err=None, elapsed_seconds: float = 0.0, pairs_processed: int = 0, pairs_matched: int = 0,
                  points_per_reference: Optional[np.ndarray] = None, device_points=None, streamed_path: Optional[str] = None,
-                 clock=None, loader: Optional[Callable[[], Tuple[np.ndarray, np.ndarray, np.ndarray]]] = None, device_normals=None):
+                 clock=None, loader: Optional[Callable[[], Tuple[np.ndarray, np.ndarray, np.ndarray]]] = None, device_normals=None, match_grid=None):
         self._arrays = (xyz, rgb, err) if loader is None else None
         self.device_normals = device_normals                  # experimental['estimate_normals']: (N,3) f32 unit normals where the points are, else None
         self._normals = None
+        self.match_grid = match_grid                          # (H, W) of the matcher's grid, when a reference was matched in this process
         self._loader = loader
         self.elapsed_seconds = float(elapsed_seconds)
         self.pairs_processed = int(pairs_processed)           # upstream's name; counts REFERENCES that produced points
@@ -295,6 +296,7 @@ class RunOutputs:
         self.pair_counter = 0
         self.rep_refs_with_points = 0
         self.rep_pairs = 0
+        self.match_grid = None                           # (H, W) of the matcher's grid (core/pipeline.py notes it at the first match)
         self.records_only = False                        # DensePlyStreamer: the survivors exist as file records only
         self.cum_body: Optional[CumulativePlyBody] = None          # bytes of the cloud so far, for the intermediate previews
         self.stream_writer: Optional[StreamedPlyWriter] = None     # config.stream_output: the output file grows while the run proceeds
@@ -419,7 +421,7 @@ class RunOutputs:
         xyz, rgb, err = arrays if arrays is not None else (None, None, None)
         return PipelineResult(xyz=xyz, rgb=rgb, err=err, elapsed_seconds=time.time() - t0, pairs_processed=refs_with_points,
                               pairs_matched=pairs, points_per_reference=counts, device_points=device_points, streamed_path=streamed_path,
-                              clock=clock, loader=loader, device_normals=device_normals)
+                              clock=clock, loader=loader, device_normals=device_normals, match_grid=self.match_grid)
 
 
 __all__ = ["PipelineResult", "ShardPlan", "Emission", "ShardLink", "RunOutputs", "arrays_from_ply", "build_preview", "cancelled"]

@@ -95,6 +95,18 @@ EXPERIMENTAL_DEFAULTS = {
     # about 400 at 512^2): under 0.03 up to r = 2, 0.057 at r = 4.  At 0.05 only the outermost cells of the widest windows on the steepest
     # planes are cut, while a foreground / background step is far over 0.05.
     "normal_depth_step_rel": 0.05,
+    # free-space filter on the final cloud (lfd_freespace_filter): every reference's own points are a sparse depth map of what it
+    # saw; a point is dropped when at least this many OTHER references triangulated a surface behind it on the same ray - they looked through
+    # it - and more references refute than confirm it.  Runs once, behind the consensus filter and in front of the point cap and the voxel
+    # filter.  1 .. 255; 0 = off: no new code runs.
+    "min_freespace_violations": 0,
+    # ... with this relative depth tolerance, in (0, 1): a depth within it of a reference's z-buffer confirms, only a depth more than it in
+    # front refutes.  The default is a judgement (the value the prototype scene of DESIGN.md 4.15 was checked at); do not set it below the
+    # relative depth noise you accept, e.g. your max_depth_sigma_rel.  Refused with the filter off unless left at the default.
+    "freespace_depth_tol_rel": 0.02,
+    # ... on z-buffer planes of this many cells along the longer image side, 8 .. 4096.  0 = automatic: ceil(sqrt(matches_per_ref)) in sampled
+    # mode (about one emitted point per cell), the longer side of the matcher's grid in dense mode.
+    "freespace_plane_cells": 0,
 }
 CONSENSUS_CAP = 8            # LFD_CONSENSUS_CAP of include/lfd_densify.h
 
@@ -320,6 +332,33 @@ class DensePipelineConfig:
                 return "experimental['min_consensus_refs'] filters f32 rows; experimental['exchange_records'] must be 'f32' with it"
             if dense and self.exp("dense_tile_segments"):
                 return ("experimental['min_consensus_refs'] needs the cloud as arrays with per-reference counts; dense mode with "
+                        "experimental['dense_tile_segments'] retires tiles unordered")
+        m_fs = self.exp("min_freespace_violations")
+        if isinstance(m_fs, bool) or not isinstance(m_fs, (int, np.integer)) or int(m_fs) < 0:
+            return "experimental['min_freespace_violations'] must be a non-negative integer (other references that have to look through a point; 0 = off)"
+        if int(m_fs) > 255:
+            return f"experimental['min_freespace_violations'] = {int(m_fs)} is more than the 255 references the filter's counts hold"
+        try:
+            tol_fs = float(self.exp("freespace_depth_tol_rel"))
+        except (TypeError, ValueError):
+            return "experimental['freespace_depth_tol_rel'] must be a number (a relative depth, in (0, 1))"
+        if not (0.0 < tol_fs < 1.0) or not (0.0 < float(np.float32(tol_fs)) < 1.0):
+            return "experimental['freespace_depth_tol_rel'] must be in (0, 1) (a relative depth)"
+        if int(m_fs) == 0 and tol_fs != float(EXPERIMENTAL_DEFAULTS["freespace_depth_tol_rel"]):
+            return "experimental['freespace_depth_tol_rel'] is the tolerance of the free-space filter: it needs experimental['min_freespace_violations'] >= 1"
+        c_fs = self.exp("freespace_plane_cells")
+        if isinstance(c_fs, bool) or not isinstance(c_fs, (int, np.integer)) or (int(c_fs) != 0 and not 8 <= int(c_fs) <= 4096):
+            return "experimental['freespace_plane_cells'] must be 0 (automatic) or an integer in 8 .. 4096 (z-buffer cells along the longer image side)"
+        if int(c_fs) != 0 and int(m_fs) == 0:
+            return "experimental['freespace_plane_cells'] is the z-buffer size of the free-space filter: it needs experimental['min_freespace_violations'] >= 1"
+        if int(m_fs) > 0:
+            if self.stream_output:
+                return ("experimental['min_freespace_violations'] has to see the whole cloud before anything is written; stream_output writes the file "
+                        "while the run proceeds")
+            if self.exchange_record_format() == "ply":
+                return "experimental['min_freespace_violations'] filters f32 rows; experimental['exchange_records'] must be 'f32' with it"
+            if dense and self.exp("dense_tile_segments"):
+                return ("experimental['min_freespace_violations'] needs the cloud as arrays with per-reference counts; dense mode with "
                         "experimental['dense_tile_segments'] retires tiles unordered")
         if not isinstance(self.exp("undistort_images"), (bool, np.bool_)):
             return "experimental['undistort_images'] must be True or False"

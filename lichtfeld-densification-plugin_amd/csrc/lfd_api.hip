@@ -22,6 +22,7 @@
 #include "lfd_sigma.hpp"
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
+#include "lfd_freespace.hpp"
 
 extern "C" __global__ void lfd_aggregate_kernel(LfdLaunch L, float* best_cert, uint8_t* best_slot);
 extern "C" __global__ void lfd_dense_kernel(LfdLaunch L);
@@ -77,6 +78,12 @@ extern "C" __global__ void lfd_consensus_wgcount_kernel(const uint8_t* keep, lon
 extern "C" __global__ void lfd_consensus_offsets_kernel(const long long* offs, int n_refs, const uint8_t* keep, const unsigned* wg_kept, long long* offs_out);
 extern "C" __global__ void lfd_consensus_scatter_kernel(const float* xyz, const float* rgb, const float* err, long long n, const uint8_t* keep,
                                                         const unsigned* wg_kept, float* o_xyz, float* o_rgb, float* o_err);
+extern "C" __global__ void lfd_freespace_fill_kernel(uint32_t* zbuf, long long n_words);
+extern "C" __global__ void lfd_freespace_splat_kernel(const float* xyz, long long n, const long long* offs, int n_refs, const LfdFreespaceCam* cams, int pw,
+                                                      int ph, uint32_t* zbuf);
+extern "C" __global__ void lfd_freespace_count_kernel(const float* xyz, long long n, const long long* offs, int n_refs, const LfdFreespaceCam* cams,
+                                                      const uint32_t* zbuf, int pw, int ph, float tol, int min_violations, uint8_t* keep,
+                                                      uint8_t* violations, uint8_t* supports);
 hipError_t lfd_corr_launch(const LfdCorrArgs& p, hipStream_t stream);     // lfd_corr.hip
 hipError_t lfd_cycle_launch(const LfdCycleArgs& p, hipStream_t stream);   // lfd_cycle.hip
 hipError_t lfd_support_launch(const LfdSupportArgs& p, hipStream_t stream);   // lfd_support.hip
@@ -558,7 +565,7 @@ void lfd_destroy(lfd_context* ctx) {
     }
     for (hipEvent_t ev : ctx->kt_start) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->kt_stop) (void)hipEventDestroy(ev);
-    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->vox, &ctx->support_ws, &ctx->prec_tab, &ctx->consensus_ws, &ctx->undist_cnt})
+    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->vox, &ctx->support_ws, &ctx->prec_tab, &ctx->consensus_ws, &ctx->undist_cnt, &ctx->freespace_ws})
         if (b->ptr) (void)hipFree(b->ptr);
     if (ctx->pinned_words) (void)hipHostFree(ctx->pinned_words);
     if (ctx->prec_pinned) (void)hipHostFree(ctx->prec_pinned);
@@ -1517,6 +1524,61 @@ int lfd_consensus_filter(lfd_context* ctx, const float* xyz, const float* rgb, c
     hipLaunchKernelGGL(lfd_consensus_gather_kernel, dim3(grid), dim3(256), 0, st, xyz, idx[cur], offs, (int)n_refs, (long long)n, spt);
     hipLaunchKernelGGL(lfd_consensus_count_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, keys[cur], spt, idx[cur], (long long)n, g.e[1], g.e[2],
                        g.sentinel, lfd_consensus_r2(radius), (int)min_refs, consensus ? LFD_CONSENSUS_CAP : (int)min_refs, keep, consensus);
+    hipLaunchKernelGGL(lfd_consensus_wgcount_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, keep, (long long)n, wg_kept);
+    hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, wg_kept, (int)n_wg, wg_kept + n_wg);
+    hipLaunchKernelGGL(lfd_consensus_offsets_kernel, dim3((unsigned)std::min<long long>(((long long)n_refs + 256) / 256, 1024)), dim3(256), 0, st, offs,
+                       (int)n_refs, keep, wg_kept, offs_out);
+    hipLaunchKernelGGL(lfd_consensus_scatter_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, xyz, rgb, err, (long long)n, keep, wg_kept, xyz_out, rgb_out,
+                       err_out);
+    LFD_HIP(ctx, hipGetLastError());
+    LFD_HIP(ctx, hipMemcpyAsync(ref_offsets_out_host, offs_out, offs_bytes, hipMemcpyDeviceToHost, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));
+    *n_out_host = ref_offsets_out_host[n_refs];
+    return LFD_OK;
+}
+
+// ---- free-space filter on the final cloud (lfd_freespace.hip) ------------------------------------------------------------------------------------
+int lfd_freespace_filter(lfd_context* ctx, const float* xyz, const float* rgb, const float* err, int64_t n, const int64_t* ref_offsets_host,
+                         int32_t n_refs, const float* cam_P_host, const int32_t* cam_wh_host, int32_t pw, int32_t ph, float tol,
+                         int32_t min_violations, float* xyz_out, float* rgb_out, float* err_out, int64_t* ref_offsets_out_host,
+                         uint8_t* violations, uint8_t* supports, int64_t* n_out_host) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_freespace_check(xyz, rgb, err, n, ref_offsets_host, n_refs, cam_P_host, cam_wh_host, pw, ph, tol, min_violations,
+                                              xyz_out, rgb_out, err_out, ref_offsets_out_host, violations, supports, n_out_host))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_freespace_filter: ") + why);
+    for (int32_t r = 0; r <= n_refs; ++r) ref_offsets_out_host[r] = 0;
+    *n_out_host = 0;
+    if (n == 0) return LFD_OK;
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const long long n_wg = (n + 255) / 256;
+    const long long n_words = (long long)n_refs * pw * ph;             // <= 2^31 - 1 (lfd_freespace_check)
+    std::vector<LfdFreespaceCam> cams((size_t)n_refs);
+    for (int32_t r = 0; r < n_refs; ++r) lfd_freespace_cam(cam_P_host + 12 * (size_t)r, cam_wh_host[2 * r], cam_wh_host[2 * r + 1], cams[(size_t)r]);
+    // workspace: z-buffers | cameras | offsets in, out | keep bytes | kept per workgroup
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t offs_bytes = ((size_t)n_refs + 1) * sizeof(long long), cam_bytes = (size_t)n_refs * sizeof(LfdFreespaceCam);
+    const size_t o_z = 0, o_cam = al(o_z + (size_t)n_words * sizeof(uint32_t)), o_off = al(o_cam + cam_bytes), o_offo = al(o_off + offs_bytes);
+    const size_t o_keep = al(o_offo + offs_bytes), o_wg = al(o_keep + (size_t)n_wg * 256);
+    const size_t total = al(o_wg + ((size_t)n_wg + 1) * sizeof(unsigned));
+    if (int rc = ensure(ctx, ctx->freespace_ws, total)) return rc;
+    unsigned char* w = static_cast<unsigned char*>(ctx->freespace_ws.ptr);
+    uint32_t* zbuf = reinterpret_cast<uint32_t*>(w + o_z);
+    LfdFreespaceCam* d_cams = reinterpret_cast<LfdFreespaceCam*>(w + o_cam);
+    long long* offs = reinterpret_cast<long long*>(w + o_off);
+    long long* offs_out = reinterpret_cast<long long*>(w + o_offo);
+    uint8_t* keep = w + o_keep;
+    unsigned* wg_kept = reinterpret_cast<unsigned*>(w + o_wg);
+
+    LFD_HIP(ctx, hipMemcpyAsync(offs, ref_offsets_host, offs_bytes, hipMemcpyHostToDevice, st));
+    LFD_HIP(ctx, hipMemcpyAsync(d_cams, cams.data(), cam_bytes, hipMemcpyHostToDevice, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));                            // `cams` is pageable memory of this call: the copy has read it
+    hipLaunchKernelGGL(lfd_freespace_fill_kernel, dim3((unsigned)std::min<long long>((n_words + 255) / 256, 4096)), dim3(256), 0, st, zbuf, n_words);
+    hipLaunchKernelGGL(lfd_freespace_splat_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, xyz, (long long)n, offs, (int)n_refs, d_cams, (int)pw, (int)ph,
+                       zbuf);
+    hipLaunchKernelGGL(lfd_freespace_count_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, xyz, (long long)n, offs, (int)n_refs, d_cams, zbuf, (int)pw,
+                       (int)ph, tol, (int)min_violations, keep, violations, supports);
     hipLaunchKernelGGL(lfd_consensus_wgcount_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, keep, (long long)n, wg_kept);
     hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, wg_kept, (int)n_wg, wg_kept + n_wg);
     hipLaunchKernelGGL(lfd_consensus_offsets_kernel, dim3((unsigned)std::min<long long>(((long long)n_refs + 256) / 256, 1024)), dim3(256), 0, st, offs,

@@ -25,6 +25,7 @@
 #include "lfd_normals.hpp"
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
+#include "lfd_freespace.hpp"
 
 void lfd_fill_kernel_params(const lfd_batch* b, const lfd_params* p, LfdKernelParams& kp);   // lfd_api.hip
 
@@ -742,6 +743,66 @@ int lfd_host_undistort_image(const uint8_t* src, int32_t w, int32_t h, int32_t c
     for (int i = 0; i < h; ++i)
         for (int j = 0; j < w; ++j) bad += lfd_undistort_pixel(p, i, j) ? 0 : 1;
     if (n_invalid_host) *n_invalid_host = bad;
+    return LFD_OK;
+}
+
+// The twin of lfd_freespace_filter: the z-buffers by a plain minimum, lfd_freespace_count_point per point on the context's threads,
+// then the stable compaction.
+int lfd_freespace_filter_host(lfd_context* ctx, const float* xyz, const float* rgb, const float* err, int64_t n, const int64_t* ref_offsets_host,
+                              int32_t n_refs, const float* cam_P_host, const int32_t* cam_wh_host, int32_t pw, int32_t ph, float tol,
+                              int32_t min_violations, float* xyz_out, float* rgb_out, float* err_out, int64_t* ref_offsets_out_host,
+                              uint8_t* violations, uint8_t* supports, int64_t* n_out_host) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    if (const char* why = lfd_freespace_check(xyz, rgb, err, n, ref_offsets_host, n_refs, cam_P_host, cam_wh_host, pw, ph, tol, min_violations,
+                                              xyz_out, rgb_out, err_out, ref_offsets_out_host, violations, supports, n_out_host))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_freespace_filter_host: ") + why);
+    for (int32_t r = 0; r <= n_refs; ++r) ref_offsets_out_host[r] = 0;
+    *n_out_host = 0;
+    if (n == 0) return LFD_OK;
+    const long long* offs = reinterpret_cast<const long long*>(ref_offsets_host);
+    const long long plane = (long long)pw * ph;
+    std::vector<LfdFreespaceCam> cams((size_t)n_refs);
+    for (int32_t r = 0; r < n_refs; ++r) lfd_freespace_cam(cam_P_host + 12 * (size_t)r, cam_wh_host[2 * r], cam_wh_host[2 * r + 1], cams[(size_t)r]);
+    std::vector<uint32_t> zbuf((size_t)n_refs * (size_t)plane, LFD_FREESPACE_EMPTY);
+    parallel_chunks(ctx, (int)n_refs, [&](int r) {                     // a reference writes its own plane only
+        uint32_t* z = zbuf.data() + (size_t)r * (size_t)plane;
+        for (long long i = offs[r]; i < offs[r + 1]; ++i) {
+            int cx, cy;
+            float d;
+            if (!lfd_freespace_project(cams[(size_t)r], (double)pw, (double)ph, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], cx, cy, d)) continue;
+            uint32_t bits;
+            std::memcpy(&bits, &d, 4);
+            uint32_t& cell = z[(size_t)cy * (size_t)pw + (size_t)cx];
+            cell = std::min(cell, bits);
+        }
+    });
+    const int n_chunks = (int)((n + kChunk - 1) / kChunk);
+    std::vector<uint8_t> keep((size_t)n);
+    parallel_chunks(ctx, n_chunks, [&](int c) {
+        const long long i1 = std::min<long long>(n, (long long)(c + 1) * kChunk);
+        for (long long i = (long long)c * kChunk; i < i1; ++i) {
+            const int own = lfd_support_ref_of(offs, n_refs, n, i);
+            int v, s;
+            lfd_freespace_count_point(cams.data(), zbuf.data(), n_refs, own, pw, ph, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], tol, v, s);
+            keep[(size_t)i] = lfd_freespace_keep(v, s, min_violations) ? 1 : 0;
+            if (violations) violations[i] = lfd_freespace_u8(v);
+            if (supports) supports[i] = lfd_freespace_u8(s);
+        }
+    });
+    // stable compaction: the input order inside and across references, every value copied as bytes
+    long long o = 0;
+    int r_next = 0;
+    for (long long i = 0; i <= n; ++i) {
+        while (r_next <= n_refs && offs[r_next] <= i) ref_offsets_out_host[r_next++] = o;
+        if (i == n) break;
+        if (!keep[(size_t)i]) continue;
+        std::memcpy(xyz_out + 3 * o, xyz + 3 * i, 12);
+        if (rgb) std::memcpy(rgb_out + 3 * o, rgb + 3 * i, 12);
+        if (err) std::memcpy(err_out + o, err + i, 4);
+        ++o;
+    }
+    *n_out_host = o;
     return LFD_OK;
 }
 

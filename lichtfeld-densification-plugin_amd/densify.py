@@ -9,6 +9,7 @@ per-reference hot path runs on the GPU.
 from __future__ import annotations
 
 import argparse
+import math
 import os
 from typing import Callable, Dict, List, Optional, Tuple
 
@@ -277,7 +278,88 @@ def _apply_consensus_filter(result, config: DensePipelineConfig, progress_callba
         loader, arrays = None, tuple(t.numpy() for t in new_pts)
     return PipelineResult(xyz=arrays[0], rgb=arrays[1], err=arrays[2], elapsed_seconds=result.elapsed_seconds, pairs_processed=result.pairs_processed,
                           pairs_matched=result.pairs_matched, points_per_reference=kept, device_points=new_pts, streamed_path=None,
-                          clock=result._clock, loader=loader, device_normals=normals)
+                          clock=result._clock, loader=loader, device_normals=normals, match_grid=result.match_grid)
+
+
+def freespace_plane(config: DensePipelineConfig, width: int, height: int, match_grid=None) -> Tuple[int, int]:
+    """(pw, ph) of the free-space filter's z-buffers for images of ``width`` x ``height``: experimental['freespace_plane_cells'] cells along the
+    longer side - 0: ceil(sqrt(matches_per_ref)) in sampled mode, the longer side of the matcher's grid (``match_grid`` = (H, W)) in dense
+    mode - and max(1, floor(cells * short / long + 0.5)) along the shorter."""
+    cells = int(config.exp("freespace_plane_cells"))
+    if cells == 0:
+        if config.triangulation_mode == "dense":
+            if match_grid is None:
+                raise RuntimeError("experimental['freespace_plane_cells'] = 0 takes the matcher's grid in dense mode, and this result does not record one")
+            cells = int(max(match_grid))
+        else:
+            cells = int(math.ceil(math.sqrt(max(1, int(config.matches_per_ref)))))
+    lng, sht = max(int(width), int(height)), min(int(width), int(height))
+    other = max(1, int(math.floor(cells * sht / lng + 0.5)))
+    return (cells, other) if int(width) >= int(height) else (other, cells)
+
+
+def _apply_freespace_filter(result, config: DensePipelineConfig, camera_records, refs_local, progress_callback=None):
+    """The free-space filter on the finished cloud (lfd_freespace_filter), where the points are, behind the consensus filter
+    and in front of the point cap and the voxel filter.  Entry i of ``result.points_per_reference`` is reference ``refs_local[i]``, whose
+    camera is ``camera_records[refs_local[i]]``.  Returns the result with the kept points (input order, same bits) and their per-reference
+    counts in place of the cloud.  Off (experimental['min_freespace_violations'] = 0): the result itself, nothing runs."""
+    min_v = int(config.exp("min_freespace_violations"))
+    if min_v <= 0 or result.streamed_path is not None:
+        return result
+    from .core import hip_backend as hb
+    from .core.sinks import PipelineResult
+    import torch
+    tol = float(config.exp("freespace_depth_tol_rel"))
+    pts = result.device_points
+    if pts is None:
+        pts = tuple(torch.from_numpy(np.ascontiguousarray(a)) for a in (result.xyz, result.rgb, result.err))
+    counts = np.asarray(result.points_per_reference, np.int64)
+    n_in = int(pts[0].shape[0])
+    if int(counts.sum()) != n_in or counts.size != len(refs_local):
+        raise RuntimeError(f"experimental['min_freespace_violations'] needs the whole cloud with its per-reference counts: this result holds {n_in:,} "
+                           f"points, the counts of {counts.size} of {len(refs_local)} references add up to {int(counts.sum()):,} (a rank of a "
+                           "gather_to_root run that is not the root)")
+    cams = [camera_records[int(r)] for r in refs_local]
+    cam_P = np.stack([np.asarray(c.P, np.float64).astype(np.float32).reshape(12) for c in cams])
+    cam_wh = np.array([[int(c.width), int(c.height)] for c in cams], np.int32)
+    plane = freespace_plane(config, cams[0].width, cams[0].height, result.match_grid)
+    if progress_callback:
+        progress_callback(93.0, "Applying free-space filter...")
+    on_gpu = bool(pts[0].is_cuda)
+    dens = hb.HipDensifier(pts[0].device) if on_gpu else hb.HostDensifier(int(config.exp("host_threads")))
+    normals = result.device_normals                  # experimental['estimate_normals']: the filter's keep decision applies to them as well
+    try:
+        xyz, rgb, err, kept, viol, supp = dens.freespace_filter(pts[0], pts[1], pts[2], counts, cam_P, cam_wh, plane, tol, min_v,
+                                                                with_counts=normals is not None)
+        if normals is not None:
+            # the compaction is the library's; its per-point counts give the rows it kept, and that is CHECKED, not assumed: the input
+            # positions under the mask must be the kept positions bit for bit before the mask is applied to the normals
+            keep = ~((viol >= min_v) & (viol > supp))
+            if int(keep.sum()) != int(xyz.shape[0]) or not torch.equal(pts[0][keep].view(torch.int32), xyz.view(torch.int32)):
+                raise RuntimeError("free-space filter: the per-point counts do not name the rows the filter kept; the normals cannot follow the points")
+            normals = normals[keep]
+    except hb.HipBackendError as exc:
+        raise RuntimeError(f"experimental['min_freespace_violations']: {exc}") from exc
+    finally:
+        dens.close()
+    n_kept = int(xyz.shape[0])
+    log.info(f"Free-space filter (tolerance {tol:g}, {min_v} refuting reference{'s' if min_v != 1 else ''}, planes of {plane[0]} x {plane[1]} cells): "
+             f"{n_in:,} points in, {n_kept:,} kept")
+    new_pts = (xyz, rgb, err)
+    if on_gpu:
+        clock = result._clock
+
+        def loader(p=new_pts, clk=clock):
+            if hasattr(clk, "stage"):
+                with clk.stage("d2h"):
+                    return tuple(t.cpu().numpy() for t in p)
+            return tuple(t.cpu().numpy() for t in p)
+        arrays = (None, None, None)
+    else:
+        loader, arrays = None, tuple(t.numpy() for t in new_pts)
+    return PipelineResult(xyz=arrays[0], rgb=arrays[1], err=arrays[2], elapsed_seconds=result.elapsed_seconds, pairs_processed=result.pairs_processed,
+                          pairs_matched=result.pairs_matched, points_per_reference=kept, device_points=new_pts, streamed_path=None,
+                          clock=result._clock, loader=loader, device_normals=normals, match_grid=result.match_grid)
 
 
 def _is_writer_rank() -> bool:
@@ -398,6 +480,7 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
             progress_callback(0.0, "Cancelled")
         return 2
     result = _apply_consensus_filter(result, config, progress_callback)      # (in front of the point cap: it has to see the whole cloud)
+    result = _apply_freespace_filter(result, config, records, refs_local, progress_callback)      # (behind it: what it removed cannot "see through" a surface)
     if progress_callback:
         progress_callback(95.0, "Writing output...")
     if result.streamed_path == config.output_path:      # config.stream_output: the file is already complete (and no cap applies to it)
@@ -450,6 +533,7 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
         return 2, "Cancelled"
     try:
         result = _apply_consensus_filter(result, config, progress_callback)  # (in front of the point cap and the voxel filter: it has to see the whole cloud)
+        result = _apply_freespace_filter(result, config, records, refs_local, progress_callback)   # (behind it, in front of cap and voxel filter)
     except RuntimeError as exc:
         return 1, str(exc)
     if result.streamed_path == config.output_path:      # config.stream_output: the PLY is complete; neither a cap nor a voxel filter applies to it
@@ -534,6 +618,12 @@ def _experimental_from_args(args) -> dict:
         exp["min_consensus_refs"] = int(args.min_consensus_refs)
     if float(getattr(args, "consensus_radius", 0.0)) != 0.0:
         exp["consensus_radius"] = float(args.consensus_radius)
+    if int(getattr(args, "min_freespace_violations", 0)) != 0:
+        exp["min_freespace_violations"] = int(args.min_freespace_violations)
+    if getattr(args, "freespace_depth_tol_rel", None) is not None:
+        exp["freespace_depth_tol_rel"] = float(args.freespace_depth_tol_rel)
+    if int(getattr(args, "freespace_plane_cells", 0)) != 0:
+        exp["freespace_plane_cells"] = int(args.freespace_plane_cells)
     if bool(getattr(args, "undistort_images", False)):
         exp["undistort_images"] = True
     if bool(getattr(args, "estimate_normals", False)):
@@ -600,6 +690,16 @@ def build_argparser() -> argparse.ArgumentParser:
                          "within --consensus_radius of it (1 .. 8; runs in front of --max_points; 0 = off)")
     ap.add_argument("--consensus_radius", type=float, default=0.0,
                     help="... within this distance in scene units (required > 0 with --min_consensus_refs)")
+    ap.add_argument("--min_freespace_violations", type=int, default=0,
+                    help="free-space filter on the final cloud: drop a point when at least this many OTHER references triangulated a surface behind it "
+                         "on the same ray (they looked through it) and more refute than confirm it (1 .. 255; runs behind --min_consensus_refs and "
+                         "in front of --max_points; 0 = off)")
+    ap.add_argument("--freespace_depth_tol_rel", type=float, default=None,
+                    help="... with this relative depth tolerance in (0, 1) (default 0.02; not below the depth noise you accept; needs "
+                         "--min_freespace_violations)")
+    ap.add_argument("--freespace_plane_cells", type=int, default=0,
+                    help="... on z-buffers of this many cells along the longer image side (8 .. 4096; 0 = automatic: ceil(sqrt(matches_per_ref)) in "
+                         "sampled mode, the matcher's grid in dense mode; needs --min_freespace_violations)")
     ap.add_argument("--undistort_images", action="store_true",
                     help="resample every image (and its mask) through its COLMAP camera's distortion model (SIMPLE_RADIAL, RADIAL, OPENCV, "
                          "FULL_OPENCV) into the pinhole image of the same intrinsics before it is matched; other distorted models are refused")
