@@ -553,6 +553,28 @@ int lfd_freespace_filter_host(lfd_context* ctx, const float* xyz, const float* r
                               int32_t min_violations, float* xyz_out, float* rgb_out, float* err_out, int64_t* ref_offsets_out_host,
                               uint8_t* violations, uint8_t* supports, int64_t* n_out_host);
 
+/* Oriented voxel fusion on the final cloud (no upstream counterpart): the merge step behind lfd_estimate_normals.  The points of a
+ * voxel are merged per SIDE their normals face, so an occupied voxel gives one oriented point per visible face: 1 or 2 rows.  Grid, keys, voxel
+ * order, colour scale and the two data refusals are lfd_voxel_downsample's, word for word.  xyz, normals, rgb: f32 [n][3] (csrc/lfd_fuse.hpp,
+ * every rounding written out, no FMA):
+ *   usable    a normal whose components are finite and, in f64, (n0 n0 + n1 n1) + n2 n2 > 0
+ *   pivot     of a voxel: the usable normal of its point with the lowest input index (a voxel may have none)
+ *   side      1 iff the normal is usable and d < 0, d = (n0 p0 + n1 p1) + n2 p2 in f64 (the products are exact); else 0.  Side 0 is never empty
+ *   per side  f64 sums from 0.0 over its points in ascending input index: xyz and rgb / s over all of them, N over the usable normals;
+ *             xyz_out, rgb_out = (f32)(sum / count); q = (N0 N0 + N1 N1) + N2 N2; normal = (f32)(N_c / sqrt(q)) if q is finite and > 0, else 0
+ *   rows      voxels in ascending (k0, k1, k2), side 0 before side 1: V .. 2 V rows for V occupied voxels, never more than n
+ * The pivot depends on the input order: one that is a gross outlier can split a voxel into two rows of similar normals (a density blip, not a wrong
+ * point).  xyz_out / normals_out / rgb_out hold n rows; count_out: NULL, or u32 [n], the points merged into each row.  *n_rows_host and
+ * *n_voxels_host are always written.  Synchronous, deterministic; the workspace belongs to the context and is reused.  On the device the normal's
+ * final division goes through a refined reciprocal: its components are within one f32 ulp of the twin's, everything else is equal bit for bit.
+ * LFD_ERR_INVALID: a null required pointer, n < 0 or > 2^31 - 1, voxel_size <= 0 or not finite, outputs that overlap inputs or each other, a
+ * "non-finite coordinate" in the input, a "key range" whose linear voxel key does not fit 63 bits (both decided before anything is sorted).
+ * n == 0 is valid.  lfd_fuse_oriented_host: the same over host pointers on a host context. */
+int lfd_fuse_oriented(lfd_context* ctx, const float* xyz, const float* normals, const float* rgb, int64_t n, double voxel_size, float* xyz_out,
+                      float* normals_out, float* rgb_out, uint32_t* count_out, int64_t* n_rows_host, int64_t* n_voxels_host);
+int lfd_fuse_oriented_host(lfd_context* ctx, const float* xyz, const float* normals, const float* rgb, int64_t n, double voxel_size, float* xyz_out,
+                           float* normals_out, float* rgb_out, uint32_t* count_out, int64_t* n_rows_host, int64_t* n_voxels_host);
+
 /* (e) multi-GPU exchange, placement step (no upstream counterpart - upstream has no multi-GPU code): n copies
  * dst[dst_offset .. +nbytes) = src[src_offset .. +nbytes) in ONE launch on `hip_stream` of device `device_index` (offsets and lengths in
  * bytes, no alignment required: 15-byte PLY records).  The overlapped exchange receives every rank's records of a round as one padded block
@@ -640,7 +662,7 @@ int lfd_host_eval_correspondence(const float* cam1, const float* cam2, float xa_
  * The per-cell arithmetic is the host build of the very source the kernels compile (csrc/lfd_geometry.hpp; IEEE
  * division / square root where the device uses the 1-ulp v_rcp / v_sqrt), spread over n_threads std::threads
  * (<= 0: all hardware threads).  A host context accepts lfd_upload_cameras, lfd_last_error, lfd_destroy and the
- * *_host calls (the three below, lfd_local_corr_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host, lfd_consensus_filter_host and lfd_freespace_filter_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
+ * *_host calls (the three below, lfd_local_corr_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host, lfd_consensus_filter_host, lfd_freespace_filter_host and lfd_fuse_oriented_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
  * context: neither side ever stands in for the other.  Semantics (orders, counts, optional outputs, LFD_ERR_CAPACITY
  * with valid counts) are those of lfd_aggregate / lfd_triangulate_dense / lfd_triangulate_indexed. */
 int lfd_create_host(int32_t n_threads, lfd_context** out);

@@ -46,6 +46,11 @@ class ConsensusInputRefused(HipBackendError):
     cell key leaves 63 bits - before sorting anything.  Nothing stands in for it: the caller reports the radius (densify.py does)."""
 
 
+class FuseInputRefused(HipBackendError):
+    """lfd_fuse_oriented refused its input - a non-finite coordinate, or a linear voxel key beyond 63 bits - before sorting anything.  Nothing
+    stands in for it: the caller reports the voxel size (densify.py does)."""
+
+
 class lfd_params(C.Structure):
     _fields_ = [("sampson_thresh", C.c_double), ("certainty_thresh", C.c_float), ("sample_cap", C.c_float),
                 ("reproj_thresh", C.c_float), ("min_parallax_deg", C.c_float), ("no_filter", C.c_int32),
@@ -205,6 +210,9 @@ def load_library() -> C.CDLL:
                                          C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.lfd_freespace_filter_host.argtypes = list(lib.lfd_freespace_filter.argtypes)
+    lib.lfd_fuse_oriented.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.lfd_fuse_oriented_host.argtypes = list(lib.lfd_fuse_oriented.argtypes)
     lib.lfd_copy_segments.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.lfd_launch_status.argtypes = [ctxp, C.POINTER(C.c_int32)]
     lib.lfd_get_pair_fundamental.argtypes = [ctxp, C.c_int32, C.POINTER(C.c_double)]
@@ -242,7 +250,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -1024,6 +1032,33 @@ def _consensus_call(fn, ctx, what, xyz, rgb, err, ref_counts, radius, min_refs, 
     return kept[0], kept[1], kept[2], np.diff(offs_out), (cons[:n] if with_consensus else None)
 
 
+def _fuse_call(fn, ctx, what, xyz, normals, rgb, voxel_size, with_counts, device, last_error):
+    """One lfd_fuse_oriented[_host] call.  ``xyz``, ``normals``, ``rgb``: (n, 3) float32 tensors on ``device``.  Returns
+    ``((xyz, normals, rgb[, counts]), n_voxels)``: the rows - views of n-row tensors, voxels in key order, side 0 before side 1 -, with
+    ``with_counts`` the int32 number of points merged into each row, and the number of occupied voxels.  Raises ``FuseInputRefused`` for a
+    non-finite coordinate or a voxel key range beyond 63 bits."""
+    n = int(xyz.shape[0])
+    tensors = []
+    for t, name in ((xyz, "xyz"), (normals, "normals"), (rgb, "rgb")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != device or t.dim() != 2 or t.shape[1] != 3 or int(t.shape[0]) != n:
+            raise ValueError(f"{what}: {name} must be a float32 tensor of {n} rows x 3 on {device}")
+        tensors.append(t.contiguous())
+    outs = [torch.empty((max(n, 1), 3), dtype=torch.float32, device=device) for _ in range(3)]
+    cnt = torch.empty((max(n, 1),), dtype=torch.int32, device=device) if with_counts else None
+    n_rows, n_vox = C.c_int64(0), C.c_int64(0)
+    ptr = lambda t: t.data_ptr() if t is not None and n > 0 else None       # noqa: E731  (an empty tensor may have no address at all)
+    rc = fn(ctx, ptr(tensors[0]), ptr(tensors[1]), ptr(tensors[2]), n, C.c_double(float(voxel_size)), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]),
+            ptr(cnt), C.byref(n_rows), C.byref(n_vox))
+    if rc != 0:
+        msg = last_error()
+        if "non-finite coordinate" in msg or "key range" in msg:
+            raise FuseInputRefused(f"{what} refused its input ({rc}): {msg}")
+        raise HipBackendError(f"{what} failed ({rc}): {msg}")
+    k = int(n_rows.value)
+    rows = tuple(o[:k] for o in outs)
+    return (rows + (cnt[:k],) if with_counts else rows), int(n_vox.value)
+
+
 def _freespace_call(fn, ctx, what, xyz, rgb, err, ref_counts, cam_P, cam_wh, plane, tol, min_violations, with_counts, device, last_error):
     """One lfd_freespace_filter[_host] call.  ``xyz`` (n, 3), ``rgb`` (n, 3) or None, ``err`` (n,) or None: float32 tensors on ``device``;
     ``ref_counts``: points per reference, in the order of the cloud; ``cam_P`` (n_refs, 3, 4) or (n_refs, 12) float32 and ``cam_wh`` (n_refs, 2)
@@ -1086,6 +1121,7 @@ class HipDensifier:
         if rc != 0:
             raise HipBackendError(f"lfd_create failed ({rc}): {self._lib.lfd_last_error(None).decode()}")
         self.n_cams = 0
+        self.fuse_voxels = 0           # occupied voxels of the last fuse_oriented call
 
     def close(self) -> None:
         if getattr(self, "_ctx", None) is not None and self._ctx.value:
@@ -1218,6 +1254,15 @@ class HipDensifier:
         ``_freespace_call`` describes.  Synchronous."""
         return _freespace_call(self._lib.lfd_freespace_filter, self._ctx, "lfd_freespace_filter", xyz, rgb, err, ref_counts, cam_P, cam_wh, plane, tol,
                                min_violations, with_counts, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
+
+    def fuse_oriented(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor, voxel_size: float, with_counts: bool = False):
+        """Oriented voxel fusion on the device (lfd_fuse_oriented): the points of every occupied voxel merged per side their
+        normals face - positions and colours averaged, normals summed and renormalised -, one row per visible face.  Returns
+        ``(xyz, normals, rgb)``, with ``with_counts`` also the points per row; ``self.fuse_voxels`` then holds the number of occupied voxels
+        of this call.  Synchronous.  Raises ``FuseInputRefused`` as ``_fuse_call`` describes."""
+        rows, self.fuse_voxels = _fuse_call(self._lib.lfd_fuse_oriented, self._ctx, "lfd_fuse_oriented", xyz, normals, rgb, voxel_size, with_counts,
+                                            self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
+        return rows
 
     def set_stream(self, stream: "torch.cuda.Stream") -> None:
         """Later calls are issued on ``stream`` (lfd_set_stream: what was issued on the previous one is waited for first).  A call with the
@@ -1662,6 +1707,7 @@ class HostDensifier:
         self.device = torch.device("cpu")
         self.n_threads = int(self._lib.lfd_host_threads(self._ctx))
         self.n_cams = 0
+        self.fuse_voxels = 0           # occupied voxels of the last fuse_oriented call
 
     close = HipDensifier.close
     __del__ = HipDensifier.__del__
@@ -1745,6 +1791,12 @@ class HostDensifier:
         """HipDensifier.freespace_filter over CPU tensors (lfd_freespace_filter_host): the same per-point routine, the same bits in every output."""
         return _freespace_call(self._lib.lfd_freespace_filter_host, self._ctx, "lfd_freespace_filter_host", xyz, rgb, err, ref_counts, cam_P, cam_wh,
                                plane, tol, min_violations, with_counts, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
+
+    def fuse_oriented(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor, voxel_size: float, with_counts: bool = False):
+        """HipDensifier.fuse_oriented over CPU tensors (lfd_fuse_oriented_host): the same rule, with IEEE sqrt and divide in the normals' last step."""
+        rows, self.fuse_voxels = _fuse_call(self._lib.lfd_fuse_oriented_host, self._ctx, "lfd_fuse_oriented_host", xyz, normals, rgb, voxel_size,
+                                            with_counts, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
+        return rows
 
     def aggregate(self, batch: PreparedBatch, params: lfd_params):
         self._same_device(batch)

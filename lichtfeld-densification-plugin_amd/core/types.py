@@ -107,6 +107,11 @@ EXPERIMENTAL_DEFAULTS = {
     # ... on z-buffer planes of this many cells along the longer image side, 8 .. 4096.  0 = automatic: ceil(sqrt(matches_per_ref)) in sampled
     # mode (about one emitted point per cell), the longer side of the matcher's grid in dense mode.
     "freespace_plane_cells": 0,
+    # oriented voxel fusion on the final cloud (lfd_fuse_oriented): the points of every occupied voxel of this size - scene
+    # units, the unit of voxel_size - are merged per side their normals face: positions and colours averaged, normals summed and renormalised,
+    # one oriented point per visible face of the voxel (the two faces of a thin wall stay two points).  Needs estimate_normals.  Runs once,
+    # behind the consensus filter, the free-space filter and the point cap, in front of packing.  0 = off: no new code runs.
+    "fuse_voxel_size": 0.0,
 }
 CONSENSUS_CAP = 8            # LFD_CONSENSUS_CAP of include/lfd_densify.h
 
@@ -396,6 +401,13 @@ class DensePipelineConfig:
                         "do to their normals is not defined")
             if not str(self.output_path).lower().endswith(".ply"):
                 return "experimental['estimate_normals'] writes the normals as PLY vertex properties: output_path must end in .ply"
+        h_fuse = self.exp("fuse_voxel_size")
+        if isinstance(h_fuse, (bool, np.bool_)) or not isinstance(h_fuse, (int, float, np.integer, np.floating)):
+            return "experimental['fuse_voxel_size'] must be a number (scene units, the unit of voxel_size; 0 = off)"
+        if not (0.0 <= float(h_fuse) < float("inf")):
+            return "experimental['fuse_voxel_size'] must be finite and >= 0 (scene units, the unit of voxel_size; 0 = off)"
+        if float(h_fuse) > 0.0 and not normals:
+            return "experimental['fuse_voxel_size'] merges points by the side their normals face: it needs experimental['estimate_normals'] = True"
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):
                 return "stream_output writes a PLY while the run proceeds: output_path must end in .ply"

@@ -23,6 +23,7 @@
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
 #include "lfd_freespace.hpp"
+#include "lfd_fuse.hpp"
 
 extern "C" __global__ void lfd_aggregate_kernel(LfdLaunch L, float* best_cert, uint8_t* best_slot);
 extern "C" __global__ void lfd_dense_kernel(LfdLaunch L);
@@ -78,6 +79,19 @@ extern "C" __global__ void lfd_consensus_wgcount_kernel(const uint8_t* keep, lon
 extern "C" __global__ void lfd_consensus_offsets_kernel(const long long* offs, int n_refs, const uint8_t* keep, const unsigned* wg_kept, long long* offs_out);
 extern "C" __global__ void lfd_consensus_scatter_kernel(const float* xyz, const float* rgb, const float* err, long long n, const uint8_t* keep,
                                                         const unsigned* wg_kept, float* o_xyz, float* o_rgb, float* o_err);
+extern "C" __global__ void lfd_fuse_side_kernel(const float* normals, long long n, const unsigned* sorted_idx, const unsigned* vstart, const unsigned* nv_p,
+                                                uint8_t* flag, unsigned* rows, unsigned* big, unsigned* n_big);
+extern "C" __global__ void lfd_fuse_side_big_kernel(const float* normals, long long n, const unsigned* sorted_idx, const unsigned* vstart, const unsigned* nv_p,
+                                                    const unsigned* big, const unsigned* n_big, uint8_t* flag, unsigned* rows);
+extern "C" __global__ void lfd_fuse_rowsum_kernel(const unsigned* rows, const unsigned* nv_p, long long chunk, unsigned* counts);
+extern "C" __global__ void lfd_fuse_rowstart_kernel(unsigned* rows, const unsigned* nv_p, long long chunk, const unsigned* counts);
+extern "C" __global__ void lfd_fuse_sums_kernel(const float* xyz, const float* normals, const float* rgb, long long n, const unsigned* sorted_idx,
+                                                const unsigned* vstart, const unsigned* nv_p, const uint8_t* flag, const unsigned* rowstart, double cscale,
+                                                float* xyz_out, float* normals_out, float* rgb_out, unsigned* count_out);
+extern "C" __global__ void lfd_fuse_sums_big_kernel(const float* xyz, const float* normals, const float* rgb, long long n, const unsigned* sorted_idx,
+                                                    const unsigned* vstart, const unsigned* nv_p, const uint8_t* flag, const unsigned* rowstart, double cscale,
+                                                    const unsigned* big, const unsigned* n_big, float* xyz_out, float* normals_out, float* rgb_out,
+                                                    unsigned* count_out);
 extern "C" __global__ void lfd_freespace_fill_kernel(uint32_t* zbuf, long long n_words);
 extern "C" __global__ void lfd_freespace_splat_kernel(const float* xyz, long long n, const long long* offs, int n_refs, const LfdFreespaceCam* cams, int pw,
                                                       int ph, uint32_t* zbuf);
@@ -565,7 +579,7 @@ void lfd_destroy(lfd_context* ctx) {
     }
     for (hipEvent_t ev : ctx->kt_start) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->kt_stop) (void)hipEventDestroy(ev);
-    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->vox, &ctx->support_ws, &ctx->prec_tab, &ctx->consensus_ws, &ctx->undist_cnt, &ctx->freespace_ws})
+    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->vox, &ctx->support_ws, &ctx->prec_tab, &ctx->consensus_ws, &ctx->undist_cnt, &ctx->freespace_ws, &ctx->fuse_ws})
         if (b->ptr) (void)hipFree(b->ptr);
     if (ctx->pinned_words) (void)hipHostFree(ctx->pinned_words);
     if (ctx->prec_pinned) (void)hipHostFree(ctx->prec_pinned);
@@ -1589,6 +1603,92 @@ int lfd_freespace_filter(lfd_context* ctx, const float* xyz, const float* rgb, c
     LFD_HIP(ctx, hipMemcpyAsync(ref_offsets_out_host, offs_out, offs_bytes, hipMemcpyDeviceToHost, st));
     LFD_HIP(ctx, hipStreamSynchronize(st));
     *n_out_host = ref_offsets_out_host[n_refs];
+    return LFD_OK;
+}
+
+// ---- oriented voxel fusion on the final cloud (lfd_fuse.hip; the grid and the sort are lfd_voxel.hip's kernels) ------------------------------------
+int lfd_fuse_oriented(lfd_context* ctx, const float* xyz, const float* normals, const float* rgb, int64_t n, double voxel_size, float* xyz_out,
+                      float* normals_out, float* rgb_out, uint32_t* count_out, int64_t* n_rows_host, int64_t* n_voxels_host) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_fuse_check(xyz, normals, rgb, n, voxel_size, xyz_out, normals_out, rgb_out, count_out, n_rows_host, n_voxels_host))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_fuse_oriented: ") + why);
+    *n_rows_host = 0;
+    *n_voxels_host = 0;
+    if (n == 0) return LFD_OK;
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // radix passes: workgroup b of G owns the items [b * chunk, (b + 1) * chunk); chunk is a multiple of the scatter's 512-item round
+    long long G = std::min<long long>(1024, (n + 4095) / 4096);
+    const long long chunk = (((n + G - 1) / G) + 511) / 512 * 512;
+    G = (n + chunk - 1) / chunk;                                       // (the voxels, at most n, are cut into the same chunks for the row scan)
+    const int n_part = (int)std::min<long long>(1024, (n + 255) / 256);
+    // workspace: partials | stats, voxel count, big-voxel count, row count | digit counts | keys x 2 | indices x 2 | voxel starts | rows |
+    // big-voxel list | flag bytes
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t o_part = 0, o_small = al(o_part + 1024 * sizeof(LfdVoxStats)), o_counts = al(o_small + sizeof(LfdVoxStats) + 12);
+    const size_t o_ka = al(o_counts + 256 * 1024 * sizeof(unsigned)), o_kb = al(o_ka + 8 * (size_t)n), o_ia = al(o_kb + 8 * (size_t)n);
+    const size_t o_ib = al(o_ia + 4 * (size_t)n), o_vs = al(o_ib + 4 * (size_t)n), o_rows = al(o_vs + 4 * (size_t)n);
+    const size_t o_big = al(o_rows + 4 * (size_t)n), o_flag = al(o_big + 4 * ((size_t)n / (LFD_VOX_BIG + 1) + 1));
+    const size_t total = al(o_flag + (size_t)n);
+    if (int rc = ensure(ctx, ctx->fuse_ws, total)) return rc;
+    unsigned char* w = static_cast<unsigned char*>(ctx->fuse_ws.ptr);
+    LfdVoxStats* part = reinterpret_cast<LfdVoxStats*>(w + o_part);
+    LfdVoxStats* stats = reinterpret_cast<LfdVoxStats*>(w + o_small);
+    unsigned* nv_dev = reinterpret_cast<unsigned*>(w + o_small + sizeof(LfdVoxStats));
+    unsigned* n_big = nv_dev + 1;
+    unsigned* n_rows_dev = nv_dev + 2;
+    unsigned* counts = reinterpret_cast<unsigned*>(w + o_counts);
+    unsigned long long* keys[2] = {reinterpret_cast<unsigned long long*>(w + o_ka), reinterpret_cast<unsigned long long*>(w + o_kb)};
+    unsigned* idx[2] = {reinterpret_cast<unsigned*>(w + o_ia), reinterpret_cast<unsigned*>(w + o_ib)};
+    unsigned* vstart = reinterpret_cast<unsigned*>(w + o_vs);
+    unsigned* rows = reinterpret_cast<unsigned*>(w + o_rows);
+    unsigned* big = reinterpret_cast<unsigned*>(w + o_big);
+    uint8_t* flag = w + o_flag;
+
+    // min / max pass; the refusals are decided before anything is sorted
+    hipLaunchKernelGGL(lfd_voxel_minmax_kernel, dim3(n_part), dim3(256), 0, st, xyz, rgb, (long long)n, part);
+    hipLaunchKernelGGL(lfd_voxel_final_kernel, dim3(1), dim3(256), 0, st, part, n_part, stats);
+    LFD_HIP(ctx, hipGetLastError());
+    LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, stats, sizeof(LfdVoxStats), hipMemcpyDeviceToHost, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));
+    LfdVoxStats s;
+    std::memcpy(&s, ctx->pinned_words, sizeof(s));
+    if (s.flags & LFD_VOX_NONFINITE) return fail(ctx, LFD_ERR_INVALID, "lfd_fuse_oriented: " LFD_FUSE_NONFINITE);
+    LfdFuseGrid g;
+    if (!lfd_fuse_grid(s.lo, s.hi, voxel_size, g)) return fail(ctx, LFD_ERR_INVALID, "lfd_fuse_oriented: " LFD_FUSE_KEY_RANGE);
+    const double cscale = lfd_fuse_cscale(s.cmax, (s.flags & LFD_VOX_NAN_RGB) != 0u);
+
+    const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(lfd_voxel_keys_kernel, dim3(grid), dim3(256), 0, st, xyz, (long long)n, g.origin[0], g.origin[1], g.origin[2], voxel_size, g.e[1],
+                       g.e[2], keys[0], idx[0]);
+    int cur = 0;
+    for (int shift = 0; shift < g.bits; shift += 8, cur ^= 1) {
+        hipLaunchKernelGGL(lfd_voxel_hist_kernel, dim3((unsigned)G), dim3(256), 0, st, keys[cur], (long long)n, chunk, shift, counts);
+        hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, counts, (int)(256 * G), (unsigned*)nullptr);
+        hipLaunchKernelGGL(lfd_voxel_scatter_kernel, dim3((unsigned)G), dim3(512), 0, st, keys[cur], idx[cur], (long long)n, chunk, shift, counts,
+                           keys[cur ^ 1], idx[cur ^ 1]);
+    }
+    hipLaunchKernelGGL(lfd_voxel_head_count_kernel, dim3((unsigned)G), dim3(256), 0, st, keys[cur], (long long)n, chunk, counts);
+    hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, counts, (int)G, nv_dev);
+    hipLaunchKernelGGL(lfd_voxel_head_scatter_kernel, dim3((unsigned)G), dim3(512), 0, st, keys[cur], (long long)n, chunk, counts, vstart);
+    // sides and rows, then the first row of every voxel, then the sums
+    LFD_HIP(ctx, hipMemsetAsync(n_big, 0, sizeof(unsigned), st));
+    const unsigned big_grid = (unsigned)std::min<long long>(n / (LFD_VOX_BIG + 1) + 1, 8192);
+    hipLaunchKernelGGL(lfd_fuse_side_kernel, dim3(grid), dim3(256), 0, st, normals, (long long)n, idx[cur], vstart, nv_dev, flag, rows, big, n_big);
+    hipLaunchKernelGGL(lfd_fuse_side_big_kernel, dim3(big_grid), dim3(64), 0, st, normals, (long long)n, idx[cur], vstart, nv_dev, big, n_big, flag, rows);
+    hipLaunchKernelGGL(lfd_fuse_rowsum_kernel, dim3((unsigned)G), dim3(256), 0, st, rows, nv_dev, chunk, counts);
+    hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, counts, (int)G, n_rows_dev);
+    hipLaunchKernelGGL(lfd_fuse_rowstart_kernel, dim3((unsigned)G), dim3(256), 0, st, rows, nv_dev, chunk, counts);
+    hipLaunchKernelGGL(lfd_fuse_sums_kernel, dim3(grid), dim3(256), 0, st, xyz, normals, rgb, (long long)n, idx[cur], vstart, nv_dev, flag, rows, cscale,
+                       xyz_out, normals_out, rgb_out, count_out);
+    hipLaunchKernelGGL(lfd_fuse_sums_big_kernel, dim3(big_grid), dim3(64), 0, st, xyz, normals, rgb, (long long)n, idx[cur], vstart, nv_dev, flag, rows,
+                       cscale, big, n_big, xyz_out, normals_out, rgb_out, count_out);
+    LFD_HIP(ctx, hipGetLastError());
+    LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, nv_dev, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));
+    *n_voxels_host = (int64_t)(unsigned)ctx->pinned_words[0];
+    *n_rows_host = (int64_t)(unsigned)ctx->pinned_words[2];
     return LFD_OK;
 }
 

@@ -26,6 +26,7 @@
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
 #include "lfd_freespace.hpp"
+#include "lfd_fuse.hpp"
 
 void lfd_fill_kernel_params(const lfd_batch* b, const lfd_params* p, LfdKernelParams& kp);   // lfd_api.hip
 
@@ -803,6 +804,65 @@ int lfd_freespace_filter_host(lfd_context* ctx, const float* xyz, const float* r
         ++o;
     }
     *n_out_host = o;
+    return LFD_OK;
+}
+
+// The twin of lfd_fuse_oriented: lfd_voxel_downsample's grid and keys, a sort of (key, index) pairs - the order of a stable sort by
+// key -, then a serial walk over the voxels with lfd_fuse.hpp's routines: the flag of every point, the two sides' sums in input order, the rows.
+int lfd_fuse_oriented_host(lfd_context* ctx, const float* xyz, const float* normals, const float* rgb, int64_t n, double voxel_size, float* xyz_out,
+                           float* normals_out, float* rgb_out, uint32_t* count_out, int64_t* n_rows_host, int64_t* n_voxels_host) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    if (const char* why = lfd_fuse_check(xyz, normals, rgb, n, voxel_size, xyz_out, normals_out, rgb_out, count_out, n_rows_host, n_voxels_host))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_fuse_oriented_host: ") + why);
+    *n_rows_host = 0;
+    *n_voxels_host = 0;
+    if (n == 0) return LFD_OK;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, cmax = -INFINITY;
+    bool nonfinite = false, nan_rgb = false;
+    for (long long i = 0; i < 3 * (long long)n; ++i) {
+        const int c = (int)(i % 3);
+        if (std::isfinite(xyz[i])) { lo[c] = std::min(lo[c], xyz[i]); hi[c] = std::max(hi[c], xyz[i]); }
+        else nonfinite = true;
+        if (std::isnan(rgb[i])) nan_rgb = true;
+        else cmax = std::max(cmax, rgb[i]);
+    }
+    if (nonfinite) return lfd_fail(ctx, LFD_ERR_INVALID, "lfd_fuse_oriented_host: " LFD_FUSE_NONFINITE);
+    LfdFuseGrid g;
+    if (!lfd_fuse_grid(lo, hi, voxel_size, g)) return lfd_fail(ctx, LFD_ERR_INVALID, "lfd_fuse_oriented_host: " LFD_FUSE_KEY_RANGE);
+    const double cscale = lfd_fuse_cscale(cmax, nan_rgb);
+    std::vector<std::pair<unsigned long long, unsigned>> order((size_t)n);
+    for (long long i = 0; i < n; ++i)
+        order[(size_t)i] = {lfd_fuse_key(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], g.origin[0], g.origin[1], g.origin[2], voxel_size, g.e[1], g.e[2]),
+                            (unsigned)i};
+    std::sort(order.begin(), order.end());
+    long long r = 0, nv = 0;
+    for (long long a = 0; a < n;) {
+        long long b = a + 1;
+        while (b < n && order[(size_t)b].first == order[(size_t)a].first) ++b;
+        LfdFuseAcc side[2];
+        lfd_fuse_clear(side[0]);
+        lfd_fuse_clear(side[1]);
+        float piv[3] = {0.0f, 0.0f, 0.0f};
+        bool has = false;
+        for (long long j = a; j < b; ++j) {
+            const long long i = order[(size_t)j].second;
+            const float* nn = normals + 3 * i;
+            const unsigned f = lfd_fuse_flag(nn, has, piv);
+            if (!has && (f & LFD_FUSE_USABLE)) { has = true; piv[0] = nn[0]; piv[1] = nn[1]; piv[2] = nn[2]; }
+            lfd_fuse_add(side[f & LFD_FUSE_SIDE], xyz + 3 * i, nn, rgb + 3 * i, (f & LFD_FUSE_USABLE) != 0u, cscale);
+        }
+        for (int s = 0; s < 2; ++s) {
+            if (!side[s].cnt) continue;
+            lfd_fuse_emit(side[s], xyz_out + 3 * r, normals_out + 3 * r, rgb_out + 3 * r);
+            if (count_out) count_out[r] = side[s].cnt;
+            ++r;
+        }
+        ++nv;
+        a = b;
+    }
+    *n_rows_host = r;
+    *n_voxels_host = nv;
     return LFD_OK;
 }
 

@@ -171,7 +171,7 @@ def _cap_normals(normals, n_before: int, max_points: int, seed: int):
     return _take_rows(normals, _cap_index(n_before, max_points, seed))
 
 
-def _finish_on_device(result, path: str, max_points: int, seed: int, clock=None) -> Optional[int]:
+def _finish_on_device(result, path: str, max_points: int, seed: int, clock=None, config=None, progress_callback=None) -> Optional[int]:
     """Point cap + output file for a result whose points are still on the GPU, without ever bringing the f32 cloud to the host: the same subset
     ``_apply_point_cap`` picks (the same generator, the same call), applied to the device tensors, then the file payload packed on the device
     (``_write_output``).  Returns the number of points written, or None when the result is not on a GPU (the host path applies)."""
@@ -180,6 +180,9 @@ def _finish_on_device(result, path: str, max_points: int, seed: int, clock=None)
         return None
     normals = _cap_normals(result.device_normals, int(pts[0].shape[0]), max_points, seed)
     pts = _cap_device_points(pts, int(pts[0].shape[0]), max_points, seed)
+    if config is not None and float(config.exp("fuse_voxel_size")) > 0.0:      # (behind the cap, in front of packing)
+        xyz, normals, rgb = _apply_oriented_fusion(config, pts[0], normals, pts[1], progress_callback)
+        pts = (xyz, rgb)
     n = int(pts[0].shape[0])
     _write_output(path, np.empty((n, 0), np.float32), None, None, pts, clock=clock, normals=normals)
     return n
@@ -362,6 +365,40 @@ def _apply_freespace_filter(result, config: DensePipelineConfig, camera_records,
                           clock=result._clock, loader=loader, device_normals=normals, match_grid=result.match_grid)
 
 
+class OrientedFusionRefused(RuntimeError):
+    """experimental['fuse_voxel_size']: the library refused the cloud (a non-finite coordinate, a voxel key range beyond 63 bits)."""
+
+
+def _apply_oriented_fusion(config: DensePipelineConfig, xyz, normals, rgb, progress_callback=None):
+    """Oriented voxel fusion of the capped cloud (lfd_fuse_oriented), where the points are: device tensors through the device
+    call, host arrays (``backend='host'``) through the twin.  Returns ``(xyz, normals, rgb)`` of the fused rows, of the kind that came in
+    (tensors on the device, NumPy arrays on the host).  The caller has checked that experimental['fuse_voxel_size'] is > 0."""
+    from .core import hip_backend as hb
+    import torch
+    h = float(config.exp("fuse_voxel_size"))
+    if normals is None:
+        raise RuntimeError("experimental['fuse_voxel_size'] needs the normals of experimental['estimate_normals']; this result carries none")
+    on_gpu = isinstance(xyz, torch.Tensor) and bool(xyz.is_cuda)
+    as_tensor = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))      # noqa: E731
+    t = tuple(as_tensor(a) for a in (xyz, normals, rgb))
+    if not on_gpu:
+        t = tuple(a.cpu() for a in t)
+    if progress_callback:
+        progress_callback(94.0, "Fusing oriented points...")
+    n_in = int(t[0].shape[0])
+    dens = hb.HipDensifier(t[0].device) if on_gpu else hb.HostDensifier(int(config.exp("host_threads")))
+    try:
+        rows = dens.fuse_oriented(t[0], t[1], t[2], h)
+        n_vox = int(dens.fuse_voxels)
+    except hb.FuseInputRefused as exc:
+        raise OrientedFusionRefused(f"experimental['fuse_voxel_size'] = {h:g} cannot be applied to this cloud: {exc}") from exc
+    finally:
+        dens.close()
+    n_rows = int(rows[0].shape[0])
+    log.info(f"Oriented fusion ({h:.4f}): {n_in:,} points in, {n_rows:,} rows out, {n_vox:,} voxels, {n_rows - n_vox:,} two-sided")
+    return rows if on_gpu else tuple(r.numpy() for r in rows)
+
+
 def _is_writer_rank() -> bool:
     """True unless this process is a non-zero rank of an initialised torch.distributed job."""
     try:
@@ -486,10 +523,14 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
     if result.streamed_path == config.output_path:      # config.stream_output: the file is already complete (and no cap applies to it)
         n_points = result.n_points
     else:
-        n_points = _finish_on_device(result, config.output_path, args.max_points, args.seed, clock=pipeline_kwargs.get("stage_clock"))
+        n_points = _finish_on_device(result, config.output_path, args.max_points, args.seed, clock=pipeline_kwargs.get("stage_clock"), config=config,
+                                     progress_callback=progress_callback)
         if n_points is None:
             normals = _cap_normals(result.normals, int(result.xyz.shape[0]), args.max_points, args.seed)
             xyz, rgb, err = _apply_point_cap(result.xyz, result.rgb, result.err, args.max_points, args.seed)
+            if float(config.exp("fuse_voxel_size")) > 0.0:
+                xyz, normals, rgb = _apply_oriented_fusion(config, xyz, normals, rgb, progress_callback)
+                err = None
             _write_output(config.output_path, xyz, rgb, err, None, normals=normals)
             n_points = int(xyz.shape[0])
     log.info(f"Dense reconstruction finished: {n_points:,} points -> {config.output_path}")
@@ -547,7 +588,11 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
         # nothing has to see the cloud on the host: the cap is applied and the file payload packed where the points are
         if progress_callback:
             progress_callback(95.0, "Writing output PLY...")
-        n_written = _finish_on_device(result, config.output_path, config.max_points, config.seed, clock=pipeline_kwargs.get("stage_clock"))
+        try:
+            n_written = _finish_on_device(result, config.output_path, config.max_points, config.seed, clock=pipeline_kwargs.get("stage_clock"),
+                                          config=config, progress_callback=progress_callback)
+        except OrientedFusionRefused as exc:
+            return 1, str(exc)
         log.info(f"Dense point cloud saved to {config.output_path} ({n_written:,} points)")
         if progress_callback:
             progress_callback(100.0, f"Done! {n_written:,} points")
@@ -574,6 +619,12 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
     normals = _cap_normals(result.normals, int(result.xyz.shape[0]), config.max_points, config.seed)      # (None without experimental['estimate_normals'])
     xyz, rgb, err = _apply_point_cap(result.xyz, result.rgb, result.err, config.max_points, config.seed)
     dev_pts = _cap_device_points(result.device_points, result.xyz.shape[0], config.max_points, config.seed)
+    if float(config.exp("fuse_voxel_size")) > 0.0:         # (needs estimate_normals, which rules the voxel filter out)
+        try:
+            xyz, normals, rgb = _apply_oriented_fusion(config, xyz, normals, rgb, progress_callback)
+        except OrientedFusionRefused as exc:
+            return 1, str(exc)
+        err = None
     if config.voxel_size > 0.0:
         if progress_callback and not announced:
             progress_callback(93.0, "Applying distance filter...")
@@ -632,6 +683,8 @@ def _experimental_from_args(args) -> dict:
         exp["normal_radius_cells"] = int(args.normal_radius_cells)
     if getattr(args, "normal_depth_step_rel", None) is not None:
         exp["normal_depth_step_rel"] = float(args.normal_depth_step_rel)
+    if float(getattr(args, "fuse_voxel_size", 0.0)) != 0.0:
+        exp["fuse_voxel_size"] = float(args.fuse_voxel_size)
     return exp
 
 
@@ -711,6 +764,10 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--normal_depth_step_rel", type=float, default=None,
                     help="... leaving out window cells whose depth differs from the point's by more than this fraction of it (> 0; default 0.05; "
                          "needs --estimate_normals)")
+    ap.add_argument("--fuse_voxel_size", type=float, default=0.0,
+                    help="oriented voxel fusion of the final cloud: merge the points of every voxel of this size (scene units) per side their normals "
+                         "face - one oriented point per visible face of a voxel; runs behind the filters and --max_points (needs "
+                         "--estimate_normals; 0 = off)")
     ap.add_argument("--keep_threads", action="store_true",
                     help="leave torch's intra-op thread count alone (by default it is lowered to the container's CPU quota; the count decides the last "
                          "bits of upstream's sampling normaliser, so a run compared bit for bit with upstream keeps upstream's setting)")
