@@ -575,6 +575,40 @@ int lfd_fuse_oriented(lfd_context* ctx, const float* xyz, const float* normals, 
 int lfd_fuse_oriented_host(lfd_context* ctx, const float* xyz, const float* normals, const float* rgb, int64_t n, double voxel_size, float* xyz_out,
                            float* normals_out, float* rgb_out, uint32_t* count_out, int64_t* n_rows_host, int64_t* n_voxels_host);
 
+/* Gaussian-ready output (no upstream counterpart): what a 3DGS trainer computes from a point file before it can start, computed where
+ * the cloud is.  lfd_knn_dist2: the mean squared distance of every point to its three nearest neighbours (distCUDA2 of the 3DGS code), EXACT.
+ * xyz: f32 [n][3]; dist2_out: f32 [n] (csrc/lfd_knn.hpp, every rounding written out, no FMA):
+ *   d2(i, j)   = (dx dx + dy dy) + dz dz in f32 for i != j, taken by INDEX: a duplicate of a point counts with distance 0
+ *   dist2[i]   = ((a + b) + c) / 3.0f, a <= b <= c the three smallest d2(i, .), in f32.  Only values enter: ties need no rule
+ * The output does not depend on the grid: it equals the brute-force evaluation over all pairs bit for bit, for every cell size, on device and twin.
+ * No search cap changes a result: an isolated point gets its true three neighbours.  cell_size: the side of the search grid's cells in scene
+ * units, 0 = automatic (from 2 L / ceil(sqrt(n)), L the longest side of the bounding box, divided by 4 while points / occupied cells > 16, at
+ * most 8 times and inside the key limits; computed on the host in f64, the same on device and twin); it changes the time a call takes, nothing
+ * else.  stats_host: NULL, or f64 [4] = {cell size used, occupied cells, points in the fullest cell, points finished by the brute-force pass}.
+ * Synchronous, deterministic; the workspace belongs to the context and is reused.
+ * LFD_ERR_INVALID: a null required pointer, n < 0 or > 2^31 - 1, cell_size negative or not finite, dist2_out overlapping xyz, "fewer than four
+ * points" for 1 <= n <= 3, a "non-finite coordinate" in the input, a "key range" with more than 2^30 cells along an axis or a linear cell key
+ * beyond 63 bits (the last three decided before anything is sorted).  n == 0 is valid.  lfd_knn_dist2_host: the same over host pointers on a host
+ * context.
+ *
+ * lfd_pack_gaussians: out[n*68] = per point 17 f32 LE in the property order of a 3DGS point_cloud.ply at SH degree 0:
+ *   x y z nx ny nz   copied bit for bit (normals: lfd_estimate_normals' / lfd_fuse_oriented's f32 [n][3])
+ *   f_dc_0..2        (q / 255.0f - 0.5f) / 0.28209479177387814f in f32, q the u8 lfd_pack_ply_normals stores for the colour
+ *   opacity          opacity_logit as given (the f32 logit of the initial opacity)
+ *   scale_0, scale_1 (f32)(0.5 log((f64) m)), m = max(dist2, 1e-7f), then min(m, (f32) max_scale^2) if max_scale > 0
+ *   scale_2          (f32)(0.5 log((f64) m) + log_flatten), log_flatten = log(flatten) <= 0: thinner along the normal
+ *   rot_0..3         (w, x, y, z) of the shortest arc from +z onto the normal: (1 + nz, -ny, nx, 0) normalised in f32 (IEEE sqrt and divide);
+ *                    (0, 1, 0, 0) where 1 + nz < 2^-23; the identity (1, 0, 0, 0) for a normal that is zero or not finite
+ * The device's log is its math library's and its division may not be correctly rounded: the three scales and the four rot values are within one
+ * f32 ulp of the twin's, every other column is equal bit for bit.  out must be 4-byte aligned.  Asynchronous on the context's stream.
+ * lfd_pack_gaussians_host: the same over host pointers on a host context (synchronous). */
+int lfd_knn_dist2(lfd_context* ctx, const float* xyz, int64_t n, double cell_size, float* dist2_out, double* stats_host);
+int lfd_knn_dist2_host(lfd_context* ctx, const float* xyz, int64_t n, double cell_size, float* dist2_out, double* stats_host);
+int lfd_pack_gaussians(lfd_context* ctx, const float* xyz, const float* normals, const float* rgb, const float* dist2, int64_t n, float opacity_logit,
+                       double log_flatten, double max_scale, uint8_t* out);
+int lfd_pack_gaussians_host(lfd_context* ctx, const float* xyz, const float* normals, const float* rgb, const float* dist2, int64_t n,
+                            float opacity_logit, double log_flatten, double max_scale, uint8_t* out);
+
 /* (e) multi-GPU exchange, placement step (no upstream counterpart - upstream has no multi-GPU code): n copies
  * dst[dst_offset .. +nbytes) = src[src_offset .. +nbytes) in ONE launch on `hip_stream` of device `device_index` (offsets and lengths in
  * bytes, no alignment required: 15-byte PLY records).  The overlapped exchange receives every rank's records of a round as one padded block
@@ -662,7 +696,7 @@ int lfd_host_eval_correspondence(const float* cam1, const float* cam2, float xa_
  * The per-cell arithmetic is the host build of the very source the kernels compile (csrc/lfd_geometry.hpp; IEEE
  * division / square root where the device uses the 1-ulp v_rcp / v_sqrt), spread over n_threads std::threads
  * (<= 0: all hardware threads).  A host context accepts lfd_upload_cameras, lfd_last_error, lfd_destroy and the
- * *_host calls (the three below, lfd_local_corr_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host, lfd_consensus_filter_host, lfd_freespace_filter_host and lfd_fuse_oriented_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
+ * *_host calls (the three below, lfd_local_corr_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host, lfd_consensus_filter_host, lfd_freespace_filter_host, lfd_fuse_oriented_host, lfd_knn_dist2_host and lfd_pack_gaussians_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
  * context: neither side ever stands in for the other.  Semantics (orders, counts, optional outputs, LFD_ERR_CAPACITY
  * with valid counts) are those of lfd_aggregate / lfd_triangulate_dense / lfd_triangulate_indexed. */
 int lfd_create_host(int32_t n_threads, lfd_context** out);

@@ -51,6 +51,11 @@ class FuseInputRefused(HipBackendError):
     stands in for it: the caller reports the voxel size (densify.py does)."""
 
 
+class KnnInputRefused(HipBackendError):
+    """lfd_knn_dist2 refused the cloud - fewer than four points, a non-finite coordinate, or a cell key range beyond the grid's limits - before
+    sorting anything.  Nothing was written."""
+
+
 class lfd_params(C.Structure):
     _fields_ = [("sampson_thresh", C.c_double), ("certainty_thresh", C.c_float), ("sample_cap", C.c_float),
                 ("reproj_thresh", C.c_float), ("min_parallax_deg", C.c_float), ("no_filter", C.c_int32),
@@ -213,6 +218,10 @@ def load_library() -> C.CDLL:
     lib.lfd_fuse_oriented.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.lfd_fuse_oriented_host.argtypes = list(lib.lfd_fuse_oriented.argtypes)
+    lib.lfd_knn_dist2.argtypes = [ctxp, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.POINTER(C.c_double)]
+    lib.lfd_knn_dist2_host.argtypes = list(lib.lfd_knn_dist2.argtypes)
+    lib.lfd_pack_gaussians.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_double, C.c_double, C.c_void_p]
+    lib.lfd_pack_gaussians_host.argtypes = list(lib.lfd_pack_gaussians.argtypes)
     lib.lfd_copy_segments.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.lfd_launch_status.argtypes = [ctxp, C.POINTER(C.c_int32)]
     lib.lfd_get_pair_fundamental.argtypes = [ctxp, C.c_int32, C.POINTER(C.c_double)]
@@ -250,7 +259,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -1059,6 +1068,54 @@ def _fuse_call(fn, ctx, what, xyz, normals, rgb, voxel_size, with_counts, device
     return (rows + (cnt[:k],) if with_counts else rows), int(n_vox.value)
 
 
+def _knn_call(fn, ctx, what, xyz, cell_size, device, last_error):
+    """One lfd_knn_dist2[_host] call.  ``xyz``: (n, 3) float32 tensor on ``device``.  Returns ``(dist2, stats)``: the (n,) float32 mean squared
+    distance of every point to its three nearest neighbours, and ``(cell size used, occupied cells, points in the fullest cell, points finished by
+    the brute-force pass)``.  Raises ``KnnInputRefused`` for fewer than four points, a non-finite coordinate or a cell key range beyond the limits."""
+    if not isinstance(xyz, torch.Tensor) or xyz.dtype != torch.float32 or xyz.device != device or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"{what}: xyz must be a float32 tensor of n rows x 3 on {device}")
+    n = int(xyz.shape[0])
+    xyz = xyz.contiguous()
+    out = torch.empty((max(n, 1),), dtype=torch.float32, device=device)
+    stats = (C.c_double * 4)()
+    rc = fn(ctx, xyz.data_ptr() if n > 0 else None, n, C.c_double(float(cell_size)), out.data_ptr() if n > 0 else None, stats)
+    if rc != 0:
+        msg = last_error()
+        if "fewer than four points" in msg or "non-finite coordinate" in msg or "key range" in msg:
+            raise KnnInputRefused(f"{what} refused its input ({rc}): {msg}")
+        raise HipBackendError(f"{what} failed ({rc}): {msg}")
+    return out[:n], (float(stats[0]), int(stats[1]), int(stats[2]), int(stats[3]))
+
+
+def gaussian_pack_arguments(opacity: float, flatten: float, max_scale: float):
+    """``(opacity_logit, log_flatten, max_scale)`` as lfd_pack_gaussians takes them: the f32 logit of the initial opacity and log(flatten), each
+    computed once in f64."""
+    import math
+    opacity, flatten, max_scale = float(opacity), float(flatten), float(max_scale)
+    if not (0.0 < opacity < 1.0) or not (0.0 < flatten <= 1.0) or not (0.0 <= max_scale < float("inf")):
+        raise ValueError("pack_gaussians: opacity must be in (0, 1), flatten in (0, 1], max_scale finite and >= 0")
+    return float(np.float32(math.log(opacity / (1.0 - opacity)))), math.log(flatten), max_scale
+
+
+def _pack_gaussians_call(fn, ctx, what, xyz, normals, rgb, dist2, opacity, flatten, max_scale, device, last_error):
+    """One lfd_pack_gaussians[_host] call: the (n*68,) u8 tensor on ``device`` - the body of a PLY whose header is ``writers.gaussian_ply_header``."""
+    n = int(xyz.shape[0])
+    tensors = []
+    for t, cols, name in ((xyz, 3, "xyz"), (normals, 3, "normals"), (rgb, 3, "rgb"), (dist2, 0, "dist2")):
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != device or int(t.shape[0]) != n
+                or (cols and (t.dim() != 2 or t.shape[1] != cols)) or (not cols and t.dim() != 1)):
+            raise ValueError(f"{what}: {name} must be a float32 tensor of {n} rows{' x 3' if cols else ''} on {device}")
+        tensors.append(t.contiguous())
+    logit, log_flatten, max_scale = gaussian_pack_arguments(opacity, flatten, max_scale)
+    out = torch.empty((max(n * 68, 4),), dtype=torch.uint8, device=device)
+    ptr = lambda t: t.data_ptr() if n > 0 else None       # noqa: E731  (an empty tensor may have no address at all)
+    rc = fn(ctx, ptr(tensors[0]), ptr(tensors[1]), ptr(tensors[2]), ptr(tensors[3]), n, C.c_float(logit), C.c_double(log_flatten),
+            C.c_double(max_scale), out.data_ptr())
+    if rc != 0:
+        raise HipBackendError(f"{what} failed ({rc}): {last_error()}")
+    return out[:n * 68]
+
+
 def _freespace_call(fn, ctx, what, xyz, rgb, err, ref_counts, cam_P, cam_wh, plane, tol, min_violations, with_counts, device, last_error):
     """One lfd_freespace_filter[_host] call.  ``xyz`` (n, 3), ``rgb`` (n, 3) or None, ``err`` (n,) or None: float32 tensors on ``device``;
     ``ref_counts``: points per reference, in the order of the cloud; ``cam_P`` (n_refs, 3, 4) or (n_refs, 12) float32 and ``cam_wh`` (n_refs, 2)
@@ -1122,6 +1179,7 @@ class HipDensifier:
             raise HipBackendError(f"lfd_create failed ({rc}): {self._lib.lfd_last_error(None).decode()}")
         self.n_cams = 0
         self.fuse_voxels = 0           # occupied voxels of the last fuse_oriented call
+        self.knn_stats = (0.0, 0, 0, 0)       # (cell size, occupied cells, fullest cell, brute-forced points) of the last knn_dist2 call
 
     def close(self) -> None:
         if getattr(self, "_ctx", None) is not None and self._ctx.value:
@@ -1373,6 +1431,23 @@ class HipDensifier:
         self._check(self._lib.lfd_pack_ply_normals(self._ctx, xyz.data_ptr(), normals.data_ptr(), rgb.data_ptr(), n, out.data_ptr()),
                     "lfd_pack_ply_normals")
         return out[:n * 27]
+
+    def knn_dist2(self, xyz: torch.Tensor, cell_size: float = 0.0) -> torch.Tensor:
+        """The exact mean squared distance of every point to its three nearest neighbours (lfd_knn_dist2): (n,) float32 on the
+        device, bit for bit what a brute-force loop over all pairs gives, whatever ``cell_size`` (the side of the search grid's cells; 0 =
+        automatic).  ``self.knn_stats`` then holds (cell size used, occupied cells, points in the fullest cell, points finished by the brute-force
+        pass).  Synchronous.  Raises ``KnnInputRefused`` as ``_knn_call`` describes."""
+        with torch.cuda.stream(self.stream):
+            out, self.knn_stats = _knn_call(self._lib.lfd_knn_dist2, self._ctx, "lfd_knn_dist2", xyz, cell_size, self.device,
+                                            lambda: self._lib.lfd_last_error(self._ctx).decode())
+        return out
+
+    def pack_gaussians(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor, dist2: torch.Tensor, opacity: float = 0.1,
+                       flatten: float = 1.0, max_scale: float = 0.0) -> torch.Tensor:
+        """(n*68,) u8 device tensor: the body of a 3DGS point_cloud.ply at SH degree 0 (lfd_pack_gaussians; ``writers.gaussian_ply_header``)."""
+        with torch.cuda.stream(self.stream):
+            return _pack_gaussians_call(self._lib.lfd_pack_gaussians, self._ctx, "lfd_pack_gaussians", xyz, normals, rgb, dist2, opacity, flatten,
+                                        max_scale, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
 
     def quantise_rgb(self, rgb: torch.Tensor) -> torch.Tensor:
         rgb = self._pts(rgb, 3, "rgb")
@@ -1708,6 +1783,7 @@ class HostDensifier:
         self.n_threads = int(self._lib.lfd_host_threads(self._ctx))
         self.n_cams = 0
         self.fuse_voxels = 0           # occupied voxels of the last fuse_oriented call
+        self.knn_stats = (0.0, 0, 0, 0)       # (cell size, occupied cells, fullest cell, brute-forced points) of the last knn_dist2 call
 
     close = HipDensifier.close
     __del__ = HipDensifier.__del__
@@ -1797,6 +1873,18 @@ class HostDensifier:
         rows, self.fuse_voxels = _fuse_call(self._lib.lfd_fuse_oriented_host, self._ctx, "lfd_fuse_oriented_host", xyz, normals, rgb, voxel_size,
                                             with_counts, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
         return rows
+
+    def knn_dist2(self, xyz: torch.Tensor, cell_size: float = 0.0) -> torch.Tensor:
+        """HipDensifier.knn_dist2 over CPU tensors (lfd_knn_dist2_host): the same bits, the same ``knn_stats``."""
+        out, self.knn_stats = _knn_call(self._lib.lfd_knn_dist2_host, self._ctx, "lfd_knn_dist2_host", xyz, cell_size, self.device,
+                                        lambda: self._lib.lfd_last_error(self._ctx).decode())
+        return out
+
+    def pack_gaussians(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor, dist2: torch.Tensor, opacity: float = 0.1,
+                       flatten: float = 1.0, max_scale: float = 0.0) -> torch.Tensor:
+        """HipDensifier.pack_gaussians over CPU tensors (lfd_pack_gaussians_host): IEEE sqrt and divide, the C library's log."""
+        return _pack_gaussians_call(self._lib.lfd_pack_gaussians_host, self._ctx, "lfd_pack_gaussians_host", xyz, normals, rgb, dist2, opacity,
+                                    flatten, max_scale, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
 
     def aggregate(self, batch: PreparedBatch, params: lfd_params):
         self._same_device(batch)

@@ -112,6 +112,18 @@ EXPERIMENTAL_DEFAULTS = {
     # one oriented point per visible face of the voxel (the two faces of a thin wall stay two points).  Needs estimate_normals.  Runs once,
     # behind the consensus filter, the free-space filter and the point cap, in front of packing.  0 = off: no new code runs.
     "fuse_voxel_size": 0.0,
+    # Gaussian-ready output (lfd_knn_dist2 + lfd_pack_gaussians): the output file is an initial Gaussian set - a PLY in the 3DGS
+    # point_cloud.ply layout at SH degree 0 (x y z nx ny nz f_dc_0..2 opacity scale_0..2 rot_0..3, 68 bytes a vertex) - instead of the 27-byte
+    # point file: the colour as the SH DC term, a constant opacity, the scale from the exact mean squared distance to the three nearest
+    # neighbours (clamped below at 1e-7, as 3DGS does), the rotation taking +z onto the normal.  Needs estimate_normals.  The last stage, behind
+    # the consensus filter, the free-space filter, the point cap and the oriented fusion.  False = off: no new code runs.
+    "gaussian_init": False,
+    # ... the Gaussian's extent along the normal relative to its extent in the plane, in (0, 1]: 1 is the isotropic 3DGS initialisation
+    "gaussian_flatten": 1.0,
+    # ... the initial opacity, in (0, 1): 0.1 is the 3DGS value
+    "gaussian_opacity": 0.1,
+    # ... an upper bound on the initial extent in scene units (what an isolated point would otherwise get is the distance to far neighbours); 0 = none
+    "gaussian_max_scale": 0.0,
 }
 CONSENSUS_CAP = 8            # LFD_CONSENSUS_CAP of include/lfd_densify.h
 
@@ -408,6 +420,23 @@ class DensePipelineConfig:
             return "experimental['fuse_voxel_size'] must be finite and >= 0 (scene units, the unit of voxel_size; 0 = off)"
         if float(h_fuse) > 0.0 and not normals:
             return "experimental['fuse_voxel_size'] merges points by the side their normals face: it needs experimental['estimate_normals'] = True"
+        g_init = self.exp("gaussian_init")
+        if not isinstance(g_init, (bool, np.bool_)):
+            return "experimental['gaussian_init'] must be True or False"
+        number = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))      # noqa: E731
+        g_flat, g_op, g_max = self.exp("gaussian_flatten"), self.exp("gaussian_opacity"), self.exp("gaussian_max_scale")
+        if not number(g_flat) or not (0.0 < float(g_flat) <= 1.0):
+            return "experimental['gaussian_flatten'] must be a number in (0, 1] (extent along the normal relative to the extent in the plane; 1 = isotropic)"
+        if not number(g_op) or not (0.0 < float(g_op) < 1.0):
+            return "experimental['gaussian_opacity'] must be a number in (0, 1) (the initial opacity; 0.1 is the 3DGS value)"
+        if not number(g_max) or not (0.0 <= float(g_max) < float("inf")):
+            return "experimental['gaussian_max_scale'] must be a finite number >= 0 (scene units; 0 = none)"
+        if not g_init:
+            for key, what in (("gaussian_flatten", "flattening"), ("gaussian_opacity", "opacity"), ("gaussian_max_scale", "largest extent")):
+                if float(self.exp(key)) != float(EXPERIMENTAL_DEFAULTS[key]):
+                    return f"experimental['{key}'] is the {what} of the initial Gaussians: it needs experimental['gaussian_init'] = True"
+        elif not normals:
+            return "experimental['gaussian_init'] orients the Gaussians by the points' normals: it needs experimental['estimate_normals'] = True"
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):
                 return "stream_output writes a PLY while the run proceeds: output_path must end in .ply"

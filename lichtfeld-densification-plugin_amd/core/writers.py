@@ -11,6 +11,8 @@ import numpy as np
 
 _PLY_REC = np.dtype([("xyz", "<f4", 3), ("rgb", "u1", 3)])                       # 15 bytes
 _PLY_NORMAL_REC = np.dtype([("xyz", "<f4", 3), ("normal", "<f4", 3), ("rgb", "u1", 3)])    # 27 bytes: experimental['estimate_normals']
+_GAUSS_REC = np.dtype([("xyz", "<f4", 3), ("normal", "<f4", 3), ("f_dc", "<f4", 3), ("opacity", "<f4"), ("scale", "<f4", 3), ("rot", "<f4", 4)])    # 68 bytes: experimental['gaussian_init']
+GAUSSIAN_PROPERTIES = ("x", "y", "z", "nx", "ny", "nz", "f_dc_0", "f_dc_1", "f_dc_2", "opacity", "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3")
 _BIN_REC = np.dtype([("id", "<u8"), ("xyz", "<f8", 3), ("rgb", "u1", 3), ("err", "<f8")])   # 43 bytes
 
 
@@ -129,6 +131,59 @@ def write_ply_packed(path_out: str, n: int, body: bytes, normals: bool = False) 
         raise ValueError(f"PLY body must be {size} bytes per vertex")
     with open(path_out, "wb") as f:
         f.write(ply_header(n, normals))
+        f.write(body)
+
+
+def gaussian_ply_header(n: int) -> bytes:
+    """The header of a 3DGS ``point_cloud.ply`` at SH degree 0 (no ``f_rest_*``): 17 float properties, 68 bytes a vertex."""
+    return ("ply\nformat binary_little_endian 1.0\n"
+            f"element vertex {int(n)}\n"
+            + "".join(f"property float {name}\n" for name in GAUSSIAN_PROPERTIES) +
+            "end_header\n").encode("ascii")
+
+
+def gaussian_records(xyz: np.ndarray, normals: np.ndarray, rgb01: np.ndarray, dist2: np.ndarray, opacity: float = 0.1, flatten: float = 1.0,
+                     max_scale: float = 0.0) -> np.ndarray:
+    """The 68-byte records of lfd_pack_gaussians in NumPy, rounding for rounding (csrc/lfd_knn.hpp): the colour through the u8 the point file
+    stores, the scale from max(dist2, 1e-7) - capped at max_scale^2 if that is > 0 - as an f64 log rounded once, the rotation taking +z onto the
+    normal.  ``dist2``: the mean squared distance to the three nearest neighbours (HostDensifier.knn_dist2)."""
+    import math
+    n = int(np.asarray(xyz).shape[0])
+    f32 = np.float32
+    rec = np.empty(n, dtype=_GAUSS_REC)
+    rec["xyz"] = np.asarray(xyz, dtype=f32).reshape(n, 3)
+    nrm = np.asarray(normals, dtype=f32).reshape(n, 3)
+    rec["normal"] = nrm
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        q = np.clip(np.nan_to_num(np.round(np.asarray(rgb01, dtype=f32).reshape(n, 3) * f32(255.0)), nan=0.0), 0, 255).astype(f32)
+        rec["f_dc"] = ((q / f32(255.0)) - f32(0.5)) / f32(0.28209479177387814)
+        rec["opacity"] = f32(math.log(float(opacity) / (1.0 - float(opacity))))
+        m = np.maximum(np.asarray(dist2, dtype=f32).reshape(n), f32(1e-7))
+        if float(max_scale) > 0.0:
+            cap = f32(min(float(max_scale) * float(max_scale), 3.4028234663852886e38))
+            m = np.minimum(m, cap if cap > 0 else f32(1.4012985e-45))
+        ls = 0.5 * np.log(m.astype(np.float64))
+        rec["scale"][:, 0] = rec["scale"][:, 1] = ls.astype(f32)
+        rec["scale"][:, 2] = (ls + math.log(float(flatten))).astype(f32)
+        rot = np.zeros((n, 4), f32)
+        rot[:, 0] = 1.0
+        usable = np.isfinite(nrm).all(1) & (nrm != 0).any(1)
+        w, x, y = f32(1.0) + nrm[:, 2], -nrm[:, 1], nrm[:, 0]
+        flip = usable & (w < f32(2.0 ** -23))
+        rot[flip] = (0.0, 1.0, 0.0, 0.0)
+        length = np.sqrt((w * w + x * x) + y * y)
+        go = usable & ~flip & np.isfinite(length) & (length > 0)
+        rot[go, 0], rot[go, 1], rot[go, 2] = (w / length)[go], (x / length)[go], (y / length)[go]
+    rec["rot"] = rot
+    return rec
+
+
+def write_gaussian_ply_packed(path_out: str, n: int, body: bytes) -> None:
+    """A 3DGS ``point_cloud.ply`` at SH degree 0 from n packed 68-byte records (HipDensifier / HostDensifier.pack_gaussians)."""
+    if len(body) != 68 * int(n):
+        raise ValueError("Gaussian PLY body must be 68 bytes per vertex")
+    with open(path_out, "wb") as f:
+        f.write(gaussian_ply_header(n))
         f.write(body)
 
 

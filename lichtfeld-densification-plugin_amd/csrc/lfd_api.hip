@@ -24,6 +24,7 @@
 #include "lfd_undistort.hpp"
 #include "lfd_freespace.hpp"
 #include "lfd_fuse.hpp"
+#include "lfd_knn.hpp"
 
 extern "C" __global__ void lfd_aggregate_kernel(LfdLaunch L, float* best_cert, uint8_t* best_slot);
 extern "C" __global__ void lfd_dense_kernel(LfdLaunch L);
@@ -92,6 +93,14 @@ extern "C" __global__ void lfd_fuse_sums_big_kernel(const float* xyz, const floa
                                                     const unsigned* vstart, const unsigned* nv_p, const uint8_t* flag, const unsigned* rowstart, double cscale,
                                                     const unsigned* big, const unsigned* n_big, float* xyz_out, float* normals_out, float* rgb_out,
                                                     unsigned* count_out);
+extern "C" __global__ void lfd_knn_keys_kernel(const float* xyz, long long n, LfdKnnGrid g, unsigned long long* keys, unsigned* idx);
+extern "C" __global__ void lfd_knn_cellmax_kernel(const unsigned* vstart, const unsigned* nv_p, long long n, unsigned* max_out);
+extern "C" __global__ void lfd_knn_gather_kernel(const float* xyz, const unsigned* sorted_idx, long long n, LfdKnnPt* spt);
+extern "C" __global__ void lfd_knn_scan_kernel(const unsigned long long* skey, const LfdKnnPt* spt, long long n, LfdKnnGrid g, float* dist2, unsigned* list,
+                                               unsigned* n_list);
+extern "C" __global__ void lfd_knn_brute_kernel(const LfdKnnPt* spt, long long n, const unsigned* list, const unsigned* n_list, float* dist2);
+extern "C" __global__ void lfd_pack_gaussians_kernel(const float* xyz, const float* normals, const float* rgb, const float* dist2, long long n, float opacity,
+                                                     double log_flatten, float max_m, float* out);
 extern "C" __global__ void lfd_freespace_fill_kernel(uint32_t* zbuf, long long n_words);
 extern "C" __global__ void lfd_freespace_splat_kernel(const float* xyz, long long n, const long long* offs, int n_refs, const LfdFreespaceCam* cams, int pw,
                                                       int ph, uint32_t* zbuf);
@@ -579,7 +588,7 @@ void lfd_destroy(lfd_context* ctx) {
     }
     for (hipEvent_t ev : ctx->kt_start) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->kt_stop) (void)hipEventDestroy(ev);
-    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->vox, &ctx->support_ws, &ctx->prec_tab, &ctx->consensus_ws, &ctx->undist_cnt, &ctx->freespace_ws, &ctx->fuse_ws})
+    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->vox, &ctx->support_ws, &ctx->prec_tab, &ctx->consensus_ws, &ctx->undist_cnt, &ctx->freespace_ws, &ctx->fuse_ws, &ctx->knn_ws})
         if (b->ptr) (void)hipFree(b->ptr);
     if (ctx->pinned_words) (void)hipHostFree(ctx->pinned_words);
     if (ctx->prec_pinned) (void)hipHostFree(ctx->prec_pinned);
@@ -1689,6 +1698,111 @@ int lfd_fuse_oriented(lfd_context* ctx, const float* xyz, const float* normals, 
     LFD_HIP(ctx, hipStreamSynchronize(st));
     *n_voxels_host = (int64_t)(unsigned)ctx->pinned_words[0];
     *n_rows_host = (int64_t)(unsigned)ctx->pinned_words[2];
+    return LFD_OK;
+}
+
+// ---- Gaussian-ready output: exact 3-NN mean squared distance and the 68-byte record (lfd_knn.hip) ---------------------------------------------------
+int lfd_knn_dist2(lfd_context* ctx, const float* xyz, int64_t n, double cell_size, float* dist2_out, double* stats_host) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_knn_check(xyz, n, cell_size, dist2_out)) return fail(ctx, LFD_ERR_INVALID, std::string("lfd_knn_dist2: ") + why);
+    if (stats_host) stats_host[0] = stats_host[1] = stats_host[2] = stats_host[3] = 0.0;
+    if (n == 0) return LFD_OK;
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // radix passes: workgroup b of G owns the items [b * chunk, (b + 1) * chunk); chunk is a multiple of the scatter's 512-item round
+    long long G = std::min<long long>(1024, (n + 4095) / 4096);
+    const long long chunk = (((n + G - 1) / G) + 511) / 512 * 512;
+    G = (n + chunk - 1) / chunk;
+    const int n_part = (int)std::min<long long>(1024, (n + 255) / 256);
+    const long long n_wg = (n + 255) / 256;
+    // workspace: partials | stats, cell count, fullest cell, listed points | digit counts | keys x 2 | indices x 2 | cell starts | sorted points | list
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t o_part = 0, o_small = al(o_part + 1024 * sizeof(LfdVoxStats)), o_counts = al(o_small + sizeof(LfdVoxStats) + 12);
+    const size_t o_ka = al(o_counts + 256 * 1024 * sizeof(unsigned)), o_kb = al(o_ka + 8 * (size_t)n), o_ia = al(o_kb + 8 * (size_t)n);
+    const size_t o_ib = al(o_ia + 4 * (size_t)n), o_vs = al(o_ib + 4 * (size_t)n), o_pt = al(o_vs + 4 * (size_t)n);
+    const size_t o_list = al(o_pt + sizeof(LfdKnnPt) * (size_t)n);
+    const size_t total = al(o_list + 4 * (size_t)n);
+    if (int rc = ensure(ctx, ctx->knn_ws, total)) return rc;
+    unsigned char* w = static_cast<unsigned char*>(ctx->knn_ws.ptr);
+    LfdVoxStats* part = reinterpret_cast<LfdVoxStats*>(w + o_part);
+    LfdVoxStats* stats = reinterpret_cast<LfdVoxStats*>(w + o_small);
+    unsigned* nv_dev = reinterpret_cast<unsigned*>(w + o_small + sizeof(LfdVoxStats));
+    unsigned* cell_max = nv_dev + 1;
+    unsigned* n_list = nv_dev + 2;
+    unsigned* counts = reinterpret_cast<unsigned*>(w + o_counts);
+    unsigned long long* keys[2] = {reinterpret_cast<unsigned long long*>(w + o_ka), reinterpret_cast<unsigned long long*>(w + o_kb)};
+    unsigned* idx[2] = {reinterpret_cast<unsigned*>(w + o_ia), reinterpret_cast<unsigned*>(w + o_ib)};
+    unsigned* vstart = reinterpret_cast<unsigned*>(w + o_vs);
+    LfdKnnPt* spt = reinterpret_cast<LfdKnnPt*>(w + o_pt);
+    unsigned* list = reinterpret_cast<unsigned*>(w + o_list);
+
+    // min / max pass; the refusals are decided before anything is sorted
+    hipLaunchKernelGGL(lfd_consensus_minmax_kernel, dim3(n_part), dim3(256), 0, st, xyz, (long long)n, part);
+    hipLaunchKernelGGL(lfd_voxel_final_kernel, dim3(1), dim3(256), 0, st, part, n_part, stats);
+    LFD_HIP(ctx, hipGetLastError());
+    LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, stats, sizeof(LfdVoxStats), hipMemcpyDeviceToHost, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));
+    LfdVoxStats s;
+    std::memcpy(&s, ctx->pinned_words, sizeof(s));
+    if (s.flags & LFD_VOX_NONFINITE) return fail(ctx, LFD_ERR_INVALID, "lfd_knn_dist2: " LFD_KNN_NONFINITE);
+    double h = cell_size > 0.0 ? cell_size : lfd_knn_auto_h(s.lo, s.hi, (long long)n);
+    LfdKnnGrid g;
+    if (!lfd_knn_grid(s.lo, s.hi, h, g)) return fail(ctx, LFD_ERR_INVALID, "lfd_knn_dist2: " LFD_KNN_KEY_RANGE);
+
+    const unsigned grid = (unsigned)std::min<long long>(n_wg, 4096);
+    int cur = 0;
+    for (int rebuilds = 0;;) {
+        cur = 0;
+        hipLaunchKernelGGL(lfd_knn_keys_kernel, dim3(grid), dim3(256), 0, st, xyz, (long long)n, g, keys[0], idx[0]);
+        for (int shift = 0; shift < g.bits; shift += 8, cur ^= 1) {
+            hipLaunchKernelGGL(lfd_voxel_hist_kernel, dim3((unsigned)G), dim3(256), 0, st, keys[cur], (long long)n, chunk, shift, counts);
+            hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, counts, (int)(256 * G), (unsigned*)nullptr);
+            hipLaunchKernelGGL(lfd_voxel_scatter_kernel, dim3((unsigned)G), dim3(512), 0, st, keys[cur], idx[cur], (long long)n, chunk, shift, counts,
+                               keys[cur ^ 1], idx[cur ^ 1]);
+        }
+        hipLaunchKernelGGL(lfd_voxel_head_count_kernel, dim3((unsigned)G), dim3(256), 0, st, keys[cur], (long long)n, chunk, counts);
+        hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, counts, (int)G, nv_dev);
+        LFD_HIP(ctx, hipGetLastError());
+        if (cell_size > 0.0) break;
+        // the automatic rule looks at the occupied cells of this grid (lfd_knn.hpp): the same decisions as the twin's
+        LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, nv_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        LFD_HIP(ctx, hipStreamSynchronize(st));
+        const long long occupied = (long long)(unsigned)ctx->pinned_words[0];
+        LfdKnnGrid finer;
+        if (!lfd_knn_refine_more((long long)n, occupied, rebuilds) || !lfd_knn_grid(s.lo, s.hi, h / 4.0, finer)) break;
+        h = h / 4.0;
+        g = finer;
+        ++rebuilds;
+    }
+    hipLaunchKernelGGL(lfd_voxel_head_scatter_kernel, dim3((unsigned)G), dim3(512), 0, st, keys[cur], (long long)n, chunk, counts, vstart);
+    LFD_HIP(ctx, hipMemsetAsync(cell_max, 0, 2 * sizeof(unsigned), st));
+    hipLaunchKernelGGL(lfd_knn_cellmax_kernel, dim3(grid), dim3(256), 0, st, vstart, nv_dev, (long long)n, cell_max);
+    hipLaunchKernelGGL(lfd_knn_gather_kernel, dim3(grid), dim3(256), 0, st, xyz, idx[cur], (long long)n, spt);
+    hipLaunchKernelGGL(lfd_knn_scan_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, keys[cur], spt, (long long)n, g, dist2_out, list, n_list);
+    hipLaunchKernelGGL(lfd_knn_brute_kernel, dim3((unsigned)std::min<long long>(n, 1024)), dim3(256), 0, st, spt, (long long)n, list, n_list, dist2_out);
+    LFD_HIP(ctx, hipGetLastError());
+    LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, nv_dev, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));
+    if (stats_host) {
+        stats_host[0] = h;
+        for (int k = 0; k < 3; ++k) stats_host[1 + k] = (double)(unsigned)ctx->pinned_words[k];
+    }
+    return LFD_OK;
+}
+
+int lfd_pack_gaussians(lfd_context* ctx, const float* xyz, const float* normals, const float* rgb, const float* dist2, int64_t n, float opacity_logit,
+                       double log_flatten, double max_scale, uint8_t* out) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_gauss_check(xyz, normals, rgb, dist2, n, opacity_logit, log_flatten, max_scale, out))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_pack_gaussians: ") + why);
+    if (n == 0) return LFD_OK;
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(lfd_pack_gaussians_kernel, dim3(grid), dim3(256), 0, ctx->stream, xyz, normals, rgb, dist2, (long long)n, opacity_logit,
+                       log_flatten, lfd_gauss_max_m(max_scale), reinterpret_cast<float*>(out));
+    LFD_HIP(ctx, hipGetLastError());
     return LFD_OK;
 }
 

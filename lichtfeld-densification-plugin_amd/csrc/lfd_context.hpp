@@ -96,6 +96,7 @@ struct lfd_context {
     DeviceBuffer consensus_ws;     // lfd_consensus_filter: statistics, digit counts, keys / indices (x 2), sorted points, offsets, keep bytes; grown on demand
     DeviceBuffer freespace_ws;     // lfd_freespace_filter: the references' z-buffers, cameras, offsets, keep bytes, kept per workgroup; grown on demand
     DeviceBuffer fuse_ws;          // lfd_fuse_oriented: lfd_voxel_downsample's workspace plus a flag byte per point and the voxels' rows; grown on demand
+    DeviceBuffer knn_ws;           // lfd_knn_dist2: statistics, digit counts, keys / indices (x 2), cell starts, sorted points, the list of unsettled points; grown on demand
     DeviceBuffer undist_cnt;       // lfd_undistort_image: the u64 counter of invalid pixels of a call that asks for it
     // lfd_refine_multiview_weighted: the table of precision-plane pointers, uploaded on the launch stream when its content differs from the last
     DeviceBuffer prec_tab;

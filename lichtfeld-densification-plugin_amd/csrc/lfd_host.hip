@@ -27,6 +27,7 @@
 #include "lfd_undistort.hpp"
 #include "lfd_freespace.hpp"
 #include "lfd_fuse.hpp"
+#include "lfd_knn.hpp"
 
 void lfd_fill_kernel_params(const lfd_batch* b, const lfd_params* p, LfdKernelParams& kp);   // lfd_api.hip
 
@@ -863,6 +864,113 @@ int lfd_fuse_oriented_host(lfd_context* ctx, const float* xyz, const float* norm
     }
     *n_rows_host = r;
     *n_voxels_host = nv;
+    return LFD_OK;
+}
+
+// The twin of lfd_knn_dist2: the same grid, keys, automatic cell size and ring scan (lfd_knn.hpp) over a sort of (key, index) pairs,
+// on the context's threads; the points no ring settles are finished by a loop over the whole cloud.
+int lfd_knn_dist2_host(lfd_context* ctx, const float* xyz, int64_t n, double cell_size, float* dist2_out, double* stats_host) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    if (const char* why = lfd_knn_check(xyz, n, cell_size, dist2_out)) return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_knn_dist2_host: ") + why);
+    if (stats_host) stats_host[0] = stats_host[1] = stats_host[2] = stats_host[3] = 0.0;
+    if (n == 0) return LFD_OK;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    bool nonfinite = false;
+    for (long long i = 0; i < 3 * (long long)n; ++i) {
+        const int c = (int)(i % 3);
+        if (std::isfinite(xyz[i])) { lo[c] = std::min(lo[c], xyz[i]); hi[c] = std::max(hi[c], xyz[i]); }
+        else nonfinite = true;
+    }
+    if (nonfinite) return lfd_fail(ctx, LFD_ERR_INVALID, "lfd_knn_dist2_host: " LFD_KNN_NONFINITE);
+    double h = cell_size > 0.0 ? cell_size : lfd_knn_auto_h(lo, hi, (long long)n);
+    LfdKnnGrid g;
+    if (!lfd_knn_grid(lo, hi, h, g)) return lfd_fail(ctx, LFD_ERR_INVALID, "lfd_knn_dist2_host: " LFD_KNN_KEY_RANGE);
+    const int n_chunks = (int)((n + kChunk - 1) / kChunk);
+    std::vector<std::pair<unsigned long long, unsigned>> order((size_t)n);
+    long long occupied = 0, fullest = 0;
+    for (int rebuilds = 0;;) {
+        parallel_chunks(ctx, n_chunks, [&](int c) {
+            const long long i1 = std::min<long long>(n, (long long)(c + 1) * kChunk);
+            for (long long i = (long long)c * kChunk; i < i1; ++i)
+                order[(size_t)i] = {lfd_knn_key(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], g), (unsigned)i};
+        });
+        std::sort(order.begin(), order.end());
+        occupied = 0;
+        fullest = 0;
+        for (long long a = 0; a < n;) {
+            long long b = a + 1;
+            while (b < n && order[(size_t)b].first == order[(size_t)a].first) ++b;
+            ++occupied;
+            fullest = std::max(fullest, b - a);
+            a = b;
+        }
+        LfdKnnGrid finer;
+        if (cell_size > 0.0 || !lfd_knn_refine_more((long long)n, occupied, rebuilds) || !lfd_knn_grid(lo, hi, h / 4.0, finer)) break;
+        h = h / 4.0;
+        g = finer;
+        ++rebuilds;
+    }
+    std::vector<unsigned long long> skey((size_t)n);
+    std::vector<LfdKnnPt> spt((size_t)n);
+    std::vector<uint8_t> open_pt((size_t)n);
+    parallel_chunks(ctx, n_chunks, [&](int c) {
+        const long long j1 = std::min<long long>(n, (long long)(c + 1) * kChunk);
+        for (long long j = (long long)c * kChunk; j < j1; ++j) {
+            const unsigned i = order[(size_t)j].second;
+            skey[(size_t)j] = order[(size_t)j].first;
+            spt[(size_t)j] = {xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], i};
+        }
+    });
+    parallel_chunks(ctx, n_chunks, [&](int c) {
+        const long long j1 = std::min<long long>(n, (long long)(c + 1) * kChunk);
+        for (long long j = (long long)c * kChunk; j < j1; ++j) {
+            float mean;
+            const bool done = lfd_knn_scan_point(skey.data(), spt.data(), (long long)n, j, g, &mean);
+            if (done) dist2_out[spt[(size_t)j].idx] = mean;
+            open_pt[(size_t)j] = done ? 0 : 1;
+        }
+    });
+    std::vector<long long> list;
+    for (long long j = 0; j < n; ++j)
+        if (open_pt[(size_t)j]) list.push_back(j);
+    parallel_chunks(ctx, (int)std::min<size_t>(list.size(), 1u << 20), [&](int c) {
+        for (size_t e = (size_t)c; e < list.size(); e += (size_t)1 << 20) {
+            const long long j = list[e];
+            const LfdKnnPt me = spt[(size_t)j];
+            float a = INFINITY, b = INFINITY, cc = INFINITY;
+            for (long long q = 0; q < n; ++q) {
+                if (q == j) continue;
+                const LfdKnnPt& p = spt[(size_t)q];
+                lfd_knn_insert(lfd_knn_d2(me.x, me.y, me.z, p.x, p.y, p.z), a, b, cc);
+            }
+            dist2_out[me.idx] = lfd_knn_mean(a, b, cc);
+        }
+    });
+    if (stats_host) {
+        stats_host[0] = h;
+        stats_host[1] = (double)occupied;
+        stats_host[2] = (double)fullest;
+        stats_host[3] = (double)list.size();
+    }
+    return LFD_OK;
+}
+
+// The twin of lfd_pack_gaussians: lfd_gauss_record per point on the context's threads (IEEE sqrt and divide, the C library's log).
+int lfd_pack_gaussians_host(lfd_context* ctx, const float* xyz, const float* normals, const float* rgb, const float* dist2, int64_t n,
+                            float opacity_logit, double log_flatten, double max_scale, uint8_t* out) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    if (const char* why = lfd_gauss_check(xyz, normals, rgb, dist2, n, opacity_logit, log_flatten, max_scale, out))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_pack_gaussians_host: ") + why);
+    const float max_m = lfd_gauss_max_m(max_scale);
+    float* o = reinterpret_cast<float*>(out);
+    const int n_chunks = (int)((n + kChunk - 1) / kChunk);
+    parallel_chunks(ctx, n_chunks, [&](int c) {
+        const long long i1 = std::min<long long>(n, (long long)(c + 1) * kChunk);
+        for (long long i = (long long)c * kChunk; i < i1; ++i)
+            lfd_gauss_record(xyz + 3 * i, normals + 3 * i, rgb + 3 * i, dist2[i], opacity_logit, log_flatten, max_m, o + LFD_GAUSS_FLOATS * i);
+    });
     return LFD_OK;
 }
 

@@ -184,6 +184,9 @@ def _finish_on_device(result, path: str, max_points: int, seed: int, clock=None,
         xyz, normals, rgb = _apply_oriented_fusion(config, pts[0], normals, pts[1], progress_callback)
         pts = (xyz, rgb)
     n = int(pts[0].shape[0])
+    if config is not None and bool(config.exp("gaussian_init")):              # (the last stage: it replaces the 27-byte packing)
+        _write_gaussians(config, path, pts[0], normals, pts[1], clock=clock, progress_callback=progress_callback)
+        return n
     _write_output(path, np.empty((n, 0), np.float32), None, None, pts, clock=clock, normals=normals)
     return n
 
@@ -399,6 +402,53 @@ def _apply_oriented_fusion(config: DensePipelineConfig, xyz, normals, rgb, progr
     return rows if on_gpu else tuple(r.numpy() for r in rows)
 
 
+class GaussianInitRefused(RuntimeError):
+    """experimental['gaussian_init']: the library refused the cloud (fewer than four points, a non-finite coordinate, a cell key range beyond the
+    grid's limits).  No file of another format is written in its place."""
+
+
+def _write_gaussians(config: DensePipelineConfig, path: str, xyz, normals, rgb, clock=None, progress_callback=None) -> None:
+    """The output file of experimental['gaussian_init'] in place of the 27-byte point file: the exact 3-nearest-neighbour scale
+    (lfd_knn_dist2) and the 68-byte records (lfd_pack_gaussians) where the final cloud is - device tensors through the device calls, host arrays
+    (``backend='host'``) through the twin -, so that only the file payload crosses PCIe."""
+    from .core import hip_backend as hb
+    from .core.stages import NULL_CLOCK
+    from .core.writers import write_gaussian_ply_packed
+    import torch
+    if normals is None:
+        raise RuntimeError("experimental['gaussian_init'] needs the normals of experimental['estimate_normals']; this result carries none")
+    if not _is_writer_rank():
+        return
+    clock = clock if clock is not None else NULL_CLOCK
+    on_gpu = isinstance(xyz, torch.Tensor) and bool(xyz.is_cuda)
+    as_tensor = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))      # noqa: E731
+    t = tuple(as_tensor(a) for a in (xyz, normals, rgb))
+    if not on_gpu:
+        t = tuple(a.cpu() for a in t)
+    if progress_callback:
+        progress_callback(96.0, "Initialising Gaussians...")
+    n = int(t[0].shape[0])
+    dens = hb.HipDensifier(t[0].device) if on_gpu else hb.HostDensifier(int(config.exp("host_threads")))
+    try:
+        try:
+            dist2 = dens.knn_dist2(t[0])
+        except hb.KnnInputRefused as exc:
+            raise GaussianInitRefused(f"experimental['gaussian_init'] cannot be applied to this cloud of {n:,} points: {exc}") from exc
+        h, cells, fullest, brute = dens.knn_stats
+        with clock.stage("d2h"):                # the file payload - 68 bytes per point - is what crosses PCIe
+            body = dens.pack_gaussians(t[0], t[1], t[2], dist2, opacity=float(config.exp("gaussian_opacity")),
+                                       flatten=float(config.exp("gaussian_flatten")), max_scale=float(config.exp("gaussian_max_scale")))
+            body = body.cpu().numpy().tobytes()
+    finally:
+        dens.close()
+    log.info(f"Gaussian initialisation: {n:,} points, cell size {h:.6g}, {cells:,} occupied cells, fullest cell {fullest:,}, {brute:,} points by brute force")
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with clock.stage("write", sync=False):
+        write_gaussian_ply_packed(path, n, body)
+
+
 def _is_writer_rank() -> bool:
     """True unless this process is a non-zero rank of an initialised torch.distributed job."""
     try:
@@ -531,7 +581,10 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
             if float(config.exp("fuse_voxel_size")) > 0.0:
                 xyz, normals, rgb = _apply_oriented_fusion(config, xyz, normals, rgb, progress_callback)
                 err = None
-            _write_output(config.output_path, xyz, rgb, err, None, normals=normals)
+            if bool(config.exp("gaussian_init")):
+                _write_gaussians(config, config.output_path, xyz, normals, rgb, clock=pipeline_kwargs.get("stage_clock"), progress_callback=progress_callback)
+            else:
+                _write_output(config.output_path, xyz, rgb, err, None, normals=normals)
             n_points = int(xyz.shape[0])
     log.info(f"Dense reconstruction finished: {n_points:,} points -> {config.output_path}")
     if progress_callback:
@@ -591,7 +644,7 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
         try:
             n_written = _finish_on_device(result, config.output_path, config.max_points, config.seed, clock=pipeline_kwargs.get("stage_clock"),
                                           config=config, progress_callback=progress_callback)
-        except OrientedFusionRefused as exc:
+        except (OrientedFusionRefused, GaussianInitRefused) as exc:
             return 1, str(exc)
         log.info(f"Dense point cloud saved to {config.output_path} ({n_written:,} points)")
         if progress_callback:
@@ -640,6 +693,11 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
             os.makedirs(d, exist_ok=True)
         if _is_writer_rank():
             write_ply(config.output_path, xyz, to_uint8_rgb(rgb))
+    elif bool(config.exp("gaussian_init")):             # (needs estimate_normals, which makes output_path a .ply)
+        try:
+            _write_gaussians(config, config.output_path, xyz, normals, rgb, clock=pipeline_kwargs.get("stage_clock"), progress_callback=progress_callback)
+        except GaussianInitRefused as exc:
+            return 1, str(exc)
     else:
         _write_output(config.output_path, xyz, rgb, err, dev_pts if normals is None else None, normals=normals)
     log.info(f"Dense point cloud saved to {config.output_path} ({xyz.shape[0]:,} points)")
@@ -685,6 +743,11 @@ def _experimental_from_args(args) -> dict:
         exp["normal_depth_step_rel"] = float(args.normal_depth_step_rel)
     if float(getattr(args, "fuse_voxel_size", 0.0)) != 0.0:
         exp["fuse_voxel_size"] = float(args.fuse_voxel_size)
+    if bool(getattr(args, "gaussian_init", False)):
+        exp["gaussian_init"] = True
+    for key in ("gaussian_flatten", "gaussian_opacity", "gaussian_max_scale"):
+        if getattr(args, key, None) is not None:
+            exp[key] = float(getattr(args, key))
     return exp
 
 
@@ -768,6 +831,15 @@ def build_argparser() -> argparse.ArgumentParser:
                     help="oriented voxel fusion of the final cloud: merge the points of every voxel of this size (scene units) per side their normals "
                          "face - one oriented point per visible face of a voxel; runs behind the filters and --max_points (needs "
                          "--estimate_normals; 0 = off)")
+    ap.add_argument("--gaussian_init", action="store_true",
+                    help="write an initial Gaussian set instead of the point file: a PLY in the 3DGS point_cloud.ply layout at SH degree 0, the scale from "
+                         "the exact distance to the three nearest neighbours, the rotation taking +z onto the normal (needs --estimate_normals)")
+    ap.add_argument("--gaussian_flatten", type=float, default=None,
+                    help="... extent along the normal relative to the extent in the plane, in (0, 1] (default 1 = isotropic, the 3DGS initialisation; "
+                         "needs --gaussian_init)")
+    ap.add_argument("--gaussian_opacity", type=float, default=None, help="... initial opacity in (0, 1) (default 0.1, the 3DGS value; needs --gaussian_init)")
+    ap.add_argument("--gaussian_max_scale", type=float, default=None,
+                    help="... upper bound on the initial extent in scene units (default 0 = none; needs --gaussian_init)")
     ap.add_argument("--keep_threads", action="store_true",
                     help="leave torch's intra-op thread count alone (by default it is lowered to the container's CPU quota; the count decides the last "
                          "bits of upstream's sampling normaliser, so a run compared bit for bit with upstream keeps upstream's setting)")
