@@ -2,7 +2,16 @@
 pass 0 was written out (tests/golden/g13_null_vector.npz, made by tests/golden/make_null_vector_fixture.py on that commit):
 bit-identical c[4] and the identical solve count for every stored matrix.  The host build divides where the device refines
 v_rcp_f64, so this pins the STRUCTURE - which solves run, which iterate a lane returns, where NaN leaves - not the device's bits
-(those are pinned by the byte comparison of bench.py --dump-outputs).  No GPU needed."""
+(those are pinned by the byte comparison of bench.py --dump-outputs).  No GPU needed.
+
+Re-recorded since (tests/golden/make_null_vector_fixture.py --rerecord), when the shifted passes began to test the sign of their pivots and
+the loop solves to keep the iterate below 2^64 - 48 records, every other one is the first recording's:
+  2474 2512 (kind 2), 2947 2949 2957 2967 2969 2971 2973 2977 2979 2982 2984 2987 2988 2989 2991 2993 2994 2995 3000 3002 3004 3005 3006
+  3008 3010 3012 3013 3014 3016 3021 3023 3028 3032 3033 3035 3039 3042 3044 3047 3050 3058 3064 3066 (kind 4), 3146 (kind 6): a shifted
+  pass found a negative pivot and searched its shift.  Among them 2949 2969 2977 2979 2993 3002 3004 3008 3010 3013, whose first record
+  was the singular vector of sigma3 instead of sigma4.
+  2841 2881 (kind 3, points at infinity): pass 0's tail loop rescaled an iterate above 2^64; c is the old one times a power of two."""
+import hashlib
 import itertools
 import os
 
@@ -13,6 +22,11 @@ from lichtfeld_densification_plugin_amd.core import hip_backend as hb
 from helpers import ROOT
 
 FIXTURE = os.path.join(ROOT, "tests", "golden", "g13_null_vector.npz")
+RERECORDED = [2474, 2512, 2841, 2881, 2947, 2949, 2957, 2967, 2969, 2971, 2973, 2977, 2979, 2982, 2984, 2987, 2988, 2989, 2991, 2993, 2994, 2995,
+              3000, 3002, 3004, 3005, 3006, 3008, 3010, 3012, 3013, 3014, 3016, 3021, 3023, 3028, 3032, 3033, 3035, 3039, 3042, 3044, 3047, 3050,
+              3058, 3064, 3066, 3146]
+WRONG_VECTOR = [2949, 2969, 2977, 2979, 2993, 3002, 3004, 3008, 3010, 3013]      # first record: v3 instead of v4
+FIRST_RECORDING_SHA256 = "ab8016674b216c91b85947b6eb42e4db2f26e6a8b807b0b6667ffb79632605aa"     # of c and it as first recorded
 KINDS = {0: "ring scene, 0.1-2 px noise", 1: "noise-free (rank-deficient)", 2: "10-60 px noise", 3: "point at infinity",
          4: "sigma4/sigma3 near 1", 5: "NaN / Inf entries", 6: "zero, identity, huge, tiny, repeated rows"}
 
@@ -46,6 +60,38 @@ def test_null_vector_is_the_recorded_one_bit_for_bit(g13, k):
         assert n == int(it[i]), (i, n, int(it[i]))
         # bit patterns, so that NaN == NaN and -0.0 != +0.0
         assert x.view(np.uint64).tolist() == c[i].view(np.uint64).tolist(), (i, x, c[i])
+
+
+def test_only_the_listed_records_were_rerecorded(g13):
+    """The records the fixture says were replaced are the ones listed above; with their first values put back, c and it are the first
+    recording's, byte for byte.  Each replaced record changed for a stated reason: a shifted pass had run (more than 9 solves) or the
+    iterate had passed 2^64 (then the new c is the old one times a power of two, same solve count).  The ten wrong vectors are among
+    them and now pass the exact rules (tests/solver_ref.py, tests/golden/g19_solver_exact.npz)."""
+    import solver_ref as sr
+    idx = g13["rerecorded"].astype(int)
+    assert idx.tolist() == RERECORDED and set(WRONG_VECTOR) <= set(RERECORDED)
+    c, it = g13["c"].copy(), g13["it"].copy()
+    c[idx], it[idx] = g13["c_prev"], g13["it_prev"]
+    assert hashlib.sha256(c.tobytes() + it.tobytes()).hexdigest() == FIRST_RECORDING_SHA256
+    for j, i in enumerate(idx):
+        old, new = g13["c_prev"][j], g13["c"][i]
+        assert old.tobytes() != new.tobytes() or int(g13["it_prev"][j]) != int(g13["it"][i]), i
+        if int(g13["it_prev"][j]) <= 9:
+            assert np.abs(old).max() > 2.0 ** 64 and int(g13["it_prev"][j]) == int(g13["it"][i]), i
+            ratio = new / old
+            assert (ratio == ratio[0]).all() and np.log2(ratio[0]) == np.round(np.log2(ratio[0])), (i, ratio)
+    fx = sr.load_fixture()
+    pos = {int(i): k for k, i in enumerate(fx["G_idx"])}
+    for i in WRONG_VECTOR:
+        k = pos[i]
+        fail, _, _ = sr.judge(fx["G_A"][k], fx["G_sigma"][k], fx["G_cls"][k], fx["G_v"][k], g13["c"][i])
+        assert fail is None, (i, fail)
+        # ... and the first record was v3: orthogonal to the exact v4, with the residual of sigma3
+        old = g13["c_prev"][RERECORDED.index(i)]
+        old = old / np.linalg.norm(old)
+        assert abs(old @ fx["G_v"][k]) < 1e-6, i
+        res = np.linalg.norm(fx["G_A"][k].astype(np.float64) @ old)
+        assert abs(res / float(fx["G_sigma"][k][2]) - 1.0) < 1e-6, (i, res)
 
 
 def _settled_reference(e, ref):
