@@ -326,6 +326,23 @@ int lfd_local_corr(lfd_context* ctx, const float* A, const float* Bf, const floa
 int lfd_local_corr_host(lfd_context* ctx, const float* A, const float* Bf, const float* warp, int32_t B, int32_t N, int32_t C, int32_t K,
                         int32_t H1, int32_t W1, const int64_t* a_strides, const int64_t* bf_strides, float* out);
 
+/* One conv block of RoMa-v2's refiners in one pass (RoMaV2/src/romav2/refiner.py: each of the three ConvRefiners runs nine blocks of depthwise 5x5
+ * convolution, eval-mode BatchNorm, ReLU and 1x1 convolution under bf16 autocast).  x (B, C, H, W) contiguous NCHW, bf16 (16-bit
+ * words) or, with x_is_f32 != 0, f32 that is rounded to bf16 on load; dw_w (C, 25) the depthwise weights as stored (f32, not rounded); scale /
+ * shift (C) the folded affine s = gamma / sqrt(var + eps), t = beta + (bias_dw - mean) s; out (B, C, H, W) bf16 as 16-bit words.  In f32 with
+ * IEEE fmaf, every rounding written out (csrc/lfd_block.hpp):
+ *   a = 0; for ky = 0..4, kx = 0..4: a = fmaf(w[c][5 ky + kx], x[y + ky - 2][x + kx - 2], a), a tap outside the plane skipped
+ *   h = relu(fmaf(s[c], a, t[c])) rounded to bf16 (nearest even; a NaN stays a quiet NaN, -0 becomes +0)
+ * pw_wT == NULL: out = h.  Otherwise pw_wT (C, C) holds the 1x1 weights TRANSPOSED - row c the weights that multiply hidden channel c - and
+ * pw_b (C) its bias: z = pw_b[o]; for c = 0..C-1: z = fmaf(pw_wT[c][o], h[c], z); out = z rounded to bf16.  Implemented for C == 32 only.
+ * One launch on the context's stream, asynchronous, no atomics.  LFD_ERR_INVALID: a null required pointer, exactly one of pw_wT / pw_b,
+ * B, C, H or W < 1, pw_wT with C != 32, H or W > 32768, B C H W > 2^31 - 1, out overlapping x.  lfd_refiner_block_host: the same routine
+ * over host pointers on a host context's threads - the same bits, whatever the thread count. */
+int lfd_refiner_block(lfd_context* ctx, const void* x, int32_t x_is_f32, int32_t B, int32_t C, int32_t H, int32_t W,
+                      const float* dw_w, const float* scale, const float* shift, const float* pw_wT, const float* pw_b, uint16_t* out);
+int lfd_refiner_block_host(lfd_context* ctx, const void* x, int32_t x_is_f32, int32_t B, int32_t C, int32_t H, int32_t W,
+                           const float* dw_w, const float* scale, const float* shift, const float* pw_wT, const float* pw_b, uint16_t* out);
+
 /* Forward-backward consistency gate on RoMa-v2's two warps (upstream has no counterpart: it reads warp_AB / overlap_AB only and its
  * "certainty threshold" is a floor, so a match that slid along its epipolar line - what a dense matcher produces at occlusions and depth steps -
  * passes every two-view test).  For each of n_pairs (reference, neighbour) pairs (1..LFD_MAX_SLOTS; the tables are HOST arrays of n_pairs DEVICE
@@ -696,7 +713,7 @@ int lfd_host_eval_correspondence(const float* cam1, const float* cam2, float xa_
  * The per-cell arithmetic is the host build of the very source the kernels compile (csrc/lfd_geometry.hpp; IEEE
  * division / square root where the device uses the 1-ulp v_rcp / v_sqrt), spread over n_threads std::threads
  * (<= 0: all hardware threads).  A host context accepts lfd_upload_cameras, lfd_last_error, lfd_destroy and the
- * *_host calls (the three below, lfd_local_corr_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host, lfd_consensus_filter_host, lfd_freespace_filter_host, lfd_fuse_oriented_host, lfd_knn_dist2_host and lfd_pack_gaussians_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
+ * *_host calls (the three below, lfd_local_corr_host, lfd_refiner_block_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host, lfd_consensus_filter_host, lfd_freespace_filter_host, lfd_fuse_oriented_host, lfd_knn_dist2_host and lfd_pack_gaussians_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
  * context: neither side ever stands in for the other.  Semantics (orders, counts, optional outputs, LFD_ERR_CAPACITY
  * with valid counts) are those of lfd_aggregate / lfd_triangulate_dense / lfd_triangulate_indexed. */
 int lfd_create_host(int32_t n_threads, lfd_context** out);

@@ -190,6 +190,8 @@ def load_library() -> C.CDLL:
     lib.lfd_quantise_rgb.argtypes = [ctxp, C.c_void_p, C.c_int64, C.c_void_p]
     lib.lfd_local_corr.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]
     lib.lfd_local_corr_host.argtypes = list(lib.lfd_local_corr.argtypes)
+    lib.lfd_refiner_block.argtypes = [ctxp, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 6
+    lib.lfd_refiner_block_host.argtypes = list(lib.lfd_refiner_block.argtypes)
     lib.lfd_cycle_gate.argtypes = ([ctxp, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                    C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p])
     lib.lfd_cycle_gate_host.argtypes = list(lib.lfd_cycle_gate.argtypes)
@@ -259,7 +261,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -757,6 +759,34 @@ def _local_corr_arguments(a, bf, warp, device):
         if bf.stride(3) != 1 or any(s % 4 for s in bf.stride()[:3]) or bf.data_ptr() % 16:
             bf = bf.contiguous()
     return a.detach(), bf.detach(), warp.detach().contiguous(), (B, N, Cc, K, H1, W1)
+
+
+def _refiner_block_call(fn, ctx, x, dw_w, scale, shift, pw_wt, pw_b, device):
+    """Shapes, dtypes and device of a refiner_block call checked, the entry point ``fn`` called; (rc, out).  ``x`` (B, C, H, W) bf16 or f32 - a
+    non-contiguous one is copied to contiguous NCHW first, same values -, ``dw_w`` (C, 25) or (C, 1, 5, 5), ``scale`` / ``shift`` (C), and
+    either both or neither of ``pw_wt`` (C, C) and ``pw_b`` (C): f32.  Everything else is the library's to refuse."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("refiner_block: x must be a bfloat16 or float32 tensor of 4 dimensions (B, C, H, W)")
+    B, Cc, H, W = (int(v) for v in x.shape)
+    small = {"dw_w": (dw_w, Cc * 25), "scale": (scale, Cc), "shift": (shift, Cc)}
+    if (pw_wt is None) != (pw_b is None):
+        raise ValueError("refiner_block: pw_wt and pw_b must both be given or both be None")
+    if pw_wt is not None:
+        small.update(pw_wt=(pw_wt, Cc * Cc), pw_b=(pw_b, Cc))
+    held = {}
+    for name, (t, n) in small.items():
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != n:
+            raise ValueError(f"refiner_block: {name} must be a float32 tensor of {n} elements for C = {Cc}")
+        held[name] = t.detach().contiguous()
+    for name, t in [("x", x)] + list(held.items()):
+        if t.device != device:
+            raise ValueError(f"refiner_block: {name} lives on {t.device}, this context computes on {device}")
+    x = x.detach().contiguous()
+    out = torch.empty((B, Cc, H, W), dtype=torch.bfloat16, device=device)
+    ptr = lambda name: held[name].data_ptr() if name in held else None      # noqa: E731
+    rc = fn(ctx, x.data_ptr(), int(x.dtype == torch.float32), B, Cc, H, W, ptr("dw_w"), ptr("scale"), ptr("shift"), ptr("pw_wt"), ptr("pw_b"),
+            out.data_ptr())
+    return rc, out
 
 
 def _cycle_gate_arguments(cert, warp_ab, warp_ba, axes, device):
@@ -1342,6 +1372,16 @@ class HipDensifier:
         self._check(self._lib.lfd_local_corr(self._ctx, a.data_ptr(), bf.data_ptr(), warp.data_ptr(), *dims, sa, sb, out.data_ptr()), "lfd_local_corr")
         return out
 
+    def refiner_block(self, x: torch.Tensor, dw_w: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, pw_wt: Optional[torch.Tensor] = None,
+                      pw_b: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One conv block of RoMa-v2's refiners (lfd_refiner_block): depthwise 5x5 with the weights ``dw_w`` (C, 25) on ``x``
+        (B, C, H, W; bf16, or f32 that is rounded to bf16 on load), the folded BatchNorm ``scale`` / ``shift`` (C), ReLU, rounded to bf16; with
+        ``pw_wt`` (C, C; the 1x1 weights TRANSPOSED) and ``pw_b`` (C) the 1x1 convolution as well - C == 32 only.  (B, C, H, W) bf16.  One
+        launch on the context's stream; a non-contiguous ``x`` is copied to contiguous NCHW first."""
+        rc, out = _refiner_block_call(self._lib.lfd_refiner_block, self._ctx, x, dw_w, scale, shift, pw_wt, pw_b, self.device)
+        self._check(rc, "lfd_refiner_block")
+        return out
+
     def cycle_gate(self, cert, warp_ab, warp_ba, w_match: int, h_match: int, certainty_thresh: float, cycle_thresh_px: float, axes=None,
                    inplace: bool = False, with_err: bool = False, rejected: Optional[torch.Tensor] = None):
         """Forward-backward consistency gate (lfd_cycle_gate) over up to 16 pairs in one launch on the context's stream.
@@ -1801,6 +1841,13 @@ class HostDensifier:
         sa, sb = (C.c_int64 * 3)(*a.stride()), (C.c_int64 * 4)(*bf.stride())
         self._check(self._lib.lfd_local_corr_host(self._ctx, a.data_ptr(), bf.data_ptr(), warp.data_ptr(), *dims, sa, sb, out.data_ptr()),
                     "lfd_local_corr_host")
+        return out
+
+    def refiner_block(self, x: torch.Tensor, dw_w: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, pw_wt: Optional[torch.Tensor] = None,
+                      pw_b: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """HipDensifier.refiner_block over CPU tensors (lfd_refiner_block_host): the same routine, the same bits, whatever the thread count."""
+        rc, out = _refiner_block_call(self._lib.lfd_refiner_block_host, self._ctx, x, dw_w, scale, shift, pw_wt, pw_b, self.device)
+        self._check(rc, "lfd_refiner_block_host")
         return out
 
     def cycle_gate(self, cert, warp_ab, warp_ba, w_match: int, h_match: int, certainty_thresh: float, cycle_thresh_px: float, axes=None,

@@ -84,7 +84,8 @@ def _make_matcher(config, dev, progress_callback):
     if not cached:
         log.info("RoMaV2 weights not found in cache; expected cache paths: " + ", ".join(romav2_cached_weights_paths()))
     matcher = RomaMatcher(device=str(dev), mode="outdoor", setting=config.roma_setting, pairs_per_forward=int(config.pairs_per_forward),
-                          fused_local_corr=bool(config.exp("fused_local_corr")))
+                          fused_local_corr=bool(config.exp("fused_local_corr")),
+                          fused_refiner_blocks=bool(config.exp("fused_refiner_blocks")))
     if float(config.exp("cycle_thresh_px")) > 0.0:       # (a matcher built here starts with the backward warp off)
         matcher.set_backward_warp(True)
     if _wants_precision(config):                         # (... and hands out no precision planes)
@@ -273,6 +274,11 @@ def run_dense_pipeline(
             elif config.exp("fused_local_corr"):
                 raise ValueError("experimental['fused_local_corr'] asks the matcher to run RoMa-v2's local correlation in the HIP kernel, but the "
                                  f"injected matcher ({type(matcher).__name__}) does not declare supports_fused_local_corr")
+            if bool(getattr(matcher, "supports_fused_refiner_blocks", False)):
+                matcher.set_fused_refiner_blocks(bool(config.exp("fused_refiner_blocks")))
+            elif config.exp("fused_refiner_blocks"):
+                raise ValueError("experimental['fused_refiner_blocks'] asks the matcher to run the conv blocks of RoMa-v2's refiners in the HIP kernel, "
+                                 f"but the injected matcher ({type(matcher).__name__}) does not declare supports_fused_refiner_blocks")
             if bool(getattr(matcher, "supports_backward_warp", False)):
                 matcher.set_backward_warp(float(config.exp("cycle_thresh_px")) > 0.0)
             elif float(config.exp("cycle_thresh_px")) > 0.0:

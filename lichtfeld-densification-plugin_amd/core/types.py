@@ -45,6 +45,10 @@ EXPERIMENTAL_DEFAULTS = {
     # RoMa-v2's local correlation (the conv refiners' one custom operator, CUDA-only upstream) through lfd_local_corr instead of the model's
     # grid_sample fallback (core/local_corr.py): within the derived error bound of the fallback, not bit for bit - hence off
     "fused_local_corr": False,
+    # the conv blocks of RoMa-v2's refiners (depthwise 5x5, eval-mode BatchNorm, ReLU, 1x1 convolution; 27 per direction and pair) through
+    # lfd_refiner_block instead of torch's separate kernels (core/refiner_blocks.py): one read and one write of the activation.
+    # Rounds less often than the bf16 autocast sequence - closer to the f32 evaluation, not bit-identical to the model's own path - hence off
+    "fused_refiner_blocks": False,
     # forward-backward consistency filter on the matcher's two warps (lfd_cycle_gate): a cell whose round trip A -> B -> A misses
     # its start by more than this many pixels of the match image loses the pair (certainty exactly 0, as if mask_b had masked it out).
     # 0.0 = off: the backward warp is not asked for and no new code runs.  Needs a matcher that hands out warp_BA (supports_backward_warp).
@@ -377,6 +381,8 @@ class DensePipelineConfig:
             if dense and self.exp("dense_tile_segments"):
                 return ("experimental['min_freespace_violations'] needs the cloud as arrays with per-reference counts; dense mode with "
                         "experimental['dense_tile_segments'] retires tiles unordered")
+        if not isinstance(self.exp("fused_refiner_blocks"), (bool, np.bool_)):
+            return "experimental['fused_refiner_blocks'] must be True or False"
         if not isinstance(self.exp("undistort_images"), (bool, np.bool_)):
             return "experimental['undistort_images'] must be True or False"
         normals = self.exp("estimate_normals")

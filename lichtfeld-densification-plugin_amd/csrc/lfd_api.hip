@@ -15,6 +15,7 @@
 
 #include "lfd_context.hpp"
 #include "lfd_corr.hpp"
+#include "lfd_block.hpp"
 #include "lfd_cycle.hpp"
 #include "lfd_support.hpp"
 #include "lfd_refine.hpp"
@@ -108,6 +109,7 @@ extern "C" __global__ void lfd_freespace_count_kernel(const float* xyz, long lon
                                                       const uint32_t* zbuf, int pw, int ph, float tol, int min_violations, uint8_t* keep,
                                                       uint8_t* violations, uint8_t* supports);
 hipError_t lfd_corr_launch(const LfdCorrArgs& p, hipStream_t stream);     // lfd_corr.hip
+hipError_t lfd_block_launch(const LfdBlockArgs& p, hipStream_t stream);   // lfd_block.hip
 hipError_t lfd_cycle_launch(const LfdCycleArgs& p, hipStream_t stream);   // lfd_cycle.hip
 hipError_t lfd_support_launch(const LfdSupportArgs& p, hipStream_t stream);   // lfd_support.hip
 hipError_t lfd_refine_launch(const LfdRefineArgs& p, hipStream_t stream);     // lfd_refine.hip
@@ -1843,6 +1845,19 @@ int lfd_local_corr(lfd_context* ctx, const float* A, const float* Bf, const floa
     if ((long long)B * N * K == 0) return LFD_OK;
     LFD_HIP(ctx, hipSetDevice(ctx->device));
     LFD_HIP(ctx, lfd_corr_launch(p, ctx->stream));
+    return LFD_OK;
+}
+
+// ---- one conv block of RoMa-v2's refiners (lfd_block.hip) --------------------------------------------------------------------------------
+int lfd_refiner_block(lfd_context* ctx, const void* x, int32_t x_is_f32, int32_t B, int32_t C, int32_t H, int32_t W, const float* dw_w,
+                      const float* scale, const float* shift, const float* pw_wT, const float* pw_b, uint16_t* out) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    LfdBlockArgs p;
+    if (const char* why = lfd_block_fill(x, x_is_f32, B, C, H, W, dw_w, scale, shift, pw_wT, pw_b, out, p))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_refiner_block: ") + why);
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    LFD_HIP(ctx, lfd_block_launch(p, ctx->stream));
     return LFD_OK;
 }
 

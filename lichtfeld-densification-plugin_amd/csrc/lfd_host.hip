@@ -18,6 +18,7 @@
 
 #include "lfd_context.hpp"
 #include "lfd_corr.hpp"
+#include "lfd_block.hpp"
 #include "lfd_cycle.hpp"
 #include "lfd_support.hpp"
 #include "lfd_refine.hpp"
@@ -284,6 +285,24 @@ int lfd_local_corr_host(lfd_context* ctx, const float* A, const float* Bf, const
                 out[e] = lfd_corr_sample(p.a + b * p.sa_b + n * p.sa_n, p.sa_c, p.bf + b * p.sb_b, p.sb_y, p.sb_x, p.sb_c, C, W1, H1, warp[2 * e], warp[2 * e + 1]);
             }
         }
+    });
+    return LFD_OK;
+}
+
+int lfd_refiner_block_host(lfd_context* ctx, const void* x, int32_t x_is_f32, int32_t B, int32_t C, int32_t H, int32_t W, const float* dw_w,
+                           const float* scale, const float* shift, const float* pw_wT, const float* pw_b, uint16_t* out) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    LfdBlockArgs p;
+    if (const char* why = lfd_block_fill(x, x_is_f32, B, C, H, W, dw_w, scale, shift, pw_wT, pw_b, out, p))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_refiner_block_host: ") + why);
+    // a chunk is one row of one plane (of one image with the pointwise part): every output element is computed by exactly one chunk, from the
+    // inputs alone, so the thread count never shows
+    const int planes = pw_wT ? B : B * C;                          // planes * H <= B C H W < 2^31
+    parallel_chunks(ctx, planes * H, [&](int chunk) {
+        const int pl = chunk / H, y = chunk - pl * H;
+        const int b = pw_wT ? pl : pl / C, c = pw_wT ? 0 : pl - b * C;
+        for (int xx = 0; xx < W; ++xx) lfd_block_pixel(p, b, c, y, xx);
     });
     return LFD_OK;
 }

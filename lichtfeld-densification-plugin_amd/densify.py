@@ -735,6 +735,8 @@ def _experimental_from_args(args) -> dict:
         exp["freespace_plane_cells"] = int(args.freespace_plane_cells)
     if bool(getattr(args, "undistort_images", False)):
         exp["undistort_images"] = True
+    if bool(getattr(args, "fused_refiner_blocks", False)):
+        exp["fused_refiner_blocks"] = True
     if bool(getattr(args, "estimate_normals", False)):
         exp["estimate_normals"] = True
     if getattr(args, "normal_radius_cells", None) is not None:
@@ -819,6 +821,9 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--undistort_images", action="store_true",
                     help="resample every image (and its mask) through its COLMAP camera's distortion model (SIMPLE_RADIAL, RADIAL, OPENCV, "
                          "FULL_OPENCV) into the pinhole image of the same intrinsics before it is matched; other distorted models are refused")
+    ap.add_argument("--fused_refiner_blocks", action="store_true",
+                    help="run the conv blocks of RoMa-v2's refiners (depthwise 5x5, BatchNorm, ReLU, 1x1) in this package's fused HIP kernel instead "
+                         "of torch's separate kernels: more accurate than the bf16 autocast sequence, not bit-identical to it")
     ap.add_argument("--estimate_normals", action="store_true",
                     help="give every point a unit surface normal, fitted to its winning neighbour's warp around its grid cell and oriented towards "
                          "its reference's camera: the PLY then has x y z nx ny nz red green blue vertices (needs a .ply --out_name)")
