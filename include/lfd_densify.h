@@ -701,6 +701,10 @@ int lfd_host_fundamental(const float* K1, const float* R1, const float* t1, cons
  * (f64 inverse iteration on A^T A), on the HOST build of the same source; out4 is un-normalised.  Returns the
  * number of solves made (>= 3) or a negative lfd_status.  CPU unit tests compare it with an f64 SVD. */
 int lfd_host_null_vector(const float* A16, double* out4);
+/* The same for the re-triangulation's solver (lfd_refine_multiview[_weighted], any number of views): the smallest eigenvector of the
+ * symmetric 4x4 matrix whose upper triangle is M10 (m00 m01 m02 m03 m11 m12 m13 m22 m23 m33, f64), HOST build; out4 is un-normalised.
+ * Returns the number of solves made (>= 3) or a negative lfd_status. */
+int lfd_host_null_vector_sym(const double* M10, double* out4);
 /* One correspondence through the per-cell routine on the HOST build of the same source (debug /
  * CPU unit tests of the arithmetic; not a fallback: no batch entry point uses it).
  * cam1/cam2: K[9] R[9] t[3] P[12] C[3] w h (as floats, 38 values).  out: x y z r g b err keep. */

@@ -255,6 +255,8 @@ def load_library() -> C.CDLL:
     lib.lfd_host_fundamental.argtypes = [fptr] * 7
     lib.lfd_host_null_vector.argtypes = [fptr, C.POINTER(C.c_double)]
     lib.lfd_host_null_vector.restype = C.c_int
+    lib.lfd_host_null_vector_sym.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.lfd_host_null_vector_sym.restype = C.c_int
     lib.lfd_host_eval_correspondence.argtypes = [fptr, fptr, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
                                                  C.c_int32, C.POINTER(lfd_params), fptr]
     for name in ("lfd_create", "lfd_set_stream", "lfd_reload_env", "lfd_kernel_timing", "lfd_kernel_timing_read", "lfd_upload_cameras", "lfd_prepare_batch", "lfd_aggregate", "lfd_triangulate_dense",
@@ -423,6 +425,18 @@ def host_null_vector(A) -> "tuple[np.ndarray, int]":
     it = load_library().lfd_host_null_vector(_fp(a), out.ctypes.data_as(C.POINTER(C.c_double)))
     if it < 0:
         raise HipBackendError("lfd_host_null_vector failed")
+    return out, int(it)
+
+
+def host_null_vector_sym(M) -> "tuple[np.ndarray, int]":
+    """Smallest eigenvector (un-normalised, f64) of a symmetric positive semi-definite 4x4 matrix through the routine the multi-view
+    re-triangulation solves with (host build of csrc/lfd_refine.hpp::lfd_null_vector_sym), and the number of solves it made."""
+    M = np.asarray(M, np.float64).reshape(4, 4)
+    m = np.ascontiguousarray(M[np.triu_indices(4)], np.float64)
+    out = np.zeros(4, np.float64)
+    it = load_library().lfd_host_null_vector_sym(m.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_double)))
+    if it < 0:
+        raise HipBackendError("lfd_host_null_vector_sym failed")
     return out, int(it)
 
 

@@ -2163,6 +2163,11 @@ int lfd_host_null_vector(const float* A16, double* out4) {
     return lfd_null_vector(A16, out4);
 }
 
+int lfd_host_null_vector_sym(const double* M10, double* out4) {
+    if (!M10 || !out4) return -LFD_ERR_INVALID;
+    return lfd_null_vector_sym(M10, out4);
+}
+
 int lfd_host_eval_correspondence(const float* cam1, const float* cam2, float xa_norm, float ya_norm, float xb_norm,
                                  float yb_norm, int32_t w_match, int32_t h_match, const lfd_params* params, float* out8) {
     if (!cam1 || !cam2 || !params || !out8 || w_match <= 1 || h_match <= 1) return LFD_ERR_INVALID;

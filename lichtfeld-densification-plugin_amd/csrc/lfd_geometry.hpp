@@ -294,6 +294,135 @@ LFD_HD bool lfd_nullvec_settled(double n0, double n1, double n2, double n3, doub
     return !more || bad;
 }
 
+// ---- the pieces of the solver, shared by lfd_null_vector_rows and lfd_null_vector_sym (lfd_refine.hpp) ------------------------------------
+// They work on the caller's variables: the upper triangle m00 .. m33 of M, the iterate x0 .. x3, the solve counter `it` and `settled`.
+//
+// M - sh I = L D L^T from the diagonal q_ii = m_ii - sh (pass 0: the m_ii themselves); s_i = d3 / d_i
+#define LFD_NULLVEC_FACTORISE_D(D, q00, q11, q22, q33)                                                                            \
+    const double r0 = lfd_recip_refined(q00);                                                                           \
+    D l10 = m01 * r0, l20 = m02 * r0, l30 = m03 * r0;                                                        \
+    const double d1 = fma(-l10, m01, q11);                                                                              \
+    const double n12 = fma(-l10, m02, m12), n13 = fma(-l10, m03, m13);                                                  \
+    const double n22 = fma(-l20, m02, q22), n23 = fma(-l20, m03, m23), n33 = fma(-l30, m03, q33);                       \
+    const double r1 = lfd_recip_refined(d1);                                                                            \
+    D l21 = n12 * r1, l31 = n13 * r1;                                                                        \
+    const double d2 = fma(-l21, n12, n22);                                                                              \
+    const double p23 = fma(-l21, n13, n23), p33 = fma(-l31, n13, n33);                                                  \
+    const double r2 = lfd_recip_refined(d2);                                                                            \
+    D l32 = p23 * r2;                                                                                              \
+    const double d3 = fma(-l32, p23, p33);                                                                              \
+    D s0 = d3 * r0, s1 = d3 * r1, s2 = d3 * r2
+#define LFD_NULLVEC_FACTORISE(q00, q11, q22, q33) LFD_NULLVEC_FACTORISE_D(const double, q00, q11, q22, q33)
+// b <- d3 * (M - sh I)^-1 a : forward (L), diagonal, backward (L^T).  Every read of a precedes the first write of b, so b may be the very variables of a
+#define LFD_NULLVEC_SOLVE(a0, a1, a2, a3, b0, b1, b2, b3)                                                                       \
+    {                                                                                                                   \
+        const double y1 = fma(-l10, a0, a1);                                                                            \
+        const double y2 = fma(-l21, y1, fma(-l20, a0, a2));                                                             \
+        const double y3 = fma(-l32, y2, fma(-l31, y1, fma(-l30, a0, a3)));                                              \
+        const double z0 = a0 * s0, z1 = y1 * s1, z2 = y2 * s2;                                                          \
+        b3 = y3;                                                                                                        \
+        b2 = fma(-l32, b3, z2);                                                                                         \
+        b1 = fma(-l21, b2, fma(-l31, b3, z1));                                                                          \
+        b0 = fma(-l10, b1, fma(-l20, b2, fma(-l30, b3, z0)));                                                           \
+    }
+// A solve multiplies |x| by up to d3 / mu4, which for a point at infinity (x3 / |x| = t -> 0: the third pivot is ~t^2) is ~1 / t^2, and
+// such a cell never settles (lfd_nullvec_settled): nine solves of pass 0 took |x| beyond 1e154, where the squares of the caller's
+// w -> 0 test overflow (Inf < Inf: the guard was skipped).  Pass 0's tail loop (before solve 5) and the shifted passes (before their solve 5; they start
+// from a rescaled x) therefore bring an iterate above 2^64 back by an exact power of two - directions, the settled test and every quotient
+// x_i / x_3 are unchanged, an iterate below 2^64 keeps its bits, and four solves at 1e28 each stay below 1e154.
+#define LFD_NULLVEC_KEEP_IN_RANGE()                                                                                             \
+    {                                                                                                                   \
+        const double mag = fabs(x0) + fabs(x1) + fabs(x2) + fabs(x3);                                                   \
+        int em;                                                                                                         \
+        (void)frexp(mag, &em);                                                                                          \
+        const int dn = ((mag > 0x1p64) && (mag < 1.7976931348623157e308)) ? -em : 0;       /* (no branch: times 2^0 otherwise) */ \
+        x0 = ldexp(x0, dn); x1 = ldexp(x1, dn); x2 = ldexp(x2, dn); x3 = ldexp(x3, dn);                                 \
+    }
+#define LFD_NULLVEC_SHIFTED_SOLVES()                                                                                            \
+        for (int k = 1; k <= LFD_NULLVEC_MAXIT; ++k) {                                                                  \
+            if (k == 5) LFD_NULLVEC_KEEP_IN_RANGE();                                                                            \
+            const double o0 = x0, o1 = x1, o2 = x2, o3 = x3;                                                            \
+            LFD_NULLVEC_SOLVE(x0, x1, x2, x3, x0, x1, x2, x3);                                                                  \
+            ++it;                                                                                                       \
+            if (k >= 2 && lfd_nullvec_settled(x0, x1, x2, x3, o0, o1, o2, o3)) { settled = true; break; }               \
+        }
+#define LFD_NULLVEC_NEGATIVE_PIVOT() ((r0 < 0.0) || (r1 < 0.0) || (r2 < 0.0) || (d3 < 0.0))       /* (the reciprocals carry the pivots' signs) */
+#define LFD_NULLVEC_PIVOTS_AT_SH(BUILD_M)                                                                                       \
+            {                                                                                                           \
+                BUILD_M();                                                                                              \
+                LFD_NULLVEC_FACTORISE(m00 - sh, m11 - sh, m22 - sh, m33 - sh);                                                  \
+                (void)s0; (void)s1; (void)s2;                                                                           \
+                neg = LFD_NULLVEC_NEGATIVE_PIVOT();                                                                             \
+            }
+// The shifted passes: a pass that has not settled after LFD_NULLVEC_MAXIT solves (sigma4/sigma3 close to 1) is followed by a pass shifted by
+// the Rayleigh quotient of its result, which separates the two smallest eigenvalues.  `BUILD_M()` (re)builds m00 .. m33 where the caller does not
+// keep them across the solves (lfd_null_vector_rows), and is empty where it does (lfd_null_vector_sym).
+//
+// The shift.  x is rescaled by an exact power of two.  rho >= mu4 lies between the two smallest eigenvalues and could sit closer to mu3; backing
+// off by the residual norm |Mx - rho x| / |x| ~ eps (mu3 - mu4) puts the shift below mu4 when x is close to v4: the shifted matrix stays
+// positive definite and the iteration converges to v4 at a rate ~eps instead of q.
+//
+// The search.  When pass 0 started nearly orthogonal to v4 and q is close to 1, x is still dominated by v3: rho then sits just below mu3, the
+// residual norm is only ~eps (mu3 - mu4) and the shift lands between mu4 and mu3, next to mu3 - the pass converged to v3.  The pivots
+// tell (Sylvester's law of inertia): M - sh I = L D L^T has as many negative d_i as M has eigenvalues below sh, so a negative pivot
+// means sh > mu4.  The shift then steps down by 2^ex, 2^(ex+1), ... (from 2^-LFD_NULLVEC_FIRST_STEP of itself) until no pivot is negative (M is positive
+// semi-definite: at the latest below 0), which brackets mu4 in [sh, sh + 2^(ex-1)], a bracket no wider than about twice the
+// distance covered, and LFD_NULLVEC_BISECT bisections move sh up inside it: sh ends below mu4 by at most ~1/2^(LFD_NULLVEC_BISECT-1)
+// of that distance (~mu3 - mu4), the pass converges to v4 at a rate of that order and the next shift comes from a vector that v4
+// dominates.  A shift without a negative pivot - every pass of a cell that was right before - is used as it is, same bits.  (NaN
+// pivots compare false: such a cell goes on as before and leaves through the NaN exit.)  The search is a branch of its own with
+// its own solves, so that the common path carries nothing for it, and it carries sh and ex only: the dense kernels have no
+// register to spare.  x - dominated by v3 - is not carried through the search: the pass starts afresh from e4, the first solve free as in
+// pass 0.
+#define LFD_NULLVEC_SHIFTED_PASSES(BUILD_M)                                                                             \
+    for (int pass = 1; !settled && pass < LFD_NULLVEC_PASSES; ++pass) {                                                 \
+        BUILD_M();                                                                                                      \
+        const double sc = lfd_pow2_inv_scale(fabs(x0) + fabs(x1) + fabs(x2) + fabs(x3));                                \
+        x0 *= sc; x1 *= sc; x2 *= sc; x3 *= sc;                                                                         \
+        const double t0 = fma(m03, x3, fma(m02, x2, fma(m01, x1, m00 * x0)));                                           \
+        const double t1 = fma(m13, x3, fma(m12, x2, fma(m11, x1, m01 * x0)));                                           \
+        const double t2 = fma(m23, x3, fma(m22, x2, fma(m12, x1, m02 * x0)));                                           \
+        const double t3 = fma(m33, x3, fma(m23, x2, fma(m13, x1, m03 * x0)));                                           \
+        const double num = fma(x3, t3, fma(x2, t2, fma(x1, t1, x0 * t0)));                                              \
+        const double den = fma(x3, x3, fma(x2, x2, fma(x1, x1, x0 * x0)));                                              \
+        const double rden = lfd_recip_refined(den);                                                                     \
+        const double rho = num * rden;                                                                                  \
+        const double e0 = fma(-rho, x0, t0), e1 = fma(-rho, x1, t1), e2 = fma(-rho, x2, t2), e3 = fma(-rho, x3, t3);    \
+        const double rr = fma(e3, e3, fma(e2, e2, fma(e1, e1, e0 * e0)));                                               \
+        double sh = rho - lfd_sqrt_rare(rr * rden);                                                                     \
+        BUILD_M();                                                                                                      \
+        {                                                                                                               \
+            LFD_NULLVEC_FACTORISE(m00 - sh, m11 - sh, m22 - sh, m33 - sh);                                                      \
+            if (!LFD_NULLVEC_NEGATIVE_PIVOT()) {                                                                                \
+                LFD_NULLVEC_SHIFTED_SOLVES();                                                                                   \
+                continue;                                                                                               \
+            }                                                                                                           \
+        }                                                                                                               \
+        {                                                                                                               \
+            int ex;                                                                                                     \
+            (void)frexp(sh, &ex);                                                                                       \
+            ex -= LFD_NULLVEC_FIRST_STEP;                                                                               \
+            bool neg = true;                                                                                            \
+            while (neg) {                                       /* stepping down */                                    \
+                sh -= ldexp(1.0, ex);                                                                                   \
+                ++ex;                                                                                                   \
+                LFD_NULLVEC_PIVOTS_AT_SH(BUILD_M);                                                                              \
+            }                                                                                                           \
+            for (int b = 1; b <= LFD_NULLVEC_BISECT; ++b) {     /* mu4 lies in [sh, sh + 2^(ex-1)]: bisections */      \
+                sh += ldexp(1.0, ex - 1 - b);                                                                           \
+                LFD_NULLVEC_PIVOTS_AT_SH(BUILD_M);                                                                              \
+                if (neg) sh -= ldexp(1.0, ex - 1 - b);                                                                  \
+            }                                                                                                           \
+            BUILD_M();                                                                                                  \
+            LFD_NULLVEC_FACTORISE(m00 - sh, m11 - sh, m22 - sh, m33 - sh);                                                      \
+            x3 = 1.0;                                                                                                   \
+            x2 = -l32;                                                                                                  \
+            x1 = fma(-l21, x2, -l31);                                                                                   \
+            x0 = fma(-l10, x1, fma(-l20, x2, -l30));                                                                    \
+            LFD_NULLVEC_SHIFTED_SOLVES();                                                                                       \
+        }                                                                                                               \
+    }
+
 // c[4]: un-normalised multiple of the singular vector; returns the number of solves made.
 // `rows(Af)` fills the 4x4 matrix (row-major f32).  It is called at the start of EVERY pass, so neither the matrix
 // nor M = A^T A stays live across the solves (30 registers on the device); the shifted passes, which are the only
@@ -318,52 +447,9 @@ LFD_HD int lfd_null_vector_rows(RowFn rows, double* c) {
             m22 = fma(a2, a2, m22); m23 = fma(a2, a3, m23); m33 = fma(a3, a3, m33);                                     \
         }                                                                                                               \
     }
-    // M - sh I = L D L^T from the diagonal q_ii = m_ii - sh (pass 0: the m_ii themselves); s_i = d3 / d_i
-#define LFD_FACTORISE_D(D, q00, q11, q22, q33)                                                                            \
-    const double r0 = lfd_recip_refined(q00);                                                                           \
-    D l10 = m01 * r0, l20 = m02 * r0, l30 = m03 * r0;                                                        \
-    const double d1 = fma(-l10, m01, q11);                                                                              \
-    const double n12 = fma(-l10, m02, m12), n13 = fma(-l10, m03, m13);                                                  \
-    const double n22 = fma(-l20, m02, q22), n23 = fma(-l20, m03, m23), n33 = fma(-l30, m03, q33);                       \
-    const double r1 = lfd_recip_refined(d1);                                                                            \
-    D l21 = n12 * r1, l31 = n13 * r1;                                                                        \
-    const double d2 = fma(-l21, n12, n22);                                                                              \
-    const double p23 = fma(-l21, n13, n23), p33 = fma(-l31, n13, n33);                                                  \
-    const double r2 = lfd_recip_refined(d2);                                                                            \
-    D l32 = p23 * r2;                                                                                              \
-    const double d3 = fma(-l32, p23, p33);                                                                              \
-    D s0 = d3 * r0, s1 = d3 * r1, s2 = d3 * r2
-#define LFD_FACTORISE(q00, q11, q22, q33) LFD_FACTORISE_D(const double, q00, q11, q22, q33)
-    // b <- d3 * (M - sh I)^-1 a : forward (L), diagonal, backward (L^T).  Every read of a precedes the first write of b, so b may be the very variables of a
-#define LFD_SOLVE(a0, a1, a2, a3, b0, b1, b2, b3)                                                                       \
-    {                                                                                                                   \
-        const double y1 = fma(-l10, a0, a1);                                                                            \
-        const double y2 = fma(-l21, y1, fma(-l20, a0, a2));                                                             \
-        const double y3 = fma(-l32, y2, fma(-l31, y1, fma(-l30, a0, a3)));                                              \
-        const double z0 = a0 * s0, z1 = y1 * s1, z2 = y2 * s2;                                                          \
-        b3 = y3;                                                                                                        \
-        b2 = fma(-l32, b3, z2);                                                                                         \
-        b1 = fma(-l21, b2, fma(-l31, b3, z1));                                                                          \
-        b0 = fma(-l10, b1, fma(-l20, b2, fma(-l30, b3, z0)));                                                           \
-    }
-    // A solve multiplies |x| by up to d3 / mu4, which for a point at infinity (x3 / |x| = t -> 0: the third pivot is ~t^2) is ~1 / t^2, and
-    // such a cell never settles (lfd_nullvec_settled): nine solves of pass 0 took |x| beyond 1e154, where the squares of the caller's
-    // w -> 0 test overflow (Inf < Inf: the guard was skipped).  Pass 0's tail loop (before solve 5) and the shifted passes (before their solve 5; they start
-    // from a rescaled x) therefore bring an iterate above 2^64 back by an exact power of two - directions, the settled test and every quotient
-    // x_i / x_3 are unchanged, an iterate below 2^64 keeps its bits, and four solves at 1e28 each stay below 1e154.
-#define LFD_KEEP_IN_RANGE()                                                                                             \
-    {                                                                                                                   \
-        const double mag = fabs(x0) + fabs(x1) + fabs(x2) + fabs(x3);                                                   \
-        int em;                                                                                                         \
-        (void)frexp(mag, &em);                                                                                          \
-        const int dn = ((mag > 0x1p64) && (mag < 1.7976931348623157e308)) ? -em : 0;       /* (no branch: times 2^0 otherwise) */ \
-        x0 = ldexp(x0, dn); x1 = ldexp(x1, dn); x2 = ldexp(x2, dn); x3 = ldexp(x3, dn);                                 \
-    }
     // Convergence monitor: the direction change between successive iterates is the error of the older one (the
     // iteration is linear with ratio q), so once it drops below LFD_NULLVEC_TOL the iterate just computed is within
     // q * TOL of v4.  Ordinary cells (q ~ 1e-4) settle after two solves.
-    // A pass that has not settled after LFD_NULLVEC_MAXIT solves (sigma4/sigma3 close to 1) is followed by a
-    // pass shifted by the Rayleigh quotient of its result, which separates the two smallest eigenvalues.
     //
     // Pass 0 is written out: it factorises M itself (no shift to subtract), takes the first solve from e4 for free and makes the
     // loop solves k = 1..4 alternately x -> w and w -> x, so that the test after each reads the previous iterate where it already
@@ -378,123 +464,37 @@ LFD_HD int lfd_null_vector_rows(RowFn rows, double* c) {
     bool settled;
     {
         LFD_BUILD_M();
-        LFD_FACTORISE(m00, m11, m22, m33);
+        LFD_NULLVEC_FACTORISE(m00, m11, m22, m33);
         // first solve from e4: the last column of L^-T
         x3 = 1.0;
         x2 = -l32;
         x1 = fma(-l21, x2, -l31);
         x0 = fma(-l10, x1, fma(-l20, x2, -l30));
         double w0, w1, w2, w3;
-        LFD_SOLVE(x0, x1, x2, x3, w0, w1, w2, w3);                    // k = 1: never tested
-        LFD_SOLVE(w0, w1, w2, w3, x0, x1, x2, x3);                    // k = 2
+        LFD_NULLVEC_SOLVE(x0, x1, x2, x3, w0, w1, w2, w3);                    // k = 1: never tested
+        LFD_NULLVEC_SOLVE(w0, w1, w2, w3, x0, x1, x2, x3);                    // k = 2
         it = 3;
         settled = lfd_nullvec_settled(x0, x1, x2, x3, w0, w1, w2, w3);
         if (!settled) {
-            LFD_SOLVE(x0, x1, x2, x3, w0, w1, w2, w3);                // k = 3
+            LFD_NULLVEC_SOLVE(x0, x1, x2, x3, w0, w1, w2, w3);                // k = 3
             it = 4;
             settled = lfd_nullvec_settled(w0, w1, w2, w3, x0, x1, x2, x3);
             if (settled) { x0 = w0; x1 = w1; x2 = w2; x3 = w3; }
             else {
-                LFD_SOLVE(w0, w1, w2, w3, x0, x1, x2, x3);            // k = 4
+                LFD_NULLVEC_SOLVE(w0, w1, w2, w3, x0, x1, x2, x3);            // k = 4
                 it = 5;
                 settled = lfd_nullvec_settled(x0, x1, x2, x3, w0, w1, w2, w3);
-                if (!settled) LFD_KEEP_IN_RANGE();
+                if (!settled) LFD_NULLVEC_KEEP_IN_RANGE();
                 for (int k = 5; !settled && k <= LFD_NULLVEC_MAXIT; ++k) {
                     const double o0 = x0, o1 = x1, o2 = x2, o3 = x3;
-                    LFD_SOLVE(x0, x1, x2, x3, x0, x1, x2, x3);
+                    LFD_NULLVEC_SOLVE(x0, x1, x2, x3, x0, x1, x2, x3);
                     ++it;
                     settled = lfd_nullvec_settled(x0, x1, x2, x3, o0, o1, o2, o3);
                 }
             }
         }
     }
-    // The shifted passes.
-    for (int pass = 1; !settled && pass < LFD_NULLVEC_PASSES; ++pass) {
-        // Rayleigh quotient of x as the shift; x rescaled by an exact power of two
-        LFD_BUILD_M();
-        const double sc = lfd_pow2_inv_scale(fabs(x0) + fabs(x1) + fabs(x2) + fabs(x3));
-        x0 *= sc; x1 *= sc; x2 *= sc; x3 *= sc;
-        const double t0 = fma(m03, x3, fma(m02, x2, fma(m01, x1, m00 * x0)));
-        const double t1 = fma(m13, x3, fma(m12, x2, fma(m11, x1, m01 * x0)));
-        const double t2 = fma(m23, x3, fma(m22, x2, fma(m12, x1, m02 * x0)));
-        const double t3 = fma(m33, x3, fma(m23, x2, fma(m13, x1, m03 * x0)));
-        const double num = fma(x3, t3, fma(x2, t2, fma(x1, t1, x0 * t0)));
-        const double den = fma(x3, x3, fma(x2, x2, fma(x1, x1, x0 * x0)));
-        const double rden = lfd_recip_refined(den);
-        const double rho = num * rden;
-        // rho >= mu4 lies between the two smallest eigenvalues and could sit closer to mu3; backing off by the
-        // residual norm |Mx - rho x| / |x| ~ eps (mu3 - mu4) puts the shift below mu4 when x is close to v4: the
-        // shifted matrix stays positive definite and the iteration converges to v4 at a rate ~eps instead of q
-        const double e0 = fma(-rho, x0, t0), e1 = fma(-rho, x1, t1), e2 = fma(-rho, x2, t2), e3 = fma(-rho, x3, t3);
-        const double rr = fma(e3, e3, fma(e2, e2, fma(e1, e1, e0 * e0)));
-        double sh = rho - lfd_sqrt_rare(rr * rden);
-        LFD_BUILD_M();
-        // When pass 0 started nearly orthogonal to v4 and q is close to 1, x is still dominated by v3: rho then sits just below mu3, the
-        // residual norm is only ~eps (mu3 - mu4) and the shift lands between mu4 and mu3, next to mu3 - the pass converged to v3.  The pivots
-        // tell (Sylvester's law of inertia): M - sh I = L D L^T has as many negative d_i as M has eigenvalues below sh, so a negative pivot
-        // means sh > mu4.  The shift then steps down by 2^ex, 2^(ex+1), ... (from 2^-LFD_NULLVEC_FIRST_STEP of itself) until no pivot is negative (M is positive
-        // semi-definite: at the latest below 0), which brackets mu4 in [sh, sh + 2^(ex-1)], a bracket no wider than about twice the
-        // distance covered, and LFD_NULLVEC_BISECT bisections move sh up inside it: sh ends below mu4 by at most ~1/2^(LFD_NULLVEC_BISECT-1)
-        // of that distance (~mu3 - mu4), the pass converges to v4 at a rate of that order and the next shift comes from a vector that v4
-        // dominates.  A shift without a negative pivot - every pass of a cell that was right before - is used as it is, same bits.  (NaN
-        // pivots compare false: such a cell goes on as before and leaves through the NaN exit.)  The search is a branch of its own with
-        // its own solves, so that the common path carries nothing for it, and it carries sh and ex only: the dense kernels have no
-        // register to spare.
-#define LFD_SHIFTED_SOLVES()                                                                                            \
-        for (int k = 1; k <= LFD_NULLVEC_MAXIT; ++k) {                                                                  \
-            if (k == 5) LFD_KEEP_IN_RANGE();                                                                            \
-            const double o0 = x0, o1 = x1, o2 = x2, o3 = x3;                                                            \
-            LFD_SOLVE(x0, x1, x2, x3, x0, x1, x2, x3);                                                                  \
-            ++it;                                                                                                       \
-            if (k >= 2 && lfd_nullvec_settled(x0, x1, x2, x3, o0, o1, o2, o3)) { settled = true; break; }               \
-        }
-#define LFD_NEGATIVE_PIVOT() ((r0 < 0.0) || (r1 < 0.0) || (r2 < 0.0) || (d3 < 0.0))       /* (the reciprocals carry the pivots' signs) */
-        {
-            LFD_FACTORISE(m00 - sh, m11 - sh, m22 - sh, m33 - sh);
-            if (!LFD_NEGATIVE_PIVOT()) {
-                LFD_SHIFTED_SOLVES();
-                continue;
-            }
-        }
-        {
-            int ex;
-            (void)frexp(sh, &ex);
-            ex -= LFD_NULLVEC_FIRST_STEP;
-            bool neg = true;
-#define LFD_PIVOTS_AT_SH()                                                                                              \
-            {                                                                                                           \
-                LFD_BUILD_M();                                                                                          \
-                LFD_FACTORISE(m00 - sh, m11 - sh, m22 - sh, m33 - sh);                                                  \
-                (void)s0; (void)s1; (void)s2;                                                                           \
-                neg = LFD_NEGATIVE_PIVOT();                                                                             \
-            }
-            while (neg) {                                       // stepping down
-                sh -= ldexp(1.0, ex);
-                ++ex;
-                LFD_PIVOTS_AT_SH();
-            }
-            for (int b = 1; b <= LFD_NULLVEC_BISECT; ++b) {     // mu4 lies in [sh, sh + 2^(ex-1)]: bisections
-                sh += ldexp(1.0, ex - 1 - b);
-                LFD_PIVOTS_AT_SH();
-                if (neg) sh -= ldexp(1.0, ex - 1 - b);
-            }
-#undef LFD_PIVOTS_AT_SH
-            LFD_BUILD_M();
-            LFD_FACTORISE(m00 - sh, m11 - sh, m22 - sh, m33 - sh);
-            // (x - dominated by v3 - is not carried through the search: the pass starts afresh from e4, the first solve free as in pass 0)
-            x3 = 1.0;
-            x2 = -l32;
-            x1 = fma(-l21, x2, -l31);
-            x0 = fma(-l10, x1, fma(-l20, x2, -l30));
-            LFD_SHIFTED_SOLVES();
-        }
-    }
-#undef LFD_SHIFTED_SOLVES
-#undef LFD_NEGATIVE_PIVOT
-#undef LFD_KEEP_IN_RANGE
-#undef LFD_FACTORISE
-#undef LFD_FACTORISE_D
-#undef LFD_SOLVE
+    LFD_NULLVEC_SHIFTED_PASSES(LFD_BUILD_M)
     c[0] = x0; c[1] = x1; c[2] = x2; c[3] = x3;
     return it;
 #undef LFD_BUILD_M

@@ -73,67 +73,55 @@ LFD_HD void lfd_refine_add_view(double* M, const float* Pi, float u, float v, bo
 
 // Smallest eigenvector of the symmetric positive semi-definite 4x4 matrix M (upper triangle as above) by the scheme of lfd_null_vector_rows
 // (DESIGN 4.1): LDL^T without pivoting, Newton-refined pivot reciprocals, inverse iteration from e4 (its first solve is the last column of
-// L^-T), lfd_nullvec_settled from the second solve on, at most LFD_NULLVEC_MAXIT solves per pass and LFD_NULLVEC_PASSES passes, every pass after
-// the first shifted by the Rayleigh quotient of the iterate backed off by its residual.  M stays where it is (ten values): this routine runs once
-// per supported point behind the dense kernel, not inside its geometry loop.  c[4]: an un-normalised multiple; returns the number of solves.
+// L^-T), lfd_nullvec_settled from the second solve on, at most LFD_NULLVEC_MAXIT solves per pass and LFD_NULLVEC_PASSES passes.  Pass 0 is a
+// plain loop here (this routine runs once per supported point behind the dense kernel, not inside its geometry loop); like lfd_null_vector_rows'
+// it brings an iterate above 2^64 back before its fifth solve.  The shifted passes ARE lfd_null_vector_rows' (LFD_NULLVEC_SHIFTED_PASSES,
+// lfd_geometry.hpp: the Rayleigh shift backed off by the residual, the negative-pivot test, the step-down and the bisections of a shift above
+// mu4, the restart from e4, the rescaling), with nothing to rebuild: M stays where it is (ten values).  c[4]: an un-normalised multiple; returns
+// the number of solves, the free first one included as lfd_null_vector_rows counts it (3 .. 1 + LFD_NULLVEC_MAXIT LFD_NULLVEC_PASSES).
 LFD_HD int lfd_null_vector_sym(const double* M, double* c) {
     const double m00 = M[0], m01 = M[1], m02 = M[2], m03 = M[3], m11 = M[4], m12 = M[5], m13 = M[6], m22 = M[7], m23 = M[8], m33 = M[9];
-    double x0 = 0.0, x1 = 0.0, x2 = 0.0, x3 = 1.0;
-    int it = 0;
+    double x0, x1, x2, x3;
+    int it = 1;
     bool settled = false;
-    for (int pass = 0; !settled && pass < LFD_NULLVEC_PASSES; ++pass) {
-        double sh = 0.0;
-        if (pass > 0) {
-            const double sc = lfd_pow2_inv_scale(fabs(x0) + fabs(x1) + fabs(x2) + fabs(x3));
-            x0 *= sc; x1 *= sc; x2 *= sc; x3 *= sc;
-            const double t0 = fma(m03, x3, fma(m02, x2, fma(m01, x1, m00 * x0)));
-            const double t1 = fma(m13, x3, fma(m12, x2, fma(m11, x1, m01 * x0)));
-            const double t2 = fma(m23, x3, fma(m22, x2, fma(m12, x1, m02 * x0)));
-            const double t3 = fma(m33, x3, fma(m23, x2, fma(m13, x1, m03 * x0)));
-            const double num = fma(x3, t3, fma(x2, t2, fma(x1, t1, x0 * t0)));
-            const double den = fma(x3, x3, fma(x2, x2, fma(x1, x1, x0 * x0)));
-            const double rden = lfd_recip_refined(den);
-            const double rho = num * rden;
-            const double e0 = fma(-rho, x0, t0), e1 = fma(-rho, x1, t1), e2 = fma(-rho, x2, t2), e3 = fma(-rho, x3, t3);
-            const double rr = fma(e3, e3, fma(e2, e2, fma(e1, e1, e0 * e0)));
-            sh = rho - lfd_sqrt_rare(rr * rden);
-        }
-        // M - sh I = L D L^T (pass 0: M itself); s_i = d3 / d_i
-        const double q00 = pass ? m00 - sh : m00, q11 = pass ? m11 - sh : m11, q22 = pass ? m22 - sh : m22, q33 = pass ? m33 - sh : m33;
-        const double r0 = lfd_recip_refined(q00);
-        const double l10 = m01 * r0, l20 = m02 * r0, l30 = m03 * r0;
-        const double d1 = fma(-l10, m01, q11);
-        const double n12 = fma(-l10, m02, m12), n13 = fma(-l10, m03, m13);
-        const double n22 = fma(-l20, m02, q22), n23 = fma(-l20, m03, m23), n33 = fma(-l30, m03, q33);
-        const double r1 = lfd_recip_refined(d1);
-        const double l21 = n12 * r1, l31 = n13 * r1;
-        const double d2 = fma(-l21, n12, n22);
-        const double p23 = fma(-l21, n13, n23), p33 = fma(-l31, n13, n33);
-        const double r2 = lfd_recip_refined(d2);
-        const double l32 = p23 * r2;
-        const double d3 = fma(-l32, p23, p33);
-        const double s0 = d3 * r0, s1 = d3 * r1, s2 = d3 * r2;
-        if (pass == 0) {         // first solve from e4: the last column of L^-T
-            x3 = 1.0;
-            x2 = -l32;
-            x1 = fma(-l21, x2, -l31);
-            x0 = fma(-l10, x1, fma(-l20, x2, -l30));
-        }
+    double rho = 0.0;
+    {
+        LFD_NULLVEC_FACTORISE(m00, m11, m22, m33);
+        // first solve from e4: the last column of L^-T
+        x3 = 1.0;
+        x2 = -l32;
+        x1 = fma(-l21, x2, -l31);
+        x0 = fma(-l10, x1, fma(-l20, x2, -l30));
         for (int k = 1; k <= LFD_NULLVEC_MAXIT; ++k) {
+            if (k == 5) LFD_NULLVEC_KEEP_IN_RANGE();
             const double o0 = x0, o1 = x1, o2 = x2, o3 = x3;
-            // x <- d3 (M - sh I)^-1 x : forward (L), diagonal, backward (L^T)
-            const double y1 = fma(-l10, o0, o1);
-            const double y2 = fma(-l21, y1, fma(-l20, o0, o2));
-            const double y3 = fma(-l32, y2, fma(-l31, y1, fma(-l30, o0, o3)));
-            const double z0 = o0 * s0, z1 = y1 * s1, z2 = y2 * s2;
-            x3 = y3;
-            x2 = fma(-l32, x3, z2);
-            x1 = fma(-l21, x2, fma(-l31, x3, z1));
-            x0 = fma(-l10, x1, fma(-l20, x2, fma(-l30, x3, z0)));
+            LFD_NULLVEC_SOLVE(x0, x1, x2, x3, x0, x1, x2, x3);
             ++it;
-            if (k >= 2 && lfd_nullvec_settled(x0, x1, x2, x3, o0, o1, o2, o3)) { settled = true; break; }
+            if (k >= 2 && lfd_nullvec_settled(x0, x1, x2, x3, o0, o1, o2, o3)) {
+                settled = true;
+                // M x = d3 o, so the Rayleigh quotient of x is d3 (x . o) / (x . x)
+                const double xo = fma(x3, o3, fma(x2, o2, fma(x1, o1, x0 * o0)));
+                const double xx = fma(x3, x3, fma(x2, x2, fma(x1, x1, x0 * x0)));
+                rho = (d3 * xo) * lfd_recip_refined(xx);
+                break;
+            }
         }
     }
+    // lfd_nullvec_settled reads a small change of direction as convergence, and pass 0 changes little next to v3 as well: started nearly
+    // orthogonal to v4 (a far point) with sigma4/sigma3 close to 1 it drifts away from v3 by less than LFD_NULLVEC_TOL per solve.  The inertia
+    // tells the two apart: M - sh I = L D L^T just below the eigenvalue the pass settled on, sh = rho (1 - 2^-10), has a negative pivot iff M
+    // has an eigenvalue below sh - x is not v4, and the shifted passes (which search their shift from such a state) take over.  2^-10 is below
+    // the gap 1 - r^2 of every r <= 0.999 the rules ask a direction for.  No negative pivot: x is returned as it is, same bits.  (NaN compares
+    // false: a NaN leaves as before.)
+    if (settled) {
+        const double sh = fma(-0x1p-10, rho, rho);
+        LFD_NULLVEC_FACTORISE(m00 - sh, m11 - sh, m22 - sh, m33 - sh);
+        (void)s0; (void)s1; (void)s2; (void)l32;
+        settled = !LFD_NULLVEC_NEGATIVE_PIVOT();
+    }
+#define LFD_SYM_KEEPS_M()
+    LFD_NULLVEC_SHIFTED_PASSES(LFD_SYM_KEEPS_M)
+#undef LFD_SYM_KEEPS_M
     c[0] = x0; c[1] = x1; c[2] = x2; c[3] = x3;
     return it;
 }
@@ -148,6 +136,7 @@ LFD_HD bool lfd_refine_dehomogenise(const double* c, float& X0, float& X1, float
     X1 = (float)(c[1] * r);
     X2 = (float)(c[2] * r);
     const bool guard = c33 < 1e-24 * n2;
+    // (the squares rely on lfd_null_vector_sym's rescaling, which keeps |c| below 1e154: a larger c would give Inf < Inf and skip the guard)
     return !guard && (n2 == n2) && lfd_finite(X0) && lfd_finite(X1) && lfd_finite(X2);
 }
 
@@ -361,3 +350,13 @@ inline const char* lfd_refine_check_precision(const lfd_batch* b, const float* c
             if (!precision[(size_t)r * b->k + j]) return "null precision plane in a valid slot";
     return nullptr;
 }
+
+// The solver's pieces (lfd_geometry.hpp) have no user behind this header.
+#undef LFD_NULLVEC_FACTORISE_D
+#undef LFD_NULLVEC_FACTORISE
+#undef LFD_NULLVEC_SOLVE
+#undef LFD_NULLVEC_KEEP_IN_RANGE
+#undef LFD_NULLVEC_SHIFTED_SOLVES
+#undef LFD_NULLVEC_NEGATIVE_PIVOT
+#undef LFD_NULLVEC_PIVOTS_AT_SH
+#undef LFD_NULLVEC_SHIFTED_PASSES

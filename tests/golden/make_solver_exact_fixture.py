@@ -47,13 +47,13 @@ GUARD_W = (0.0, 1e-14, 1e-13, 4e-13, 5e-13, 2e-12, 2.5e-12, 1e-11)
 
 
 def exact(A):
-    """(sigma[4] descending, unit v[4]) of a finite f32 4x4 matrix, f64-rounded from an 80-digit eigen-decomposition of A^T A."""
+    """(sigma[4] descending, unit v[4]) of a finite f32 m x 4 matrix, f64-rounded from an 80-digit eigen-decomposition of A^T A."""
     import mpmath as mp
     mp.mp.dps = DIGITS
-    A = np.asarray(A, np.float32).reshape(4, 4)
+    A = np.asarray(A, np.float32).reshape(-1, 4)
     if not np.isfinite(A).all():
         return np.full(4, np.nan), np.full(4, np.nan)
-    a = mp.matrix([[mp.mpf(float(A[i, j])) for j in range(4)] for i in range(4)])
+    a = mp.matrix([[mp.mpf(float(A[i, j])) for j in range(4)] for i in range(A.shape[0])])
     M = a.T * a
     if max(abs(M[i, j]) for i in range(4) for j in range(4)) == 0:
         return np.zeros(4), np.array([0.0, 0.0, 0.0, 1.0])
@@ -72,10 +72,10 @@ def no_pivot(A):
     is of this kind (its first three columns are dependent)."""
     import mpmath as mp
     mp.mp.dps = DIGITS
-    A = np.asarray(A, np.float32).reshape(4, 4)
+    A = np.asarray(A, np.float32).reshape(-1, 4)
     if not np.isfinite(A).all():
         return False
-    a = mp.matrix([[mp.mpf(float(A[i, j])) for j in range(4)] for i in range(4)])
+    a = mp.matrix([[mp.mpf(float(A[i, j])) for j in range(4)] for i in range(A.shape[0])])
     M = a.T * a
     scale = max(abs(M[i, i]) for i in range(4))
     if scale == 0:

@@ -1,5 +1,7 @@
 """The rules the triangulation solver (csrc/lfd_geometry.hpp::lfd_null_vector_rows) is judged by against the exact answers of
-tests/golden/g19_solver_exact.npz (made by tests/golden/make_solver_exact_fixture.py), for the host and the GPU tests alike.
+tests/golden/g19_solver_exact.npz (made by tests/golden/make_solver_exact_fixture.py), for the host and the GPU tests alike - and the
+re-triangulation's solver (csrc/lfd_refine.hpp::lfd_null_vector_sym) by the same rules, on the same matrices and on those of
+tests/golden/g21_refine_solver_exact.npz, through lfd_refine_multiview[_weighted] (run_refine / check_refine at the end of this file).
 
     r    sigma4 / sigma3 of the exact singular values (its class is stored: the sigmas are f32)
     v    the exact unit null vector
@@ -131,15 +133,20 @@ def scene_s(fx):
     return cams, ids[0], ids[1:], cert, warp
 
 
-def injected_cameras(A, uid=0):
-    """Reference and neighbour camera whose DLT matrix at pixel 0 (warp value -1 on all four channels) is A exactly: rows of -A as the first two
-    rows of P, third row (0, 0, 0, 1) - the depth of X is X[3]."""
+def injected_cameras(A, uid=0, ref_scale=1.0):
+    """Reference and neighbour cameras whose DLT rows at pixel 0 (warp value -1 on all four channels) are the rows of A exactly, a pair per
+    camera (A: 2n x 4, n cameras, the reference first): rows of -A as the first two rows of P, third row (0, 0, 0, 1) - the depth of X is
+    X[3].  ``ref_scale``: a power of two that the reference's two rows are multiplied by (the weighted re-triangulation, see run_refine)."""
     import lichtfeld_densification_plugin_amd as lfd
-    A = np.asarray(A, np.float32).reshape(4, 4)
+    A = np.asarray(A, np.float32).reshape(-1, 4)
+    assert A.shape[0] % 2 == 0 and A.shape[0] >= 2
     out = []
-    for h in range(2):
+    for h in range(A.shape[0] // 2):
         P = np.zeros((3, 4), np.float32)
-        P[0], P[1], P[2, 3] = -A[2 * h], -A[2 * h + 1], 1.0
+        with np.errstate(all="ignore"):
+            P[0], P[1], P[2, 3] = -A[2 * h], -A[2 * h + 1], 1.0
+            if h == 0 and ref_scale != 1.0:
+                P[:2] *= np.float32(ref_scale)
         out.append(lfd.CameraRecord(uid=uid + h, image_path="", width=M_MATCH, height=M_MATCH, K=np.eye(3, dtype=np.float32),
                                     R=np.eye(3, dtype=np.float32), t=np.zeros((3, 1), np.float32), P=P, C=np.zeros(3, np.float32)))
     return out
@@ -196,3 +203,166 @@ def run_family_m(dens, fx, torch, device, batch_refs=102):
             if b > a:
                 emitted[i], xyz[i] = True, got[a]
     return emitted, xyz
+
+
+# ---- feeding chosen matrices to the multi-view re-triangulation (lfd_refine_multiview[_weighted], csrc/lfd_refine.hpp) -------------------------
+# Gates wide open but finite: with them every finite case away from the w -> 0 guard has to come back accepted, so no gate can hide a wrong vector.
+REFINE_TAU, REFINE_THR = 1e15, 1e30
+REFINE_LAM = 4.0                 # the weighted variant's lam (the sum of the neighbours' mean precisions): a power of four
+ACCEPTED, WEIGHTED = 0x80, 0x40
+
+
+def refine_cases():
+    """The cases of the re-triangulation tests, family -> dict(A[N, 2n, 4], sigma, cls, v, nopivot, names): ``G`` every g13 matrix of
+    kinds 0..4 and ``M`` g19's family M (two views), ``V3`` and ``V4`` the three- and four-view matrices of g21_refine_solver_exact.npz.
+    ``names``: what a failure is reported under (G: the g13 index)."""
+    fx = load_fixture()
+    g21 = np.load(os.path.join(GOLDEN, "g21_refine_solver_exact.npz"))
+    out = {}
+    for fam in "GM":
+        n = fx[fam + "_A"].shape[0]
+        out[fam] = dict(A=fx[fam + "_A"], sigma=fx[fam + "_sigma"], cls=fx[fam + "_cls"], v=fx[fam + "_v"],
+                        nopivot=fx["M_nopivot"] if fam == "M" else np.zeros(n, bool), names=fx["G_idx"] if fam == "G" else np.arange(n))
+    for fam in ("V3", "V4"):
+        n = g21[fam + "_A"].shape[0]
+        out[fam] = dict(A=g21[fam + "_A"], sigma=g21[fam + "_sigma"], cls=g21[fam + "_cls"], v=g21[fam + "_v"], nopivot=g21[fam + "_nopivot"],
+                        names=np.arange(n))
+    return out
+
+
+def refine_subset(cases):
+    """What the wider kernels (k = 5, 9) are given: g13's classes 1..3, family M and g21 whole."""
+    keep = np.isin(cases["G"]["cls"], (1, 2, 3))
+    out = dict(cases)
+    out["G"] = {key: val[keep] for key, val in cases["G"].items()}
+    return out
+
+
+def refine_slots(n_views, k, winner):
+    """Slots of the live neighbours besides the winner, ascending: the n_views - 2 candidates that carry rows of A, then the null view.  They are
+    spread over the free slots, so that with k = 9 slots beyond the eighth are live."""
+    free = [j for j in range(k) if j != winner]
+    others = n_views - 1
+    assert len(free) >= others >= 1
+    pick = [free[-1]] if others == 1 else [free[int(round(t))] for t in np.linspace(0, len(free) - 1, others)]
+    assert len(set(pick)) == others and pick == sorted(pick)
+    return pick
+
+
+def refine_winner(i, k):
+    """The winning slot of case i: first, middle and last slot in turn."""
+    return (0, k // 2, k - 1)[i % 3]
+
+
+def run_refine(dens, A, torch, device, precision, k=None, batch_refs=100):
+    """The matrices A[N, 2n, 4] (n = 2, 3 or 4 views) through ``dens.refine_multiview`` (HipDensifier or its CPU twin), one reference with one
+    cell and one hand-made input point (xyz = 0, err = 0) each, ``batch_refs`` references per launch, gates REFINE_TAU / REFINE_THR.
+
+    The reference carries rows 0-1, the winning slot rows 2-3, n - 2 further live slots the other row pairs (the routine's view order: reference,
+    winner, candidates by ascending slot) and one more live slot - the null view - has zero rows: it makes every point a candidate and adds
+    exact zeros, so M = A^T A.  The other slots of the ``k`` (default n) are dead (certainty 0).  Every view sees pixel 0 with depth exactly 1, and
+    the input point (0, 0, 0) is within REFINE_TAU of every view.
+
+    ``precision``: the weighted variant on the same M.  Every view that carries rows has the plane (1, 0, 1), the null view (p, 0, p) with
+    p = REFINE_LAM - (n - 1), so lam = REFINE_LAM = 4, and the reference is injected with its rows halved (exact in f32): it enters with weight
+    lam, 4 (A[0:2] / 2)^T (A[0:2] / 2).  A case whose halved rows would not be exact (underflow) is flagged ``skipped``.  Dead slots carry NaN
+    planes.
+
+    Returns dict(status[N] u8, xyz[N, 3] f32, err[N] f32, skipped[N] bool, n_extra: n - 1)."""
+    import lichtfeld_densification_plugin_amd as lfd
+    from lichtfeld_densification_plugin_amd.core import hip_backend as hb
+    A = np.asarray(A, np.float32)
+    N, n_views = A.shape[0], A.shape[1] // 2
+    k = n_views if k is None else k
+    scale = 1.0 / np.sqrt(REFINE_LAM) if precision else 1.0
+    with np.errstate(all="ignore"):
+        ref_rows = A[:, :2].astype(np.float32)
+        back = (ref_rows * np.float32(scale)) / np.float32(scale)
+    skipped = ~((back == ref_rows) | ~np.isfinite(ref_rows)).all(axis=(1, 2))
+    t32 = lambda v, shape: torch.full(shape, v, dtype=torch.float32, device=device)
+    live, dead, warp = t32(0.9, (M_GRID, M_GRID)), t32(0.0, (M_GRID, M_GRID)), t32(-1.0, (M_GRID, M_GRID, 4))
+    image = torch.zeros((M_MATCH, M_MATCH, 3), dtype=torch.uint8, device=device)
+    plane = lambda p: torch.tensor([p, 0.0, p], dtype=torch.float32, device=device).reshape(M_GRID, M_GRID, 3).contiguous()
+    one, null_plane, nan_plane = plane(1.0), plane(REFINE_LAM - (n_views - 1)), plane(float("nan"))
+    status, xyz, err = np.zeros(N, np.uint8), np.zeros((N, 3), np.float32), np.zeros(N, np.float32)
+    for lo in range(0, N, batch_refs):
+        hi = min(N, lo + batch_refs)
+        cams = injected_cameras(np.zeros((2, 4), np.float32))          # camera 0: zero rows - the null view and every dead slot
+        refs, slots = [], []
+        for i in range(lo, hi):
+            s = refine_winner(i, k)
+            others = refine_slots(n_views, k, s)
+            mine = injected_cameras(A[i], uid=len(cams), ref_scale=scale)
+            base = len(cams)
+            cams += mine
+            nbr, cert, prec = [0] * k, [dead] * k, [nan_plane] * k
+            nbr[s], cert[s], prec[s] = base + 1, live, one
+            for c, j in enumerate(others[:-1]):
+                nbr[j], cert[j], prec[j] = base + 2 + c, live, one
+            cert[others[-1]], prec[others[-1]] = live, null_plane
+            refs.append(hb.ReferenceInputs(ref_cam=base, nbr_cams=nbr, cert=cert, warp=[warp] * k, image=image, precision=prec if precision else None))
+            slots.append(s)
+        dens.upload_cameras(cams)
+        batch = hb.PreparedBatch(refs, M_MATCH, M_MATCH)
+        m = hi - lo
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+        pts = hb.TriangulationOutput(xyz=z((m, 3), torch.float32), rgb=z((m, 3), torch.float32), err=z((m,), torch.float32), cell=z((m,), torch.int32),
+                                     slot=torch.tensor(slots, dtype=torch.uint8, device=device), ref_offsets=np.arange(m + 1, dtype=np.int64),
+                                     seg_counts=np.zeros((m, k), np.int32))
+        res, st = dens.refine_multiview(batch, pts, REFINE_TAU, REFINE_THR, with_status=True, precision=precision)
+        status[lo:hi], xyz[lo:hi], err[lo:hi] = st.cpu().numpy(), res.xyz.cpu().numpy(), res.err.cpu().numpy()
+    return dict(status=status, xyz=xyz, err=err, skipped=skipped, n_extra=n_views - 1)
+
+
+def check_refine(out, A, sigma, cls, v, nopivot, weighted, names=None):
+    """The rules for what run_refine returned for the cases (A, sigma, cls, v; ``nopivot``: bool per case, see the fixture's M_nopivot).
+
+      every case            a point that is not accepted keeps the bits of its xyz and err (here: zeros)
+      non-finite A          not accepted
+      finite A              the status carries n_extra (and WEIGHTED when ``weighted``): the candidates are counted before the solve
+      ... guard expected    (|v3|/|v| < 1e-12 / 2) not accepted
+      ... guard band        finite
+      ... ``nopivot``       may come back unaccepted; an accepted one is judged
+      ... every other       ACCEPTED, and judge(..., device=True) on (x, y, z, 1): the output is f32 on the host as well
+    Returns (failed [(name, what)], counts dict)."""
+    failed, counts = [], dict(judged=0, guard=0, band=0, nonfinite=0, nopivot_unaccepted=0, skipped=int(out["skipped"].sum()))
+    want = out["n_extra"] | (WEIGHTED if weighted else 0)
+    for i in range(A.shape[0]):
+        if out["skipped"][i]:
+            continue
+        name = int(names[i]) if names is not None else i
+        st, xyz, err = int(out["status"][i]), out["xyz"][i], out["err"][i]
+        accepted = bool(st & ACCEPTED)
+        if not accepted and (xyz.view(np.uint32).any() or err.view(np.uint32).any()):
+            failed.append((name, f"not accepted (status {st:#x}) but moved: {xyz} {err}"))
+            continue
+        if cls[i] < 0:
+            counts["nonfinite"] += 1
+            if accepted:
+                failed.append((name, f"non-finite matrix accepted (status {st:#x})"))
+            continue
+        if (st & 0x7f) != want:
+            failed.append((name, f"status {st:#x}, expected {want:#x} beside ACCEPTED"))
+            continue
+        unique = cls[i] != 3          # (class 3 - r > 0.999, rank <= 2 - has no unique v that could say whether the guard is due: it has to be accepted)
+        if unique and guard_expected(v[i]):
+            counts["guard"] += 1
+            if accepted:
+                failed.append((name, f"guard expected but accepted: {xyz}"))
+            continue
+        if unique and in_guard_band(v[i]):
+            counts["band"] += 1
+            if not (np.isfinite(xyz).all() and np.isfinite(err)):
+                failed.append((name, f"guard band, not finite: {xyz} {err}"))
+            continue
+        if not accepted:
+            if nopivot[i]:
+                counts["nopivot_unaccepted"] += 1
+            else:
+                failed.append((name, f"finite, away from the guard, not accepted (status {st:#x})"))
+            continue
+        fail, _, _ = judge(A[i], sigma[i], cls[i], v[i], np.array([float(xyz[0]), float(xyz[1]), float(xyz[2]), 1.0]), device=True)
+        counts["judged"] += 1
+        if fail:
+            failed.append((name, fail))
+    return failed, counts
