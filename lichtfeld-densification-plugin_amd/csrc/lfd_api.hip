@@ -502,6 +502,149 @@ int check_points(lfd_context* ctx, const lfd_points* out, const long long* ref_o
     return LFD_OK;
 }
 
+// The LfdLaunch of a batch for the calls that only read it (support, refine, normals, sigma): the batch's tables and per-pair constants, derived
+// again only when the batch differs from the last one seen (no threshold reaches them).
+int batch_launch(lfd_context* ctx, const lfd_batch* batch, LfdLaunch& L) {
+    lfd_params none;
+    std::memset(&none, 0, sizeof(none));
+    return prepare_launch(ctx, batch, &none, nullptr, 0, L, nullptr);
+}
+
+// ---- what the stages on the final cloud share (voxel, consensus, free-space, fuse, kNN): plan, workspace, statistics, sort, heads, compaction -------
+// All of them are synchronous and run on the context's stream, so they carve one workspace, ctx->cloud_ws; each writes or clears what it reads.
+struct CloudPlan {
+    long long n;
+    long long G, chunk;          // radix passes: workgroup b of G owns the items [b * chunk, (b + 1) * chunk); chunk is a multiple of the scatter's 512-item round
+    int n_part;                  // workgroups (= partial results) of the min / max pass
+    long long n_wg;              // workgroups of the kernels that give a thread to every point
+    unsigned grid;               // ... and of those that stride over the points
+};
+
+CloudPlan cloud_plan(int64_t n) {
+    CloudPlan p;
+    p.n = n;
+    p.G = std::min<long long>(1024, (n + 4095) / 4096);
+    p.chunk = (((n + p.G - 1) / p.G) + 511) / 512 * 512;
+    p.G = (n + p.chunk - 1) / p.chunk;
+    p.n_part = (int)std::min<long long>(1024, (n + 255) / 256);
+    p.n_wg = (n + 255) / 256;
+    p.grid = (unsigned)std::min<long long>(p.n_wg, 4096);
+    return p;
+}
+
+// Bump allocator over the workspace: every region starts on a 256-byte boundary.  A layout is run twice (carve_cloud_ws): without a buffer for
+// the size, then over the buffer.
+struct Bump {
+    unsigned char* base;         // null: sizing only, every region comes back null
+    size_t at = 0;
+    template <class T>
+    T* take(size_t count, size_t extra_bytes = 0) {
+        const size_t o = at;
+        at = (at + count * sizeof(T) + extra_bytes + 255) & ~size_t(255);
+        return base ? reinterpret_cast<T*>(base + o) : nullptr;
+    }
+};
+
+template <class Layout>
+int carve_cloud_ws(lfd_context* ctx, Layout&& layout) {
+    Bump size{nullptr};
+    layout(size);
+    if (int rc = ensure(ctx, ctx->cloud_ws, size.at)) return rc;
+    Bump b{static_cast<unsigned char*>(ctx->cloud_ws.ptr)};
+    layout(b);
+    return LFD_OK;
+}
+
+struct CloudSort {               // partials | stats + counters | digit counts | keys x 2 | indices x 2 | cell starts
+    LfdVoxStats *part, *stats;
+    unsigned* counters;          // the stage's few words behind the statistics; [0] is the number of occupied cells where there are heads
+    unsigned* counts;
+    unsigned long long* keys[2];
+    unsigned* idx[2];
+    unsigned* vstart;            // null for a stage without heads
+};
+
+CloudSort carve_sort(Bump& b, long long n, int n_counters, bool heads) {
+    CloudSort w;
+    w.part = b.take<LfdVoxStats>(1024);
+    w.stats = b.take<LfdVoxStats>(1, (size_t)n_counters * sizeof(unsigned));
+    w.counters = w.stats ? reinterpret_cast<unsigned*>(w.stats + 1) : nullptr;
+    w.counts = b.take<unsigned>(256 * 1024);
+    for (int i = 0; i < 2; ++i) w.keys[i] = b.take<unsigned long long>((size_t)n);
+    for (int i = 0; i < 2; ++i) w.idx[i] = b.take<unsigned>((size_t)n);
+    w.vstart = heads ? b.take<unsigned>((size_t)n) : nullptr;
+    return w;
+}
+
+// min / max pass (with rgb: lfd_voxel_minmax_kernel, colour maximum and NaN flag too; without: lfd_consensus_minmax_kernel) and its read-back.
+// The stream is idle when this returns: a stage decides its refusals on `s` before anything is sorted.
+int cloud_stats(lfd_context* ctx, const CloudPlan& p, const CloudSort& w, const float* xyz, const float* rgb, LfdVoxStats& s) {
+    hipStream_t st = ctx->stream;
+    if (rgb) hipLaunchKernelGGL(lfd_voxel_minmax_kernel, dim3(p.n_part), dim3(256), 0, st, xyz, rgb, p.n, w.part);
+    else hipLaunchKernelGGL(lfd_consensus_minmax_kernel, dim3(p.n_part), dim3(256), 0, st, xyz, p.n, w.part);
+    hipLaunchKernelGGL(lfd_voxel_final_kernel, dim3(1), dim3(256), 0, st, w.part, p.n_part, w.stats);
+    LFD_HIP(ctx, hipGetLastError());
+    LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, w.stats, sizeof(LfdVoxStats), hipMemcpyDeviceToHost, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));
+    std::memcpy(&s, ctx->pinned_words, sizeof(s));
+    return LFD_OK;
+}
+
+// stable LSD radix sort of (keys[0], idx[0]) over the low `bits` bits, 8 at a time; returns which of the two buffers holds the result
+int cloud_sort(hipStream_t st, const CloudPlan& p, const CloudSort& w, int bits) {
+    int cur = 0;
+    for (int shift = 0; shift < bits; shift += 8, cur ^= 1) {
+        hipLaunchKernelGGL(lfd_voxel_hist_kernel, dim3((unsigned)p.G), dim3(256), 0, st, w.keys[cur], p.n, p.chunk, shift, w.counts);
+        hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, w.counts, (int)(256 * p.G), (unsigned*)nullptr);
+        hipLaunchKernelGGL(lfd_voxel_scatter_kernel, dim3((unsigned)p.G), dim3(512), 0, st, w.keys[cur], w.idx[cur], p.n, p.chunk, shift, w.counts,
+                           w.keys[cur ^ 1], w.idx[cur ^ 1]);
+    }
+    return cur;
+}
+
+// heads of the sorted keys: the number of occupied cells goes to counters[0] ...
+void cloud_heads_count(hipStream_t st, const CloudPlan& p, const CloudSort& w, int cur) {
+    hipLaunchKernelGGL(lfd_voxel_head_count_kernel, dim3((unsigned)p.G), dim3(256), 0, st, w.keys[cur], p.n, p.chunk, w.counts);
+    hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, w.counts, (int)p.G, w.counters);
+}
+
+// ... and the first sorted position of every cell to vstart
+void cloud_heads_scatter(hipStream_t st, const CloudPlan& p, const CloudSort& w, int cur) {
+    hipLaunchKernelGGL(lfd_voxel_head_scatter_kernel, dim3((unsigned)p.G), dim3(512), 0, st, w.keys[cur], p.n, p.chunk, w.counts, w.vstart);
+}
+
+struct CloudCompact {            // offsets in, out | keep bytes | kept per workgroup
+    long long *offs, *offs_out;
+    uint8_t* keep;
+    unsigned* wg_kept;
+};
+
+CloudCompact carve_compact(Bump& b, const CloudPlan& p, int32_t n_refs) {
+    CloudCompact c;
+    c.offs = b.take<long long>((size_t)n_refs + 1);
+    c.offs_out = b.take<long long>((size_t)n_refs + 1);
+    c.keep = b.take<uint8_t>((size_t)p.n_wg * 256);
+    c.wg_kept = b.take<unsigned>((size_t)p.n_wg + 1);
+    return c;
+}
+
+// From the keep bytes to the compacted cloud, its reference offsets and its size on the host.  The stream is idle when this returns.
+int cloud_compact(lfd_context* ctx, const CloudPlan& p, const CloudCompact& c, const float* xyz, const float* rgb, const float* err, int32_t n_refs,
+                  float* xyz_out, float* rgb_out, float* err_out, int64_t* ref_offsets_out_host, int64_t* n_out_host) {
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL(lfd_consensus_wgcount_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, st, c.keep, p.n, c.wg_kept);
+    hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, c.wg_kept, (int)p.n_wg, c.wg_kept + p.n_wg);
+    hipLaunchKernelGGL(lfd_consensus_offsets_kernel, dim3((unsigned)std::min<long long>(((long long)n_refs + 256) / 256, 1024)), dim3(256), 0, st, c.offs,
+                       (int)n_refs, c.keep, c.wg_kept, c.offs_out);
+    hipLaunchKernelGGL(lfd_consensus_scatter_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, st, xyz, rgb, err, p.n, c.keep, c.wg_kept, xyz_out, rgb_out,
+                       err_out);
+    LFD_HIP(ctx, hipGetLastError());
+    LFD_HIP(ctx, hipMemcpyAsync(ref_offsets_out_host, c.offs_out, ((size_t)n_refs + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));
+    *n_out_host = ref_offsets_out_host[n_refs];
+    return LFD_OK;
+}
+
 }  // namespace
 
 int lfd_fail(lfd_context* ctx, int code, const std::string& msg) {
@@ -590,7 +733,7 @@ void lfd_destroy(lfd_context* ctx) {
     }
     for (hipEvent_t ev : ctx->kt_start) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->kt_stop) (void)hipEventDestroy(ev);
-    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->vox, &ctx->support_ws, &ctx->prec_tab, &ctx->consensus_ws, &ctx->undist_cnt, &ctx->freespace_ws, &ctx->fuse_ws, &ctx->knn_ws})
+    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->cloud_ws, &ctx->support_ws, &ctx->prec_tab, &ctx->undist_cnt})
         if (b->ptr) (void)hipFree(b->ptr);
     if (ctx->pinned_words) (void)hipHostFree(ctx->pinned_words);
     if (ctx->prec_pinned) (void)hipHostFree(ctx->prec_pinned);
@@ -1402,73 +1545,34 @@ int lfd_voxel_downsample(lfd_context* ctx, const float* xyz, const float* rgb, i
     if (n == 0) return LFD_OK;
     LFD_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    // radix passes: workgroup b of G owns the items [b * chunk, (b + 1) * chunk); chunk is a multiple of the scatter's 512-item round
-    long long G = std::min<long long>(1024, (n + 4095) / 4096);
-    const long long chunk = (((n + G - 1) / G) + 511) / 512 * 512;
-    G = (n + chunk - 1) / chunk;
-    const int n_part = (int)std::min<long long>(1024, (n + 255) / 256);
-    // workspace: partials | stats, voxel count, big-voxel count | digit counts | keys x 2 | indices x 2 | voxel starts | big-voxel list
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t o_part = 0, o_small = al(o_part + 1024 * sizeof(LfdVoxStats)), o_counts = al(o_small + sizeof(LfdVoxStats) + 8);
-    const size_t o_ka = al(o_counts + 256 * 1024 * sizeof(unsigned)), o_kb = al(o_ka + 8 * (size_t)n), o_ia = al(o_kb + 8 * (size_t)n);
-    const size_t o_ib = al(o_ia + 4 * (size_t)n), o_vs = al(o_ib + 4 * (size_t)n), o_big = al(o_vs + 4 * (size_t)n);
-    const size_t total = al(o_big + 4 * ((size_t)n / (LFD_VOX_BIG + 1) + 1));
-    if (int rc = ensure(ctx, ctx->vox, total)) return rc;
-    unsigned char* w = static_cast<unsigned char*>(ctx->vox.ptr);
-    LfdVoxStats* part = reinterpret_cast<LfdVoxStats*>(w + o_part);
-    LfdVoxStats* stats = reinterpret_cast<LfdVoxStats*>(w + o_small);
-    unsigned* nv_dev = reinterpret_cast<unsigned*>(w + o_small + sizeof(LfdVoxStats));
-    unsigned* n_big = nv_dev + 1;
-    unsigned* counts = reinterpret_cast<unsigned*>(w + o_counts);
-    unsigned long long* keys[2] = {reinterpret_cast<unsigned long long*>(w + o_ka), reinterpret_cast<unsigned long long*>(w + o_kb)};
-    unsigned* idx[2] = {reinterpret_cast<unsigned*>(w + o_ia), reinterpret_cast<unsigned*>(w + o_ib)};
-    unsigned* vstart = reinterpret_cast<unsigned*>(w + o_vs);
-    unsigned* big = reinterpret_cast<unsigned*>(w + o_big);
+    const CloudPlan p = cloud_plan(n);
+    CloudSort w;                                                       // counters: voxel count, big-voxel count
+    unsigned* big = nullptr;                                           // big-voxel list
+    if (int rc = carve_cloud_ws(ctx, [&](Bump& b) {
+            w = carve_sort(b, p.n, 2, true);
+            big = b.take<unsigned>((size_t)n / (LFD_VOX_BIG + 1) + 1);
+        }))
+        return rc;
+    unsigned *nv_dev = w.counters, *n_big = w.counters + 1;
 
-    // min / max pass; the refusals are decided before anything is sorted
-    hipLaunchKernelGGL(lfd_voxel_minmax_kernel, dim3(n_part), dim3(256), 0, st, xyz, rgb, (long long)n, part);
-    hipLaunchKernelGGL(lfd_voxel_final_kernel, dim3(1), dim3(256), 0, st, part, n_part, stats);
-    LFD_HIP(ctx, hipGetLastError());
-    LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, stats, sizeof(LfdVoxStats), hipMemcpyDeviceToHost, st));
-    LFD_HIP(ctx, hipStreamSynchronize(st));
+    // the refusals are decided before anything is sorted
     LfdVoxStats s;
-    std::memcpy(&s, ctx->pinned_words, sizeof(s));
-    if (s.flags & LFD_VOX_NONFINITE) return fail(ctx, LFD_ERR_INVALID, "lfd_voxel_downsample: non-finite coordinate in the input");
-    double origin[3];
-    unsigned long long E[3];
-    for (int c = 0; c < 3; ++c) {
-        origin[c] = (double)s.lo[c] - 0.5 * voxel_size;
-        const double kmax = std::floor(((double)s.hi[c] - origin[c]) / voxel_size);   // the key is monotone in the coordinate
-        if (!(kmax < 9223372036854775808.0))
-            return fail(ctx, LFD_ERR_INVALID, "lfd_voxel_downsample: key range: the linear voxel key does not fit 63 bits");
-        E[c] = (unsigned long long)kmax + 1ull;
-    }
-    unsigned __int128 cells = (unsigned __int128)E[0] * E[1];              // every E_c <= 2^63: neither product overflows 128 bits
-    if (cells <= ((unsigned __int128)1 << 63)) cells *= E[2];
-    if (cells > ((unsigned __int128)1 << 63))
-        return fail(ctx, LFD_ERR_INVALID, "lfd_voxel_downsample: key range: the linear voxel key does not fit 63 bits");
-    const unsigned long long max_key = (unsigned long long)cells - 1ull;
-    const int bits = max_key ? 64 - __builtin_clzll(max_key) : 0;
-    const double cscale = (s.flags & LFD_VOX_NAN_RGB) ? 1.0 : ((double)s.cmax > 1.0 ? 255.0 : 1.0);
+    if (int rc = cloud_stats(ctx, p, w, xyz, rgb, s)) return rc;
+    if (s.flags & LFD_VOX_NONFINITE) return fail(ctx, LFD_ERR_INVALID, "lfd_voxel_downsample: " LFD_FUSE_NONFINITE);
+    LfdFuseGrid g;
+    if (!lfd_fuse_grid(s.lo, s.hi, voxel_size, g)) return fail(ctx, LFD_ERR_INVALID, "lfd_voxel_downsample: " LFD_FUSE_KEY_RANGE);
+    const double cscale = lfd_fuse_cscale(s.cmax, (s.flags & LFD_VOX_NAN_RGB) != 0u);
 
-    const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(lfd_voxel_keys_kernel, dim3(grid), dim3(256), 0, st, xyz, (long long)n, origin[0], origin[1], origin[2], voxel_size, E[1], E[2],
-                       keys[0], idx[0]);
-    int cur = 0;
-    for (int shift = 0; shift < bits; shift += 8, cur ^= 1) {
-        hipLaunchKernelGGL(lfd_voxel_hist_kernel, dim3((unsigned)G), dim3(256), 0, st, keys[cur], (long long)n, chunk, shift, counts);
-        hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, counts, (int)(256 * G), (unsigned*)nullptr);
-        hipLaunchKernelGGL(lfd_voxel_scatter_kernel, dim3((unsigned)G), dim3(512), 0, st, keys[cur], idx[cur], (long long)n, chunk, shift, counts,
-                           keys[cur ^ 1], idx[cur ^ 1]);
-    }
-    hipLaunchKernelGGL(lfd_voxel_head_count_kernel, dim3((unsigned)G), dim3(256), 0, st, keys[cur], (long long)n, chunk, counts);
-    hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, counts, (int)G, nv_dev);
-    hipLaunchKernelGGL(lfd_voxel_head_scatter_kernel, dim3((unsigned)G), dim3(512), 0, st, keys[cur], (long long)n, chunk, counts, vstart);
+    hipLaunchKernelGGL(lfd_voxel_keys_kernel, dim3(p.grid), dim3(256), 0, st, xyz, p.n, g.origin[0], g.origin[1], g.origin[2], voxel_size, g.e[1],
+                       g.e[2], w.keys[0], w.idx[0]);
+    const int cur = cloud_sort(st, p, w, g.bits);
+    cloud_heads_count(st, p, w, cur);
+    cloud_heads_scatter(st, p, w, cur);
     LFD_HIP(ctx, hipMemsetAsync(n_big, 0, sizeof(unsigned), st));
-    hipLaunchKernelGGL(lfd_voxel_sums_kernel, dim3(grid), dim3(256), 0, st, xyz, rgb, (long long)n, idx[cur], vstart, nv_dev, cscale, xyz_out, rgb_out,
+    hipLaunchKernelGGL(lfd_voxel_sums_kernel, dim3(p.grid), dim3(256), 0, st, xyz, rgb, p.n, w.idx[cur], w.vstart, nv_dev, cscale, xyz_out, rgb_out,
                        big, n_big);
     const unsigned big_grid = (unsigned)std::min<long long>(n / (LFD_VOX_BIG + 1) + 1, 8192);
-    hipLaunchKernelGGL(lfd_voxel_sums_big_kernel, dim3(big_grid), dim3(64), 0, st, xyz, rgb, (long long)n, idx[cur], vstart, nv_dev, cscale, big, n_big,
+    hipLaunchKernelGGL(lfd_voxel_sums_big_kernel, dim3(big_grid), dim3(64), 0, st, xyz, rgb, p.n, w.idx[cur], w.vstart, nv_dev, cscale, big, n_big,
                        xyz_out, rgb_out);
     LFD_HIP(ctx, hipGetLastError());
     LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, nv_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -1491,42 +1595,21 @@ int lfd_consensus_filter(lfd_context* ctx, const float* xyz, const float* rgb, c
     if (n == 0) return LFD_OK;
     LFD_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    // radix passes: workgroup b of G owns the items [b * chunk, (b + 1) * chunk); chunk is a multiple of the scatter's 512-item round
-    long long G = std::min<long long>(1024, (n + 4095) / 4096);
-    const long long chunk = (((n + G - 1) / G) + 511) / 512 * 512;
-    G = (n + chunk - 1) / chunk;
-    const int n_part = (int)std::min<long long>(1024, (n + 255) / 256);
-    const long long n_wg = (n + 255) / 256;
-    // workspace: partials | stats | digit counts | keys x 2 | indices x 2 | sorted points | offsets in, out | keep bytes | kept per workgroup
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t offs_bytes = ((size_t)n_refs + 1) * sizeof(long long);
-    const size_t o_part = 0, o_small = al(o_part + 1024 * sizeof(LfdVoxStats)), o_counts = al(o_small + sizeof(LfdVoxStats));
-    const size_t o_ka = al(o_counts + 256 * 1024 * sizeof(unsigned)), o_kb = al(o_ka + 8 * (size_t)n), o_ia = al(o_kb + 8 * (size_t)n);
-    const size_t o_ib = al(o_ia + 4 * (size_t)n), o_pt = al(o_ib + 4 * (size_t)n), o_off = al(o_pt + sizeof(LfdConsensusPt) * (size_t)n);
-    const size_t o_offo = al(o_off + offs_bytes), o_keep = al(o_offo + offs_bytes), o_wg = al(o_keep + (size_t)n_wg * 256);
-    const size_t total = al(o_wg + ((size_t)n_wg + 1) * sizeof(unsigned));
-    if (int rc = ensure(ctx, ctx->consensus_ws, total)) return rc;
-    unsigned char* w = static_cast<unsigned char*>(ctx->consensus_ws.ptr);
-    LfdVoxStats* part = reinterpret_cast<LfdVoxStats*>(w + o_part);
-    LfdVoxStats* stats = reinterpret_cast<LfdVoxStats*>(w + o_small);
-    unsigned* counts = reinterpret_cast<unsigned*>(w + o_counts);
-    unsigned long long* keys[2] = {reinterpret_cast<unsigned long long*>(w + o_ka), reinterpret_cast<unsigned long long*>(w + o_kb)};
-    unsigned* idx[2] = {reinterpret_cast<unsigned*>(w + o_ia), reinterpret_cast<unsigned*>(w + o_ib)};
-    LfdConsensusPt* spt = reinterpret_cast<LfdConsensusPt*>(w + o_pt);
-    long long* offs = reinterpret_cast<long long*>(w + o_off);
-    long long* offs_out = reinterpret_cast<long long*>(w + o_offo);
-    uint8_t* keep = w + o_keep;
-    unsigned* wg_kept = reinterpret_cast<unsigned*>(w + o_wg);
+    const CloudPlan p = cloud_plan(n);
+    CloudSort w;
+    LfdConsensusPt* spt = nullptr;                                     // sorted points
+    CloudCompact c;
+    if (int rc = carve_cloud_ws(ctx, [&](Bump& b) {
+            w = carve_sort(b, p.n, 0, false);
+            spt = b.take<LfdConsensusPt>((size_t)n);
+            c = carve_compact(b, p, n_refs);
+        }))
+        return rc;
 
-    // min / max pass over the finite points; the key-range refusal is decided before anything is sorted
-    LFD_HIP(ctx, hipMemcpyAsync(offs, ref_offsets_host, offs_bytes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(lfd_consensus_minmax_kernel, dim3(n_part), dim3(256), 0, st, xyz, (long long)n, part);
-    hipLaunchKernelGGL(lfd_voxel_final_kernel, dim3(1), dim3(256), 0, st, part, n_part, stats);
-    LFD_HIP(ctx, hipGetLastError());
-    LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, stats, sizeof(LfdVoxStats), hipMemcpyDeviceToHost, st));
-    LFD_HIP(ctx, hipStreamSynchronize(st));
+    // min / max over the finite points; the key-range refusal is decided before anything is sorted
+    LFD_HIP(ctx, hipMemcpyAsync(c.offs, ref_offsets_host, ((size_t)n_refs + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
     LfdVoxStats s;
-    std::memcpy(&s, ctx->pinned_words, sizeof(s));
+    if (int rc = cloud_stats(ctx, p, w, xyz, nullptr, s)) return rc;
     if (!(s.lo[0] <= s.hi[0])) {                                   // no finite point: nothing agrees with anything
         if (consensus) LFD_HIP(ctx, hipMemsetAsync(consensus, 0, (size_t)n, st));
         LFD_HIP(ctx, hipStreamSynchronize(st));
@@ -1536,30 +1619,13 @@ int lfd_consensus_filter(lfd_context* ctx, const float* xyz, const float* rgb, c
     if (!lfd_consensus_grid(s.lo, s.hi, radius, g))
         return fail(ctx, LFD_ERR_INVALID, "lfd_consensus_filter: key range: more than 2^30 cells along an axis or a linear cell key beyond 63 bits");
 
-    const unsigned grid = (unsigned)std::min<long long>(n_wg, 4096);
-    hipLaunchKernelGGL(lfd_consensus_keys_kernel, dim3(grid), dim3(256), 0, st, xyz, (long long)n, g.origin[0], g.origin[1], g.origin[2], g.h, g.e[1],
-                       g.e[2], g.sentinel, keys[0], idx[0]);
-    int cur = 0;
-    for (int shift = 0; shift < g.bits; shift += 8, cur ^= 1) {
-        hipLaunchKernelGGL(lfd_voxel_hist_kernel, dim3((unsigned)G), dim3(256), 0, st, keys[cur], (long long)n, chunk, shift, counts);
-        hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, counts, (int)(256 * G), (unsigned*)nullptr);
-        hipLaunchKernelGGL(lfd_voxel_scatter_kernel, dim3((unsigned)G), dim3(512), 0, st, keys[cur], idx[cur], (long long)n, chunk, shift, counts,
-                           keys[cur ^ 1], idx[cur ^ 1]);
-    }
-    hipLaunchKernelGGL(lfd_consensus_gather_kernel, dim3(grid), dim3(256), 0, st, xyz, idx[cur], offs, (int)n_refs, (long long)n, spt);
-    hipLaunchKernelGGL(lfd_consensus_count_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, keys[cur], spt, idx[cur], (long long)n, g.e[1], g.e[2],
-                       g.sentinel, lfd_consensus_r2(radius), (int)min_refs, consensus ? LFD_CONSENSUS_CAP : (int)min_refs, keep, consensus);
-    hipLaunchKernelGGL(lfd_consensus_wgcount_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, keep, (long long)n, wg_kept);
-    hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, wg_kept, (int)n_wg, wg_kept + n_wg);
-    hipLaunchKernelGGL(lfd_consensus_offsets_kernel, dim3((unsigned)std::min<long long>(((long long)n_refs + 256) / 256, 1024)), dim3(256), 0, st, offs,
-                       (int)n_refs, keep, wg_kept, offs_out);
-    hipLaunchKernelGGL(lfd_consensus_scatter_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, xyz, rgb, err, (long long)n, keep, wg_kept, xyz_out, rgb_out,
-                       err_out);
-    LFD_HIP(ctx, hipGetLastError());
-    LFD_HIP(ctx, hipMemcpyAsync(ref_offsets_out_host, offs_out, offs_bytes, hipMemcpyDeviceToHost, st));
-    LFD_HIP(ctx, hipStreamSynchronize(st));
-    *n_out_host = ref_offsets_out_host[n_refs];
-    return LFD_OK;
+    hipLaunchKernelGGL(lfd_consensus_keys_kernel, dim3(p.grid), dim3(256), 0, st, xyz, p.n, g.origin[0], g.origin[1], g.origin[2], g.h, g.e[1],
+                       g.e[2], g.sentinel, w.keys[0], w.idx[0]);
+    const int cur = cloud_sort(st, p, w, g.bits);
+    hipLaunchKernelGGL(lfd_consensus_gather_kernel, dim3(p.grid), dim3(256), 0, st, xyz, w.idx[cur], c.offs, (int)n_refs, p.n, spt);
+    hipLaunchKernelGGL(lfd_consensus_count_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, st, w.keys[cur], spt, w.idx[cur], p.n, g.e[1], g.e[2],
+                       g.sentinel, lfd_consensus_r2(radius), (int)min_refs, consensus ? LFD_CONSENSUS_CAP : (int)min_refs, c.keep, consensus);
+    return cloud_compact(ctx, p, c, xyz, rgb, err, n_refs, xyz_out, rgb_out, err_out, ref_offsets_out_host, n_out_host);
 }
 
 // ---- free-space filter on the final cloud (lfd_freespace.hip) ------------------------------------------------------------------------------------
@@ -1577,44 +1643,29 @@ int lfd_freespace_filter(lfd_context* ctx, const float* xyz, const float* rgb, c
     if (n == 0) return LFD_OK;
     LFD_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const long long n_wg = (n + 255) / 256;
+    const CloudPlan p = cloud_plan(n);
     const long long n_words = (long long)n_refs * pw * ph;             // <= 2^31 - 1 (lfd_freespace_check)
     std::vector<LfdFreespaceCam> cams((size_t)n_refs);
     for (int32_t r = 0; r < n_refs; ++r) lfd_freespace_cam(cam_P_host + 12 * (size_t)r, cam_wh_host[2 * r], cam_wh_host[2 * r + 1], cams[(size_t)r]);
-    // workspace: z-buffers | cameras | offsets in, out | keep bytes | kept per workgroup
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t offs_bytes = ((size_t)n_refs + 1) * sizeof(long long), cam_bytes = (size_t)n_refs * sizeof(LfdFreespaceCam);
-    const size_t o_z = 0, o_cam = al(o_z + (size_t)n_words * sizeof(uint32_t)), o_off = al(o_cam + cam_bytes), o_offo = al(o_off + offs_bytes);
-    const size_t o_keep = al(o_offo + offs_bytes), o_wg = al(o_keep + (size_t)n_wg * 256);
-    const size_t total = al(o_wg + ((size_t)n_wg + 1) * sizeof(unsigned));
-    if (int rc = ensure(ctx, ctx->freespace_ws, total)) return rc;
-    unsigned char* w = static_cast<unsigned char*>(ctx->freespace_ws.ptr);
-    uint32_t* zbuf = reinterpret_cast<uint32_t*>(w + o_z);
-    LfdFreespaceCam* d_cams = reinterpret_cast<LfdFreespaceCam*>(w + o_cam);
-    long long* offs = reinterpret_cast<long long*>(w + o_off);
-    long long* offs_out = reinterpret_cast<long long*>(w + o_offo);
-    uint8_t* keep = w + o_keep;
-    unsigned* wg_kept = reinterpret_cast<unsigned*>(w + o_wg);
+    uint32_t* zbuf = nullptr;                                          // the references' z-buffers, filled before they are read
+    LfdFreespaceCam* d_cams = nullptr;
+    CloudCompact c;
+    if (int rc = carve_cloud_ws(ctx, [&](Bump& b) {
+            zbuf = b.take<uint32_t>((size_t)n_words);
+            d_cams = b.take<LfdFreespaceCam>((size_t)n_refs);
+            c = carve_compact(b, p, n_refs);
+        }))
+        return rc;
 
-    LFD_HIP(ctx, hipMemcpyAsync(offs, ref_offsets_host, offs_bytes, hipMemcpyHostToDevice, st));
-    LFD_HIP(ctx, hipMemcpyAsync(d_cams, cams.data(), cam_bytes, hipMemcpyHostToDevice, st));
+    LFD_HIP(ctx, hipMemcpyAsync(c.offs, ref_offsets_host, ((size_t)n_refs + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    LFD_HIP(ctx, hipMemcpyAsync(d_cams, cams.data(), (size_t)n_refs * sizeof(LfdFreespaceCam), hipMemcpyHostToDevice, st));
     LFD_HIP(ctx, hipStreamSynchronize(st));                            // `cams` is pageable memory of this call: the copy has read it
     hipLaunchKernelGGL(lfd_freespace_fill_kernel, dim3((unsigned)std::min<long long>((n_words + 255) / 256, 4096)), dim3(256), 0, st, zbuf, n_words);
-    hipLaunchKernelGGL(lfd_freespace_splat_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, xyz, (long long)n, offs, (int)n_refs, d_cams, (int)pw, (int)ph,
+    hipLaunchKernelGGL(lfd_freespace_splat_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, st, xyz, p.n, c.offs, (int)n_refs, d_cams, (int)pw, (int)ph,
                        zbuf);
-    hipLaunchKernelGGL(lfd_freespace_count_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, xyz, (long long)n, offs, (int)n_refs, d_cams, zbuf, (int)pw,
-                       (int)ph, tol, (int)min_violations, keep, violations, supports);
-    hipLaunchKernelGGL(lfd_consensus_wgcount_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, keep, (long long)n, wg_kept);
-    hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, wg_kept, (int)n_wg, wg_kept + n_wg);
-    hipLaunchKernelGGL(lfd_consensus_offsets_kernel, dim3((unsigned)std::min<long long>(((long long)n_refs + 256) / 256, 1024)), dim3(256), 0, st, offs,
-                       (int)n_refs, keep, wg_kept, offs_out);
-    hipLaunchKernelGGL(lfd_consensus_scatter_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, xyz, rgb, err, (long long)n, keep, wg_kept, xyz_out, rgb_out,
-                       err_out);
-    LFD_HIP(ctx, hipGetLastError());
-    LFD_HIP(ctx, hipMemcpyAsync(ref_offsets_out_host, offs_out, offs_bytes, hipMemcpyDeviceToHost, st));
-    LFD_HIP(ctx, hipStreamSynchronize(st));
-    *n_out_host = ref_offsets_out_host[n_refs];
-    return LFD_OK;
+    hipLaunchKernelGGL(lfd_freespace_count_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, st, xyz, p.n, c.offs, (int)n_refs, d_cams, zbuf, (int)pw,
+                       (int)ph, tol, (int)min_violations, c.keep, violations, supports);
+    return cloud_compact(ctx, p, c, xyz, rgb, err, n_refs, xyz_out, rgb_out, err_out, ref_offsets_out_host, n_out_host);
 }
 
 // ---- oriented voxel fusion on the final cloud (lfd_fuse.hip; the grid and the sort are lfd_voxel.hip's kernels) ------------------------------------
@@ -1629,71 +1680,43 @@ int lfd_fuse_oriented(lfd_context* ctx, const float* xyz, const float* normals, 
     if (n == 0) return LFD_OK;
     LFD_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    // radix passes: workgroup b of G owns the items [b * chunk, (b + 1) * chunk); chunk is a multiple of the scatter's 512-item round
-    long long G = std::min<long long>(1024, (n + 4095) / 4096);
-    const long long chunk = (((n + G - 1) / G) + 511) / 512 * 512;
-    G = (n + chunk - 1) / chunk;                                       // (the voxels, at most n, are cut into the same chunks for the row scan)
-    const int n_part = (int)std::min<long long>(1024, (n + 255) / 256);
-    // workspace: partials | stats, voxel count, big-voxel count, row count | digit counts | keys x 2 | indices x 2 | voxel starts | rows |
-    // big-voxel list | flag bytes
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t o_part = 0, o_small = al(o_part + 1024 * sizeof(LfdVoxStats)), o_counts = al(o_small + sizeof(LfdVoxStats) + 12);
-    const size_t o_ka = al(o_counts + 256 * 1024 * sizeof(unsigned)), o_kb = al(o_ka + 8 * (size_t)n), o_ia = al(o_kb + 8 * (size_t)n);
-    const size_t o_ib = al(o_ia + 4 * (size_t)n), o_vs = al(o_ib + 4 * (size_t)n), o_rows = al(o_vs + 4 * (size_t)n);
-    const size_t o_big = al(o_rows + 4 * (size_t)n), o_flag = al(o_big + 4 * ((size_t)n / (LFD_VOX_BIG + 1) + 1));
-    const size_t total = al(o_flag + (size_t)n);
-    if (int rc = ensure(ctx, ctx->fuse_ws, total)) return rc;
-    unsigned char* w = static_cast<unsigned char*>(ctx->fuse_ws.ptr);
-    LfdVoxStats* part = reinterpret_cast<LfdVoxStats*>(w + o_part);
-    LfdVoxStats* stats = reinterpret_cast<LfdVoxStats*>(w + o_small);
-    unsigned* nv_dev = reinterpret_cast<unsigned*>(w + o_small + sizeof(LfdVoxStats));
-    unsigned* n_big = nv_dev + 1;
-    unsigned* n_rows_dev = nv_dev + 2;
-    unsigned* counts = reinterpret_cast<unsigned*>(w + o_counts);
-    unsigned long long* keys[2] = {reinterpret_cast<unsigned long long*>(w + o_ka), reinterpret_cast<unsigned long long*>(w + o_kb)};
-    unsigned* idx[2] = {reinterpret_cast<unsigned*>(w + o_ia), reinterpret_cast<unsigned*>(w + o_ib)};
-    unsigned* vstart = reinterpret_cast<unsigned*>(w + o_vs);
-    unsigned* rows = reinterpret_cast<unsigned*>(w + o_rows);
-    unsigned* big = reinterpret_cast<unsigned*>(w + o_big);
-    uint8_t* flag = w + o_flag;
+    const CloudPlan p = cloud_plan(n);
+    CloudSort w;                                                       // counters: voxel count, big-voxel count, row count
+    unsigned *rows = nullptr, *big = nullptr;                          // rows of every voxel, big-voxel list
+    uint8_t* flag = nullptr;                                           // flag byte of every sorted point
+    if (int rc = carve_cloud_ws(ctx, [&](Bump& b) {
+            w = carve_sort(b, p.n, 3, true);
+            rows = b.take<unsigned>((size_t)n);
+            big = b.take<unsigned>((size_t)n / (LFD_VOX_BIG + 1) + 1);
+            flag = b.take<uint8_t>((size_t)n);
+        }))
+        return rc;
+    unsigned *nv_dev = w.counters, *n_big = w.counters + 1, *n_rows_dev = w.counters + 2;
 
-    // min / max pass; the refusals are decided before anything is sorted
-    hipLaunchKernelGGL(lfd_voxel_minmax_kernel, dim3(n_part), dim3(256), 0, st, xyz, rgb, (long long)n, part);
-    hipLaunchKernelGGL(lfd_voxel_final_kernel, dim3(1), dim3(256), 0, st, part, n_part, stats);
-    LFD_HIP(ctx, hipGetLastError());
-    LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, stats, sizeof(LfdVoxStats), hipMemcpyDeviceToHost, st));
-    LFD_HIP(ctx, hipStreamSynchronize(st));
+    // the refusals are decided before anything is sorted
     LfdVoxStats s;
-    std::memcpy(&s, ctx->pinned_words, sizeof(s));
+    if (int rc = cloud_stats(ctx, p, w, xyz, rgb, s)) return rc;
     if (s.flags & LFD_VOX_NONFINITE) return fail(ctx, LFD_ERR_INVALID, "lfd_fuse_oriented: " LFD_FUSE_NONFINITE);
     LfdFuseGrid g;
     if (!lfd_fuse_grid(s.lo, s.hi, voxel_size, g)) return fail(ctx, LFD_ERR_INVALID, "lfd_fuse_oriented: " LFD_FUSE_KEY_RANGE);
     const double cscale = lfd_fuse_cscale(s.cmax, (s.flags & LFD_VOX_NAN_RGB) != 0u);
 
-    const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(lfd_voxel_keys_kernel, dim3(grid), dim3(256), 0, st, xyz, (long long)n, g.origin[0], g.origin[1], g.origin[2], voxel_size, g.e[1],
-                       g.e[2], keys[0], idx[0]);
-    int cur = 0;
-    for (int shift = 0; shift < g.bits; shift += 8, cur ^= 1) {
-        hipLaunchKernelGGL(lfd_voxel_hist_kernel, dim3((unsigned)G), dim3(256), 0, st, keys[cur], (long long)n, chunk, shift, counts);
-        hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, counts, (int)(256 * G), (unsigned*)nullptr);
-        hipLaunchKernelGGL(lfd_voxel_scatter_kernel, dim3((unsigned)G), dim3(512), 0, st, keys[cur], idx[cur], (long long)n, chunk, shift, counts,
-                           keys[cur ^ 1], idx[cur ^ 1]);
-    }
-    hipLaunchKernelGGL(lfd_voxel_head_count_kernel, dim3((unsigned)G), dim3(256), 0, st, keys[cur], (long long)n, chunk, counts);
-    hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, counts, (int)G, nv_dev);
-    hipLaunchKernelGGL(lfd_voxel_head_scatter_kernel, dim3((unsigned)G), dim3(512), 0, st, keys[cur], (long long)n, chunk, counts, vstart);
-    // sides and rows, then the first row of every voxel, then the sums
+    hipLaunchKernelGGL(lfd_voxel_keys_kernel, dim3(p.grid), dim3(256), 0, st, xyz, p.n, g.origin[0], g.origin[1], g.origin[2], voxel_size, g.e[1],
+                       g.e[2], w.keys[0], w.idx[0]);
+    const int cur = cloud_sort(st, p, w, g.bits);
+    cloud_heads_count(st, p, w, cur);
+    cloud_heads_scatter(st, p, w, cur);
+    // sides and rows, then the first row of every voxel (the voxels, at most n, are cut into the sort's chunks for the row scan), then the sums
     LFD_HIP(ctx, hipMemsetAsync(n_big, 0, sizeof(unsigned), st));
     const unsigned big_grid = (unsigned)std::min<long long>(n / (LFD_VOX_BIG + 1) + 1, 8192);
-    hipLaunchKernelGGL(lfd_fuse_side_kernel, dim3(grid), dim3(256), 0, st, normals, (long long)n, idx[cur], vstart, nv_dev, flag, rows, big, n_big);
-    hipLaunchKernelGGL(lfd_fuse_side_big_kernel, dim3(big_grid), dim3(64), 0, st, normals, (long long)n, idx[cur], vstart, nv_dev, big, n_big, flag, rows);
-    hipLaunchKernelGGL(lfd_fuse_rowsum_kernel, dim3((unsigned)G), dim3(256), 0, st, rows, nv_dev, chunk, counts);
-    hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, counts, (int)G, n_rows_dev);
-    hipLaunchKernelGGL(lfd_fuse_rowstart_kernel, dim3((unsigned)G), dim3(256), 0, st, rows, nv_dev, chunk, counts);
-    hipLaunchKernelGGL(lfd_fuse_sums_kernel, dim3(grid), dim3(256), 0, st, xyz, normals, rgb, (long long)n, idx[cur], vstart, nv_dev, flag, rows, cscale,
+    hipLaunchKernelGGL(lfd_fuse_side_kernel, dim3(p.grid), dim3(256), 0, st, normals, p.n, w.idx[cur], w.vstart, nv_dev, flag, rows, big, n_big);
+    hipLaunchKernelGGL(lfd_fuse_side_big_kernel, dim3(big_grid), dim3(64), 0, st, normals, p.n, w.idx[cur], w.vstart, nv_dev, big, n_big, flag, rows);
+    hipLaunchKernelGGL(lfd_fuse_rowsum_kernel, dim3((unsigned)p.G), dim3(256), 0, st, rows, nv_dev, p.chunk, w.counts);
+    hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, w.counts, (int)p.G, n_rows_dev);
+    hipLaunchKernelGGL(lfd_fuse_rowstart_kernel, dim3((unsigned)p.G), dim3(256), 0, st, rows, nv_dev, p.chunk, w.counts);
+    hipLaunchKernelGGL(lfd_fuse_sums_kernel, dim3(p.grid), dim3(256), 0, st, xyz, normals, rgb, p.n, w.idx[cur], w.vstart, nv_dev, flag, rows, cscale,
                        xyz_out, normals_out, rgb_out, count_out);
-    hipLaunchKernelGGL(lfd_fuse_sums_big_kernel, dim3(big_grid), dim3(64), 0, st, xyz, normals, rgb, (long long)n, idx[cur], vstart, nv_dev, flag, rows,
+    hipLaunchKernelGGL(lfd_fuse_sums_big_kernel, dim3(big_grid), dim3(64), 0, st, xyz, normals, rgb, p.n, w.idx[cur], w.vstart, nv_dev, flag, rows,
                        cscale, big, n_big, xyz_out, normals_out, rgb_out, count_out);
     LFD_HIP(ctx, hipGetLastError());
     LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, nv_dev, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -1712,59 +1735,31 @@ int lfd_knn_dist2(lfd_context* ctx, const float* xyz, int64_t n, double cell_siz
     if (n == 0) return LFD_OK;
     LFD_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    // radix passes: workgroup b of G owns the items [b * chunk, (b + 1) * chunk); chunk is a multiple of the scatter's 512-item round
-    long long G = std::min<long long>(1024, (n + 4095) / 4096);
-    const long long chunk = (((n + G - 1) / G) + 511) / 512 * 512;
-    G = (n + chunk - 1) / chunk;
-    const int n_part = (int)std::min<long long>(1024, (n + 255) / 256);
-    const long long n_wg = (n + 255) / 256;
-    // workspace: partials | stats, cell count, fullest cell, listed points | digit counts | keys x 2 | indices x 2 | cell starts | sorted points | list
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t o_part = 0, o_small = al(o_part + 1024 * sizeof(LfdVoxStats)), o_counts = al(o_small + sizeof(LfdVoxStats) + 12);
-    const size_t o_ka = al(o_counts + 256 * 1024 * sizeof(unsigned)), o_kb = al(o_ka + 8 * (size_t)n), o_ia = al(o_kb + 8 * (size_t)n);
-    const size_t o_ib = al(o_ia + 4 * (size_t)n), o_vs = al(o_ib + 4 * (size_t)n), o_pt = al(o_vs + 4 * (size_t)n);
-    const size_t o_list = al(o_pt + sizeof(LfdKnnPt) * (size_t)n);
-    const size_t total = al(o_list + 4 * (size_t)n);
-    if (int rc = ensure(ctx, ctx->knn_ws, total)) return rc;
-    unsigned char* w = static_cast<unsigned char*>(ctx->knn_ws.ptr);
-    LfdVoxStats* part = reinterpret_cast<LfdVoxStats*>(w + o_part);
-    LfdVoxStats* stats = reinterpret_cast<LfdVoxStats*>(w + o_small);
-    unsigned* nv_dev = reinterpret_cast<unsigned*>(w + o_small + sizeof(LfdVoxStats));
-    unsigned* cell_max = nv_dev + 1;
-    unsigned* n_list = nv_dev + 2;
-    unsigned* counts = reinterpret_cast<unsigned*>(w + o_counts);
-    unsigned long long* keys[2] = {reinterpret_cast<unsigned long long*>(w + o_ka), reinterpret_cast<unsigned long long*>(w + o_kb)};
-    unsigned* idx[2] = {reinterpret_cast<unsigned*>(w + o_ia), reinterpret_cast<unsigned*>(w + o_ib)};
-    unsigned* vstart = reinterpret_cast<unsigned*>(w + o_vs);
-    LfdKnnPt* spt = reinterpret_cast<LfdKnnPt*>(w + o_pt);
-    unsigned* list = reinterpret_cast<unsigned*>(w + o_list);
+    const CloudPlan p = cloud_plan(n);
+    CloudSort w;                                                       // counters: cell count, fullest cell, listed points
+    LfdKnnPt* spt = nullptr;                                           // sorted points
+    unsigned* list = nullptr;                                          // the points the grid scan did not settle
+    if (int rc = carve_cloud_ws(ctx, [&](Bump& b) {
+            w = carve_sort(b, p.n, 3, true);
+            spt = b.take<LfdKnnPt>((size_t)n);
+            list = b.take<unsigned>((size_t)n);
+        }))
+        return rc;
+    unsigned *nv_dev = w.counters, *cell_max = w.counters + 1, *n_list = w.counters + 2;
 
-    // min / max pass; the refusals are decided before anything is sorted
-    hipLaunchKernelGGL(lfd_consensus_minmax_kernel, dim3(n_part), dim3(256), 0, st, xyz, (long long)n, part);
-    hipLaunchKernelGGL(lfd_voxel_final_kernel, dim3(1), dim3(256), 0, st, part, n_part, stats);
-    LFD_HIP(ctx, hipGetLastError());
-    LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, stats, sizeof(LfdVoxStats), hipMemcpyDeviceToHost, st));
-    LFD_HIP(ctx, hipStreamSynchronize(st));
+    // the refusals are decided before anything is sorted
     LfdVoxStats s;
-    std::memcpy(&s, ctx->pinned_words, sizeof(s));
+    if (int rc = cloud_stats(ctx, p, w, xyz, nullptr, s)) return rc;
     if (s.flags & LFD_VOX_NONFINITE) return fail(ctx, LFD_ERR_INVALID, "lfd_knn_dist2: " LFD_KNN_NONFINITE);
     double h = cell_size > 0.0 ? cell_size : lfd_knn_auto_h(s.lo, s.hi, (long long)n);
     LfdKnnGrid g;
     if (!lfd_knn_grid(s.lo, s.hi, h, g)) return fail(ctx, LFD_ERR_INVALID, "lfd_knn_dist2: " LFD_KNN_KEY_RANGE);
 
-    const unsigned grid = (unsigned)std::min<long long>(n_wg, 4096);
     int cur = 0;
     for (int rebuilds = 0;;) {
-        cur = 0;
-        hipLaunchKernelGGL(lfd_knn_keys_kernel, dim3(grid), dim3(256), 0, st, xyz, (long long)n, g, keys[0], idx[0]);
-        for (int shift = 0; shift < g.bits; shift += 8, cur ^= 1) {
-            hipLaunchKernelGGL(lfd_voxel_hist_kernel, dim3((unsigned)G), dim3(256), 0, st, keys[cur], (long long)n, chunk, shift, counts);
-            hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, counts, (int)(256 * G), (unsigned*)nullptr);
-            hipLaunchKernelGGL(lfd_voxel_scatter_kernel, dim3((unsigned)G), dim3(512), 0, st, keys[cur], idx[cur], (long long)n, chunk, shift, counts,
-                               keys[cur ^ 1], idx[cur ^ 1]);
-        }
-        hipLaunchKernelGGL(lfd_voxel_head_count_kernel, dim3((unsigned)G), dim3(256), 0, st, keys[cur], (long long)n, chunk, counts);
-        hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, counts, (int)G, nv_dev);
+        hipLaunchKernelGGL(lfd_knn_keys_kernel, dim3(p.grid), dim3(256), 0, st, xyz, p.n, g, w.keys[0], w.idx[0]);
+        cur = cloud_sort(st, p, w, g.bits);
+        cloud_heads_count(st, p, w, cur);
         LFD_HIP(ctx, hipGetLastError());
         if (cell_size > 0.0) break;
         // the automatic rule looks at the occupied cells of this grid (lfd_knn.hpp): the same decisions as the twin's
@@ -1777,12 +1772,12 @@ int lfd_knn_dist2(lfd_context* ctx, const float* xyz, int64_t n, double cell_siz
         g = finer;
         ++rebuilds;
     }
-    hipLaunchKernelGGL(lfd_voxel_head_scatter_kernel, dim3((unsigned)G), dim3(512), 0, st, keys[cur], (long long)n, chunk, counts, vstart);
-    LFD_HIP(ctx, hipMemsetAsync(cell_max, 0, 2 * sizeof(unsigned), st));
-    hipLaunchKernelGGL(lfd_knn_cellmax_kernel, dim3(grid), dim3(256), 0, st, vstart, nv_dev, (long long)n, cell_max);
-    hipLaunchKernelGGL(lfd_knn_gather_kernel, dim3(grid), dim3(256), 0, st, xyz, idx[cur], (long long)n, spt);
-    hipLaunchKernelGGL(lfd_knn_scan_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, keys[cur], spt, (long long)n, g, dist2_out, list, n_list);
-    hipLaunchKernelGGL(lfd_knn_brute_kernel, dim3((unsigned)std::min<long long>(n, 1024)), dim3(256), 0, st, spt, (long long)n, list, n_list, dist2_out);
+    cloud_heads_scatter(st, p, w, cur);
+    LFD_HIP(ctx, hipMemsetAsync(cell_max, 0, 2 * sizeof(unsigned), st));           // cell_max and n_list
+    hipLaunchKernelGGL(lfd_knn_cellmax_kernel, dim3(p.grid), dim3(256), 0, st, w.vstart, nv_dev, p.n, cell_max);
+    hipLaunchKernelGGL(lfd_knn_gather_kernel, dim3(p.grid), dim3(256), 0, st, xyz, w.idx[cur], p.n, spt);
+    hipLaunchKernelGGL(lfd_knn_scan_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, st, w.keys[cur], spt, p.n, g, dist2_out, list, n_list);
+    hipLaunchKernelGGL(lfd_knn_brute_kernel, dim3((unsigned)std::min<long long>(n, 1024)), dim3(256), 0, st, spt, p.n, list, n_list, dist2_out);
     LFD_HIP(ctx, hipGetLastError());
     LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, nv_dev, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
     LFD_HIP(ctx, hipStreamSynchronize(st));
@@ -1893,11 +1888,8 @@ int lfd_support_filter(lfd_context* ctx, const lfd_batch* batch, const lfd_point
     int code = LFD_ERR_INVALID;
     if (const char* why = lfd_support_check(in, ref_offsets_in, min_support, support_thresh_px, out, ref_offsets_out, &code))
         return fail(ctx, code, std::string("lfd_support_filter: ") + why);
-    // the batch's tables and per-pair constants, derived again only when the batch differs from the last one seen (no threshold reaches them)
-    lfd_params none;
-    std::memset(&none, 0, sizeof(none));
     LfdLaunch L;
-    int rc = prepare_launch(ctx, batch, &none, nullptr, 0, L, nullptr);
+    int rc = batch_launch(ctx, batch, L);
     if (rc != LFD_OK) return rc;
     LfdSupportArgs p;
     std::memset(&p, 0, sizeof(p));
@@ -1961,11 +1953,8 @@ static int refine_impl(lfd_context* ctx, const char* name, const lfd_batch* batc
     if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
     if (const char* why = lfd_refine_check(in, ref_offsets, support_thresh_px, reproj_thresh, xyz_out, err_out, status))
         return fail(ctx, LFD_ERR_INVALID, std::string(name) + ": " + why);
-    // the batch's tables and per-pair constants, derived again only when the batch differs from the last one seen (no threshold reaches them)
-    lfd_params none;
-    std::memset(&none, 0, sizeof(none));
     LfdLaunch L;
-    int rc = prepare_launch(ctx, batch, &none, nullptr, 0, L, nullptr);
+    int rc = batch_launch(ctx, batch, L);
     if (rc != LFD_OK) return rc;
     LfdRefineArgs p;
     std::memset(&p, 0, sizeof(p));
@@ -2008,11 +1997,8 @@ int lfd_estimate_normals(lfd_context* ctx, const lfd_batch* batch, const lfd_poi
     if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
     if (const char* why = lfd_normals_check(in, ref_offsets, radius_cells, depth_step_rel, reproj_thresh, normals_out, status))
         return fail(ctx, LFD_ERR_INVALID, std::string("lfd_estimate_normals: ") + why);
-    // the batch's tables and per-pair constants, derived again only when the batch differs from the last one seen (no threshold reaches them)
-    lfd_params none;
-    std::memset(&none, 0, sizeof(none));
     LfdLaunch L;
-    int rc = prepare_launch(ctx, batch, &none, nullptr, 0, L, nullptr);
+    int rc = batch_launch(ctx, batch, L);
     if (rc != LFD_OK) return rc;
     LfdNormalArgs p;
     std::memset(&p, 0, sizeof(p));
@@ -2041,11 +2027,8 @@ int lfd_depth_sigma_filter(lfd_context* ctx, const lfd_batch* batch, const lfd_p
     if (const char* why = lfd_sigma_check(in, ref_offsets_in, precision, iso_sigma_px, refine_status, support_thresh_px, max_rel_sigma, out,
                                           ref_offsets_out, sigma_rel, sigma_rel_out, &code))
         return fail(ctx, code, std::string("lfd_depth_sigma_filter: ") + why);
-    // the batch's tables and per-pair constants, derived again only when the batch differs from the last one seen (no threshold reaches them)
-    lfd_params none;
-    std::memset(&none, 0, sizeof(none));
     LfdLaunch L;
-    int rc = prepare_launch(ctx, batch, &none, nullptr, 0, L, nullptr);
+    int rc = batch_launch(ctx, batch, L);
     if (rc != LFD_OK) return rc;
     LfdSigmaArgs p;
     std::memset(&p, 0, sizeof(p));

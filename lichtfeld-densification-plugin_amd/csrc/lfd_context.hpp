@@ -91,12 +91,11 @@ struct lfd_context {
     DeviceBuffer sel_chain;                      // lfd_triangulate_sampled_chain: chain block, the stream's ring of doubles, the keys of its twists
     DeviceBuffer stamps;           // profiling builds: phase stamps of the dense kernel
     DeviceBuffer seg_scan;         // tile segments: exclusive prefix of the last table handed to lfd_order_segments / lfd_pack_*_segments
-    DeviceBuffer vox;              // lfd_voxel_downsample: statistics, digit counts, keys / indices (x 2), voxel starts; grown on demand
+    // The one scratch area of the stages on the final cloud (lfd_voxel_downsample, lfd_consensus_filter, lfd_freespace_filter, lfd_fuse_oriented,
+    // lfd_knn_dist2), grown on demand.  Each call carves it anew (lfd_api.hip: carve_cloud_ws) and writes or clears every word before it reads it;
+    // the stages may share it because each of them returns with the stream idle.
+    DeviceBuffer cloud_ws;
     DeviceBuffer support_ws;       // lfd_support_filter: support count of every input point, kept points per workgroup; grown on demand
-    DeviceBuffer consensus_ws;     // lfd_consensus_filter: statistics, digit counts, keys / indices (x 2), sorted points, offsets, keep bytes; grown on demand
-    DeviceBuffer freespace_ws;     // lfd_freespace_filter: the references' z-buffers, cameras, offsets, keep bytes, kept per workgroup; grown on demand
-    DeviceBuffer fuse_ws;          // lfd_fuse_oriented: lfd_voxel_downsample's workspace plus a flag byte per point and the voxels' rows; grown on demand
-    DeviceBuffer knn_ws;           // lfd_knn_dist2: statistics, digit counts, keys / indices (x 2), cell starts, sorted points, the list of unsettled points; grown on demand
     DeviceBuffer undist_cnt;       // lfd_undistort_image: the u64 counter of invalid pixels of a call that asks for it
     // lfd_refine_multiview_weighted: the table of precision-plane pointers, uploaded on the launch stream when its content differs from the last
     DeviceBuffer prec_tab;

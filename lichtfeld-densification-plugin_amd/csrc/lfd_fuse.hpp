@@ -4,7 +4,8 @@
 // The points of a voxel are merged per SIDE: side 1 holds the points whose usable normal has a negative dot product with the voxel's pivot - the
 // usable normal of its point with the lowest input index -, side 0 everything else.  Every rounding is written out and nothing is contracted (the
 // build uses -ffp-contract=off): the products of two f32 values are exact in f64, so only the additions round.  Grid, keys, voxel order and colour
-// scale are lfd_voxel_downsample's (lfd_voxel.hip, lfd_api.hip), restated here for the twin.
+// scale are lfd_voxel_downsample's: lfd_fuse_grid and lfd_fuse_cscale below are the one statement of that arithmetic, used by both device entry
+// points (lfd_api.hip) and by the twin (lfd_host.hip).
 #pragma once
 
 #include <math.h>
