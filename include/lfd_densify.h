@@ -626,6 +626,27 @@ int lfd_pack_gaussians(lfd_context* ctx, const float* xyz, const float* normals,
 int lfd_pack_gaussians_host(lfd_context* ctx, const float* xyz, const float* normals, const float* rgb, const float* dist2, int64_t n,
                             float opacity_logit, double log_flatten, double max_scale, uint8_t* out);
 
+/* Spatial point cap (no upstream counterpart - upstream caps by a uniform random draw, which keeps the cloud's density contrast): of n
+ * points keep at most `budget`, spread over the occupied space.  xyz: f32 [n][3]; err: f32 [n] or NULL; keep_out: i64 [min(budget, n)], the kept
+ * INPUT INDICES in ascending order - the kept cloud is the input under a mask, in input order.  The rule (csrc/lfd_cap.hpp; integers and single
+ * IEEE f64 operations, no FMA), exact: device, twin and a reference written from these lines agree element for element.
+ *   box        o_c = the f32 minimum per axis; L = the longest side of the bounding box, f64 from the f32 min and max
+ *   key        q_c = min(2^21 - 1, floor((((f64) x_c - o_c) / L) * 2^21)) (0 where L = 0); 63-bit Morton interleave, axis 0 the high bit of a triple
+ *   cells(l)   the number of distinct key >> 3 (21 - l), l = 0 .. 21
+ *   lev        the smallest l with cells(l) >= budget, 21 if there is none; c = cells(lev)
+ *   picked     cell k of c in key order iff floor((k + 1) budget / c) > floor(k budget / c): exactly `budget` cells; all cells when c < budget
+ *   kept       of a picked cell the point of smallest error by the monotone integer image of its f32 bits (-0 < +0, NaNs by their bits), the
+ *              lowest input index on ties and with err NULL
+ * *n_keep_host = min(budget, c), or n when n <= budget (every point is kept).  stats_host: NULL, or f64 [4] = {lev, cells(lev), cells(lev - 1)
+ * (0 at level 0), L}.  Synchronous, deterministic; the workspace belongs to the context and is reused.
+ * LFD_ERR_INVALID: a null required pointer, n < 0 or > 2^31 - 1, budget < 1, keep_out overlapping xyz or err, a "non-finite coordinate" in the input
+ * (decided before anything is sorted).  n == 0 is valid.  lfd_cap_spatial_host: the same over host pointers on a host context, whatever its
+ * thread count. */
+int lfd_cap_spatial(lfd_context* ctx, const float* xyz, const float* err, int64_t n, int64_t budget, int64_t* keep_out, int64_t* n_keep_host,
+                    double* stats_host);
+int lfd_cap_spatial_host(lfd_context* ctx, const float* xyz, const float* err, int64_t n, int64_t budget, int64_t* keep_out, int64_t* n_keep_host,
+                         double* stats_host);
+
 /* (e) multi-GPU exchange, placement step (no upstream counterpart - upstream has no multi-GPU code): n copies
  * dst[dst_offset .. +nbytes) = src[src_offset .. +nbytes) in ONE launch on `hip_stream` of device `device_index` (offsets and lengths in
  * bytes, no alignment required: 15-byte PLY records).  The overlapped exchange receives every rank's records of a round as one padded block
@@ -717,7 +738,7 @@ int lfd_host_eval_correspondence(const float* cam1, const float* cam2, float xa_
  * The per-cell arithmetic is the host build of the very source the kernels compile (csrc/lfd_geometry.hpp; IEEE
  * division / square root where the device uses the 1-ulp v_rcp / v_sqrt), spread over n_threads std::threads
  * (<= 0: all hardware threads).  A host context accepts lfd_upload_cameras, lfd_last_error, lfd_destroy and the
- * *_host calls (the three below, lfd_local_corr_host, lfd_refiner_block_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host, lfd_consensus_filter_host, lfd_freespace_filter_host, lfd_fuse_oriented_host, lfd_knn_dist2_host and lfd_pack_gaussians_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
+ * *_host calls (the three below, lfd_local_corr_host, lfd_refiner_block_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host, lfd_consensus_filter_host, lfd_freespace_filter_host, lfd_fuse_oriented_host, lfd_knn_dist2_host, lfd_pack_gaussians_host and lfd_cap_spatial_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
  * context: neither side ever stands in for the other.  Semantics (orders, counts, optional outputs, LFD_ERR_CAPACITY
  * with valid counts) are those of lfd_aggregate / lfd_triangulate_dense / lfd_triangulate_indexed. */
 int lfd_create_host(int32_t n_threads, lfd_context** out);

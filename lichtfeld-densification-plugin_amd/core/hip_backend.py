@@ -56,6 +56,11 @@ class KnnInputRefused(HipBackendError):
     sorting anything.  Nothing was written."""
 
 
+class CapInputRefused(HipBackendError):
+    """lfd_cap_spatial refused the cloud - a non-finite coordinate - before sorting anything.  Nothing stands in for it: the caller reports the
+    knob (densify.py does)."""
+
+
 class lfd_params(C.Structure):
     _fields_ = [("sampson_thresh", C.c_double), ("certainty_thresh", C.c_float), ("sample_cap", C.c_float),
                 ("reproj_thresh", C.c_float), ("min_parallax_deg", C.c_float), ("no_filter", C.c_int32),
@@ -224,6 +229,8 @@ def load_library() -> C.CDLL:
     lib.lfd_knn_dist2_host.argtypes = list(lib.lfd_knn_dist2.argtypes)
     lib.lfd_pack_gaussians.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_double, C.c_double, C.c_void_p]
     lib.lfd_pack_gaussians_host.argtypes = list(lib.lfd_pack_gaussians.argtypes)
+    lib.lfd_cap_spatial.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    lib.lfd_cap_spatial_host.argtypes = list(lib.lfd_cap_spatial.argtypes)
     lib.lfd_copy_segments.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.lfd_launch_status.argtypes = [ctxp, C.POINTER(C.c_int32)]
     lib.lfd_get_pair_fundamental.argtypes = [ctxp, C.c_int32, C.POINTER(C.c_double)]
@@ -263,7 +270,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_cap_spatial", "lfd_cap_spatial_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -1131,6 +1138,32 @@ def _knn_call(fn, ctx, what, xyz, cell_size, device, last_error):
     return out[:n], (float(stats[0]), int(stats[1]), int(stats[2]), int(stats[3]))
 
 
+def _cap_call(fn, ctx, what, xyz, err, budget, device, last_error):
+    """One lfd_cap_spatial[_host] call.  ``xyz``: (n, 3) float32 tensor on ``device``; ``err``: (n,) float32 tensor there, or None.  Returns
+    ``(keep, stats)``: the int64 tensor of the kept input indices, ascending, on ``device``, and ``(level, cells at that level, cells one level
+    up, longest side of the bounding box)``.  Raises ``CapInputRefused`` for a non-finite coordinate."""
+    if not isinstance(xyz, torch.Tensor) or xyz.dtype != torch.float32 or xyz.device != device or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"{what}: xyz must be a float32 tensor of n rows x 3 on {device}")
+    n = int(xyz.shape[0])
+    if err is not None and (not isinstance(err, torch.Tensor) or err.dtype != torch.float32 or err.device != device or err.dim() != 1
+                            or int(err.shape[0]) != n):
+        raise ValueError(f"{what}: err must be None or a float32 tensor of {n} values on {device}")
+    budget = int(budget)
+    xyz = xyz.contiguous()
+    err = err.contiguous() if err is not None else None
+    keep = torch.empty((max(min(budget, n), 1),), dtype=torch.int64, device=device)
+    n_keep = C.c_int64(0)
+    stats = (C.c_double * 4)()
+    rc = fn(ctx, xyz.data_ptr() if n > 0 else None, err.data_ptr() if err is not None and n > 0 else None, n, budget,
+            keep.data_ptr() if n > 0 else None, C.byref(n_keep), stats)
+    if rc != 0:
+        msg = last_error()
+        if "non-finite coordinate" in msg:
+            raise CapInputRefused(f"{what} refused its input ({rc}): {msg}")
+        raise HipBackendError(f"{what} failed ({rc}): {msg}")
+    return keep[:int(n_keep.value)], (int(stats[0]), int(stats[1]), int(stats[2]), float(stats[3]))
+
+
 def gaussian_pack_arguments(opacity: float, flatten: float, max_scale: float):
     """``(opacity_logit, log_flatten, max_scale)`` as lfd_pack_gaussians takes them: the f32 logit of the initial opacity and log(flatten), each
     computed once in f64."""
@@ -1224,6 +1257,7 @@ class HipDensifier:
         self.n_cams = 0
         self.fuse_voxels = 0           # occupied voxels of the last fuse_oriented call
         self.knn_stats = (0.0, 0, 0, 0)       # (cell size, occupied cells, fullest cell, brute-forced points) of the last knn_dist2 call
+        self.cap_stats = (0, 0, 0, 0.0)       # (level, cells at it, cells one level up, longest side of the box) of the last cap_spatial call
 
     def close(self) -> None:
         if getattr(self, "_ctx", None) is not None and self._ctx.value:
@@ -1495,6 +1529,17 @@ class HipDensifier:
             out, self.knn_stats = _knn_call(self._lib.lfd_knn_dist2, self._ctx, "lfd_knn_dist2", xyz, cell_size, self.device,
                                             lambda: self._lib.lfd_last_error(self._ctx).decode())
         return out
+
+    def cap_spatial(self, xyz: torch.Tensor, err: Optional[torch.Tensor], budget: int) -> torch.Tensor:
+        """The spatial point cap (lfd_cap_spatial): the int64 device tensor of the input indices of at most ``budget`` points, one
+        per cell of the coarsest Morton level with ``budget`` occupied cells, picked evenly along the curve, each cell's point of smallest ``err``
+        (lowest index on ties and with ``err`` None); ascending, so ``xyz[keep]`` is the input under a mask.  ``self.cap_stats`` then holds
+        (level, cells at that level, cells one level up, longest side of the bounding box).  Synchronous.  Raises ``CapInputRefused`` for a
+        non-finite coordinate."""
+        with torch.cuda.stream(self.stream):
+            keep, self.cap_stats = _cap_call(self._lib.lfd_cap_spatial, self._ctx, "lfd_cap_spatial", xyz, err, budget, self.device,
+                                             lambda: self._lib.lfd_last_error(self._ctx).decode())
+        return keep
 
     def pack_gaussians(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor, dist2: torch.Tensor, opacity: float = 0.1,
                        flatten: float = 1.0, max_scale: float = 0.0) -> torch.Tensor:
@@ -1838,6 +1883,7 @@ class HostDensifier:
         self.n_cams = 0
         self.fuse_voxels = 0           # occupied voxels of the last fuse_oriented call
         self.knn_stats = (0.0, 0, 0, 0)       # (cell size, occupied cells, fullest cell, brute-forced points) of the last knn_dist2 call
+        self.cap_stats = (0, 0, 0, 0.0)       # (level, cells at it, cells one level up, longest side of the box) of the last cap_spatial call
 
     close = HipDensifier.close
     __del__ = HipDensifier.__del__
@@ -1940,6 +1986,12 @@ class HostDensifier:
         out, self.knn_stats = _knn_call(self._lib.lfd_knn_dist2_host, self._ctx, "lfd_knn_dist2_host", xyz, cell_size, self.device,
                                         lambda: self._lib.lfd_last_error(self._ctx).decode())
         return out
+
+    def cap_spatial(self, xyz: torch.Tensor, err: Optional[torch.Tensor], budget: int) -> torch.Tensor:
+        """HipDensifier.cap_spatial over CPU tensors (lfd_cap_spatial_host): the same indices, the same ``cap_stats``, whatever the thread count."""
+        keep, self.cap_stats = _cap_call(self._lib.lfd_cap_spatial_host, self._ctx, "lfd_cap_spatial_host", xyz, err, budget, self.device,
+                                         lambda: self._lib.lfd_last_error(self._ctx).decode())
+        return keep
 
     def pack_gaussians(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor, dist2: torch.Tensor, opacity: float = 0.1,
                        flatten: float = 1.0, max_scale: float = 0.0) -> torch.Tensor:

@@ -128,7 +128,13 @@ EXPERIMENTAL_DEFAULTS = {
     "gaussian_opacity": 0.1,
     # ... an upper bound on the initial extent in scene units (what an isolated point would otherwise get is the distance to far neighbours); 0 = none
     "gaussian_max_scale": 0.0,
+    # how max_points chooses.  "random": upstream's uniform draw, which keeps the cloud's density contrast - what many references
+    # saw is kept many times over.  "spatial" (lfd_cap_spatial): one point per cell of the coarsest Morton level that has max_points occupied
+    # cells, the cells picked evenly along the curve, each cell's point of smallest reprojection error; the kept points stay in input order.
+    # Needs max_points > 0.  "random" = today's behaviour: no new code runs.
+    "cap_mode": "random",
 }
+CAP_MODES = ("random", "spatial")
 CONSENSUS_CAP = 8            # LFD_CONSENSUS_CAP of include/lfd_densify.h
 
 
@@ -443,6 +449,11 @@ class DensePipelineConfig:
                     return f"experimental['{key}'] is the {what} of the initial Gaussians: it needs experimental['gaussian_init'] = True"
         elif not normals:
             return "experimental['gaussian_init'] orients the Gaussians by the points' normals: it needs experimental['estimate_normals'] = True"
+        cap_mode = self.exp("cap_mode")
+        if not isinstance(cap_mode, str) or cap_mode not in CAP_MODES:
+            return "experimental['cap_mode'] must be 'random' (upstream's draw) or 'spatial' (one point per cell along the Morton curve)"
+        if cap_mode == "spatial" and int(self.max_points) <= 0:
+            return "experimental['cap_mode'] = 'spatial' is how max_points chooses: it needs max_points > 0"
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):
                 return "stream_output writes a PLY while the run proceeds: output_path must end in .ply"

@@ -26,6 +26,7 @@
 #include "lfd_freespace.hpp"
 #include "lfd_fuse.hpp"
 #include "lfd_knn.hpp"
+#include "lfd_cap.hpp"
 
 extern "C" __global__ void lfd_aggregate_kernel(LfdLaunch L, float* best_cert, uint8_t* best_slot);
 extern "C" __global__ void lfd_dense_kernel(LfdLaunch L);
@@ -102,6 +103,13 @@ extern "C" __global__ void lfd_knn_scan_kernel(const unsigned long long* skey, c
 extern "C" __global__ void lfd_knn_brute_kernel(const LfdKnnPt* spt, long long n, const unsigned* list, const unsigned* n_list, float* dist2);
 extern "C" __global__ void lfd_pack_gaussians_kernel(const float* xyz, const float* normals, const float* rgb, const float* dist2, long long n, float opacity,
                                                      double log_flatten, float max_m, float* out);
+extern "C" __global__ void lfd_cap_keys_kernel(const float* xyz, long long n, LfdCapBox box, unsigned long long* keys, unsigned* idx);
+extern "C" __global__ void lfd_cap_levels_kernel(const unsigned long long* keys, long long n, unsigned* hist);
+extern "C" __global__ void lfd_cap_coarsen_kernel(unsigned long long* keys, long long n, int shift);
+extern "C" __global__ void lfd_cap_rep_kernel(const unsigned* sorted_idx, const unsigned* vstart, const unsigned* nc_p, const float* err, long long n,
+                                              unsigned long long budget, unsigned long long* rep);
+extern "C" __global__ void lfd_cap_mark_kernel(const unsigned long long* rep, const unsigned* nc_p, long long n, unsigned long long budget, uint8_t* keep);
+extern "C" __global__ void lfd_cap_index_kernel(const uint8_t* keep, const unsigned* wg_kept, long long n, long long capacity, long long* keep_out);
 extern "C" __global__ void lfd_freespace_fill_kernel(uint32_t* zbuf, long long n_words);
 extern "C" __global__ void lfd_freespace_splat_kernel(const float* xyz, long long n, const long long* offs, int n_refs, const LfdFreespaceCam* cams, int pw,
                                                       int ph, uint32_t* zbuf);
@@ -628,12 +636,17 @@ CloudCompact carve_compact(Bump& b, const CloudPlan& p, int32_t n_refs) {
     return c;
 }
 
+// kept points in front of every 256 input points (wg_kept[b]) and in all (wg_kept[n_wg]) from the keep bytes
+void cloud_compact_prefix(hipStream_t st, const CloudPlan& p, const CloudCompact& c) {
+    hipLaunchKernelGGL(lfd_consensus_wgcount_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, st, c.keep, p.n, c.wg_kept);
+    hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, c.wg_kept, (int)p.n_wg, c.wg_kept + p.n_wg);
+}
+
 // From the keep bytes to the compacted cloud, its reference offsets and its size on the host.  The stream is idle when this returns.
 int cloud_compact(lfd_context* ctx, const CloudPlan& p, const CloudCompact& c, const float* xyz, const float* rgb, const float* err, int32_t n_refs,
                   float* xyz_out, float* rgb_out, float* err_out, int64_t* ref_offsets_out_host, int64_t* n_out_host) {
     hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(lfd_consensus_wgcount_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, st, c.keep, p.n, c.wg_kept);
-    hipLaunchKernelGGL(lfd_voxel_scan_kernel, dim3(1), dim3(1024), 0, st, c.wg_kept, (int)p.n_wg, c.wg_kept + p.n_wg);
+    cloud_compact_prefix(st, p, c);
     hipLaunchKernelGGL(lfd_consensus_offsets_kernel, dim3((unsigned)std::min<long long>(((long long)n_refs + 256) / 256, 1024)), dim3(256), 0, st, c.offs,
                        (int)n_refs, c.keep, c.wg_kept, c.offs_out);
     hipLaunchKernelGGL(lfd_consensus_scatter_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, st, xyz, rgb, err, p.n, c.keep, c.wg_kept, xyz_out, rgb_out,
@@ -708,7 +721,7 @@ int lfd_create(int device_index, void* hip_stream, lfd_context** out) {
     read_env_switches(ctx);      // profiling / A-B switches: read ONCE here, never on a launch path
     e = hipSetDevice(device_index);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&ctx->n_cus, hipDeviceAttributeMultiprocessorCount, device_index);
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&ctx->pinned_words), 16 * sizeof(int), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&ctx->pinned_words), 32 * sizeof(int), hipHostMallocDefault);
     if (e != hipSuccess) {
         std::string m = std::string("context init: ") + hipGetErrorString(e);
         delete ctx;
@@ -1803,7 +1816,71 @@ int lfd_pack_gaussians(lfd_context* ctx, const float* xyz, const float* normals,
     return LFD_OK;
 }
 
-// ---- image undistortion in front of everything else (lfd_undistort.hip) -------------------------------------------------------------------------
+// ---- spatial point cap on the final cloud (lfd_cap.hip; the sort, the heads and the compaction prefix are the shared ones) ---------------------------
+int lfd_cap_spatial(lfd_context* ctx, const float* xyz, const float* err, int64_t n, int64_t budget, int64_t* keep_out, int64_t* n_keep_host,
+                    double* stats_host) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_cap_check(xyz, err, n, budget, keep_out, n_keep_host)) return fail(ctx, LFD_ERR_INVALID, std::string("lfd_cap_spatial: ") + why);
+    *n_keep_host = 0;
+    if (stats_host) stats_host[0] = stats_host[1] = stats_host[2] = stats_host[3] = 0.0;
+    if (n == 0) return LFD_OK;
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const CloudPlan p = cloud_plan(n);
+    CloudSort w;                                                       // counters: cell count, then the 22 level bins
+    unsigned long long* rep = nullptr;                                 // (rank, index) minimum of every cell
+    CloudCompact c;
+    if (int rc = carve_cloud_ws(ctx, [&](Bump& b) {
+            w = carve_sort(b, p.n, 1 + LFD_CAP_LEVELS + 1, true);
+            rep = b.take<unsigned long long>((size_t)n);
+            c = carve_compact(b, p, 0);
+        }))
+        return rc;
+    unsigned *nc_dev = w.counters, *hist_dev = w.counters + 1;
+
+    // the refusal is decided before anything is sorted
+    LfdVoxStats s;
+    if (int rc = cloud_stats(ctx, p, w, xyz, nullptr, s)) return rc;
+    if (s.flags & LFD_VOX_NONFINITE) return fail(ctx, LFD_ERR_INVALID, "lfd_cap_spatial: " LFD_CAP_NONFINITE);
+    const LfdCapBox box = lfd_cap_box(s.lo, s.hi);
+
+    LFD_HIP(ctx, hipMemsetAsync(hist_dev, 0, (LFD_CAP_LEVELS + 1) * sizeof(unsigned), st));
+    hipLaunchKernelGGL(lfd_cap_keys_kernel, dim3(p.grid), dim3(256), 0, st, xyz, p.n, box, w.keys[0], w.idx[0]);
+    const int cur = cloud_sort(st, p, w, 3 * LFD_CAP_LEVELS);
+    hipLaunchKernelGGL(lfd_cap_levels_kernel, dim3(p.grid), dim3(256), 0, st, w.keys[cur], p.n, hist_dev);
+    LFD_HIP(ctx, hipGetLastError());
+    LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, hist_dev, (LFD_CAP_LEVELS + 1) * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));
+    unsigned long long hist[LFD_CAP_LEVELS + 1];
+    for (int l = 0; l <= LFD_CAP_LEVELS; ++l) hist[l] = (unsigned long long)(unsigned)ctx->pinned_words[l];
+    long long cells = 0;
+    const int lev = lfd_cap_level(hist, (long long)budget, box.L, &cells, stats_host);
+
+    if (n <= budget) {                                                 // the cap does not act: every point is kept
+        LFD_HIP(ctx, hipMemsetAsync(c.keep, 1, (size_t)n, st));
+    } else {
+        if (lev < LFD_CAP_LEVELS)
+            hipLaunchKernelGGL(lfd_cap_coarsen_kernel, dim3(p.grid), dim3(256), 0, st, w.keys[cur], p.n, 3 * (LFD_CAP_LEVELS - lev));
+        cloud_heads_count(st, p, w, cur);
+        cloud_heads_scatter(st, p, w, cur);
+        LFD_HIP(ctx, hipMemsetAsync(rep, 0xff, (size_t)n * sizeof(unsigned long long), st));
+        LFD_HIP(ctx, hipMemsetAsync(c.keep, 0, (size_t)n, st));
+        hipLaunchKernelGGL(lfd_cap_rep_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, st, w.idx[cur], w.vstart, nc_dev, err, p.n,
+                           (unsigned long long)budget, rep);
+        hipLaunchKernelGGL(lfd_cap_mark_kernel, dim3(p.grid), dim3(256), 0, st, rep, nc_dev, p.n, (unsigned long long)budget, c.keep);
+    }
+    cloud_compact_prefix(st, p, c);
+    hipLaunchKernelGGL(lfd_cap_index_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, st, c.keep, c.wg_kept, p.n, (long long)std::min<int64_t>(budget, n),
+                       reinterpret_cast<long long*>(keep_out));
+    LFD_HIP(ctx, hipGetLastError());
+    LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, c.wg_kept + p.n_wg, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));
+    *n_keep_host = (int64_t)(unsigned)ctx->pinned_words[0];
+    return LFD_OK;
+}
+
+// ---- image undistortion in front of everything else (lfd_undistort.hip)-------------------------------------------------------------------------
 int lfd_undistort_image(lfd_context* ctx, const uint8_t* src, int32_t w, int32_t h, int32_t channels, int32_t nearest, const double intr[4],
                         const double dist[8], uint8_t* dst, uint8_t* valid255, int64_t* n_invalid_host) {
     if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");

@@ -69,7 +69,7 @@ struct lfd_context {
     int cur = 0;                   // slot of the last launch
     int last_used = -1;            // ... -1 before the first one
     hipStream_t prep_stream = nullptr;   // lfd_prepare_batch's uploads and setup kernels (created on first use)
-    int* pinned_words = nullptr;   // 16 pinned ints: landing place of the small synchronous read-backs (status, selection count)
+    int* pinned_words = nullptr;   // 32 pinned ints: landing place of the small synchronous read-backs (status, selection count)
     // look-back workspace: [0] u64 ticket counter, [1..] tile states
     DeviceBuffer ws;
     unsigned long long tickets_issued = 0;   // host mirror of the device ticket counter (indexed kernel)

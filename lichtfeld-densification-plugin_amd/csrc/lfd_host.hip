@@ -29,6 +29,7 @@
 #include "lfd_freespace.hpp"
 #include "lfd_fuse.hpp"
 #include "lfd_knn.hpp"
+#include "lfd_cap.hpp"
 
 void lfd_fill_kernel_params(const lfd_batch* b, const lfd_params* p, LfdKernelParams& kp);   // lfd_api.hip
 
@@ -990,6 +991,66 @@ int lfd_pack_gaussians_host(lfd_context* ctx, const float* xyz, const float* nor
         for (long long i = (long long)c * kChunk; i < i1; ++i)
             lfd_gauss_record(xyz + 3 * i, normals + 3 * i, rgb + 3 * i, dist2[i], opacity_logit, log_flatten, max_m, o + LFD_GAUSS_FLOATS * i);
     });
+    return LFD_OK;
+}
+
+// The twin of lfd_cap_spatial: the same box, keys, level, picks and error ranks (lfd_cap.hpp) over a stable sort of (key, index) pairs.
+// The keys are made on the context's threads; everything behind them is one ordered walk, so the result does not depend on the thread count.
+int lfd_cap_spatial_host(lfd_context* ctx, const float* xyz, const float* err, int64_t n, int64_t budget, int64_t* keep_out, int64_t* n_keep_host,
+                         double* stats_host) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    if (const char* why = lfd_cap_check(xyz, err, n, budget, keep_out, n_keep_host))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_cap_spatial_host: ") + why);
+    *n_keep_host = 0;
+    if (stats_host) stats_host[0] = stats_host[1] = stats_host[2] = stats_host[3] = 0.0;
+    if (n == 0) return LFD_OK;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    bool nonfinite = false;
+    for (long long i = 0; i < 3 * (long long)n; ++i) {
+        const int c = (int)(i % 3);
+        if (std::isfinite(xyz[i])) { lo[c] = std::min(lo[c], xyz[i]); hi[c] = std::max(hi[c], xyz[i]); }
+        else nonfinite = true;
+    }
+    if (nonfinite) return lfd_fail(ctx, LFD_ERR_INVALID, "lfd_cap_spatial_host: " LFD_CAP_NONFINITE);
+    const LfdCapBox box = lfd_cap_box(lo, hi);
+    const int n_chunks = (int)((n + kChunk - 1) / kChunk);
+    std::vector<std::pair<unsigned long long, unsigned>> order((size_t)n);
+    parallel_chunks(ctx, n_chunks, [&](int c) {
+        const long long i1 = std::min<long long>(n, (long long)(c + 1) * kChunk);
+        for (long long i = (long long)c * kChunk; i < i1; ++i)
+            order[(size_t)i] = {lfd_cap_key(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], box), (unsigned)i};
+    });
+    std::stable_sort(order.begin(), order.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    unsigned long long hist[LFD_CAP_LEVELS + 1] = {};
+    for (long long j = 1; j < n; ++j) ++hist[lfd_cap_pair_level(order[(size_t)j].first, order[(size_t)j - 1].first)];
+    long long cells = 0;
+    const int lev = lfd_cap_level(hist, (long long)budget, box.L, &cells, stats_host);
+    if (n <= budget) {                                                 // the cap does not act: every point is kept
+        for (long long i = 0; i < n; ++i) keep_out[i] = i;
+        *n_keep_host = n;
+        return LFD_OK;
+    }
+    std::vector<uint8_t> keep((size_t)n, 0);
+    long long k = 0;
+    for (long long a = 0; a < n; ++k) {
+        const unsigned long long cell = lfd_cap_cell_key(order[(size_t)a].first, lev);
+        long long b = a;
+        unsigned long long best = ~0ull;
+        for (; b < n && lfd_cap_cell_key(order[(size_t)b].first, lev) == cell; ++b) {
+            const unsigned i = order[(size_t)b].second;
+            uint32_t bits = 0u;
+            if (err) std::memcpy(&bits, err + i, sizeof(bits));
+            best = std::min(best, lfd_cap_pack(err ? lfd_cap_rank(bits) : 0u, i));
+        }
+        if (lfd_cap_pick((unsigned long long)k, (unsigned long long)budget, (unsigned long long)cells)) keep[(size_t)(best & 0xffffffffull)] = 1;
+        a = b;
+    }
+    long long kept = 0;
+    const long long capacity = std::min<long long>(budget, n);
+    for (long long i = 0; i < n; ++i)
+        if (keep[(size_t)i] && kept < capacity) keep_out[kept++] = i;
+    *n_keep_host = kept;
     return LFD_OK;
 }
 

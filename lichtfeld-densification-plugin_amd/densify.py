@@ -151,24 +151,57 @@ def _cap_index(n_before: int, max_points: int, seed: int) -> Optional[np.ndarray
     return None
 
 
-def _take_rows(a, keep: Optional[np.ndarray]):
-    """``a`` (a NumPy array, a tensor wherever it lives, or None) under the cap's index."""
+class SpatialCapRefused(RuntimeError):
+    """experimental['cap_mode'] = 'spatial': the library refused the cloud (a non-finite coordinate).  No draw stands in for it."""
+
+
+def _cap_keep(xyz, err, max_points: int, seed: int, cap_mode: str = "random", host_threads: int = 0, progress_callback=None):
+    """The rows the point cap keeps of this cloud, or None when the cap does not act - beside ``_cap_index``, the one place the choice is made:
+    the points, the normals and the GPU copy all index with what this returns.  ``cap_mode`` 'random': ``_cap_index``, a NumPy index.
+    'spatial' (DESIGN.md 4.19): lfd_cap_spatial where ``xyz`` / ``err`` are - device tensors through the device call, an int64 tensor that
+    stays on the GPU; host arrays or CPU tensors through the twin, a NumPy index.  Ascending: the kept cloud is the input under a mask."""
+    n_before = int(xyz.shape[0])
+    if cap_mode != "spatial":
+        return _cap_index(n_before, max_points, seed)
+    if not (max_points > 0 and n_before > max_points):
+        return None
+    from .core import hip_backend as hb
+    import torch
+    as_tensor = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))      # noqa: E731
+    t_xyz, t_err = as_tensor(xyz), (None if err is None else as_tensor(err))
+    on_gpu = bool(t_xyz.is_cuda)
+    if progress_callback:
+        progress_callback(95.0, "Choosing points (spatial cap)...")
+    dens = hb.HipDensifier(t_xyz.device) if on_gpu else hb.HostDensifier(int(host_threads))
+    try:
+        keep = dens.cap_spatial(t_xyz, t_err, int(max_points))
+        lev, cells, _above, _side = dens.cap_stats
+    except hb.CapInputRefused as exc:
+        raise SpatialCapRefused(f"experimental['cap_mode'] = 'spatial' cannot be applied to this cloud of {n_before:,} points: {exc}") from exc
+    finally:
+        dens.close()
+    log.info(f"Spatial cap: {n_before:,} points in, {int(keep.shape[0]):,} kept, level {lev}, {cells:,} cells")
+    return keep if on_gpu else keep.numpy()
+
+
+def _take_rows(a, keep):
+    """``a`` (a NumPy array, a tensor wherever it lives, or None) under the cap's index (a NumPy index, or a tensor wherever it lives)."""
     if a is None or keep is None:
         return a
     if isinstance(a, np.ndarray):
-        return a[keep]
+        return a[keep if isinstance(keep, np.ndarray) else keep.cpu().numpy()]
     import torch
-    return a[torch.from_numpy(keep).to(a.device)]
+    return a[(torch.from_numpy(keep) if isinstance(keep, np.ndarray) else keep).to(a.device)]
 
 
-def _apply_point_cap(xyz, rgb, err, max_points: int, seed: int):
-    keep = _cap_index(int(xyz.shape[0]), max_points, seed)
+def _apply_point_cap(xyz, rgb, err, max_points: int, seed: int, cap_mode: str = "random", host_threads: int = 0):
+    keep = _cap_keep(xyz, err, max_points, seed, cap_mode, host_threads)
     return _take_rows(xyz, keep), _take_rows(rgb, keep), _take_rows(err, keep)
 
 
-def _cap_normals(normals, n_before: int, max_points: int, seed: int):
-    """The normals of the points ``_apply_point_cap`` / ``_cap_device_points`` keep (``_cap_index``).  None stays None."""
-    return _take_rows(normals, _cap_index(n_before, max_points, seed))
+def _cap_args(config) -> dict:
+    """``_cap_keep``'s mode arguments of a configuration (None: upstream's draw)."""
+    return {} if config is None else {"cap_mode": str(config.exp("cap_mode")), "host_threads": int(config.exp("host_threads"))}
 
 
 def _finish_on_device(result, path: str, max_points: int, seed: int, clock=None, config=None, progress_callback=None) -> Optional[int]:
@@ -178,8 +211,9 @@ def _finish_on_device(result, path: str, max_points: int, seed: int, clock=None,
     pts = result.device_points
     if pts is None or not pts[0].is_cuda:
         return None
-    normals = _cap_normals(result.device_normals, int(pts[0].shape[0]), max_points, seed)
-    pts = _cap_device_points(pts, int(pts[0].shape[0]), max_points, seed)
+    keep = _cap_keep(pts[0], pts[2] if len(pts) > 2 else None, max_points, seed, progress_callback=progress_callback, **_cap_args(config))
+    normals = _take_rows(result.device_normals, keep)           # (the index of a spatial cap is a device tensor: it never leaves the GPU)
+    pts = _cap_device_points(pts, keep)
     if config is not None and float(config.exp("fuse_voxel_size")) > 0.0:      # (behind the cap, in front of packing)
         xyz, normals, rgb = _apply_oriented_fusion(config, pts[0], normals, pts[1], progress_callback)
         pts = (xyz, rgb)
@@ -500,12 +534,11 @@ def _write_output(path: str, xyz, rgb, err, device_points=None, clock=None, as_p
         write_points3D_bin(path, xyz, rgb8, err)
 
 
-def _cap_device_points(device_points, n_before: int, max_points: int, seed: int):
-    """The same subset _apply_point_cap picks (``_cap_index``), applied to the GPU copy."""
-    if device_points is None:
+def _cap_device_points(device_points, keep):
+    """The GPU copy under the cap's index (``_cap_keep``)."""
+    if device_points is None or keep is None:
         return device_points
-    keep = _cap_index(n_before, max_points, seed)
-    return device_points if keep is None else tuple(_take_rows(t, keep) for t in device_points)
+    return tuple(_take_rows(t, keep) for t in device_points)
 
 
 def _was_cancelled(cb) -> bool:
@@ -576,8 +609,9 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
         n_points = _finish_on_device(result, config.output_path, args.max_points, args.seed, clock=pipeline_kwargs.get("stage_clock"), config=config,
                                      progress_callback=progress_callback)
         if n_points is None:
-            normals = _cap_normals(result.normals, int(result.xyz.shape[0]), args.max_points, args.seed)
-            xyz, rgb, err = _apply_point_cap(result.xyz, result.rgb, result.err, args.max_points, args.seed)
+            keep = _cap_keep(result.xyz, result.err, args.max_points, args.seed, progress_callback=progress_callback, **_cap_args(config))
+            normals = _take_rows(result.normals, keep)
+            xyz, rgb, err = (_take_rows(a, keep) for a in (result.xyz, result.rgb, result.err))
             if float(config.exp("fuse_voxel_size")) > 0.0:
                 xyz, normals, rgb = _apply_oriented_fusion(config, xyz, normals, rgb, progress_callback)
                 err = None
@@ -644,7 +678,7 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
         try:
             n_written = _finish_on_device(result, config.output_path, config.max_points, config.seed, clock=pipeline_kwargs.get("stage_clock"),
                                           config=config, progress_callback=progress_callback)
-        except (OrientedFusionRefused, GaussianInitRefused) as exc:
+        except (SpatialCapRefused, OrientedFusionRefused, GaussianInitRefused) as exc:
             return 1, str(exc)
         log.info(f"Dense point cloud saved to {config.output_path} ({n_written:,} points)")
         if progress_callback:
@@ -656,8 +690,12 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
         if progress_callback:
             progress_callback(93.0, "Applying distance filter...")
         announced = True
-        dev_pts = _cap_device_points(result.device_points, int(result.device_points[0].shape[0]), config.max_points, config.seed)
-        voxels = _voxel_filter_on_device(dev_pts, config.voxel_size)
+        try:
+            keep = _cap_keep(result.device_points[0], result.device_points[2], config.max_points, config.seed, progress_callback=progress_callback,
+                             **_cap_args(config))
+        except SpatialCapRefused as exc:
+            return 1, str(exc)
+        voxels = _voxel_filter_on_device(_cap_device_points(result.device_points, keep), config.voxel_size)
         if voxels is not None:
             n_vox = int(voxels[0].shape[0])
             log.info(f"Distance filter ({config.voxel_size:.4f}): {n_vox:,} points remaining")
@@ -669,9 +707,15 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
             if progress_callback:
                 progress_callback(100.0, f"Done! {n_vox:,} points")
             return 0, config.output_path
-    normals = _cap_normals(result.normals, int(result.xyz.shape[0]), config.max_points, config.seed)      # (None without experimental['estimate_normals'])
-    xyz, rgb, err = _apply_point_cap(result.xyz, result.rgb, result.err, config.max_points, config.seed)
-    dev_pts = _cap_device_points(result.device_points, result.xyz.shape[0], config.max_points, config.seed)
+    on_gpu = result.device_points is not None and result.device_points[0].is_cuda
+    try:                                                # (one choice, made where the cloud is, for the host arrays and the GPU copy alike)
+        keep = _cap_keep(result.device_points[0] if on_gpu else result.xyz, result.device_points[2] if on_gpu else result.err, config.max_points,
+                         config.seed, progress_callback=progress_callback, **_cap_args(config))
+    except SpatialCapRefused as exc:
+        return 1, str(exc)
+    normals = _take_rows(result.normals, keep)          # (None without experimental['estimate_normals'])
+    xyz, rgb, err = (_take_rows(a, keep) for a in (result.xyz, result.rgb, result.err))
+    dev_pts = _cap_device_points(result.device_points, keep)
     if float(config.exp("fuse_voxel_size")) > 0.0:         # (needs estimate_normals, which rules the voxel filter out)
         try:
             xyz, normals, rgb = _apply_oriented_fusion(config, xyz, normals, rgb, progress_callback)
@@ -750,6 +794,8 @@ def _experimental_from_args(args) -> dict:
     for key in ("gaussian_flatten", "gaussian_opacity", "gaussian_max_scale"):
         if getattr(args, key, None) is not None:
             exp[key] = float(getattr(args, key))
+    if str(getattr(args, "cap_mode", "random")) != "random":
+        exp["cap_mode"] = str(args.cap_mode)
     return exp
 
 
@@ -845,6 +891,9 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--gaussian_opacity", type=float, default=None, help="... initial opacity in (0, 1) (default 0.1, the 3DGS value; needs --gaussian_init)")
     ap.add_argument("--gaussian_max_scale", type=float, default=None,
                     help="... upper bound on the initial extent in scene units (default 0 = none; needs --gaussian_init)")
+    ap.add_argument("--cap_mode", type=str, default="random", choices=["random", "spatial"],
+                    help="how --max_points chooses: 'random' is upstream's uniform draw; 'spatial' keeps one point per cell along a Morton curve over "
+                         "the cloud - the point of smallest reprojection error -, so sparse regions are not starved (needs --max_points)")
     ap.add_argument("--keep_threads", action="store_true",
                     help="leave torch's intra-op thread count alone (by default it is lowered to the container's CPU quota; the count decides the last "
                          "bits of upstream's sampling normaliser, so a run compared bit for bit with upstream keeps upstream's setting)")
