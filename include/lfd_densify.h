@@ -343,6 +343,30 @@ int lfd_refiner_block(lfd_context* ctx, const void* x, int32_t x_is_f32, int32_t
 int lfd_refiner_block_host(lfd_context* ctx, const void* x, int32_t x_is_f32, int32_t B, int32_t C, int32_t H, int32_t W,
                            const float* dw_w, const float* scale, const float* shift, const float* pw_wT, const float* pw_b, uint16_t* out);
 
+/* The output head of RoMa-v2's refiners in one pass (RoMaV2/src/romav2/refiner.py: behind its nine blocks each ConvRefiner casts z to f32, runs two
+ * 1x1 convolutions, hidden -> 2 and hidden -> 4, and about a dozen element-wise kernels).  z (B, C, H, W) contiguous NCHW, bf16 (16-bit
+ * words) or, with z_is_f32 != 0, f32 - used as given, nothing is rounded on load; head_w (6, C) f32, rows 0..1 the warp head's weights, rows 2..5
+ * the confidence head's; head_b (6) f32 (zeros for a convolution without bias); prev_warp (B, H, W, 2) f32 read through prev_warp_strides[4],
+ * element strides in the order b, y, x, c (NULL: contiguous); prev_conf (B, H, W, prev_dim) f32 through prev_conf_strides[4], prev_dim 0 (prev_conf
+ * NULL), 1 or 4; refine_init the model's 4.0.  warp (B, H, W, 2) and conf (B, H, W, 4) f32 contiguous.  In f32 with IEEE fmaf and division, every
+ * rounding written out (csrc/lfd_head.hpp):
+ *   a[o] = head_b[o]; for c = 0..C-1: a[o] = fmaf(head_w[o][c], z[c], a[o])
+ *   warp.x = prev_warp.x + a[0] / (refine_init * (float)W), warp.y = prev_warp.y + a[1] / (refine_init * (float)H)
+ *   sp(v) = v > 20 ? v : (float)log1p(exp((double)v)); l00 = sp(a[3]) + 1e-6f, l10 = a[4], l11 = sp(a[5]) + 1e-6f
+ *   d = (a[2], l00 l00, l00 l10, l10 l10 + l11 l11); conf = prev + d (prev_dim 1: channels 1..3 of prev are +0; prev_dim 0: conf = d)
+ * warp and conf[..., 0] are the same bits on device and host; conf[..., 1:4] pass through the libraries' exp and log1p and may differ by
+ * 2^-21 of d plus the rounding of the last addition.  One launch on the context's stream, asynchronous, no atomics, no address formed
+ * from data.  LFD_ERR_INVALID: a null required pointer, prev_dim not 0, 1 or 4, prev_conf given or missing contrary to prev_dim, B, C, H or W < 1,
+ * H or W > 32768, B C H W > 2^31 - 1, a negative stride or one above 2^31 - 1, refine_init not finite or <= 0, an output overlapping an input or
+ * the other output.  lfd_refiner_head_host: the same routine over host pointers on a host context's threads - the same bits, whatever the thread
+ * count. */
+int lfd_refiner_head(lfd_context* ctx, const void* z, int32_t z_is_f32, int32_t B, int32_t C, int32_t H, int32_t W, const float* head_w,
+                     const float* head_b, const float* prev_warp, const int64_t* prev_warp_strides, const float* prev_conf,
+                     const int64_t* prev_conf_strides, int32_t prev_dim, float refine_init, float* warp, float* conf);
+int lfd_refiner_head_host(lfd_context* ctx, const void* z, int32_t z_is_f32, int32_t B, int32_t C, int32_t H, int32_t W, const float* head_w,
+                          const float* head_b, const float* prev_warp, const int64_t* prev_warp_strides, const float* prev_conf,
+                          const int64_t* prev_conf_strides, int32_t prev_dim, float refine_init, float* warp, float* conf);
+
 /* Forward-backward consistency gate on RoMa-v2's two warps (upstream has no counterpart: it reads warp_AB / overlap_AB only and its
  * "certainty threshold" is a floor, so a match that slid along its epipolar line - what a dense matcher produces at occlusions and depth steps -
  * passes every two-view test).  For each of n_pairs (reference, neighbour) pairs (1..LFD_MAX_SLOTS; the tables are HOST arrays of n_pairs DEVICE
@@ -738,7 +762,7 @@ int lfd_host_eval_correspondence(const float* cam1, const float* cam2, float xa_
  * The per-cell arithmetic is the host build of the very source the kernels compile (csrc/lfd_geometry.hpp; IEEE
  * division / square root where the device uses the 1-ulp v_rcp / v_sqrt), spread over n_threads std::threads
  * (<= 0: all hardware threads).  A host context accepts lfd_upload_cameras, lfd_last_error, lfd_destroy and the
- * *_host calls (the three below, lfd_local_corr_host, lfd_refiner_block_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host, lfd_consensus_filter_host, lfd_freespace_filter_host, lfd_fuse_oriented_host, lfd_knn_dist2_host, lfd_pack_gaussians_host and lfd_cap_spatial_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
+ * *_host calls (the three below, lfd_local_corr_host, lfd_refiner_block_host, lfd_refiner_head_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host, lfd_consensus_filter_host, lfd_freespace_filter_host, lfd_fuse_oriented_host, lfd_knn_dist2_host, lfd_pack_gaussians_host and lfd_cap_spatial_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
  * context: neither side ever stands in for the other.  Semantics (orders, counts, optional outputs, LFD_ERR_CAPACITY
  * with valid counts) are those of lfd_aggregate / lfd_triangulate_dense / lfd_triangulate_indexed. */
 int lfd_create_host(int32_t n_threads, lfd_context** out);

@@ -197,6 +197,9 @@ def load_library() -> C.CDLL:
     lib.lfd_local_corr_host.argtypes = list(lib.lfd_local_corr.argtypes)
     lib.lfd_refiner_block.argtypes = [ctxp, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 6
     lib.lfd_refiner_block_host.argtypes = list(lib.lfd_refiner_block.argtypes)
+    lib.lfd_refiner_head.argtypes = ([ctxp, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p,
+                                     C.POINTER(C.c_int64), C.c_int32, C.c_float, C.c_void_p, C.c_void_p])
+    lib.lfd_refiner_head_host.argtypes = list(lib.lfd_refiner_head.argtypes)
     lib.lfd_cycle_gate.argtypes = ([ctxp, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                    C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p])
     lib.lfd_cycle_gate_host.argtypes = list(lib.lfd_cycle_gate.argtypes)
@@ -270,7 +273,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_cap_spatial", "lfd_cap_spatial_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_refiner_head", "lfd_refiner_head_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_cap_spatial", "lfd_cap_spatial_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -808,6 +811,41 @@ def _refiner_block_call(fn, ctx, x, dw_w, scale, shift, pw_wt, pw_b, device):
     rc = fn(ctx, x.data_ptr(), int(x.dtype == torch.float32), B, Cc, H, W, ptr("dw_w"), ptr("scale"), ptr("shift"), ptr("pw_wt"), ptr("pw_b"),
             out.data_ptr())
     return rc, out
+
+
+def _refiner_head_call(fn, ctx, z, head_w, head_b, prev_warp, prev_conf, refine_init, device):
+    """Dtypes, devices and layout of a refiner_head call checked, the entry point ``fn`` called; (rc, warp, conf).  ``z`` (B, C, H, W) bf16 or
+    f32, contiguous NCHW - the call exists to read z once, so another layout is refused, not copied -, ``head_w`` (6, C) and ``head_b`` (6) f32, ``prev_warp`` (B, H, W, 2)
+    and ``prev_conf`` (B, H, W, 1 or 4; or None) f32 in ANY layout: they are handed over with their own strides, nothing is copied.  Shapes
+    and values are the library's to refuse."""
+    if not isinstance(z, torch.Tensor) or z.dim() != 4 or z.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("refiner_head: z must be a bfloat16 or float32 tensor of 4 dimensions (B, C, H, W)")
+    if not z.is_contiguous():
+        raise ValueError(f"refiner_head: z must be contiguous NCHW, got strides {tuple(z.stride())} for shape {tuple(z.shape)}")
+    B, Cc, H, W = (int(v) for v in z.shape)
+    for name, t, shape in (("head_w", head_w, (6, Cc)), ("head_b", head_b, (6,))):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise ValueError(f"refiner_head: {name} must be a float32 tensor of shape {shape} for C = {Cc}")
+    for name, t in (("prev_warp", prev_warp), ("prev_conf", prev_conf)):
+        if t is None and name == "prev_conf":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or tuple(t.shape[:3]) != (B, H, W):
+            raise ValueError(f"refiner_head: {name} must be a float32 tensor of shape ({B}, {H}, {W}, D)")
+    if int(prev_warp.shape[3]) != 2:
+        raise ValueError(f"refiner_head: prev_warp must have 2 channels, got {int(prev_warp.shape[3])}")
+    for name, t in (("z", z), ("head_w", head_w), ("head_b", head_b), ("prev_warp", prev_warp), ("prev_conf", prev_conf)):
+        if t is not None and t.device != device:
+            raise ValueError(f"refiner_head: {name} lives on {t.device}, this context computes on {device}")
+    z, head_w, head_b, prev_warp = z.detach(), head_w.detach().contiguous(), head_b.detach().contiguous(), prev_warp.detach()
+    prev_dim, pc_ptr, pc_strides = 0, None, None
+    if prev_conf is not None:
+        prev_conf = prev_conf.detach()
+        prev_dim, pc_ptr, pc_strides = int(prev_conf.shape[3]), prev_conf.data_ptr(), (C.c_int64 * 4)(*prev_conf.stride())
+    warp = torch.empty((B, H, W, 2), dtype=torch.float32, device=device)
+    conf = torch.empty((B, H, W, 4), dtype=torch.float32, device=device)
+    rc = fn(ctx, z.data_ptr(), int(z.dtype == torch.float32), B, Cc, H, W, head_w.data_ptr(), head_b.data_ptr(), prev_warp.data_ptr(),
+            (C.c_int64 * 4)(*prev_warp.stride()), pc_ptr, pc_strides, prev_dim, float(refine_init), warp.data_ptr(), conf.data_ptr())
+    return rc, warp, conf
 
 
 def _cycle_gate_arguments(cert, warp_ab, warp_ba, axes, device):
@@ -1430,6 +1468,17 @@ class HipDensifier:
         self._check(rc, "lfd_refiner_block")
         return out
 
+    def refiner_head(self, z: torch.Tensor, head_w: torch.Tensor, head_b: torch.Tensor, prev_warp: torch.Tensor,
+                     prev_conf: Optional[torch.Tensor] = None, refine_init: float = 4.0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The output head of RoMa-v2's refiners (lfd_refiner_head): the two 1x1 convolutions ``head_w`` (6, C; rows 0..1 the warp
+        head, 2..5 the confidence head) / ``head_b`` (6) on ``z`` (B, C, H, W; bf16 or f32, used as given), the warp update
+        ``prev_warp + a[0:2] / (refine_init (W, H))``, softplus and the Cholesky-to-precision conversion, and the addition of ``prev_conf``
+        (B, H, W, 1 or 4; None: nothing is added).  (warp (B, H, W, 2), conf (B, H, W, 4)) f32.  One launch on the context's stream;
+        ``prev_warp`` and ``prev_conf`` are read through their own strides; a ``z`` that is not contiguous NCHW raises ValueError."""
+        rc, warp, conf = _refiner_head_call(self._lib.lfd_refiner_head, self._ctx, z, head_w, head_b, prev_warp, prev_conf, refine_init, self.device)
+        self._check(rc, "lfd_refiner_head")
+        return warp, conf
+
     def cycle_gate(self, cert, warp_ab, warp_ba, w_match: int, h_match: int, certainty_thresh: float, cycle_thresh_px: float, axes=None,
                    inplace: bool = False, with_err: bool = False, rejected: Optional[torch.Tensor] = None):
         """Forward-backward consistency gate (lfd_cycle_gate) over up to 16 pairs in one launch on the context's stream.
@@ -1909,6 +1958,14 @@ class HostDensifier:
         rc, out = _refiner_block_call(self._lib.lfd_refiner_block_host, self._ctx, x, dw_w, scale, shift, pw_wt, pw_b, self.device)
         self._check(rc, "lfd_refiner_block_host")
         return out
+
+    def refiner_head(self, z: torch.Tensor, head_w: torch.Tensor, head_b: torch.Tensor, prev_warp: torch.Tensor,
+                     prev_conf: Optional[torch.Tensor] = None, refine_init: float = 4.0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """HipDensifier.refiner_head over CPU tensors (lfd_refiner_head_host): the same routine, the same bits, whatever the thread count."""
+        rc, warp, conf = _refiner_head_call(self._lib.lfd_refiner_head_host, self._ctx, z, head_w, head_b, prev_warp, prev_conf, refine_init,
+                                            self.device)
+        self._check(rc, "lfd_refiner_head_host")
+        return warp, conf
 
     def cycle_gate(self, cert, warp_ab, warp_ba, w_match: int, h_match: int, certainty_thresh: float, cycle_thresh_px: float, axes=None,
                    inplace: bool = False, with_err: bool = False, rejected: Optional[torch.Tensor] = None):

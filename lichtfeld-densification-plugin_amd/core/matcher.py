@@ -165,6 +165,18 @@ def _refiner_blocks_installed(shim, model):
 
 
 @contextlib.contextmanager
+def _refiner_head_installed(shim, model):
+    """While the block runs, the refiners under ``model.refiners`` have ``shim``'s forward (core/refiner_head.py): their own sub-modules up to
+    the activation behind the ninth block, then one lfd_refiner_head call; their own comes back afterwards, also when the block raises.
+    ``shim`` None: nothing is imported and nothing is touched."""
+    if shim is None:
+        yield
+        return
+    with shim.installed(model):
+        yield
+
+
+@contextlib.contextmanager
 def _bidirectional_forced(model, on: bool):
     """While the block runs, ``model.bidirectional`` is True when ``on`` - the presets turbo / fast / base run the model one way only, and the
     backward warp exists only in a two-way forward; the previous value comes back afterwards, also when the block raises.  ``on`` False (or a
@@ -187,16 +199,21 @@ class RomaMatcher:
     supports_feature_keys = True      # match_grids_batch(..., keys=(ref_key, [nbr_keys])) shares backbone features between references
     supports_fused_local_corr = True  # set_fused_local_corr(True): the refiners' local correlation runs in this package's HIP kernel
     supports_fused_refiner_blocks = True  # set_fused_refiner_blocks(True): the refiners' conv blocks run in this package's fused HIP kernel
+    supports_fused_refiner_head = True    # set_fused_refiner_head(True): the refiners' output head runs in this package's fused HIP kernel
     supports_backward_warp = True     # set_backward_warp(True): match_grids_batch returns (warp, cert, warp_BA) triples
     supports_precision = True         # set_precision(True): ... (warp, cert, warp_BA or None, precision) 4-tuples
 
     def __init__(self, device: str = "cuda", mode: str = "outdoor", setting: str = "fast", two_channel: bool = True,
-                 pairs_per_forward: int = 1, fused_local_corr: bool = False, fused_refiner_blocks: bool = False):
+                 pairs_per_forward: int = 1, fused_local_corr: bool = False, fused_refiner_blocks: bool = False,
+                 fused_refiner_head: bool = False):
         """``fused_local_corr``: the local correlation of the model's conv refiners is computed by lfd_local_corr (core/local_corr.py) instead
         of the model's grid_sample fallback; results agree within the bound of DESIGN.md 4.6, not bit for bit, so the default is off.
         ``fused_refiner_blocks``: the conv blocks of the model's refiners (depthwise 5x5, BatchNorm, ReLU, 1x1) are computed by
         lfd_refiner_block (core/refiner_blocks.py) instead of torch's separate kernels; results agree with the model's own bf16 path within
         the bound of DESIGN.md 4.18 (the fused block rounds less often), not bit for bit, so the default is off.
+        ``fused_refiner_head``: what each refiner runs behind its ninth block (f32 cast, the two 1x1 heads, warp update, softplus, precision
+        conversion, addition of the previous state) is one lfd_refiner_head launch (core/refiner_head.py) instead of about twenty torch
+        kernels; results agree with the model's own f32 tail within the bound of DESIGN.md 4.20, not bit for bit, so the default is off.
         ``pairs_per_forward`` > 1: the neighbours of a reference go through the model that many at a time (one batched forward,
         RoMaV2/tests/test_bidirectional.py runs B = 8) instead of one pair per forward as upstream's loop does (core/matcher.py:175-188
         there).  Batched GEMMs may round differently from single ones: the default stays 1, upstream's behaviour."""
@@ -218,10 +235,12 @@ class RomaMatcher:
         self.pairs_per_forward = max(1, int(pairs_per_forward))
         self._local_corr = None
         self._refiner_blocks = None
+        self._refiner_head = None
         self._backward = False
         self._precision = False
         self.set_fused_local_corr(fused_local_corr)
         self.set_fused_refiner_blocks(fused_refiner_blocks)
+        self.set_fused_refiner_head(fused_refiner_head)
         self._axes: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
         log.info(f"RoMaV2 initialized (setting={setting}, H_lr={self.model.H_lr}, W_lr={self.model.W_lr}, device={device})")
 
@@ -264,6 +283,22 @@ class RomaMatcher:
     @property
     def fused_refiner_blocks(self) -> bool:
         return self._refiner_blocks is not None
+
+    def set_fused_refiner_head(self, on: bool) -> None:
+        """The model's files are not modified: for the duration of each ``match_grids_batch`` call the refiners under ``model.refiners`` carry
+        an instance-level ``forward`` of a core.refiner_head.FusedRefinerHead, removed again afterwards."""
+        if bool(on) == (self._refiner_head is not None):
+            return
+        if on:
+            from .refiner_head import FusedRefinerHead
+            self._refiner_head = FusedRefinerHead()
+        else:
+            self._refiner_head.close()
+            self._refiner_head = None
+
+    @property
+    def fused_refiner_head(self) -> bool:
+        return self._refiner_head is not None
 
     def set_backward_warp(self, on: bool) -> None:
         """``match_grids_batch`` returns (warp, cert, warp_BA) triples: ``warp_BA`` (Hb, Wb, 2) is the model's own backward warp - normalised
@@ -318,7 +353,7 @@ class RomaMatcher:
         if not imB_list:
             return []
         with _local_corr_installed(self._local_corr), _refiner_blocks_installed(self._refiner_blocks, self.model), \
-                _bidirectional_forced(self.model, self._backward):
+                _refiner_head_installed(self._refiner_head, self.model), _bidirectional_forced(self.model, self._backward):
             return self._match_grids_batch(imA, imB_list, keys)
 
     @torch.inference_mode()
@@ -405,6 +440,8 @@ class RomaMatcher:
             self._local_corr.close()
         if self._refiner_blocks is not None:
             self._refiner_blocks.close()
+        if self._refiner_head is not None:
+            self._refiner_head.close()
         self._axes.clear()
         gc.collect()
         if torch.cuda.is_available():

@@ -85,7 +85,8 @@ def _make_matcher(config, dev, progress_callback):
         log.info("RoMaV2 weights not found in cache; expected cache paths: " + ", ".join(romav2_cached_weights_paths()))
     matcher = RomaMatcher(device=str(dev), mode="outdoor", setting=config.roma_setting, pairs_per_forward=int(config.pairs_per_forward),
                           fused_local_corr=bool(config.exp("fused_local_corr")),
-                          fused_refiner_blocks=bool(config.exp("fused_refiner_blocks")))
+                          fused_refiner_blocks=bool(config.exp("fused_refiner_blocks")),
+                          fused_refiner_head=bool(config.exp("fused_refiner_head")))
     if float(config.exp("cycle_thresh_px")) > 0.0:       # (a matcher built here starts with the backward warp off)
         matcher.set_backward_warp(True)
     if _wants_precision(config):                         # (... and hands out no precision planes)
@@ -279,6 +280,11 @@ def run_dense_pipeline(
             elif config.exp("fused_refiner_blocks"):
                 raise ValueError("experimental['fused_refiner_blocks'] asks the matcher to run the conv blocks of RoMa-v2's refiners in the HIP kernel, "
                                  f"but the injected matcher ({type(matcher).__name__}) does not declare supports_fused_refiner_blocks")
+            if bool(getattr(matcher, "supports_fused_refiner_head", False)):
+                matcher.set_fused_refiner_head(bool(config.exp("fused_refiner_head")))
+            elif config.exp("fused_refiner_head"):
+                raise ValueError("experimental['fused_refiner_head'] asks the matcher to run the output head of RoMa-v2's refiners in the HIP kernel, "
+                                 f"but the injected matcher ({type(matcher).__name__}) does not declare supports_fused_refiner_head")
             if bool(getattr(matcher, "supports_backward_warp", False)):
                 matcher.set_backward_warp(float(config.exp("cycle_thresh_px")) > 0.0)
             elif float(config.exp("cycle_thresh_px")) > 0.0:

@@ -49,6 +49,10 @@ EXPERIMENTAL_DEFAULTS = {
     # lfd_refiner_block instead of torch's separate kernels (core/refiner_blocks.py): one read and one write of the activation.
     # Rounds less often than the bf16 autocast sequence - closer to the f32 evaluation, not bit-identical to the model's own path - hence off
     "fused_refiner_blocks": False,
+    # what each of RoMa-v2's refiners runs behind its ninth block (f32 cast, two 1x1 convolutions, warp update, softplus, Cholesky-to-precision
+    # conversion, addition of the previous state: about twenty torch kernels) through ONE lfd_refiner_head launch (core/refiner_head.py,
+    # DESIGN.md 4.20).  Within the derived rounding bound of the model's own f32 tail, not bit for bit - hence off
+    "fused_refiner_head": False,
     # forward-backward consistency filter on the matcher's two warps (lfd_cycle_gate): a cell whose round trip A -> B -> A misses
     # its start by more than this many pixels of the match image loses the pair (certainty exactly 0, as if mask_b had masked it out).
     # 0.0 = off: the backward warp is not asked for and no new code runs.  Needs a matcher that hands out warp_BA (supports_backward_warp).
@@ -389,6 +393,8 @@ class DensePipelineConfig:
                         "experimental['dense_tile_segments'] retires tiles unordered")
         if not isinstance(self.exp("fused_refiner_blocks"), (bool, np.bool_)):
             return "experimental['fused_refiner_blocks'] must be True or False"
+        if not isinstance(self.exp("fused_refiner_head"), (bool, np.bool_)):
+            return "experimental['fused_refiner_head'] must be True or False"
         if not isinstance(self.exp("undistort_images"), (bool, np.bool_)):
             return "experimental['undistort_images'] must be True or False"
         normals = self.exp("estimate_normals")

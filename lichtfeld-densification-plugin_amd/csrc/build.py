@@ -14,8 +14,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(os.path.dirname(HERE), "liblfd_densify.so")
-SOURCES = ["lfd_api.hip", "lfd_kernels.hip", "lfd_select.hip", "lfd_writer.hip", "lfd_host.hip", "lfd_image.hip", "lfd_voxel.hip", "lfd_corr.hip", "lfd_cycle.hip", "lfd_support.hip", "lfd_refine.hip", "lfd_sigma.hip", "lfd_normals.hip", "lfd_consensus.hip", "lfd_undistort.hip", "lfd_freespace.hip", "lfd_fuse.hip", "lfd_knn.hip", "lfd_block.hip", "lfd_cap.hip"]
-HEADERS = ["lfd_device.hpp", "lfd_geometry.hpp", "lfd_context.hpp", "lfd_corr.hpp", "lfd_cycle.hpp", "lfd_support.hpp", "lfd_refine.hpp", "lfd_sigma.hpp", "lfd_normals.hpp", "lfd_consensus.hpp", "lfd_undistort.hpp", "lfd_freespace.hpp", "lfd_fuse.hpp", "lfd_knn.hpp", "lfd_block.hpp", "lfd_cap.hpp", os.path.join("..", "..", "include", "lfd_densify.h")]
+SOURCES = ["lfd_api.hip", "lfd_kernels.hip", "lfd_select.hip", "lfd_writer.hip", "lfd_host.hip", "lfd_image.hip", "lfd_voxel.hip", "lfd_corr.hip", "lfd_cycle.hip", "lfd_support.hip", "lfd_refine.hip", "lfd_sigma.hip", "lfd_normals.hip", "lfd_consensus.hip", "lfd_undistort.hip", "lfd_freespace.hip", "lfd_fuse.hip", "lfd_knn.hip", "lfd_block.hip", "lfd_cap.hip", "lfd_head.hip"]
+HEADERS = ["lfd_device.hpp", "lfd_geometry.hpp", "lfd_context.hpp", "lfd_corr.hpp", "lfd_cycle.hpp", "lfd_support.hpp", "lfd_refine.hpp", "lfd_sigma.hpp", "lfd_normals.hpp", "lfd_consensus.hpp", "lfd_undistort.hpp", "lfd_freespace.hpp", "lfd_fuse.hpp", "lfd_knn.hpp", "lfd_block.hpp", "lfd_cap.hpp", "lfd_head.hpp", os.path.join("..", "..", "include", "lfd_densify.h")]
 # -amdgpu-sched-strategy=max-ilp: the dense kernel is bound by its vector arithmetic (long dependent f64 chains); the
 # ILP-first machine scheduler is worth 3.5 % on it (profiles/history.md (r1/ablation.txt)), instruction semantics are unchanged
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
@@ -23,7 +23,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 SCHED_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 # ... except where it costs registers for nothing: the refiner-block kernels (lfd_block.hip) are bound by memory and by plain f32 FMAs on 25 + 32
 # wave-uniform weights held in SGPRs; hoisting every scalar load to the top spills 40 and 46 SGPRs there, the default scheduler none.
-DEFAULT_SCHED = ("lfd_block.hip",)
+# The refiner-head kernel (lfd_head.hip) streams z once and is bound by memory; max-ilp lifts its loads and the two f64 softplus evaluations per pixel
+# over each other and costs 64 / 98 .. 108 VGPRs (2- / 4-pixel lanes) against 50 .. 52 / 96: one wave per SIMD less for the 4-pixel kernels.
+DEFAULT_SCHED = ("lfd_block.hip", "lfd_head.hip")
 # Flags of one source only.  lfd_kernels.hip without the SLP vectoriser: a v_pk_*_f32 is cheaper per operation than two scalar instructions only
 # when both halves already sit in a register pair (profiles/r7/fma_f32_packing.txt); in the dense kernels the pairing costs more than it saves - moves to
 # assemble the pairs, scalar instructions, SGPR spill reloads inside the geometry loop.  Same arithmetic, same bits; -1.7 % of the dense kernel's time

@@ -16,6 +16,7 @@
 #include "lfd_context.hpp"
 #include "lfd_corr.hpp"
 #include "lfd_block.hpp"
+#include "lfd_head.hpp"
 #include "lfd_cycle.hpp"
 #include "lfd_support.hpp"
 #include "lfd_refine.hpp"
@@ -118,6 +119,7 @@ extern "C" __global__ void lfd_freespace_count_kernel(const float* xyz, long lon
                                                       uint8_t* violations, uint8_t* supports);
 hipError_t lfd_corr_launch(const LfdCorrArgs& p, hipStream_t stream);     // lfd_corr.hip
 hipError_t lfd_block_launch(const LfdBlockArgs& p, hipStream_t stream);   // lfd_block.hip
+hipError_t lfd_head_launch(const LfdHeadArgs& p, hipStream_t stream);     // lfd_head.hip
 hipError_t lfd_cycle_launch(const LfdCycleArgs& p, hipStream_t stream);   // lfd_cycle.hip
 hipError_t lfd_support_launch(const LfdSupportArgs& p, hipStream_t stream);   // lfd_support.hip
 hipError_t lfd_refine_launch(const LfdRefineArgs& p, hipStream_t stream);     // lfd_refine.hip
@@ -1930,6 +1932,21 @@ int lfd_refiner_block(lfd_context* ctx, const void* x, int32_t x_is_f32, int32_t
         return fail(ctx, LFD_ERR_INVALID, std::string("lfd_refiner_block: ") + why);
     LFD_HIP(ctx, hipSetDevice(ctx->device));
     LFD_HIP(ctx, lfd_block_launch(p, ctx->stream));
+    return LFD_OK;
+}
+
+// ---- the output head of RoMa-v2's refiners (lfd_head.hip) ---------------------------------------------------------------------------------
+int lfd_refiner_head(lfd_context* ctx, const void* z, int32_t z_is_f32, int32_t B, int32_t C, int32_t H, int32_t W, const float* head_w,
+                     const float* head_b, const float* prev_warp, const int64_t* prev_warp_strides, const float* prev_conf,
+                     const int64_t* prev_conf_strides, int32_t prev_dim, float refine_init, float* warp, float* conf) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    LfdHeadArgs p;
+    if (const char* why = lfd_head_fill(z, z_is_f32, B, C, H, W, head_w, head_b, prev_warp, prev_warp_strides, prev_conf, prev_conf_strides, prev_dim,
+                                        refine_init, warp, conf, p))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_refiner_head: ") + why);
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    LFD_HIP(ctx, lfd_head_launch(p, ctx->stream));
     return LFD_OK;
 }
 

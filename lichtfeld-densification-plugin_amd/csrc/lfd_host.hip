@@ -19,6 +19,7 @@
 #include "lfd_context.hpp"
 #include "lfd_corr.hpp"
 #include "lfd_block.hpp"
+#include "lfd_head.hpp"
 #include "lfd_cycle.hpp"
 #include "lfd_support.hpp"
 #include "lfd_refine.hpp"
@@ -304,6 +305,23 @@ int lfd_refiner_block_host(lfd_context* ctx, const void* x, int32_t x_is_f32, in
         const int pl = chunk / H, y = chunk - pl * H;
         const int b = pw_wT ? pl : pl / C, c = pw_wT ? 0 : pl - b * C;
         for (int xx = 0; xx < W; ++xx) lfd_block_pixel(p, b, c, y, xx);
+    });
+    return LFD_OK;
+}
+
+int lfd_refiner_head_host(lfd_context* ctx, const void* z, int32_t z_is_f32, int32_t B, int32_t C, int32_t H, int32_t W, const float* head_w,
+                          const float* head_b, const float* prev_warp, const int64_t* prev_warp_strides, const float* prev_conf,
+                          const int64_t* prev_conf_strides, int32_t prev_dim, float refine_init, float* warp, float* conf) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    LfdHeadArgs p;
+    if (const char* why = lfd_head_fill(z, z_is_f32, B, C, H, W, head_w, head_b, prev_warp, prev_warp_strides, prev_conf, prev_conf_strides, prev_dim,
+                                        refine_init, warp, conf, p))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_refiner_head_host: ") + why);
+    // a chunk is one row of one image: every output element is computed by exactly one chunk, from the inputs alone, so the thread count never shows
+    parallel_chunks(ctx, B * H, [&](int chunk) {                   // B H <= B C H W < 2^31
+        const int b = chunk / H, y = chunk - b * H;
+        for (int xx = 0; xx < W; ++xx) lfd_head_pixel(p, b, y, xx);
     });
     return LFD_OK;
 }

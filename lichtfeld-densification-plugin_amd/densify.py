@@ -781,6 +781,8 @@ def _experimental_from_args(args) -> dict:
         exp["undistort_images"] = True
     if bool(getattr(args, "fused_refiner_blocks", False)):
         exp["fused_refiner_blocks"] = True
+    if bool(getattr(args, "fused_refiner_head", False)):
+        exp["fused_refiner_head"] = True
     if bool(getattr(args, "estimate_normals", False)):
         exp["estimate_normals"] = True
     if getattr(args, "normal_radius_cells", None) is not None:
@@ -870,6 +872,10 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--fused_refiner_blocks", action="store_true",
                     help="run the conv blocks of RoMa-v2's refiners (depthwise 5x5, BatchNorm, ReLU, 1x1) in this package's fused HIP kernel instead "
                          "of torch's separate kernels: more accurate than the bf16 autocast sequence, not bit-identical to it")
+    ap.add_argument("--fused_refiner_head", action="store_true",
+                    help="run what each of RoMa-v2's refiners computes behind its conv blocks (the two 1x1 heads, the warp update, softplus and the "
+                         "precision conversion) in one launch of this package's HIP kernel instead of about twenty torch kernels: within rounding "
+                         "of the model's own f32 tail, not bit-identical to it")
     ap.add_argument("--estimate_normals", action="store_true",
                     help="give every point a unit surface normal, fitted to its winning neighbour's warp around its grid cell and oriented towards "
                          "its reference's camera: the PLY then has x y z nx ny nz red green blue vertices (needs a .ply --out_name)")
