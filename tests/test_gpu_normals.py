@@ -77,7 +77,7 @@ def within_one_ulp(a, b):
     return np.abs(a.astype(np.float64) - b.astype(np.float64)) <= np.spacing(np.maximum(np.abs(a), np.abs(b)).astype(np.float32))
 
 
-@pytest.mark.parametrize("R", [1, 4])
+@pytest.mark.parametrize("R", [1, 2, 4])
 @pytest.mark.parametrize("channels", [2, 4])
 @pytest.mark.parametrize("H,W", [(20, 24), (6, 8)])
 def test_noise_free_device_equals_twin(dens, twin, H, W, channels, R):
@@ -90,7 +90,7 @@ def test_noise_free_device_equals_twin(dens, twin, H, W, channels, R):
         assert ok.all(), kind
 
 
-@pytest.mark.parametrize("R", [1, 3])
+@pytest.mark.parametrize("R", [1, 2, 3])
 @pytest.mark.parametrize("scene", ["noisy", "in_band"])
 def test_noisy_device_against_twin_and_reference(dens, twin, scene, R):
     """``noisy``: the scene whose reference flags at most BAND_CAP of the points (tests/test_normals_host.py checks the same scene and seed on
