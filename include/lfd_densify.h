@@ -536,6 +536,38 @@ int lfd_estimate_normals(lfd_context* ctx, const lfd_batch* batch, const lfd_poi
 int lfd_estimate_normals_host(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets, int32_t radius_cells,
                               float depth_step_rel, float reproj_thresh, float* normals_out, uint8_t* status, int64_t* counters);
 
+/* Multi-view point colour (no upstream counterpart - upstream's colour is the bilinear sample of the reference image alone).  A
+ * column rewrite, not a filter: no point, count or order changes.  Per input point X of reference r made by winning slot s on cell c, all in
+ * f32 with every rounding written out (csrc/lfd_colour.hpp):
+ *   guard        the three rgb values are copied bit for bit with status 0 where X or in->rgb[i] is not finite, the cell lies outside the grid
+ *                or s >= n_slots[r] (no address is formed from the cell or the slot)
+ *   views        in this order: the reference, whose colour is in->rgb[i] as it stands; the winning slot s unless its observation (the last
+ *                two channels of warp[r, s][c]) is not finite; every slot j != s, j < n_slots[r], ascending, that lfd_support_filter's
+ *                candidate test accepts for X at support_thresh_px - the same routine, hence the same set
+ *   colour       of neighbour j: the four-tap f32 blend lfd_triangulate_* use for the reference image, applied to nbr_image[r * k + j] at
+ *                the match pixel ((xb + 1) * 0.5) * (w_match - 1), ((yb + 1) * 0.5) * (h_match - 1) of its observation (xb, yb)
+ *   mode 1       mean: per channel sum = c_ref; sum = sum + c_s; sum = sum + c_j ...; the result is sum * RN_f32(1 / n), the factor from
+ *                a table (1 / n in f64, rounded once)
+ *   mode 2       median: per channel the middle one of the n values in ascending order, (lo + hi) * 0.5f of the two middle ones for even n
+ * nbr_image: HOST array [n_refs * k] of DEVICE images u8 [h_match * w_match * 3] (entries at j >= n_slots[r] are ignored); the table is kept on
+ * the device, compared with what it holds and uploaded on the context's stream when it differs, without synchronising.  `in` and ref_offsets
+ * are what a triangulation call or any post-stage wrote (cell, slot and rgb required, err unused).  rgb_out: exactly in->rgb (in place), or
+ * f32 [3 * in->capacity] overlapping nothing of `in`; status: NULL or u8 [in->capacity], the number of views n blended (0: guarded); points
+ * beyond the last offset are not touched.  counters: NULL or device i64 [2], ADDED to: points blended, the sum of their n (integer adds only).
+ * One launch on the context's stream, asynchronous and deterministic; the batch is prepared as lfd_support_filter prepares it.
+ * LFD_ERR_INVALID: a null required pointer, missing cell / slot / rgb, a null image in a valid slot, mode outside {1, 2}, support_thresh_px
+ * <= 0 or not finite, rgb_out or status partially overlapping `in` or each other, a capacity beyond 2^31 - 1.  lfd_colour_multiview_host: the
+ * same routine over host pointers (host images, counters: host i64 [2]) on a host context's threads, the same bits.  A host context is served
+ * by _host only, a device context refuses _host (LFD_ERR_STATE). */
+#define LFD_COLOUR_MEAN 1
+#define LFD_COLOUR_MEDIAN 2
+int lfd_colour_multiview(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets,
+                         const uint8_t* const* nbr_image, float support_thresh_px, int32_t mode, float* rgb_out, uint8_t* status,
+                         int64_t* counters);
+int lfd_colour_multiview_host(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets,
+                              const uint8_t* const* nbr_image, float support_thresh_px, int32_t mode, float* rgb_out, uint8_t* status,
+                              int64_t* counters);
+
 /* Cross-reference consensus filter on the final cloud (no upstream counterpart - the cloud upstream writes is the plain union of what
  * every reference triangulated on its own).  The cloud is the concatenation of n_refs references' points; a point is kept iff at least min_refs
  * OTHER references own a point within `radius` of it - the fusion rule of multi-view stereo, one level above lfd_support_filter, which only sees

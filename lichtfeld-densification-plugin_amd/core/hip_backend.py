@@ -217,6 +217,9 @@ def load_library() -> C.CDLL:
     lib.lfd_estimate_normals.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_points), C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_void_p,
                                          C.c_void_p, C.c_void_p]
     lib.lfd_estimate_normals_host.argtypes = list(lib.lfd_estimate_normals.argtypes)
+    lib.lfd_colour_multiview.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_points), C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]
+    lib.lfd_colour_multiview_host.argtypes = list(lib.lfd_colour_multiview.argtypes)
     lib.lfd_pack_ply_normals.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.lfd_consensus_filter.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_float, C.c_int32,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)]
@@ -273,7 +276,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_refiner_head", "lfd_refiner_head_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_cap_spatial", "lfd_cap_spatial_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_refiner_head", "lfd_refiner_head_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_colour_multiview", "lfd_colour_multiview_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_cap_spatial", "lfd_cap_spatial_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -482,6 +485,7 @@ class ReferenceInputs:
     mask_b: Optional[List[Optional[torch.Tensor]]] = None
     fundamental: Optional[Sequence[np.ndarray]] = None   # per slot (3,3) f32: upstream's F for the pair (see PreparedBatch)
     precision: Optional[List[torch.Tensor]] = None   # per slot (H,W,3) f32: RoMa-v2's precision (q00, q01, q11), match px^-2
+    nbr_images: Optional[List[torch.Tensor]] = None  # per slot (h_match,w_match,3) u8: the neighbour's match-size image (lfd_colour_multiview)
 
 
 @dataclasses.dataclass
@@ -588,6 +592,17 @@ class PreparedBatch:
                     self.precision[i * k + j] = self._chk(r.precision[j], torch.float32, (H, W, 3), "precision").data_ptr()
         elif any(r.precision is not None for r in self.refs):
             raise ValueError("precision planes must be given for every reference of a batch or for none")
+        # the neighbours' images of lfd_colour_multiview: a table of its own like the precision planes', present when EVERY reference has them
+        self.nbr_images = None
+        if all(r.nbr_images is not None for r in self.refs):
+            self.nbr_images = (C.c_void_p * (n * k))()
+            for i, r in enumerate(self.refs):
+                if len(r.nbr_images) != len(r.cert):
+                    raise ValueError("nbr_images / cert length mismatch")
+                for j in range(len(r.cert)):
+                    self.nbr_images[i * k + j] = self._chk(r.nbr_images[j], torch.uint8, (h_match, w_match, 3), "nbr_images").data_ptr()
+        elif any(r.nbr_images is not None for r in self.refs):
+            raise ValueError("neighbour images must be given for every reference of a batch or for none")
         self.fundamental = None
         if cameras is not None or any(r.fundamental is not None for r in self.refs):
             fund = np.zeros((n * k, 9), np.float32)
@@ -1032,6 +1047,54 @@ def _normals_call(fn, ctx, batch, src, radius, depth_step_rel, reproj_thresh, wi
         src.normals_valid = True
         return rc, src, status
     return rc, dataclasses.replace(src, normals=normals[:cap]), status
+
+
+COLOUR_MODES = {"mean": 1, "median": 2}      # LFD_COLOUR_MEAN, LFD_COLOUR_MEDIAN of include/lfd_densify.h
+
+
+def _colour_call(fn, ctx, batch, src, support_thresh_px, mode, with_status, counters, device):
+    """One lfd_colour_multiview[_host] call.  ``src``: the OutputBuffers a triangulation launch or a post-stage wrote for ``batch`` - their
+    ``rgb`` is rewritten IN PLACE, asynchronously, and the buffers are returned - or a collected TriangulationOutput (the result is a copy
+    with a new rgb tensor).  ``mode``: "mean" or "median".  ``counters``: None, or an int64 [2] tensor on the context's device that is added
+    to (points blended, the sum of their views).  Returns (rc, result or None, status or None)."""
+    if mode not in COLOUR_MODES:
+        raise ValueError("colour_multiview: mode must be 'mean' or 'median'")
+    if batch.nbr_images is None:
+        raise ValueError("colour_multiview: the batch's references carry no neighbour images (ReferenceInputs.nbr_images)")
+    collected = isinstance(src, TriangulationOutput)
+    if src.cell is None or src.slot is None:
+        raise ValueError("colour_multiview: the source buffers need the cell / slot outputs (with_cell=True)")
+    if counters is not None and (counters.dtype != torch.int64 or counters.numel() != 2 or counters.device != device or not counters.is_contiguous()):
+        raise ValueError(f"colour_multiview: counters must be a contiguous int64 tensor of two elements on {device}")
+    if collected:
+        n = int(src.xyz.shape[0])
+        keep = [src.xyz.contiguous(), src.rgb.contiguous(), src.cell.contiguous(), src.slot.contiguous()]
+        if n == 0:                            # (an empty tensor may have no address at all; the library wants its arrays)
+            keep = [torch.zeros((1, 3) if t.dim() == 2 else (1,), dtype=t.dtype, device=t.device) for t in keep]
+        if any(t.device != device for t in keep):
+            raise ValueError(f"colour_multiview: the points live on {keep[0].device}, this context computes on {device}")
+        offs = torch.from_numpy(np.ascontiguousarray(src.ref_offsets, np.int64)).to(device)
+        pts = lfd_points(xyz=keep[0].data_ptr(), rgb=keep[1].data_ptr(), err=None, cell=keep[2].data_ptr(), slot=keep[3].data_ptr(), capacity=n)
+        n_refs, k, cap = int(len(src.ref_offsets)) - 1, int(src.seg_counts.shape[1]), n
+        rgb_out = torch.empty((max(n, 1), 3), dtype=torch.float32, device=device)
+    else:
+        if src.xyz.device != device:
+            raise ValueError(f"colour_multiview: the points live on {src.xyz.device}, this context computes on {device}")
+        keep, offs, pts, n_refs, k, cap = [], src.ref_offsets, src.c, src._n_refs, src._k, src.capacity
+        rgb_out = src.rgb
+    if n_refs != batch.n_refs or k != batch.k:
+        raise ValueError(f"colour_multiview: the points were made for {n_refs} references x {k} slots, the batch has {batch.n_refs} x {batch.k}")
+    status = torch.zeros((max(cap, 1),), dtype=torch.uint8, device=device) if with_status else None
+    rc = fn(ctx, C.byref(batch.c), C.byref(pts), offs.data_ptr(), C.cast(batch.nbr_images, C.c_void_p), C.c_float(float(support_thresh_px)),
+            int(COLOUR_MODES[mode]), rgb_out.data_ptr(), status.data_ptr() if with_status else None,
+            counters.data_ptr() if counters is not None else None)
+    if rc != 0:
+        return rc, None, None
+    if with_status:
+        status = status[:cap]
+    if not collected:
+        return rc, src, status
+    return rc, dataclasses.replace(src, rgb=rgb_out[:cap], _packed=None), status
 
 
 def _depth_sigma_call(fn, ctx, batch, src, max_rel_sigma, iso_sigma_px, refine_status, support_thresh_px, with_sigma, into, device):
@@ -1558,6 +1621,22 @@ class HipDensifier:
         self._check(rc, "lfd_estimate_normals")
         return (res, status) if with_status else res
 
+    def colour_multiview(self, batch: PreparedBatch, out_buffers, support_thresh_px: float, mode: str, with_status: bool = False,
+                         counters: Optional[torch.Tensor] = None):
+        """Multi-view point colour (lfd_colour_multiview): the colour of every point ``out_buffers`` holds for ``batch`` (an
+        OutputBuffers a launch or a post-stage wrote - rewritten in place, asynchronously on the context's stream - or a collected
+        TriangulationOutput, whose copy carries the new ``rgb``) becomes the ``mode`` ("mean" / "median") over the views that see it: its
+        reference (the colour it has), the neighbour that won it and every other neighbour the support filter's test confirms within
+        ``support_thresh_px``, each sampled from ``ReferenceInputs.nbr_images``.  Points, counts and order are untouched.  ``counters``: int64
+        [2] on the device, added to (points blended, the sum of their views).  With ``with_status`` a pair (result, uint8 per point: views
+        blended, 0 = left as it was)."""
+        self._same_device(batch)
+        with torch.cuda.stream(self.stream):
+            rc, res, status = _colour_call(self._lib.lfd_colour_multiview, self._ctx, batch, out_buffers, support_thresh_px, mode, with_status,
+                                           counters, self.device)
+        self._check(rc, "lfd_colour_multiview")
+        return (res, status) if with_status else res
+
     def pack_ply_normals(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
         """(n*27,) u8 device tensor: the body of a PLY whose header lists x y z nx ny nz red green blue."""
         xyz, normals, rgb = self._pts(xyz, 3, "xyz"), self._pts(normals, 3, "normals"), self._pts(rgb, 3, "rgb")
@@ -2011,6 +2090,15 @@ class HostDensifier:
         rc, res, status = _normals_call(self._lib.lfd_estimate_normals_host, self._ctx, batch, out_buffers, radius, depth_step_rel, reproj_thresh,
                                         with_status, counters, self.device)
         self._check(rc, "lfd_estimate_normals_host")
+        return (res, status) if with_status else res
+
+    def colour_multiview(self, batch: PreparedBatch, out_buffers, support_thresh_px: float, mode: str, with_status: bool = False,
+                         counters: Optional[torch.Tensor] = None):
+        """HipDensifier.colour_multiview over CPU tensors (lfd_colour_multiview_host): the same per-point routine, the same bits."""
+        self._same_device(batch)
+        rc, res, status = _colour_call(self._lib.lfd_colour_multiview_host, self._ctx, batch, out_buffers, support_thresh_px, mode, with_status,
+                                       counters, self.device)
+        self._check(rc, "lfd_colour_multiview_host")
         return (res, status) if with_status else res
 
     def pack_ply_normals(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:

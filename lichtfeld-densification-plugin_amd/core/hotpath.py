@@ -96,6 +96,10 @@ class HotPath:
         self.normal_radius = int(config.exp("normal_radius_cells"))
         self.normal_depth_step = float(config.exp("normal_depth_step_rel"))
         self._normal_counter: Optional[torch.Tensor] = None     # int64 [2] where the kernels run: points fitted / fallen back, added to
+        # multi-view point colour (lfd_colour_multiview): a column rewrite behind the stages that move or drop points
+        self.colour_mode = str(config.exp("multiview_colour"))
+        self.colour = self.colour_mode != "off"
+        self._colour_counter: Optional[torch.Tensor] = None     # int64 [2] where the kernels run: points blended / the sum of their views, added to
         on = bool(config.exp("undistort_images"))
         self._distortion = [c.active_distortion() if on else None for c in cams]
 
@@ -146,10 +150,27 @@ class HotPath:
             with self.clock.stage("kernel"):
                 res = self._sigma_gated(batch, res, status)
             self._support_count(res)
+        if self.colour:
+            with self.clock.stage("kernel"):
+                res = self._recoloured(batch, res)
         if self.normals:
             with self.clock.stage("kernel"):
                 res = self._with_normals(batch, res)
         return res
+
+    def _recoloured(self, batch: hb.PreparedBatch, out):
+        """``out`` (buffers on the stream: in place; or a collected result: a copy) with the colour of every point blended over the views that
+        see it: one launch of lfd_colour_multiview on the stream that made the points, behind every stage that moves or drops them.  The
+        counters stay where the kernels run until ``colour_totals``; like the re-triangulation's they count every launch issued."""
+        if self._colour_counter is None:
+            self._colour_counter = torch.zeros(2, dtype=torch.int64, device=self.dev)
+        return self.dens.colour_multiview(batch, out, self.support_thresh_px, self.colour_mode, counters=self._colour_counter)
+
+    def colour_totals(self) -> Tuple[int, int]:
+        """(points whose colour was blended, the sum of the views blended into them) over the launches of the run: the one read of the counters."""
+        if self._colour_counter is None:
+            return 0, 0
+        return tuple(int(v) for v in self._colour_counter.cpu())
 
     def _with_normals(self, batch: hb.PreparedBatch, out):
         """``out`` (buffers on the stream, or a collected result) with the normals of the points it holds NOW: one launch of
@@ -213,6 +234,8 @@ class HotPath:
             finally:
                 self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, _pool_kind(out)), []).append(out)
             out = into
+        if self.colour:
+            out = self._recoloured(batch, out)
         if self.normals:
             out = self._with_normals(batch, out)
         return out
@@ -330,7 +353,7 @@ class HotPath:
             use_masks = d["mask_a"] is not None or any(m is not None for m in d["nbr_masks"])
             return hb.ReferenceInputs(ref_cam=packed.ref_index, nbr_cams=list(packed.nbr_indices), cert=certs, warp=warps,
                                       image=d["image"], mask_a=d["mask_a"], mask_b=list(d["nbr_masks"]) if use_masks else None,
-                                      precision=precision)
+                                      precision=precision, nbr_images=list(d["nbr_images"]) if self.colour else None)
         use_masks = packed.mask_a is not None or any(m is not None for m in packed.nbr_masks)
         mask_b = None
         with self.clock.stage("prepare"):        # the host-prepared image and masks cross to where the kernels run
@@ -338,8 +361,10 @@ class HotPath:
                 mask_b = [_upload_u8(m, dev) if m is not None else None for m in packed.nbr_masks]
             image = _upload_u8(packed.image, dev)
             mask_a = _upload_u8(packed.mask_a, dev) if packed.mask_a is not None else None
+            # (multi-view colour: the neighbours' match-size images cross beside the reference's)
+            nbr_images = [_upload_u8(im, dev) for im in packed.nbr_images] if self.colour else None
         return hb.ReferenceInputs(ref_cam=packed.ref_index, nbr_cams=list(packed.nbr_indices), cert=certs, warp=warps, image=image,
-                                  mask_a=mask_a, mask_b=mask_b, precision=precision)
+                                  mask_a=mask_a, mask_b=mask_b, precision=precision, nbr_images=nbr_images)
 
     def sampled(self, ref: hb.ReferenceInputs, axes, rng, device_seed: Optional[int], need_best: bool = False
                 ) -> Tuple[Optional[hb.TriangulationOutput], Optional[torch.Tensor]]:
@@ -624,7 +649,7 @@ class HotPath:
             if bool(self.config.exp("dense_tile_segments")):
                 # unordered retirement (no look-back), raster order restored from the tile table: the same result, bit for bit
                 return self.dens.order_segments(self.dens.triangulate_dense_segments(batch, self.params))
-            if (self.min_support > 0 or self.refine or self.max_sigma > 0.0 or self.normals) and not self.on_host:
+            if (self.min_support > 0 or self.refine or self.max_sigma > 0.0 or self.colour or self.normals) and not self.on_host:
                 # the launch, the filter, the re-triangulation and / or the gate behind it on the same stream, then the one read-back of the offsets
                 cap = batch.n_refs * batch.H * batch.W
                 out = hb.OutputBuffers(cap, batch.n_refs, batch.k, self.dev)
@@ -636,6 +661,8 @@ class HotPath:
                     out, status = self._refined(batch, out, self.max_sigma > 0.0)
                 if self.max_sigma > 0.0:
                     out = self._sigma_gated(batch, out, status)
+                if self.colour:
+                    out = self._recoloured(batch, out)
                 if self.normals:
                     out = self._with_normals(batch, out)
                 self.dens.check_launches()

@@ -243,6 +243,9 @@ def run_dense_pipeline(
         # (a condition of the world, not of the configuration: every rank sees it and stops here, before anything is set up)
         raise ValueError("experimental['estimate_normals'] cannot run sharded over several GPUs: the exchange of a sharded run does not carry the "
                          "normals (rows of xyz, rgb, err or 15-byte records)")
+    if world > 1 and str(config.exp("multiview_colour")) != "off":
+        raise ValueError("experimental['multiview_colour'] cannot run sharded over several GPUs: like the normals it is a stage of the single-GPU "
+                         "run, and the sharded schedules have not been taken through it")
     config, dev = _resolve_backend(config, backend, device)
     per_ref_rng = bool(config.per_reference_rng) or world > 1
     # refs_per_launch = 0 (the default): several references per launch where the results do not depend on it and nobody watches the run proceed
@@ -353,6 +356,10 @@ def run_dense_pipeline(
             n_in, n_kept = hot.sigma_totals()
             noise = f"isotropic match noise {hot.iso_sigma_px:g} px" if hot.iso_sigma_px > 0.0 else "the matcher's precision planes"
             log.info(f"Depth-uncertainty gate: relative depth sigma at most {hot.max_sigma:g} ({noise}), {n_in} points in, {n_kept} kept")
+        if hot.colour:
+            n_col, n_views = hot.colour_totals()
+            log.info(f"Multi-view colour: {hot.colour_mode} over the confirming views (within {hot.support_thresh_px:g} px), {n_col} points blended, "
+                     f"{(n_views / n_col if n_col else 0.0):.2f} views per point")
         if hot.normals:
             n_fit, n_fell = hot.normal_totals()
             log.info(f"Surface normals: window radius {hot.normal_radius} cell(s), depth step {hot.normal_depth_step:g}, {n_fit} points fitted, "

@@ -137,8 +137,15 @@ EXPERIMENTAL_DEFAULTS = {
     # cells, the cells picked evenly along the curve, each cell's point of smallest reprojection error; the kept points stay in input order.
     # Needs max_points > 0.  "random" = today's behaviour: no new code runs.
     "cap_mode": "random",
+    # multi-view point colour (lfd_colour_multiview): a point's colour becomes the "mean" or the "median", per channel, over the
+    # views that see it - its reference (upstream's colour), the neighbour that won it and every other loaded neighbour that the support
+    # filter's test confirms within support_threshold() - instead of the one photograph's sample.  Rewrites rgb only: no point, count or order
+    # changes, and it works with or without min_support_views.  Behind support filter, re-triangulation and depth gate, in front of the
+    # normals.  "off" = today's colour: no new code runs and every output stays byte-identical.
+    "multiview_colour": "off",
 }
 CAP_MODES = ("random", "spatial")
+COLOUR_MODES = ("off", "mean", "median")
 CONSENSUS_CAP = 8            # LFD_CONSENSUS_CAP of include/lfd_densify.h
 
 
@@ -460,6 +467,20 @@ class DensePipelineConfig:
             return "experimental['cap_mode'] must be 'random' (upstream's draw) or 'spatial' (one point per cell along the Morton curve)"
         if cap_mode == "spatial" and int(self.max_points) <= 0:
             return "experimental['cap_mode'] = 'spatial' is how max_points chooses: it needs max_points > 0"
+        colour = self.exp("multiview_colour")
+        if not isinstance(colour, str) or colour not in COLOUR_MODES:
+            return "experimental['multiview_colour'] must be 'off' (the reference's colour alone), 'mean' or 'median' (over the views that see the point)"
+        if colour != "off":
+            if not (self.support_threshold() > 0.0):
+                return ("experimental['multiview_colour'] takes the other neighbours by the support filter's test: experimental['support_thresh_px'] or, "
+                        "for its default, reproj_thresh must be > 0")
+            if self.stream_output:
+                return ("experimental['multiview_colour'] rewrites the colour of points held as arrays (xyz, rgb, cell, slot); stream_output writes "
+                        "15-byte records while the run proceeds")
+            if self.exp("dense_tile_segments"):
+                return "experimental['multiview_colour'] needs the ordered dense result; experimental['dense_tile_segments'] retires tiles unordered"
+            if self.exchange_record_format() == "ply":
+                return "experimental['multiview_colour'] rewrites f32 rows; experimental['exchange_records'] must be 'f32' with it"
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):
                 return "stream_output writes a PLY while the run proceeds: output_path must end in .ply"

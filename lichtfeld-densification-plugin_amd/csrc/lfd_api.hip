@@ -21,6 +21,7 @@
 #include "lfd_support.hpp"
 #include "lfd_refine.hpp"
 #include "lfd_normals.hpp"
+#include "lfd_colour.hpp"
 #include "lfd_sigma.hpp"
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
@@ -125,6 +126,7 @@ hipError_t lfd_support_launch(const LfdSupportArgs& p, hipStream_t stream);   //
 hipError_t lfd_refine_launch(const LfdRefineArgs& p, hipStream_t stream);     // lfd_refine.hip
 hipError_t lfd_sigma_launch(const LfdSigmaArgs& p, hipStream_t stream);       // lfd_sigma.hip
 hipError_t lfd_normals_launch(const LfdNormalArgs& p, hipStream_t stream);    // lfd_normals.hip
+hipError_t lfd_colour_launch(const LfdColourArgs& p, hipStream_t stream);     // lfd_colour.hip
 extern "C" __global__ void lfd_pack_ply_normals_kernel(const float* xyz, const float* normals, const float* rgb, long long n, unsigned char* out);
 extern "C" __global__ void lfd_select_topm_kernel(LfdSelectArgs A);
 extern "C" __global__ void lfd_select_filter_mw_kernel(LfdSelectArgs A, LfdSelectNorms norms);
@@ -748,11 +750,13 @@ void lfd_destroy(lfd_context* ctx) {
     }
     for (hipEvent_t ev : ctx->kt_start) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->kt_stop) (void)hipEventDestroy(ev);
-    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->cloud_ws, &ctx->support_ws, &ctx->prec_tab, &ctx->undist_cnt})
+    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->cloud_ws, &ctx->support_ws, &ctx->prec.tab, &ctx->colour_img.tab, &ctx->undist_cnt})
         if (b->ptr) (void)hipFree(b->ptr);
     if (ctx->pinned_words) (void)hipHostFree(ctx->pinned_words);
-    if (ctx->prec_pinned) (void)hipHostFree(ctx->prec_pinned);
-    if (ctx->prec_free) (void)hipEventDestroy(ctx->prec_free);
+    for (lfd_context::PointerTable* t : {&ctx->prec, &ctx->colour_img}) {
+        if (t->pinned) (void)hipHostFree(t->pinned);
+        if (t->free_ev) (void)hipEventDestroy(t->free_ev);
+    }
     delete ctx;
 }
 
@@ -2008,34 +2012,39 @@ int lfd_support_filter(lfd_context* ctx, const lfd_batch* batch, const lfd_point
 }
 
 // ---- multi-view re-triangulation of supported points (lfd_refine.hip) ------------------------------------------------------------------------
-// The table of precision-plane pointers of a batch, where the kernel reads it: like the batch's descriptor tables it is compared with what the
-// device already holds and uploaded only when it differs, on the launch stream (an earlier launch still reading the old table precedes the
-// copy in it), from a pinned staging buffer that is waited for only while its last upload is still on its way.
-static int upload_precision_table(lfd_context* ctx, const lfd_batch* b, const float* const* precision, const float* const** d_tab) {
-    const size_t n = (size_t)b->n_refs * b->k, bytes = n * sizeof(const float*);
+// A table of per-(reference, slot) device pointers of a batch (precision planes, neighbour images), where the kernel reads it: like the batch's
+// descriptor tables it is compared with what the device already holds and uploaded only when it differs, on the launch stream (an earlier
+// launch still reading the old table precedes the copy in it), from a pinned staging buffer that is waited for only while its last upload is
+// still on its way.  Entries of slots the batch does not use are null.
+static int upload_pointer_table(lfd_context* ctx, lfd_context::PointerTable& t, const lfd_batch* b, const void* const* ptrs, const void* const** d_tab) {
+    const size_t n = (size_t)b->n_refs * b->k, bytes = n * sizeof(const void*);
     std::vector<unsigned char> blob(bytes, 0);
-    const float** tab = reinterpret_cast<const float**>(blob.data());
+    const void** tab = reinterpret_cast<const void**>(blob.data());
     for (int r = 0; r < b->n_refs; ++r)
-        for (int j = 0; j < b->n_slots[r]; ++j) tab[(size_t)r * b->k + j] = precision[(size_t)r * b->k + j];
-    if (!ctx->prec_tab.ptr || ctx->prec_cache != blob) {
-        int rc = ensure(ctx, ctx->prec_tab, bytes);
+        for (int j = 0; j < b->n_slots[r]; ++j) tab[(size_t)r * b->k + j] = ptrs[(size_t)r * b->k + j];
+    if (!t.tab.ptr || t.cache != blob) {
+        int rc = ensure(ctx, t.tab, bytes);
         if (rc != LFD_OK) return rc;
-        if (!ctx->prec_free) LFD_HIP(ctx, hipEventCreateWithFlags(&ctx->prec_free, hipEventDisableTiming));
-        if (ctx->prec_in_flight) { LFD_HIP(ctx, hipEventSynchronize(ctx->prec_free)); ctx->prec_in_flight = false; }
-        if (ctx->prec_pinned_bytes < bytes) {
-            if (ctx->prec_pinned) LFD_HIP(ctx, hipHostFree(ctx->prec_pinned));
-            ctx->prec_pinned = nullptr;
-            ctx->prec_pinned_bytes = std::max<size_t>(bytes * 2, 4096);
-            LFD_HIP(ctx, hipHostMalloc(&ctx->prec_pinned, ctx->prec_pinned_bytes, hipHostMallocDefault));
+        if (!t.free_ev) LFD_HIP(ctx, hipEventCreateWithFlags(&t.free_ev, hipEventDisableTiming));
+        if (t.in_flight) { LFD_HIP(ctx, hipEventSynchronize(t.free_ev)); t.in_flight = false; }
+        if (t.pinned_bytes < bytes) {
+            if (t.pinned) LFD_HIP(ctx, hipHostFree(t.pinned));
+            t.pinned = nullptr;
+            t.pinned_bytes = std::max<size_t>(bytes * 2, 4096);
+            LFD_HIP(ctx, hipHostMalloc(&t.pinned, t.pinned_bytes, hipHostMallocDefault));
         }
-        std::memcpy(ctx->prec_pinned, blob.data(), bytes);
-        LFD_HIP(ctx, hipMemcpyAsync(ctx->prec_tab.ptr, ctx->prec_pinned, bytes, hipMemcpyHostToDevice, ctx->stream));
-        LFD_HIP(ctx, hipEventRecord(ctx->prec_free, ctx->stream));
-        ctx->prec_in_flight = true;
-        ctx->prec_cache.swap(blob);
+        std::memcpy(t.pinned, blob.data(), bytes);
+        LFD_HIP(ctx, hipMemcpyAsync(t.tab.ptr, t.pinned, bytes, hipMemcpyHostToDevice, ctx->stream));
+        LFD_HIP(ctx, hipEventRecord(t.free_ev, ctx->stream));
+        t.in_flight = true;
+        t.cache.swap(blob);
     }
-    *d_tab = static_cast<const float* const*>(ctx->prec_tab.ptr);
+    *d_tab = static_cast<const void* const*>(t.tab.ptr);
     return LFD_OK;
+}
+
+static int upload_precision_table(lfd_context* ctx, const lfd_batch* b, const float* const* precision, const float* const** d_tab) {
+    return upload_pointer_table(ctx, ctx->prec, b, reinterpret_cast<const void* const*>(precision), reinterpret_cast<const void* const**>(d_tab));
 }
 
 // Both re-triangulation calls.  weighted: lfd_refine_multiview_weighted (precision checked behind the batch, its table uploaded, three
@@ -2107,6 +2116,36 @@ int lfd_estimate_normals(lfd_context* ctx, const lfd_batch* batch, const lfd_poi
     p.n_refs = batch->n_refs; p.k = batch->k; p.radius = radius_cells; p.depth_step_rel = depth_step_rel;
     p.g = launch_geom(batch, L, 0.0f, reproj_thresh);
     LFD_HIP(ctx, lfd_normals_launch(p, ctx->stream));
+    return LFD_OK;
+}
+
+// ---- multi-view point colour (lfd_colour.hip) --------------------------------------------------------------------------------------------------
+int lfd_colour_multiview(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets,
+                         const uint8_t* const* nbr_image, float support_thresh_px, int32_t mode, float* rgb_out, uint8_t* status,
+                         int64_t* counters) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_colour_check(in, ref_offsets, nbr_image, support_thresh_px, mode, rgb_out, status))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_colour_multiview: ") + why);
+    LfdLaunch L;
+    int rc = batch_launch(ctx, batch, L);
+    if (rc != LFD_OK) return rc;
+    if (const char* why = lfd_colour_check_images(batch, nbr_image)) return fail(ctx, LFD_ERR_INVALID, std::string("lfd_colour_multiview: ") + why);
+    LfdColourArgs p;
+    std::memset(&p, 0, sizeof(p));
+    rc = upload_pointer_table(ctx, ctx->colour_img, batch, reinterpret_cast<const void* const*>(nbr_image),
+                              reinterpret_cast<const void* const**>(&p.img));
+    if (rc != LFD_OK) return rc;
+    p.n_wg = (int32_t)((in->capacity + 255) / 256);
+    p.refs = L.refs; p.slots = L.slots; p.pair_const = L.pair_const;
+    p.offs = reinterpret_cast<const long long*>(ref_offsets);
+    p.xyz = in->xyz; p.rgb = in->rgb; p.cell = in->cell; p.slot = in->slot;
+    p.o_rgb = rgb_out; p.status = status;
+    p.counters = reinterpret_cast<unsigned long long*>(counters);
+    p.capacity = in->capacity;
+    p.n_refs = batch->n_refs; p.k = batch->k; p.mode = mode;
+    p.g = launch_geom(batch, L, support_thresh_px, 0.0f);
+    LFD_HIP(ctx, lfd_colour_launch(p, ctx->stream));
     return LFD_OK;
 }
 

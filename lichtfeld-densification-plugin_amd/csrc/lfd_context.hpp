@@ -97,13 +97,17 @@ struct lfd_context {
     DeviceBuffer cloud_ws;
     DeviceBuffer support_ws;       // lfd_support_filter: support count of every input point, kept points per workgroup; grown on demand
     DeviceBuffer undist_cnt;       // lfd_undistort_image: the u64 counter of invalid pixels of a call that asks for it
-    // lfd_refine_multiview_weighted: the table of precision-plane pointers, uploaded on the launch stream when its content differs from the last
-    DeviceBuffer prec_tab;
-    std::vector<unsigned char> prec_cache;       // what `prec_tab` holds (or will hold once the stream has caught up)
-    void* prec_pinned = nullptr;                 // host staging of that upload
-    size_t prec_pinned_bytes = 0;
-    hipEvent_t prec_free = nullptr;              // behind the upload that last read `prec_pinned`
-    bool prec_in_flight = false;
+    // A table of device pointers a per-point stage reads (one per (reference, slot)), uploaded on the launch stream when its content differs from
+    // the last: lfd_refine_multiview_weighted's / lfd_depth_sigma_filter's precision planes, lfd_colour_multiview's neighbour images
+    struct PointerTable {
+        DeviceBuffer tab;
+        std::vector<unsigned char> cache;        // what `tab` holds (or will hold once the stream has caught up)
+        void* pinned = nullptr;                  // host staging of that upload
+        size_t pinned_bytes = 0;
+        hipEvent_t free_ev = nullptr;            // behind the upload that last read `pinned`
+        bool in_flight = false;
+    };
+    PointerTable prec, colour_img;
     // N3 image preparation: coefficient / index tables of the last size pair
     DeviceBuffer img_tab, msk_tab;
     int img_key[4] = {0, 0, 0, 0}, img_ks[2] = {0, 0};

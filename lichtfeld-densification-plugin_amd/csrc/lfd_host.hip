@@ -25,6 +25,7 @@
 #include "lfd_refine.hpp"
 #include "lfd_sigma.hpp"
 #include "lfd_normals.hpp"
+#include "lfd_colour.hpp"
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
 #include "lfd_freespace.hpp"
@@ -592,6 +593,67 @@ int lfd_estimate_normals_host(lfd_context* ctx, const lfd_batch* b, const lfd_po
             normals_out[3 * i] = nrm[0]; normals_out[3 * i + 1] = nrm[1]; normals_out[3 * i + 2] = nrm[2];
             if (status) status[i] = (uint8_t)st;
             ++count[(size_t)c * 2 + ((st & LFD_NORMAL_FITTED) ? 0 : 1)];
+        }
+    });
+    if (counters)
+        for (int c = 0; c < n_chunks; ++c)
+            for (int e = 0; e < 2; ++e) counters[e] += count[(size_t)c * 2 + e];
+    return LFD_OK;
+}
+
+// The twin of lfd_colour_multiview: the routine of lfd_colour.hpp per point over host pointers, on the context's threads.
+int lfd_colour_multiview_host(lfd_context* ctx, const lfd_batch* b, const lfd_points* in, const int64_t* ref_offsets,
+                              const uint8_t* const* nbr_image, float support_thresh_px, int32_t mode, float* rgb_out, uint8_t* status,
+                              int64_t* counters) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    if (const char* why = lfd_colour_check(in, ref_offsets, nbr_image, support_thresh_px, mode, rgb_out, status))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_colour_multiview_host: ") + why);
+    lfd_params none;
+    std::memset(&none, 0, sizeof(none));
+    int rc = validate_host(ctx, b, &none);
+    if (rc != LFD_OK) return rc;
+    if (const char* why = lfd_colour_check_images(b, nbr_image)) return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_colour_multiview_host: ") + why);
+    HostLaunch L;
+    prepare_host(b, &none, L);
+    std::vector<LfdSlot> slot;
+    make_slot_table(ctx, L, slot, nullptr);
+    const LfdSupportGeom g = make_geom(L, support_thresh_px, 0.0f);
+    const long long cap = in->capacity;
+    const long long* offs = reinterpret_cast<const long long*>(ref_offsets);
+    const long long total = lfd_support_clamp(offs[b->n_refs], cap);
+    const int n_chunks = (int)((total + kChunk - 1) / kChunk);
+    std::vector<long long> count((size_t)n_chunks * 2, 0);             // per chunk: points blended, the sum of their n
+    parallel_chunks(ctx, n_chunks, [&](int c) {
+        const long long i1 = std::min<long long>(total, (long long)(c + 1) * kChunk);
+        for (long long i = (long long)c * kChunk; i < i1; ++i) {
+            const int r = lfd_support_ref_of(offs, b->n_refs, cap, i);
+            const int cell = in->cell[i], s = (int)in->slot[i], ns = b->n_slots[r];
+            const float X0 = in->xyz[3 * i], X1 = in->xyz[3 * i + 1], X2 = in->xyz[3 * i + 2];
+            float rgb[3] = {in->rgb[3 * i], in->rgb[3 * i + 1], in->rgb[3 * i + 2]};
+            unsigned n = 0u;
+            if (lfd_colour_guarded(X0, X1, X2, rgb[0], rgb[1], rgb[2], cell, L.HW, s, ns)) {
+                if (rgb_out != in->rgb) std::memcpy(rgb_out + 3 * i, in->rgb + 3 * i, 3 * sizeof(float));      // bit for bit
+            } else {
+                const LfdSlot* sl = &slot[(size_t)r * LFD_MAX_SLOTS];
+                float cj[LFD_MAX_SLOTS], wx[LFD_MAX_SLOTS], wy[LFD_MAX_SLOTS];
+                for (int j = 0; j < LFD_MAX_SLOTS; ++j) {
+                    cj[j] = 0.0f; wx[j] = 0.0f; wy[j] = 0.0f;
+                    if (j < ns && j != s) {
+                        const float* wv = sl[j].warp + (size_t)cell * g.C + (g.C - 2);
+                        cj[j] = sl[j].cert[cell]; wx[j] = wv[0]; wy[j] = wv[1];
+                    }
+                }
+                const float* ws = sl[s].warp + (size_t)cell * g.C + (g.C - 2);
+                const uint8_t* const* img = nbr_image + (size_t)r * b->k;
+                n = mode == LFD_COLOUR_MEAN
+                        ? lfd_colour_point<LFD_MAX_SLOTS, LFD_COLOUR_MEAN>(sl, img, ns, s, g, cj, wx, wy, ws[0], ws[1], X0, X1, X2, rgb)
+                        : lfd_colour_point<LFD_MAX_SLOTS, LFD_COLOUR_MEDIAN>(sl, img, ns, s, g, cj, wx, wy, ws[0], ws[1], X0, X1, X2, rgb);
+                rgb_out[3 * i] = rgb[0]; rgb_out[3 * i + 1] = rgb[1]; rgb_out[3 * i + 2] = rgb[2];
+                count[(size_t)c * 2] += 1;
+                count[(size_t)c * 2 + 1] += n;
+            }
+            if (status) status[i] = (uint8_t)n;
         }
     });
     if (counters)

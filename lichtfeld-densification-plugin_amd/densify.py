@@ -783,6 +783,8 @@ def _experimental_from_args(args) -> dict:
         exp["fused_refiner_blocks"] = True
     if bool(getattr(args, "fused_refiner_head", False)):
         exp["fused_refiner_head"] = True
+    if str(getattr(args, "multiview_colour", None) or "off") != "off":
+        exp["multiview_colour"] = str(args.multiview_colour)
     if bool(getattr(args, "estimate_normals", False)):
         exp["estimate_normals"] = True
     if getattr(args, "normal_radius_cells", None) is not None:
@@ -876,6 +878,9 @@ def build_argparser() -> argparse.ArgumentParser:
                     help="run what each of RoMa-v2's refiners computes behind its conv blocks (the two 1x1 heads, the warp update, softplus and the "
                          "precision conversion) in one launch of this package's HIP kernel instead of about twenty torch kernels: within rounding "
                          "of the model's own f32 tail, not bit-identical to it")
+    ap.add_argument("--multiview_colour", choices=("off", "mean", "median"), default="off",
+                    help="colour every point by the mean or the median, per channel, over the views that see it (its reference, the neighbour "
+                         "that made it and every other neighbour that confirms it within the support threshold) instead of the reference alone")
     ap.add_argument("--estimate_normals", action="store_true",
                     help="give every point a unit surface normal, fitted to its winning neighbour's warp around its grid cell and oriented towards "
                          "its reference's camera: the PLY then has x y z nx ny nz red green blue vertices (needs a .ply --out_name)")
