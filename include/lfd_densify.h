@@ -626,6 +626,32 @@ int lfd_freespace_filter_host(lfd_context* ctx, const float* xyz, const float* r
                               int32_t min_violations, float* xyz_out, float* rgb_out, float* err_out, int64_t* ref_offsets_out_host,
                               uint8_t* violations, uint8_t* supports, int64_t* n_out_host);
 
+/* Depth and normal maps of the final cloud, one per camera (no upstream counterpart).  A point cloud is not watertight: a plain
+ * z-buffer shows the back wall through the gaps of the front wall, so a cell is kept only when nothing clearly nearer lies around it.  xyz: f32
+ * [n][3]; normals: NULL or f32 [n][3]; cam_P_host / cam_wh_host: HOST f32 [n_cams][12] / i32 [n_cams][2] as for lfd_freespace_filter, whose
+ * projection decides "inside", cell and depth d of a point in a camera; all cameras share one pw x ph plane (csrc/lfd_depth.hpp):
+ *   key          ((u64) bits(d) << 32) | (u32) i for point i: positive finite f32 order like their bits, so the smallest key is the nearest point,
+ *                the lowest index at equal depth; empty is (0x7f800000 << 32) | 0xffffffff
+ *   splat        K[c][cell] = the smallest key of the points inside camera c whose cell lies within Chebyshev distance splat_cells (0 .. 3) of
+ *                `cell` (the part of the window inside the plane)
+ *   visibility   D the depth of K[c][cell], m the smallest finite depth of K[c] within distance window_cells (0 .. 8; 0: every cell with data is
+ *                kept) of `cell`; kept iff D <= hi, f32: t = tol m, hi = m + t.  tol in (0, 1)
+ *   outputs      depth_out f32 [n_cams][ph][pw]: D, 0 where there is no data or the cell was not kept; index_out: NULL, or i32 of the same shape,
+ *                the winner's index, -1 for no data; normal_out: NULL iff normals is NULL, else f32 [n_cams][ph][pw][3], a copy of the winner's
+ *                three values, 0 0 0 for no data
+ * The result does not depend on the order of the points' arrival.  Cameras are rendered in batches whose u64 planes live in the context's
+ * workspace: cams_per_batch cameras when non-zero, else as many as keep them at or below 256 MiB; the outputs do not depend on it.  Synchronous on
+ * the context's stream.  n == 0 is valid: every cell is "no data".  LFD_ERR_INVALID: a null required pointer or half of normals / normal_out,
+ * n < 0 or > 2^31 - 1, n_cams < 1, pw, ph, w or h below 1, n_cams pw ph > 2^31 - 1, an entry of P that is not finite, splat_cells, window_cells
+ * or tol out of range, cams_per_batch < 0, arrays that overlap; nothing is written then.  lfd_render_depth_host: the same over host pointers on a
+ * host context's threads, by the definition; every output equals the device's bit for bit. */
+int lfd_render_depth(lfd_context* ctx, const float* xyz, int64_t n, const float* normals, const float* cam_P_host, const int32_t* cam_wh_host,
+                     int32_t n_cams, int32_t pw, int32_t ph, int32_t splat_cells, int32_t window_cells, float tol, int32_t cams_per_batch,
+                     float* depth_out, int32_t* index_out, float* normal_out);
+int lfd_render_depth_host(lfd_context* ctx, const float* xyz, int64_t n, const float* normals, const float* cam_P_host, const int32_t* cam_wh_host,
+                          int32_t n_cams, int32_t pw, int32_t ph, int32_t splat_cells, int32_t window_cells, float tol, int32_t cams_per_batch,
+                          float* depth_out, int32_t* index_out, float* normal_out);
+
 /* Oriented voxel fusion on the final cloud (no upstream counterpart): the merge step behind lfd_estimate_normals.  The points of a
  * voxel are merged per SIDE their normals face, so an occupied voxel gives one oriented point per visible face: 1 or 2 rows.  Grid, keys, voxel
  * order, colour scale and the two data refusals are lfd_voxel_downsample's, word for word.  xyz, normals, rgb: f32 [n][3] (csrc/lfd_fuse.hpp,
@@ -794,7 +820,7 @@ int lfd_host_eval_correspondence(const float* cam1, const float* cam2, float xa_
  * The per-cell arithmetic is the host build of the very source the kernels compile (csrc/lfd_geometry.hpp; IEEE
  * division / square root where the device uses the 1-ulp v_rcp / v_sqrt), spread over n_threads std::threads
  * (<= 0: all hardware threads).  A host context accepts lfd_upload_cameras, lfd_last_error, lfd_destroy and the
- * *_host calls (the three below, lfd_local_corr_host, lfd_refiner_block_host, lfd_refiner_head_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host, lfd_consensus_filter_host, lfd_freespace_filter_host, lfd_fuse_oriented_host, lfd_knn_dist2_host, lfd_pack_gaussians_host and lfd_cap_spatial_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
+ * *_host calls (the three below, lfd_local_corr_host, lfd_refiner_block_host, lfd_refiner_head_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host, lfd_consensus_filter_host, lfd_freespace_filter_host, lfd_render_depth_host, lfd_fuse_oriented_host, lfd_knn_dist2_host, lfd_pack_gaussians_host and lfd_cap_spatial_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
  * context: neither side ever stands in for the other.  Semantics (orders, counts, optional outputs, LFD_ERR_CAPACITY
  * with valid counts) are those of lfd_aggregate / lfd_triangulate_dense / lfd_triangulate_indexed. */
 int lfd_create_host(int32_t n_threads, lfd_context** out);

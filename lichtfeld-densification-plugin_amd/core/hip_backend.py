@@ -228,6 +228,9 @@ def load_library() -> C.CDLL:
                                          C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.lfd_freespace_filter_host.argtypes = list(lib.lfd_freespace_filter.argtypes)
+    lib.lfd_render_depth.argtypes = [ctxp, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lfd_render_depth_host.argtypes = list(lib.lfd_render_depth.argtypes)
     lib.lfd_fuse_oriented.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.lfd_fuse_oriented_host.argtypes = list(lib.lfd_fuse_oriented.argtypes)
@@ -276,7 +279,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_refiner_head", "lfd_refiner_head_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_colour_multiview", "lfd_colour_multiview_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_cap_spatial", "lfd_cap_spatial_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_refiner_head", "lfd_refiner_head_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_colour_multiview", "lfd_colour_multiview_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_render_depth", "lfd_render_depth_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_cap_spatial", "lfd_cap_spatial_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -1336,6 +1339,43 @@ def _freespace_call(fn, ctx, what, xyz, rgb, err, ref_counts, cam_P, cam_wh, pla
     return kept[0], kept[1], kept[2], np.diff(offs_out), (viol[:n] if with_counts else None), (supp[:n] if with_counts else None)
 
 
+def _depth_call(fn, ctx, what, xyz, normals, cam_P, cam_wh, plane, splat_cells, window_cells, tol, with_index, cams_per_batch, device, last_error):
+    """One lfd_render_depth[_host] call.  ``xyz`` (n, 3) and ``normals`` (n, 3) or None: float32 tensors on ``device``, or arrays (then the
+    results are arrays too); ``cam_P`` (n_cams, 3, 4) or (n_cams, 12) float32 and ``cam_wh`` (n_cams, 2) int32: every camera's projection and
+    image size (host arrays); ``plane`` = (pw, ph).  Returns ``(depth, index, normal)``: float32 (n_cams, ph, pw) with 0 for no data, int32 of
+    the same shape with -1 for no data (None without ``with_index``), float32 (n_cams, ph, pw, 3) (None without ``normals``)."""
+    as_arrays = not torch.is_tensor(xyz)
+    if as_arrays:
+        xyz = torch.from_numpy(np.ascontiguousarray(np.asarray(xyz, np.float32))).to(device)
+        normals = None if normals is None else torch.from_numpy(np.ascontiguousarray(np.asarray(normals, np.float32))).to(device)
+    n = int(xyz.shape[0])
+    for t, name in ((xyz, "xyz"), (normals, "normals")):
+        if t is not None and (t.dtype != torch.float32 or t.device != device or t.dim() != 2 or tuple(t.shape) != (n, 3)):
+            raise ValueError(f"{what}: {name} must be a float32 tensor of {n} rows x 3 on {device}")
+    xyz = xyz.contiguous()
+    normals = None if normals is None else normals.contiguous()
+    P = np.ascontiguousarray(np.asarray(cam_P, np.float32).reshape(-1, 12))
+    wh = np.ascontiguousarray(np.asarray(cam_wh, np.int32).reshape(-1, 2))
+    n_cams, pw, ph = int(P.shape[0]), int(plane[0]), int(plane[1])
+    if wh.shape[0] != n_cams:
+        raise ValueError(f"{what}: cam_P and cam_wh must hold one camera each, not {n_cams} and {wh.shape[0]}")
+    if n_cams < 1 or pw < 1 or ph < 1 or n_cams * pw * ph > 0x7fffffff:
+        raise ValueError(f"{what}: {n_cams} cameras on a {pw} x {ph} plane: at least one camera and one cell, at most 2^31 - 1 cells")
+    depth = torch.empty((n_cams, ph, pw), dtype=torch.float32, device=device)
+    index = torch.empty((n_cams, ph, pw), dtype=torch.int32, device=device) if with_index else None
+    normal = torch.empty((n_cams, ph, pw, 3), dtype=torch.float32, device=device) if normals is not None else None
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None       # noqa: E731  (an empty tensor may have no address at all)
+    # normals of no points: the call wants a non-null address next to normal_out and reads nothing through it
+    nptr = None if normals is None else (normals.data_ptr() if n > 0 else normal.data_ptr())
+    rc = fn(ctx, ptr(xyz), n, nptr, P.ctypes.data_as(C.POINTER(C.c_float)), wh.ctypes.data_as(C.POINTER(C.c_int32)), n_cams, pw, ph, int(splat_cells), int(window_cells),
+            C.c_float(float(tol)), int(cams_per_batch), ptr(depth), ptr(index), ptr(normal))
+    if rc != 0:
+        raise HipBackendError(f"{what} failed ({rc}): {last_error()}")
+    if as_arrays:
+        return tuple(None if t is None else t.cpu().numpy() for t in (depth, index, normal))
+    return depth, index, normal
+
+
 class HipDensifier:
     """One context = one GPU + one stream (``torch.cuda.current_stream`` of the device at creation,
     unless a stream is given).  Not thread-safe: use one per thread, as the C-ABI requires."""
@@ -1491,6 +1531,14 @@ class HipDensifier:
         ``_freespace_call`` describes.  Synchronous."""
         return _freespace_call(self._lib.lfd_freespace_filter, self._ctx, "lfd_freespace_filter", xyz, rgb, err, ref_counts, cam_P, cam_wh, plane, tol,
                                min_violations, with_counts, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
+
+    def render_depth(self, xyz, normals, cam_P, cam_wh, plane, splat_cells: int = 1, window_cells: int = 3, tol: float = 0.02,
+                     with_index: bool = False, cams_per_batch: int = 0):
+        """Depth and normal maps of a cloud on the device (lfd_render_depth): every camera's nearest point per cell of its
+        ``plane``, splatted over ``2 splat_cells + 1`` cells, and dropped where something nearer by more than ``tol`` lies within
+        ``window_cells``.  Returns ``(depth, index, normal)`` as ``_depth_call`` describes.  Synchronous."""
+        return _depth_call(self._lib.lfd_render_depth, self._ctx, "lfd_render_depth", xyz, normals, cam_P, cam_wh, plane, splat_cells, window_cells,
+                           tol, with_index, cams_per_batch, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
 
     def fuse_oriented(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor, voxel_size: float, with_counts: bool = False):
         """Oriented voxel fusion on the device (lfd_fuse_oriented): the points of every occupied voxel merged per side their
@@ -2119,6 +2167,12 @@ class HostDensifier:
         """HipDensifier.freespace_filter over CPU tensors (lfd_freespace_filter_host): the same per-point routine, the same bits in every output."""
         return _freespace_call(self._lib.lfd_freespace_filter_host, self._ctx, "lfd_freespace_filter_host", xyz, rgb, err, ref_counts, cam_P, cam_wh,
                                plane, tol, min_violations, with_counts, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
+
+    def render_depth(self, xyz, normals, cam_P, cam_wh, plane, splat_cells: int = 1, window_cells: int = 3, tol: float = 0.02,
+                     with_index: bool = False, cams_per_batch: int = 0):
+        """HipDensifier.render_depth over CPU tensors or arrays (lfd_render_depth_host): the rule by its definition, the same bits in every output."""
+        return _depth_call(self._lib.lfd_render_depth_host, self._ctx, "lfd_render_depth_host", xyz, normals, cam_P, cam_wh, plane, splat_cells,
+                           window_cells, tol, with_index, cams_per_batch, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
 
     def fuse_oriented(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor, voxel_size: float, with_counts: bool = False):
         """HipDensifier.fuse_oriented over CPU tensors (lfd_fuse_oriented_host): the same rule, with IEEE sqrt and divide in the normals' last step."""

@@ -246,6 +246,9 @@ def run_dense_pipeline(
     if world > 1 and str(config.exp("multiview_colour")) != "off":
         raise ValueError("experimental['multiview_colour'] cannot run sharded over several GPUs: like the normals it is a stage of the single-GPU "
                          "run, and the sharded schedules have not been taken through it")
+    if world > 1 and str(config.exp("depth_maps_dir")) != "":
+        raise ValueError("experimental['depth_maps_dir'] cannot run sharded over several GPUs: the maps are a stage of the single-GPU run, and with "
+                         "gather_to_root only one rank would hold the cloud they are rendered from")
     config, dev = _resolve_backend(config, backend, device)
     per_ref_rng = bool(config.per_reference_rng) or world > 1
     # refs_per_launch = 0 (the default): several references per launch where the results do not depend on it and nobody watches the run proceed

@@ -143,6 +143,23 @@ EXPERIMENTAL_DEFAULTS = {
     # changes, and it works with or without min_support_views.  Behind support filter, re-triangulation and depth gate, in front of the
     # normals.  "off" = today's colour: no new code runs and every output stays byte-identical.
     "multiview_colour": "off",
+    # per-camera depth and normal maps rendered from the final cloud (lfd_render_depth): a directory - relative to the output
+    # file's own - that receives <image stem>.npy (f32 (ph, pw): depth along the camera's z axis in scene units, 0 = no data), with
+    # estimate_normals <image stem>_normal.npy (f32 (ph, pw, 3): world frame, the PLY's normals, 0 0 0 = no data) and depth_maps.json, for EVERY
+    # loaded camera, not only the references.  The cloud rendered is the one behind the consensus and free-space filters and in front of
+    # max_points, fusion and the voxel filter; a side output: the point file does not change by a byte.  "" = off: no new code runs.
+    "depth_maps_dir": "",
+    # ... on planes of this many cells along the longer image side, 8 .. 4096; 0 = automatic, by freespace_plane_cells' rule: ceil(sqrt(
+    # matches_per_ref)) in sampled mode, the longer side of the matcher's grid in dense mode.  All cameras share the plane of the first.
+    "depth_map_cells": 0,
+    # ... every point drawn as a square of 2 r + 1 cells at its own depth, r = 0 .. 3: closes the gaps between the points of one surface
+    "depth_map_splat_cells": 1,
+    # ... and a cell dropped when something nearer lies within this many cells, 0 .. 8 (0: no test): a cloud is not watertight, and this is
+    # what keeps the back wall from showing through the gaps of the front wall.  Background this close to a silhouette is dropped too.
+    "depth_map_window_cells": 3,
+    # ... "nearer" meaning by more than this fraction of the nearer depth, in (0, 1).  The free-space filter's default and, like it, a
+    # judgement, not a measurement; a surface whose depth changes by more across the window loses its far side.
+    "depth_map_tol_rel": 0.02,
 }
 CAP_MODES = ("random", "spatial")
 COLOUR_MODES = ("off", "mean", "median")
@@ -481,6 +498,37 @@ class DensePipelineConfig:
                 return "experimental['multiview_colour'] needs the ordered dense result; experimental['dense_tile_segments'] retires tiles unordered"
             if self.exchange_record_format() == "ply":
                 return "experimental['multiview_colour'] rewrites f32 rows; experimental['exchange_records'] must be 'f32' with it"
+        maps_dir = self.exp("depth_maps_dir")
+        if not isinstance(maps_dir, str):
+            return "experimental['depth_maps_dir'] must be a string (a directory for the per-camera depth maps; '' = off)"
+        c_dm, r_dm, w_dm = self.exp("depth_map_cells"), self.exp("depth_map_splat_cells"), self.exp("depth_map_window_cells")
+        integer = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer))      # noqa: E731
+        if not integer(c_dm) or (int(c_dm) != 0 and not 8 <= int(c_dm) <= 4096):
+            return "experimental['depth_map_cells'] must be 0 (automatic) or an integer in 8 .. 4096 (cells along the longer image side)"
+        if not integer(r_dm) or not 0 <= int(r_dm) <= 3:
+            return "experimental['depth_map_splat_cells'] must be an integer in 0 .. 3 (cells around a point's own that it is drawn into)"
+        if not integer(w_dm) or not 0 <= int(w_dm) <= 8:
+            return "experimental['depth_map_window_cells'] must be an integer in 0 .. 8 (cells around a cell in which nothing may be nearer; 0 = no test)"
+        try:
+            tol_dm = float(self.exp("depth_map_tol_rel"))
+        except (TypeError, ValueError):
+            return "experimental['depth_map_tol_rel'] must be a number (a relative depth, in (0, 1))"
+        if isinstance(self.exp("depth_map_tol_rel"), (bool, np.bool_)) or not (0.0 < tol_dm < 1.0) or not (0.0 < float(np.float32(tol_dm)) < 1.0):
+            return "experimental['depth_map_tol_rel'] must be in (0, 1) (a relative depth)"
+        if maps_dir == "":
+            for key, what in (("depth_map_cells", "plane size"), ("depth_map_splat_cells", "splat radius"), ("depth_map_window_cells", "visibility window"),
+                              ("depth_map_tol_rel", "depth tolerance")):
+                if float(self.exp(key)) != float(EXPERIMENTAL_DEFAULTS[key]):
+                    return f"experimental['{key}'] is the {what} of the depth maps: it needs experimental['depth_maps_dir']"
+        else:
+            if self.stream_output:
+                return ("experimental['depth_maps_dir'] renders the whole cloud, held as arrays; stream_output writes the file while the run proceeds "
+                        "and keeps no cloud")
+            if self.exchange_record_format() == "ply":
+                return "experimental['depth_maps_dir'] renders f32 rows; experimental['exchange_records'] must be 'f32' with it"
+            if self.exp("dense_tile_segments"):
+                return ("experimental['depth_maps_dir'] needs the cloud as arrays; dense mode with experimental['dense_tile_segments'] retires tiles "
+                        "into the file's records")
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):
                 return "stream_output writes a PLY while the run proceeds: output_path must end in .ply"

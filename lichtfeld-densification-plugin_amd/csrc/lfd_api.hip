@@ -26,6 +26,7 @@
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
 #include "lfd_freespace.hpp"
+#include "lfd_depth.hpp"
 #include "lfd_fuse.hpp"
 #include "lfd_knn.hpp"
 #include "lfd_cap.hpp"
@@ -118,6 +119,11 @@ extern "C" __global__ void lfd_freespace_splat_kernel(const float* xyz, long lon
 extern "C" __global__ void lfd_freespace_count_kernel(const float* xyz, long long n, const long long* offs, int n_refs, const LfdFreespaceCam* cams,
                                                       const uint32_t* zbuf, int pw, int ph, float tol, int min_violations, uint8_t* keep,
                                                       uint8_t* violations, uint8_t* supports);
+extern "C" __global__ void lfd_depth_fill_kernel(unsigned long long* keys, long long n_words);
+extern "C" __global__ void lfd_depth_splat_kernel(const float* xyz, long long n, const LfdFreespaceCam* cams, int n_batch, int pw, int ph,
+                                                  unsigned long long* keys);
+extern "C" __global__ void lfd_depth_resolve_kernel(const unsigned long long* keys, int pw, int ph, int tiles_x, int tiles_y, int r, int R, float tol,
+                                                    const float* normals, float* depth_out, int* index_out, float* normal_out);
 hipError_t lfd_corr_launch(const LfdCorrArgs& p, hipStream_t stream);     // lfd_corr.hip
 hipError_t lfd_block_launch(const LfdBlockArgs& p, hipStream_t stream);   // lfd_block.hip
 hipError_t lfd_head_launch(const LfdHeadArgs& p, hipStream_t stream);     // lfd_head.hip
@@ -1685,6 +1691,47 @@ int lfd_freespace_filter(lfd_context* ctx, const float* xyz, const float* rgb, c
     hipLaunchKernelGGL(lfd_freespace_count_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, st, xyz, p.n, c.offs, (int)n_refs, d_cams, zbuf, (int)pw,
                        (int)ph, tol, (int)min_violations, c.keep, violations, supports);
     return cloud_compact(ctx, p, c, xyz, rgb, err, n_refs, xyz_out, rgb_out, err_out, ref_offsets_out_host, n_out_host);
+}
+
+// ---- depth and normal maps of the final cloud (lfd_depth.hip) -------------------------------------------------------------------------------------
+int lfd_render_depth(lfd_context* ctx, const float* xyz, int64_t n, const float* normals, const float* cam_P_host, const int32_t* cam_wh_host,
+                     int32_t n_cams, int32_t pw, int32_t ph, int32_t splat_cells, int32_t window_cells, float tol, int32_t cams_per_batch,
+                     float* depth_out, int32_t* index_out, float* normal_out) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_depth_check(xyz, n, normals, cam_P_host, cam_wh_host, n_cams, pw, ph, splat_cells, window_cells, tol, cams_per_batch,
+                                          depth_out, index_out, normal_out))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_render_depth: ") + why);
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const long long cells = (long long)pw * ph;                        // n_cams * cells <= 2^31 - 1 (lfd_depth_check)
+    const int32_t per = lfd_depth_batch(n_cams, pw, ph, cams_per_batch);
+    std::vector<LfdFreespaceCam> cams((size_t)n_cams);
+    for (int32_t c = 0; c < n_cams; ++c) lfd_freespace_cam(cam_P_host + 12 * (size_t)c, cam_wh_host[2 * c], cam_wh_host[2 * c + 1], cams[(size_t)c]);
+    unsigned long long* keys = nullptr;                                // the u64 planes of one batch, filled before they are read
+    LfdFreespaceCam* d_cams = nullptr;
+    if (int rc = carve_cloud_ws(ctx, [&](Bump& b) {
+            keys = b.take<unsigned long long>((size_t)per * (size_t)cells);
+            d_cams = b.take<LfdFreespaceCam>((size_t)n_cams);
+        }))
+        return rc;
+    LFD_HIP(ctx, hipMemcpyAsync(d_cams, cams.data(), (size_t)n_cams * sizeof(LfdFreespaceCam), hipMemcpyHostToDevice, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));                            // `cams` is pageable memory of this call: the copy has read it
+    const int tiles_x = (pw + 31) / 32, tiles_y = (ph + 15) / 16;      // lfd_depth.hip: LFD_DEPTH_TW x LFD_DEPTH_TH
+    const unsigned n_wg = (unsigned)((n + 255) / 256);
+    for (int32_t c0 = 0; c0 < n_cams; c0 += per) {
+        const int nb = (int)std::min<int32_t>(per, n_cams - c0);
+        const long long n_words = (long long)nb * cells, o = (long long)c0 * cells;
+        hipLaunchKernelGGL(lfd_depth_fill_kernel, dim3((unsigned)std::min<long long>((n_words + 255) / 256, 4096)), dim3(256), 0, st, keys, n_words);
+        if (n > 0) hipLaunchKernelGGL(lfd_depth_splat_kernel, dim3(n_wg), dim3(256), 0, st, xyz, (long long)n, d_cams + c0, nb, (int)pw, (int)ph, keys);
+        // tiles_x tiles_y nb <= nb cells <= 2^31 - 1 workgroups
+        hipLaunchKernelGGL(lfd_depth_resolve_kernel, dim3((unsigned)((long long)tiles_x * tiles_y * nb)), dim3(256), 0, st, keys, (int)pw, (int)ph, tiles_x,
+                           tiles_y, (int)splat_cells, (int)window_cells, tol, normals, depth_out + o, index_out ? index_out + o : nullptr,
+                           normal_out ? normal_out + 3 * o : nullptr);
+    }
+    LFD_HIP(ctx, hipGetLastError());
+    LFD_HIP(ctx, hipStreamSynchronize(st));                            // the workspace is free for the next stage on return
+    return LFD_OK;
 }
 
 // ---- oriented voxel fusion on the final cloud (lfd_fuse.hip; the grid and the sort are lfd_voxel.hip's kernels) ------------------------------------

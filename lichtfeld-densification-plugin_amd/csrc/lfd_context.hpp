@@ -92,7 +92,7 @@ struct lfd_context {
     DeviceBuffer stamps;           // profiling builds: phase stamps of the dense kernel
     DeviceBuffer seg_scan;         // tile segments: exclusive prefix of the last table handed to lfd_order_segments / lfd_pack_*_segments
     // The one scratch area of the stages on the final cloud (lfd_voxel_downsample, lfd_consensus_filter, lfd_freespace_filter, lfd_fuse_oriented,
-    // lfd_knn_dist2), grown on demand.  Each call carves it anew (lfd_api.hip: carve_cloud_ws) and writes or clears every word before it reads it;
+    // lfd_knn_dist2, lfd_render_depth), grown on demand.  Each call carves it anew (lfd_api.hip: carve_cloud_ws) and writes or clears every word before it reads it;
     // the stages may share it because each of them returns with the stream idle.
     DeviceBuffer cloud_ws;
     DeviceBuffer support_ws;       // lfd_support_filter: support count of every input point, kept points per workgroup; grown on demand

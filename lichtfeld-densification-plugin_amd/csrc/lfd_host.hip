@@ -29,6 +29,7 @@
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
 #include "lfd_freespace.hpp"
+#include "lfd_depth.hpp"
 #include "lfd_fuse.hpp"
 #include "lfd_knn.hpp"
 #include "lfd_cap.hpp"
@@ -905,6 +906,58 @@ int lfd_freespace_filter_host(lfd_context* ctx, const float* xyz, const float* r
         ++o;
     }
     *n_out_host = o;
+    return LFD_OK;
+}
+
+// The twin of lfd_render_depth, by the definition and with neither identity: a camera at a time on the context's threads, every point
+// written into every cell of its footprint, then every cell's window walked.
+int lfd_render_depth_host(lfd_context* ctx, const float* xyz, int64_t n, const float* normals, const float* cam_P_host, const int32_t* cam_wh_host,
+                          int32_t n_cams, int32_t pw, int32_t ph, int32_t splat_cells, int32_t window_cells, float tol, int32_t cams_per_batch,
+                          float* depth_out, int32_t* index_out, float* normal_out) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    if (const char* why = lfd_depth_check(xyz, n, normals, cam_P_host, cam_wh_host, n_cams, pw, ph, splat_cells, window_cells, tol, cams_per_batch,
+                                          depth_out, index_out, normal_out))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_render_depth_host: ") + why);
+    const size_t cells = (size_t)pw * (size_t)ph;
+    const int r = splat_cells, R = window_cells;
+    parallel_chunks(ctx, (int)n_cams, [&](int c) {                     // a camera writes its own planes only
+        LfdFreespaceCam cam;
+        lfd_freespace_cam(cam_P_host + 12 * (size_t)c, cam_wh_host[2 * c], cam_wh_host[2 * c + 1], cam);
+        std::vector<uint64_t> K(cells, LFD_DEPTH_EMPTY);
+        for (long long i = 0; i < n; ++i) {
+            int cx, cy;
+            float d;
+            if (!lfd_freespace_project(cam, (double)pw, (double)ph, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], cx, cy, d)) continue;
+            const uint64_t key = lfd_depth_key(d, (uint32_t)i);
+            for (int yy = std::max(0, cy - r); yy <= std::min(ph - 1, cy + r); ++yy)
+                for (int xx = std::max(0, cx - r); xx <= std::min(pw - 1, cx + r); ++xx) {
+                    uint64_t& cell = K[(size_t)yy * (size_t)pw + (size_t)xx];
+                    cell = std::min(cell, key);
+                }
+        }
+        for (int y = 0; y < ph; ++y)
+            for (int x = 0; x < pw; ++x) {
+                const uint64_t key = K[(size_t)y * (size_t)pw + (size_t)x];
+                bool keep = !lfd_depth_key_empty(key);
+                if (keep) {
+                    uint32_t m = LFD_FREESPACE_EMPTY;                  // the cell itself is in its window: m <= its depth bits
+                    for (int yy = std::max(0, y - R); yy <= std::min(ph - 1, y + R); ++yy)
+                        for (int xx = std::max(0, x - R); xx <= std::min(pw - 1, x + R); ++xx)
+                            m = std::min(m, lfd_depth_key_bits(K[(size_t)yy * (size_t)pw + (size_t)xx]));
+                    keep = lfd_depth_keep(lfd_depth_key_bits(key), m, tol);
+                }
+                const size_t o = (size_t)c * cells + (size_t)y * (size_t)pw + (size_t)x;
+                const uint32_t dbits = keep ? lfd_depth_key_bits(key) : 0u;
+                std::memcpy(depth_out + o, &dbits, 4);
+                const int32_t idx = keep ? (int32_t)lfd_depth_key_index(key) : -1;
+                if (index_out) index_out[o] = idx;
+                if (normal_out) {
+                    if (keep) std::memcpy(normal_out + 3 * o, normals + 3 * (size_t)idx, 12);
+                    else normal_out[3 * o] = normal_out[3 * o + 1] = normal_out[3 * o + 2] = 0.0f;
+                }
+            }
+    });
     return LFD_OK;
 }
 

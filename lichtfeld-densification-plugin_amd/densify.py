@@ -321,21 +321,31 @@ def _apply_consensus_filter(result, config: DensePipelineConfig, progress_callba
                           clock=result._clock, loader=loader, device_normals=normals, match_grid=result.match_grid)
 
 
-def freespace_plane(config: DensePipelineConfig, width: int, height: int, match_grid=None) -> Tuple[int, int]:
-    """(pw, ph) of the free-space filter's z-buffers for images of ``width`` x ``height``: experimental['freespace_plane_cells'] cells along the
-    longer side - 0: ceil(sqrt(matches_per_ref)) in sampled mode, the longer side of the matcher's grid (``match_grid`` = (H, W)) in dense
-    mode - and max(1, floor(cells * short / long + 0.5)) along the shorter."""
-    cells = int(config.exp("freespace_plane_cells"))
+def _image_plane(config: DensePipelineConfig, cells_key: str, width: int, height: int, match_grid=None) -> Tuple[int, int]:
+    """(pw, ph) of a plane over images of ``width`` x ``height``: experimental[``cells_key``] cells along the longer side - 0:
+    ceil(sqrt(matches_per_ref)) in sampled mode, the longer side of the matcher's grid (``match_grid`` = (H, W)) in dense mode - and
+    max(1, floor(cells * short / long + 0.5)) along the shorter."""
+    cells = int(config.exp(cells_key))
     if cells == 0:
         if config.triangulation_mode == "dense":
             if match_grid is None:
-                raise RuntimeError("experimental['freespace_plane_cells'] = 0 takes the matcher's grid in dense mode, and this result does not record one")
+                raise RuntimeError(f"experimental['{cells_key}'] = 0 takes the matcher's grid in dense mode, and this result does not record one")
             cells = int(max(match_grid))
         else:
             cells = int(math.ceil(math.sqrt(max(1, int(config.matches_per_ref)))))
     lng, sht = max(int(width), int(height)), min(int(width), int(height))
     other = max(1, int(math.floor(cells * sht / lng + 0.5)))
     return (cells, other) if int(width) >= int(height) else (other, cells)
+
+
+def freespace_plane(config: DensePipelineConfig, width: int, height: int, match_grid=None) -> Tuple[int, int]:
+    """(pw, ph) of the free-space filter's z-buffers: ``_image_plane`` by experimental['freespace_plane_cells']."""
+    return _image_plane(config, "freespace_plane_cells", width, height, match_grid)
+
+
+def depth_map_plane(config: DensePipelineConfig, width: int, height: int, match_grid=None) -> Tuple[int, int]:
+    """(pw, ph) of the depth maps: ``_image_plane`` by experimental['depth_map_cells']."""
+    return _image_plane(config, "depth_map_cells", width, height, match_grid)
 
 
 def _apply_freespace_filter(result, config: DensePipelineConfig, camera_records, refs_local, progress_callback=None):
@@ -483,6 +493,71 @@ def _write_gaussians(config: DensePipelineConfig, path: str, xyz, normals, rgb, 
         write_gaussian_ply_packed(path, n, body)
 
 
+DEPTH_MAP_BYTES = 256 << 20      # _write_depth_maps renders as many cameras per call as keep the maps of a call below this
+
+
+def _write_depth_maps(result, config: DensePipelineConfig, camera_records, progress_callback=None) -> None:
+    """Per-camera depth and normal maps of the finished cloud (lfd_render_depth), rendered where the points are, behind the
+    consensus and free-space filters and in front of the point cap, the fusion and the voxel filter.  EVERY record of ``camera_records`` gets
+    ``<stem of its image file>.npy`` - f32 (ph, pw), depth along its z axis in scene units, 0 = no data - and, when the run estimated normals,
+    ``<stem>_normal.npy`` - f32 (ph, pw, 3), world frame, 0 0 0 = no data - in experimental['depth_maps_dir'] (relative: to the output file's
+    directory), next to ``depth_maps.json``.  A side output: ``result`` is not changed.  Off (''): nothing runs."""
+    maps_dir = str(config.exp("depth_maps_dir"))
+    if maps_dir == "" or not _is_writer_rank():
+        return
+    import json
+    from .core import hip_backend as hb
+    import torch
+    if result.streamed_path is not None:
+        raise RuntimeError("experimental['depth_maps_dir'] renders the cloud held as arrays: this result was streamed to its file")
+    if not os.path.isabs(maps_dir):
+        maps_dir = os.path.join(os.path.dirname(os.path.abspath(config.output_path)), maps_dir)
+    stems = {}                                       # stem -> its record, in the order of the records
+    for rec in camera_records:
+        stem = os.path.splitext(os.path.basename(str(rec.image_path)))[0]
+        if stem == "" or stem in stems:
+            raise RuntimeError(f"experimental['depth_maps_dir'] names a camera's maps after its image file: {stems.get(stem, rec).image_path!r} and "
+                               f"{rec.image_path!r} both give {stem!r}")
+        stems[stem] = rec
+    xyz = result.device_points[0] if result.device_points is not None else torch.from_numpy(np.ascontiguousarray(result.xyz, np.float32))
+    normals = result.device_normals                  # experimental['estimate_normals']: on the device the points are on
+    cam_P = np.stack([np.asarray(c.P, np.float64).astype(np.float32).reshape(12) for c in camera_records])
+    cam_wh = np.array([[int(c.width), int(c.height)] for c in camera_records], np.int32)
+    plane = depth_map_plane(config, camera_records[0].width, camera_records[0].height, result.match_grid)
+    r, R, tol = int(config.exp("depth_map_splat_cells")), int(config.exp("depth_map_window_cells")), float(config.exp("depth_map_tol_rel"))
+    if progress_callback:
+        progress_callback(94.0, "Rendering depth maps...")
+    os.makedirs(maps_dir, exist_ok=True)
+    per_call = max(1, DEPTH_MAP_BYTES // (plane[0] * plane[1] * (16 if normals is not None else 4)))
+    dens = hb.HipDensifier(xyz.device) if xyz.is_cuda else hb.HostDensifier(int(config.exp("host_threads")))
+    names, entries = list(stems), []
+    try:
+        for c0 in range(0, len(camera_records), per_call):
+            c1 = min(len(camera_records), c0 + per_call)
+            depth, _, normal = dens.render_depth(xyz, normals, cam_P[c0:c1], cam_wh[c0:c1], plane, r, R, tol)
+            depth = depth.cpu().numpy()
+            normal = None if normal is None else normal.cpu().numpy()
+            for c in range(c0, c1):
+                rec, stem = camera_records[c], names[c]
+                d = depth[c - c0]
+                np.save(os.path.join(maps_dir, stem + ".npy"), d)
+                if normal is not None:
+                    np.save(os.path.join(maps_dir, stem + "_normal.npy"), normal[c - c0])
+                valid = d > 0
+                entries.append({"image": os.path.basename(str(rec.image_path)), "depth": stem + ".npy",
+                                "normal": stem + "_normal.npy" if normal is not None else None, "width": int(rec.width), "height": int(rec.height),
+                                "valid_cells": int(valid.sum()), "depth_min": float(d[valid].min()) if valid.any() else None,
+                                "depth_max": float(d[valid].max()) if valid.any() else None})
+    except hb.HipBackendError as exc:
+        raise RuntimeError(f"experimental['depth_maps_dir']: {exc}") from exc
+    finally:
+        dens.close()
+    with open(os.path.join(maps_dir, "depth_maps.json"), "w") as f:
+        json.dump({"plane": {"width": int(plane[0]), "height": int(plane[1])}, "splat_cells": r, "window_cells": R, "tol_rel": tol,
+                   "points": int(xyz.shape[0]), "normals": normals is not None, "no_data": 0.0, "cameras": entries}, f, indent=1)
+    log.info(f"Depth maps ({plane[0]} x {plane[1]} cells, splat {r}, window {R}, tolerance {tol:g}): {len(entries)} cameras -> {maps_dir}")
+
+
 def _is_writer_rank() -> bool:
     """True unless this process is a non-zero rank of an initialised torch.distributed job."""
     try:
@@ -601,6 +676,7 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
         return 2
     result = _apply_consensus_filter(result, config, progress_callback)      # (in front of the point cap: it has to see the whole cloud)
     result = _apply_freespace_filter(result, config, records, refs_local, progress_callback)      # (behind it: what it removed cannot "see through" a surface)
+    _write_depth_maps(result, config, records, progress_callback)      # (a side output of the densest filtered cloud, in front of cap, fusion and voxel filter)
     if progress_callback:
         progress_callback(95.0, "Writing output...")
     if result.streamed_path == config.output_path:      # config.stream_output: the file is already complete (and no cap applies to it)
@@ -662,6 +738,7 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
     try:
         result = _apply_consensus_filter(result, config, progress_callback)  # (in front of the point cap and the voxel filter: it has to see the whole cloud)
         result = _apply_freespace_filter(result, config, records, refs_local, progress_callback)   # (behind it, in front of cap and voxel filter)
+        _write_depth_maps(result, config, records, progress_callback)      # (a side output of that cloud)
     except RuntimeError as exc:
         return 1, str(exc)
     if result.streamed_path == config.output_path:      # config.stream_output: the PLY is complete; neither a cap nor a voxel filter applies to it
@@ -777,6 +854,11 @@ def _experimental_from_args(args) -> dict:
         exp["freespace_depth_tol_rel"] = float(args.freespace_depth_tol_rel)
     if int(getattr(args, "freespace_plane_cells", 0)) != 0:
         exp["freespace_plane_cells"] = int(args.freespace_plane_cells)
+    if str(getattr(args, "depth_maps_dir", "") or "") != "":
+        exp["depth_maps_dir"] = str(args.depth_maps_dir)
+    for key, cast in (("depth_map_cells", int), ("depth_map_splat_cells", int), ("depth_map_window_cells", int), ("depth_map_tol_rel", float)):
+        if getattr(args, key, None) is not None:
+            exp[key] = cast(getattr(args, key))
     if bool(getattr(args, "undistort_images", False)):
         exp["undistort_images"] = True
     if bool(getattr(args, "fused_refiner_blocks", False)):
@@ -868,6 +950,19 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--freespace_plane_cells", type=int, default=0,
                     help="... on z-buffers of this many cells along the longer image side (8 .. 4096; 0 = automatic: ceil(sqrt(matches_per_ref)) in "
                          "sampled mode, the matcher's grid in dense mode; needs --min_freespace_violations)")
+    ap.add_argument("--depth_maps_dir", type=str, default="",
+                    help="write a depth map - and with --estimate_normals a normal map - of the filtered cloud for EVERY loaded camera into this "
+                         "directory (relative: to the output file's), <image stem>.npy / <image stem>_normal.npy and depth_maps.json; the point file "
+                         "does not change ('' = off)")
+    ap.add_argument("--depth_map_cells", type=int, default=None,
+                    help="... on planes of this many cells along the longer image side (8 .. 4096; 0 = automatic, as --freespace_plane_cells; needs "
+                         "--depth_maps_dir)")
+    ap.add_argument("--depth_map_splat_cells", type=int, default=None,
+                    help="... every point drawn as a square of 2 r + 1 cells at its depth (0 .. 3, default 1; needs --depth_maps_dir)")
+    ap.add_argument("--depth_map_window_cells", type=int, default=None,
+                    help="... a cell dropped when something nearer lies within this many cells (0 .. 8, default 3; 0 = no test; needs --depth_maps_dir)")
+    ap.add_argument("--depth_map_tol_rel", type=float, default=None,
+                    help="... nearer by more than this fraction of the nearer depth, in (0, 1) (default 0.02; needs --depth_maps_dir)")
     ap.add_argument("--undistort_images", action="store_true",
                     help="resample every image (and its mask) through its COLMAP camera's distortion model (SIMPLE_RADIAL, RADIAL, OPENCV, "
                          "FULL_OPENCV) into the pinhole image of the same intrinsics before it is matched; other distorted models are refused")
