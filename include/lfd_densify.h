@@ -568,6 +568,36 @@ int lfd_colour_multiview_host(lfd_context* ctx, const lfd_batch* batch, const lf
                               const uint8_t* const* nbr_image, float support_thresh_px, int32_t mode, float* rgb_out, uint8_t* status,
                               int64_t* counters);
 
+/* Per-image exposure gains, the statistics (no upstream counterpart).  Reads only: no point, colour, count or order changes.
+ * The views of a point are lfd_colour_multiview's, by the same routines (csrc/lfd_colour.hpp): the reference, whose colour is in->rgb[i]; the
+ * winning slot unless its observation is not finite; every other slot lfd_support_filter's candidate test accepts at support_thresh_px; a
+ * guarded point (see there) has none.  For each (point of reference r, confirming slot j) the neighbour's colour is sampled as there, and
+ *   the sample counts iff all six values - the reference's r, g, b and the neighbour's - lie in [0.05f, 0.95f] (f32 comparisons);
+ *   each value is quantised as (uint32_t)(c * 16777216.0f): exact, a power of two and a truncation;
+ *   row [r * k + j] of table, u64 [n_refs * k][7], receives N += 1, Sref[0..3) += q_ref, Snbr[0..3) += q_nbr (columns 0, 1..3, 4..6).
+ * The table is ADDED to, never cleared; integer additions only, so its content does not depend on launch geometry or thread count and the
+ * device and the twin agree on every element.  nbr_image, `in`, ref_offsets: as lfd_colour_multiview.  table: device u64 [n_refs * k * 7],
+ * overlapping nothing of `in`.  One launch on the context's stream, asynchronous; at most one global atomic per (workgroup, reference, slot,
+ * quantity).  LFD_ERR_INVALID: a null required pointer, missing cell / slot / rgb, a null image in a valid slot, support_thresh_px <= 0 or not
+ * finite, a table overlapping `in`, a capacity beyond 2^31 - 1.  lfd_gain_accumulate_host: the same routine over host pointers on a host
+ * context's threads, the same integers.  A host context is served by _host only, a device context refuses _host (LFD_ERR_STATE). */
+int lfd_gain_accumulate(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets,
+                        const uint8_t* const* nbr_image, float support_thresh_px, uint64_t* table);
+int lfd_gain_accumulate_host(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets,
+                             const uint8_t* const* nbr_image, float support_thresh_px, uint64_t* table);
+
+/* Per-image exposure gains, the compensation.  The cloud is the concatenation of n_refs references' points, reference r's in
+ * [ref_offsets[r], ref_offsets[r + 1]) (i64 [n_refs + 1], clamped to [0, n]); per point i of reference r and channel ch, in f32 with one
+ * rounding: rgb_out[3 i + ch] = min(rgb[3 i + ch] * factors[3 r + ch], 1.0f); a value that is not finite is copied bit for bit.  Points at
+ * and beyond ref_offsets[n_refs] are not touched.  rgb, rgb_out: f32 [3 * n], rgb_out exactly rgb (in place) or overlapping nothing of it;
+ * factors: f32 [n_refs * 3], used as they stand.  All four arrays where the context computes (device memory / host memory for _host).  One
+ * launch on the context's stream, asynchronous.  LFD_ERR_INVALID: a null pointer, n outside [0, 2^31 - 1], n_refs <= 0, a partial overlap.
+ * LFD_ERR_STATE: the other kind of context. */
+int lfd_gain_apply(lfd_context* ctx, const float* rgb, int64_t n, const int64_t* ref_offsets, int32_t n_refs, const float* factors,
+                   float* rgb_out);
+int lfd_gain_apply_host(lfd_context* ctx, const float* rgb, int64_t n, const int64_t* ref_offsets, int32_t n_refs, const float* factors,
+                        float* rgb_out);
+
 /* Cross-reference consensus filter on the final cloud (no upstream counterpart - the cloud upstream writes is the plain union of what
  * every reference triangulated on its own).  The cloud is the concatenation of n_refs references' points; a point is kept iff at least min_refs
  * OTHER references own a point within `radius` of it - the fusion rule of multi-view stereo, one level above lfd_support_filter, which only sees

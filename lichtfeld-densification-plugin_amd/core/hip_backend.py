@@ -220,6 +220,10 @@ def load_library() -> C.CDLL:
     lib.lfd_colour_multiview.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_points), C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p,
                                          C.c_void_p, C.c_void_p]
     lib.lfd_colour_multiview_host.argtypes = list(lib.lfd_colour_multiview.argtypes)
+    lib.lfd_gain_accumulate.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_points), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+    lib.lfd_gain_accumulate_host.argtypes = list(lib.lfd_gain_accumulate.argtypes)
+    lib.lfd_gain_apply.argtypes = [ctxp, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.lfd_gain_apply_host.argtypes = list(lib.lfd_gain_apply.argtypes)
     lib.lfd_pack_ply_normals.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.lfd_consensus_filter.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_float, C.c_int32,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)]
@@ -279,7 +283,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_refiner_head", "lfd_refiner_head_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_colour_multiview", "lfd_colour_multiview_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_render_depth", "lfd_render_depth_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_cap_spatial", "lfd_cap_spatial_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_refiner_head", "lfd_refiner_head_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_colour_multiview", "lfd_colour_multiview_host", "lfd_gain_accumulate", "lfd_gain_accumulate_host", "lfd_gain_apply", "lfd_gain_apply_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_render_depth", "lfd_render_depth_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_cap_spatial", "lfd_cap_spatial_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -1100,6 +1104,66 @@ def _colour_call(fn, ctx, batch, src, support_thresh_px, mode, with_status, coun
     return rc, dataclasses.replace(src, rgb=rgb_out[:cap], _packed=None), status
 
 
+GAIN_QUANTITIES = 7                          # LFD_GAIN_QUANTITIES of csrc/lfd_gain.hpp: N, Sref[3], Snbr[3] per (reference, slot)
+
+
+def _gain_accumulate_call(fn, ctx, batch, src, support_thresh_px, table, device):
+    """One lfd_gain_accumulate[_host] call.  ``src``: the OutputBuffers a launch or a post-stage wrote for ``batch``, or a collected
+    TriangulationOutput; nothing of it changes.  ``table``: None (a zeroed one is made) or a contiguous int64 (n_refs * k, 7) tensor on the
+    context's device - the library's u64 sums, far below 2^63 - that is ADDED to.  Returns (rc, table)."""
+    if batch.nbr_images is None:
+        raise ValueError("gain_accumulate: the batch's references carry no neighbour images (ReferenceInputs.nbr_images)")
+    if src.cell is None or src.slot is None:
+        raise ValueError("gain_accumulate: the source buffers need the cell / slot outputs (with_cell=True)")
+    rows = batch.n_refs * batch.k
+    if table is None:
+        table = torch.zeros((rows, GAIN_QUANTITIES), dtype=torch.int64, device=device)
+    elif table.dtype != torch.int64 or tuple(table.shape) != (rows, GAIN_QUANTITIES) or table.device != device or not table.is_contiguous():
+        raise ValueError(f"gain_accumulate: table must be a contiguous int64 ({rows}, {GAIN_QUANTITIES}) tensor on {device}")
+    if isinstance(src, TriangulationOutput):
+        n = int(src.xyz.shape[0])
+        keep = [src.xyz.contiguous(), src.rgb.contiguous(), src.cell.contiguous(), src.slot.contiguous()]
+        if n == 0:                            # (an empty tensor may have no address at all; the library wants its arrays)
+            keep = [torch.zeros((1, 3) if t.dim() == 2 else (1,), dtype=t.dtype, device=t.device) for t in keep]
+        if any(t.device != device for t in keep):
+            raise ValueError(f"gain_accumulate: the points live on {keep[0].device}, this context computes on {device}")
+        offs = torch.from_numpy(np.ascontiguousarray(src.ref_offsets, np.int64)).to(device)
+        pts = lfd_points(xyz=keep[0].data_ptr(), rgb=keep[1].data_ptr(), err=None, cell=keep[2].data_ptr(), slot=keep[3].data_ptr(), capacity=n)
+        n_refs, k = int(len(src.ref_offsets)) - 1, int(src.seg_counts.shape[1])
+    else:
+        if src.xyz.device != device:
+            raise ValueError(f"gain_accumulate: the points live on {src.xyz.device}, this context computes on {device}")
+        keep, offs, pts, n_refs, k = [], src.ref_offsets, src.c, src._n_refs, src._k
+    if n_refs != batch.n_refs or k != batch.k:
+        raise ValueError(f"gain_accumulate: the points were made for {n_refs} references x {k} slots, the batch has {batch.n_refs} x {batch.k}")
+    rc = fn(ctx, C.byref(batch.c), C.byref(pts), offs.data_ptr(), C.cast(batch.nbr_images, C.c_void_p), C.c_float(float(support_thresh_px)),
+            table.data_ptr())
+    del keep
+    return rc, table
+
+
+def _gain_apply_call(fn, ctx, rgb, ref_counts, factors, device):
+    """One lfd_gain_apply[_host] call.  ``rgb`` (n, 3) float32 where the context computes; ``ref_counts``: points per reference, in the order
+    of the cloud; ``factors`` (n_refs, 3) float32 (array or tensor).  Returns (rc, a new (n, 3) tensor)."""
+    counts = np.ascontiguousarray(np.asarray(ref_counts, np.int64).reshape(-1))
+    n = int(rgb.shape[0])
+    if rgb.dtype != torch.float32 or rgb.dim() != 2 or rgb.shape[1] != 3 or rgb.device != device:
+        raise ValueError(f"gain_apply: rgb must be a float32 (n, 3) tensor on {device}")
+    if counts.size < 1 or (counts < 0).any() or int(counts.sum()) != n:
+        raise ValueError(f"gain_apply: ref_counts must be non-negative counts, one per reference, that add up to the {n} points")
+    f = torch.as_tensor(np.ascontiguousarray(np.asarray(factors.cpu() if isinstance(factors, torch.Tensor) else factors, np.float32)))
+    if tuple(f.shape) != (counts.size, 3):
+        raise ValueError(f"gain_apply: factors must be ({counts.size}, 3) float32, one row per reference")
+    offs = torch.from_numpy(np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)).to(device)
+    f = f.to(device)
+    src = rgb.contiguous()
+    out = torch.empty((max(n, 1), 3), dtype=torch.float32, device=device)
+    if n == 0:
+        return 0, out[:0]
+    rc = fn(ctx, src.data_ptr(), n, offs.data_ptr(), int(counts.size), f.data_ptr(), out.data_ptr())
+    return rc, out[:n]
+
+
 def _depth_sigma_call(fn, ctx, batch, src, max_rel_sigma, iso_sigma_px, refine_status, support_thresh_px, with_sigma, into, device):
     """One lfd_depth_sigma_filter[_host] call.  ``src``, ``into`` and the result: as in ``_support_filter_call``.  ``iso_sigma_px`` > 0: the
     isotropic form; 0: the batch's precision planes.  ``refine_status``: None (the winner alone places a point) or the uint8 status tensor of
@@ -1685,6 +1749,26 @@ class HipDensifier:
         self._check(rc, "lfd_colour_multiview")
         return (res, status) if with_status else res
 
+    def gain_accumulate(self, batch: PreparedBatch, out_buffers, support_thresh_px: float, table: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The exposure statistics of per-image gain compensation (lfd_gain_accumulate): for every point ``out_buffers`` holds for
+        ``batch`` (an OutputBuffers on the context's stream, or a collected TriangulationOutput; nothing of it changes) and every neighbour
+        slot that confirms it - the multi-view colour's views - the reference's and the neighbour's colour are added, as exact integers, to row
+        ``ref * k + slot`` of ``table``: int64 (n_refs * k, 7) on the device, columns N, Sref[3], Snbr[3], ADDED to (None: a zeroed one is
+        made).  Asynchronous; returns the table."""
+        self._same_device(batch)
+        with torch.cuda.stream(self.stream):
+            rc, table = _gain_accumulate_call(self._lib.lfd_gain_accumulate, self._ctx, batch, out_buffers, support_thresh_px, table, self.device)
+        self._check(rc, "lfd_gain_accumulate")
+        return table
+
+    def gain_apply(self, rgb: torch.Tensor, ref_counts, factors) -> torch.Tensor:
+        """Gain compensation of a cloud's colours (lfd_gain_apply): a new (n, 3) tensor min(rgb * f, 1) per channel, f the row
+        of ``factors`` (n_refs, 3) of the point's reference - the cloud is the concatenation of ``ref_counts`` points per reference."""
+        with torch.cuda.stream(self.stream):
+            rc, out = _gain_apply_call(self._lib.lfd_gain_apply, self._ctx, rgb, ref_counts, factors, self.device)
+        self._check(rc, "lfd_gain_apply")
+        return out
+
     def pack_ply_normals(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
         """(n*27,) u8 device tensor: the body of a PLY whose header lists x y z nx ny nz red green blue."""
         xyz, normals, rgb = self._pts(xyz, 3, "xyz"), self._pts(normals, 3, "normals"), self._pts(rgb, 3, "rgb")
@@ -2148,6 +2232,19 @@ class HostDensifier:
                                        counters, self.device)
         self._check(rc, "lfd_colour_multiview_host")
         return (res, status) if with_status else res
+
+    def gain_accumulate(self, batch: PreparedBatch, out_buffers, support_thresh_px: float, table: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """HipDensifier.gain_accumulate over CPU tensors (lfd_gain_accumulate_host): the same routine, the same integers."""
+        self._same_device(batch)
+        rc, table = _gain_accumulate_call(self._lib.lfd_gain_accumulate_host, self._ctx, batch, out_buffers, support_thresh_px, table, self.device)
+        self._check(rc, "lfd_gain_accumulate_host")
+        return table
+
+    def gain_apply(self, rgb: torch.Tensor, ref_counts, factors) -> torch.Tensor:
+        """HipDensifier.gain_apply over CPU tensors (lfd_gain_apply_host): the same bits."""
+        rc, out = _gain_apply_call(self._lib.lfd_gain_apply_host, self._ctx, rgb, ref_counts, factors, self.device)
+        self._check(rc, "lfd_gain_apply_host")
+        return out
 
     def pack_ply_normals(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
         """HipDensifier.pack_ply_normals over CPU tensors: the host writer's records (core/writers.py), the same bytes."""

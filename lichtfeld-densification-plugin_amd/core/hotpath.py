@@ -100,6 +100,11 @@ class HotPath:
         self.colour_mode = str(config.exp("multiview_colour"))
         self.colour = self.colour_mode != "off"
         self._colour_counter: Optional[torch.Tensor] = None     # int64 [2] where the kernels run: points blended / the sum of their views, added to
+        # per-image exposure gains (lfd_gain_accumulate): statistics where the colour stage would run; reads only
+        self.gain_mode = str(config.exp("gain_compensation"))
+        self.gain = self.gain_mode != "off"
+        self._uids = [int(c.uid) for c in cams]
+        self._gain_parts: list = []                             # (table where the kernels run, reference uids, neighbour uids) per launch the run used
         on = bool(config.exp("undistort_images"))
         self._distortion = [c.active_distortion() if on else None for c in cams]
 
@@ -153,10 +158,44 @@ class HotPath:
         if self.colour:
             with self.clock.stage("kernel"):
                 res = self._recoloured(batch, res)
+        if self.gain:
+            with self.clock.stage("kernel"):
+                self._gain_commit(self._gain_launch(batch, res))
         if self.normals:
             with self.clock.stage("kernel"):
                 res = self._with_normals(batch, res)
         return res
+
+    # -- per-image exposure gains (lfd_gain_accumulate) -------------------------------------------------------------------------
+    def _gain_launch(self, batch: hb.PreparedBatch, out):
+        """One launch of lfd_gain_accumulate over the points ``out`` holds NOW (buffers on the stream, or a collected result), behind every
+        stage that moves or drops them, into a zeroed table of the launch's own: (table, reference uids, neighbour uids) with a row per
+        (reference, slot) of the batch.  Nothing is read back here.  A launch has a table of its own so that a grouped call that is redone,
+        or dropped as a whole, leaves no trace: only what ``_gain_commit`` is given reaches the run's statistics - decided per launch where
+        its result is collected (``finish_sampled``), never by a flag that outlives the launch."""
+        table = self.dens.gain_accumulate(batch, out, self.support_thresh_px)
+        ref_uid = np.zeros(batch.n_refs * batch.k, np.int64)
+        nbr_uid = np.full(batch.n_refs * batch.k, -1, np.int64)           # (-1: a slot the reference does not use; dropped in gain_rows)
+        for i, r in enumerate(batch.refs):
+            ref_uid[i * batch.k:(i + 1) * batch.k] = self._uids[int(r.ref_cam)]
+            for j, c in enumerate(r.nbr_cams):
+                nbr_uid[i * batch.k + j] = self._uids[int(c)]
+        return table, ref_uid, nbr_uid
+
+    def _gain_commit(self, part) -> None:
+        if part is not None:
+            self._gain_parts.append(part)
+
+    def gain_rows(self):
+        """The run's statistics as core.gains.GainRows on the host: the tables are concatenated where they are and read with one copy."""
+        from .gains import GainRows
+        if not self._gain_parts:
+            return GainRows.empty()
+        table = torch.cat([t for t, _r, _n in self._gain_parts], 0).cpu().numpy().view(np.uint64)
+        ref_uid = np.concatenate([r for _t, r, _n in self._gain_parts])
+        nbr_uid = np.concatenate([n for _t, _r, n in self._gain_parts])
+        live = nbr_uid >= 0
+        return GainRows(ref_uid[live], nbr_uid[live], table[live])
 
     def _recoloured(self, batch: hb.PreparedBatch, out):
         """``out`` (buffers on the stream: in place; or a collected result: a copy) with the colour of every point blended over the views that
@@ -236,6 +275,8 @@ class HotPath:
             out = into
         if self.colour:
             out = self._recoloured(batch, out)
+        if self.gain:
+            out.gain_pending = self._gain_launch(batch, out)       # (committed in finish_sampled, when the result is one the run uses)
         if self.normals:
             out = self._with_normals(batch, out)
         return out
@@ -353,7 +394,7 @@ class HotPath:
             use_masks = d["mask_a"] is not None or any(m is not None for m in d["nbr_masks"])
             return hb.ReferenceInputs(ref_cam=packed.ref_index, nbr_cams=list(packed.nbr_indices), cert=certs, warp=warps,
                                       image=d["image"], mask_a=d["mask_a"], mask_b=list(d["nbr_masks"]) if use_masks else None,
-                                      precision=precision, nbr_images=list(d["nbr_images"]) if self.colour else None)
+                                      precision=precision, nbr_images=list(d["nbr_images"]) if (self.colour or self.gain) else None)
         use_masks = packed.mask_a is not None or any(m is not None for m in packed.nbr_masks)
         mask_b = None
         with self.clock.stage("prepare"):        # the host-prepared image and masks cross to where the kernels run
@@ -362,7 +403,7 @@ class HotPath:
             image = _upload_u8(packed.image, dev)
             mask_a = _upload_u8(packed.mask_a, dev) if packed.mask_a is not None else None
             # (multi-view colour: the neighbours' match-size images cross beside the reference's)
-            nbr_images = [_upload_u8(im, dev) for im in packed.nbr_images] if self.colour else None
+            nbr_images = [_upload_u8(im, dev) for im in packed.nbr_images] if (self.colour or self.gain) else None
         return hb.ReferenceInputs(ref_cam=packed.ref_index, nbr_cams=list(packed.nbr_indices), cert=certs, warp=warps, image=image,
                                   mask_a=mask_a, mask_b=mask_b, precision=precision, nbr_images=nbr_images)
 
@@ -464,6 +505,7 @@ class HotPath:
         free = self._buf_pool.setdefault((int(capacity), int(n_refs), int(k), int(filtered)), [])
         out = free.pop() if free else hb.OutputBuffers(int(capacity), int(n_refs), int(k), self.dev)
         out.normals_valid = False              # (whatever fills them next has not had its normals estimated)
+        out.gain_pending = None
         return out
 
     # -- upstream's normaliser without stalling the launch stream ---------------------------------------------------------------
@@ -618,9 +660,14 @@ class HotPath:
             except Exception:
                 self._support_void = True              # (the caller redoes the call, and drops what was launched behind it)
                 raise
-            if not check_selection and any(int(st) in hb.SELECT_VOIDS_STREAM for st in res.sel_status):
+            void = not check_selection and any(int(st) in hb.SELECT_VOIDS_STREAM for st in res.sel_status)
+            if void:
                 self._support_void = True              # (a chained call that is void as a whole: core/strategies.py::SampledLoop._recover)
             self._support_count(res)
+            # the gain statistics of THIS call follow its points: kept unless the call is void as a whole (the caller redoes its references);
+            # an exception above keeps nothing, and a caller that drops the result clears ``gain_pending`` first (SampledLoop._recover)
+            if not void:
+                self._gain_commit(getattr(out, "gain_pending", None))
             if not res.count and check_selection:
                 return None
             return dataclasses.replace(res, xyz=res.xyz.clone(), rgb=res.rgb.clone(), err=res.err.clone(),
@@ -628,6 +675,7 @@ class HotPath:
                                        slot=res.slot.clone() if res.slot is not None else None, _packed=None,
                                        normals=res.normals.clone() if res.normals is not None else None)
         finally:
+            out.gain_pending = None
             self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, _pool_kind(out)), []).append(out)
 
     def pack_ply_tensor(self, xyz: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
@@ -649,7 +697,7 @@ class HotPath:
             if bool(self.config.exp("dense_tile_segments")):
                 # unordered retirement (no look-back), raster order restored from the tile table: the same result, bit for bit
                 return self.dens.order_segments(self.dens.triangulate_dense_segments(batch, self.params))
-            if (self.min_support > 0 or self.refine or self.max_sigma > 0.0 or self.colour or self.normals) and not self.on_host:
+            if (self.min_support > 0 or self.refine or self.max_sigma > 0.0 or self.colour or self.gain or self.normals) and not self.on_host:
                 # the launch, the filter, the re-triangulation and / or the gate behind it on the same stream, then the one read-back of the offsets
                 cap = batch.n_refs * batch.H * batch.W
                 out = hb.OutputBuffers(cap, batch.n_refs, batch.k, self.dev)
@@ -663,6 +711,8 @@ class HotPath:
                     out = self._sigma_gated(batch, out, status)
                 if self.colour:
                     out = self._recoloured(batch, out)
+                if self.gain:
+                    self._gain_commit(self._gain_launch(batch, out))
                 if self.normals:
                     out = self._with_normals(batch, out)
                 self.dens.check_launches()

@@ -246,6 +246,9 @@ def run_dense_pipeline(
     if world > 1 and str(config.exp("multiview_colour")) != "off":
         raise ValueError("experimental['multiview_colour'] cannot run sharded over several GPUs: like the normals it is a stage of the single-GPU "
                          "run, and the sharded schedules have not been taken through it")
+    if world > 1 and str(config.exp("gain_compensation")) != "off":
+        raise ValueError("experimental['gain_compensation'] cannot run sharded over several GPUs: like the multi-view colour it is a stage of the "
+                         "single-GPU run, and the exchange of a sharded run does not carry the statistics")
     if world > 1 and str(config.exp("depth_maps_dir")) != "":
         raise ValueError("experimental['depth_maps_dir'] cannot run sharded over several GPUs: the maps are a stage of the single-GPU run, and with "
                          "gather_to_root only one rank would hold the cloud they are rendered from")
@@ -269,7 +272,7 @@ def run_dense_pipeline(
                          cancel_requested=cancel_requested, total_pairs_est=total_pairs_est)
     t0 = time.time()
     own_matcher = matcher is None
-    prefetch = hot = feat_cache = strategy = None
+    prefetch = hot = feat_cache = strategy = gain_rows = None
     rank_status, rank_error = 0, None         # 0 fine, 1 cancelled, 2 failed: agreed on by all ranks before the exchange step (core/distributed.py)
     try:
         if own_matcher:
@@ -363,6 +366,10 @@ def run_dense_pipeline(
             n_col, n_views = hot.colour_totals()
             log.info(f"Multi-view colour: {hot.colour_mode} over the confirming views (within {hot.support_thresh_px:g} px), {n_col} points blended, "
                      f"{(n_views / n_col if n_col else 0.0):.2f} views per point")
+        if hot.gain:
+            gain_rows = hot.gain_rows()
+            log.info(f"Gain compensation: {int(gain_rows.table[:, 0].sum())} samples in {int((gain_rows.table[:, 0] > 0).sum())} of "
+                     f"{gain_rows.table.shape[0]} (reference, neighbour) rows (within {hot.support_thresh_px:g} px)")
         if hot.normals:
             n_fit, n_fell = hot.normal_totals()
             log.info(f"Surface normals: window radius {hot.normal_radius} cell(s), depth step {hot.normal_depth_step:g}, {n_fit} points fitted, "
@@ -389,7 +396,9 @@ def run_dense_pipeline(
         raise_if_cancelled(cancel_requested)
     if progress_callback:
         progress_callback(90.0, "Finalizing triangulation...")
-    return outputs.result(t0, clock)
+    result = outputs.result(t0, clock)
+    result.gain_rows = gain_rows          # experimental['gain_compensation']: the run's statistics, for the solve (densify.py)
+    return result
 
 
 def _release(prefetch, strategy, feat_cache, own_matcher, matcher, outputs: RunOutputs, hot, debug_state) -> Optional[BaseException]:

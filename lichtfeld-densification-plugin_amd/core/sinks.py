@@ -39,6 +39,7 @@ class PipelineResult:
         self.device_normals = device_normals                  # experimental['estimate_normals']: (N,3) f32 unit normals where the points are, else None
         self._normals = None
         self.match_grid = match_grid                          # (H, W) of the matcher's grid, when a reference was matched in this process
+        self.gain_rows = None                                 # experimental['gain_compensation']: core.gains.GainRows of the run, else None
         self._loader = loader
         self.elapsed_seconds = float(elapsed_seconds)
         self.pairs_processed = int(pairs_processed)           # upstream's name; counts REFERENCES that produced points

@@ -270,6 +270,8 @@ class SampledLoop:
         while self.chain_fly:
             later, handle, _place = self.chain_fly.pop(0)
             try:
+                if getattr(handle[1], "gain_pending", None) is not None:
+                    handle[1].gain_pending = None       # (experimental['gain_compensation']: its statistics go with its results)
                 self.hot.finish_sampled(handle, check_selection=False)       # waited for, its buffers back in the pool, its results dropped
             except Exception:
                 pass

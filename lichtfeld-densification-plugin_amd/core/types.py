@@ -143,6 +143,12 @@ EXPERIMENTAL_DEFAULTS = {
     # changes, and it works with or without min_support_views.  Behind support filter, re-triangulation and depth gate, in front of the
     # normals.  "off" = today's colour: no new code runs and every output stays byte-identical.
     "multiview_colour": "off",
+    # per-image exposure gains (lfd_gain_accumulate / lfd_gain_apply): while each reference is resident the colour of its points
+    # and of every view that confirms them (the multi-view colour's views, within support_threshold()) is summed per (reference, neighbour);
+    # at the end of the run one factor per image ("luma") or per image and channel ("rgb") is solved from those sums over the whole pair graph
+    # and every point's colour is multiplied by its reference's factor: the cloud comes out at one exposure, and <output>.gains.json lists the
+    # factors.  Rewrites rgb only, once, in front of the consensus filter.  "off" = no new code runs and every output stays byte-identical.
+    "gain_compensation": "off",
     # per-camera depth and normal maps rendered from the final cloud (lfd_render_depth): a directory - relative to the output
     # file's own - that receives <image stem>.npy (f32 (ph, pw): depth along the camera's z axis in scene units, 0 = no data), with
     # estimate_normals <image stem>_normal.npy (f32 (ph, pw, 3): world frame, the PLY's normals, 0 0 0 = no data) and depth_maps.json, for EVERY
@@ -163,6 +169,7 @@ EXPERIMENTAL_DEFAULTS = {
 }
 CAP_MODES = ("random", "spatial")
 COLOUR_MODES = ("off", "mean", "median")
+GAIN_MODES = ("off", "luma", "rgb")
 CONSENSUS_CAP = 8            # LFD_CONSENSUS_CAP of include/lfd_densify.h
 
 
@@ -529,6 +536,24 @@ class DensePipelineConfig:
             if self.exp("dense_tile_segments"):
                 return ("experimental['depth_maps_dir'] needs the cloud as arrays; dense mode with experimental['dense_tile_segments'] retires tiles "
                         "into the file's records")
+        gain = self.exp("gain_compensation")
+        if not isinstance(gain, str) or gain not in GAIN_MODES:
+            return ("experimental['gain_compensation'] must be 'off', 'luma' (one exposure factor per image) or 'rgb' (one per image and "
+                    "channel)")
+        if gain != "off":
+            if colour != "off":
+                return ("experimental['gain_compensation'] cannot run with experimental['multiview_colour']: the blend would need each view's "
+                        "factor before the solve exists; a two-pass driver is out of scope")
+            if not (self.support_threshold() > 0.0):
+                return ("experimental['gain_compensation'] takes the confirming views by the support filter's test: "
+                        "experimental['support_thresh_px'] or, for its default, reproj_thresh must be > 0")
+            if self.stream_output:
+                return ("experimental['gain_compensation'] rewrites the colour of the collected cloud once the run's factors are solved; "
+                        "stream_output writes 15-byte records while the run proceeds")
+            if self.exp("dense_tile_segments"):
+                return "experimental['gain_compensation'] needs the ordered dense result; experimental['dense_tile_segments'] retires tiles unordered"
+            if self.exchange_record_format() == "ply":
+                return "experimental['gain_compensation'] rewrites f32 rows; experimental['exchange_records'] must be 'f32' with it"
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):
                 return "stream_output writes a PLY while the run proceeds: output_path must end in .ply"

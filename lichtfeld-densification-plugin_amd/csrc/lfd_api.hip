@@ -22,6 +22,7 @@
 #include "lfd_refine.hpp"
 #include "lfd_normals.hpp"
 #include "lfd_colour.hpp"
+#include "lfd_gain.hpp"
 #include "lfd_sigma.hpp"
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
@@ -133,6 +134,8 @@ hipError_t lfd_refine_launch(const LfdRefineArgs& p, hipStream_t stream);     //
 hipError_t lfd_sigma_launch(const LfdSigmaArgs& p, hipStream_t stream);       // lfd_sigma.hip
 hipError_t lfd_normals_launch(const LfdNormalArgs& p, hipStream_t stream);    // lfd_normals.hip
 hipError_t lfd_colour_launch(const LfdColourArgs& p, hipStream_t stream);     // lfd_colour.hip
+hipError_t lfd_gain_launch(const LfdGainArgs& p, hipStream_t stream);         // lfd_gain.hip
+hipError_t lfd_gain_apply_launch(const LfdGainApplyArgs& p, hipStream_t stream);
 extern "C" __global__ void lfd_pack_ply_normals_kernel(const float* xyz, const float* normals, const float* rgb, long long n, unsigned char* out);
 extern "C" __global__ void lfd_select_topm_kernel(LfdSelectArgs A);
 extern "C" __global__ void lfd_select_filter_mw_kernel(LfdSelectArgs A, LfdSelectNorms norms);
@@ -2193,6 +2196,50 @@ int lfd_colour_multiview(lfd_context* ctx, const lfd_batch* batch, const lfd_poi
     p.n_refs = batch->n_refs; p.k = batch->k; p.mode = mode;
     p.g = launch_geom(batch, L, support_thresh_px, 0.0f);
     LFD_HIP(ctx, lfd_colour_launch(p, ctx->stream));
+    return LFD_OK;
+}
+
+// ---- per-image exposure gains (lfd_gain.hip) ----------------------------------------------------------------------------------------------------
+int lfd_gain_accumulate(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets,
+                        const uint8_t* const* nbr_image, float support_thresh_px, uint64_t* table) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_gain_check(in, ref_offsets, nbr_image, support_thresh_px, table, 0))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_gain_accumulate: ") + why);
+    LfdLaunch L;
+    int rc = batch_launch(ctx, batch, L);
+    if (rc != LFD_OK) return rc;
+    if (const char* why = lfd_gain_check(in, ref_offsets, nbr_image, support_thresh_px, table, (long long)batch->n_refs * batch->k))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_gain_accumulate: ") + why);
+    if (const char* why = lfd_colour_check_images(batch, nbr_image)) return fail(ctx, LFD_ERR_INVALID, std::string("lfd_gain_accumulate: ") + why);
+    LfdGainArgs p;
+    std::memset(&p, 0, sizeof(p));
+    // (the image table is the colour stage's: the two stages never run in one configuration, and the cache compares content anyway)
+    rc = upload_pointer_table(ctx, ctx->colour_img, batch, reinterpret_cast<const void* const*>(nbr_image),
+                              reinterpret_cast<const void* const**>(&p.img));
+    if (rc != LFD_OK) return rc;
+    p.n_wg = (int32_t)((in->capacity + 255) / 256);
+    p.refs = L.refs; p.slots = L.slots; p.pair_const = L.pair_const;
+    p.offs = reinterpret_cast<const long long*>(ref_offsets);
+    p.xyz = in->xyz; p.rgb = in->rgb; p.cell = in->cell; p.slot = in->slot;
+    p.table = reinterpret_cast<unsigned long long*>(table);
+    p.capacity = in->capacity;
+    p.n_refs = batch->n_refs; p.k = batch->k;
+    p.g = launch_geom(batch, L, support_thresh_px, 0.0f);
+    LFD_HIP(ctx, lfd_gain_launch(p, ctx->stream));
+    return LFD_OK;
+}
+
+int lfd_gain_apply(lfd_context* ctx, const float* rgb, int64_t n, const int64_t* ref_offsets, int32_t n_refs, const float* factors, float* rgb_out) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_gain_apply_check(rgb, n, ref_offsets, n_refs, factors, rgb_out))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_gain_apply: ") + why);
+    LfdGainApplyArgs p;
+    std::memset(&p, 0, sizeof(p));
+    p.offs = reinterpret_cast<const long long*>(ref_offsets);
+    p.factors = factors; p.rgb = rgb; p.o_rgb = rgb_out; p.n = n; p.n_refs = n_refs;
+    LFD_HIP(ctx, lfd_gain_apply_launch(p, ctx->stream));
     return LFD_OK;
 }
 

@@ -26,6 +26,7 @@
 #include "lfd_sigma.hpp"
 #include "lfd_normals.hpp"
 #include "lfd_colour.hpp"
+#include "lfd_gain.hpp"
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
 #include "lfd_freespace.hpp"
@@ -660,6 +661,92 @@ int lfd_colour_multiview_host(lfd_context* ctx, const lfd_batch* b, const lfd_po
     if (counters)
         for (int c = 0; c < n_chunks; ++c)
             for (int e = 0; e < 2; ++e) counters[e] += count[(size_t)c * 2 + e];
+    return LFD_OK;
+}
+
+// The twin of lfd_gain_accumulate: the routine of lfd_gain.hpp per (point, slot) over host pointers, on the context's threads.
+// A chunk keeps the sums of the reference it is in and adds them to the table when the reference changes: integer additions, order-free.
+int lfd_gain_accumulate_host(lfd_context* ctx, const lfd_batch* b, const lfd_points* in, const int64_t* ref_offsets,
+                             const uint8_t* const* nbr_image, float support_thresh_px, uint64_t* table) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    if (const char* why = lfd_gain_check(in, ref_offsets, nbr_image, support_thresh_px, table, 0))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_gain_accumulate_host: ") + why);
+    lfd_params none;
+    std::memset(&none, 0, sizeof(none));
+    int rc = validate_host(ctx, b, &none);
+    if (rc != LFD_OK) return rc;
+    if (const char* why = lfd_gain_check(in, ref_offsets, nbr_image, support_thresh_px, table, (long long)b->n_refs * b->k))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_gain_accumulate_host: ") + why);
+    if (const char* why = lfd_colour_check_images(b, nbr_image)) return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_gain_accumulate_host: ") + why);
+    HostLaunch L;
+    prepare_host(b, &none, L);
+    std::vector<LfdSlot> slot;
+    make_slot_table(ctx, L, slot, nullptr);
+    const LfdSupportGeom g = make_geom(L, support_thresh_px, 0.0f);
+    const long long cap = in->capacity;
+    const long long* offs = reinterpret_cast<const long long*>(ref_offsets);
+    const long long total = lfd_support_clamp(offs[b->n_refs], cap);
+    const int n_chunks = (int)((total + kChunk - 1) / kChunk);
+    parallel_chunks(ctx, n_chunks, [&](int c) {
+        uint64_t acc[LFD_MAX_SLOTS * LFD_GAIN_QUANTITIES];
+        int cur = -1;
+        auto flush = [&]() {
+            if (cur < 0) return;
+            for (int t = 0; t < b->k * LFD_GAIN_QUANTITIES; ++t)
+                if (acc[t]) __atomic_fetch_add(&table[(size_t)cur * b->k * LFD_GAIN_QUANTITIES + t], acc[t], __ATOMIC_RELAXED);
+        };
+        const long long i1 = std::min<long long>(total, (long long)(c + 1) * kChunk);
+        for (long long i = (long long)c * kChunk; i < i1; ++i) {
+            const int r = lfd_support_ref_of(offs, b->n_refs, cap, i);
+            if (r != cur) {
+                flush();
+                cur = r;
+                std::memset(acc, 0, sizeof(acc));
+            }
+            const int cell = in->cell[i], s = (int)in->slot[i], ns = b->n_slots[r];
+            const float X0 = in->xyz[3 * i], X1 = in->xyz[3 * i + 1], X2 = in->xyz[3 * i + 2];
+            const float rgb[3] = {in->rgb[3 * i], in->rgb[3 * i + 1], in->rgb[3 * i + 2]};
+            if (lfd_colour_guarded(X0, X1, X2, rgb[0], rgb[1], rgb[2], cell, L.HW, s, ns)) continue;
+            const bool ref_ok = lfd_gain_in_range(rgb[0]) && lfd_gain_in_range(rgb[1]) && lfd_gain_in_range(rgb[2]);
+            if (!ref_ok) continue;
+            const uint32_t qr[3] = {lfd_gain_quantise(rgb[0]), lfd_gain_quantise(rgb[1]), lfd_gain_quantise(rgb[2])};
+            const LfdSlot* sl = &slot[(size_t)r * LFD_MAX_SLOTS];
+            const uint8_t* const* img = nbr_image + (size_t)r * b->k;
+            for (int j = 0; j < ns; ++j) {
+                const float* wv = sl[j].warp + (size_t)cell * g.C + (g.C - 2);
+                uint32_t q[3];
+                if (!lfd_gain_sample(sl[j], img[j], g, j == s, ref_ok, sl[j].cert[cell], wv[0], wv[1], X0, X1, X2, q)) continue;
+                uint64_t* a = acc + j * LFD_GAIN_QUANTITIES;
+                a[0] += 1;
+                for (int e = 0; e < 3; ++e) { a[1 + e] += qr[e]; a[4 + e] += q[e]; }
+            }
+        }
+        flush();
+    });
+    return LFD_OK;
+}
+
+// The twin of lfd_gain_apply: lfd_gain_value per colour value, the same bits.
+int lfd_gain_apply_host(lfd_context* ctx, const float* rgb, int64_t n, const int64_t* ref_offsets, int32_t n_refs, const float* factors,
+                        float* rgb_out) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    if (const char* why = lfd_gain_apply_check(rgb, n, ref_offsets, n_refs, factors, rgb_out))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_gain_apply_host: ") + why);
+    const long long* offs = reinterpret_cast<const long long*>(ref_offsets);
+    const long long total = lfd_support_clamp(offs[n_refs], n);
+    const int n_chunks = (int)((total + kChunk - 1) / kChunk);
+    parallel_chunks(ctx, n_chunks, [&](int c) {
+        const long long i1 = std::min<long long>(total, (long long)(c + 1) * kChunk);
+        for (long long i = (long long)c * kChunk; i < i1; ++i) {
+            const int r = lfd_support_ref_of(offs, n_refs, n, i);
+            for (int ch = 0; ch < 3; ++ch) {
+                const float v = lfd_gain_value(rgb[3 * i + ch], factors[3 * r + ch]);
+                std::memcpy(rgb_out + 3 * i + ch, &v, sizeof(float));                       // (bit for bit, a NaN's payload included)
+            }
+        }
+    });
     return LFD_OK;
 }
 

@@ -264,6 +264,67 @@ def _voxel_filter_on_device(device_points, voxel_size: float):
         dens.close()
 
 
+def _apply_gain_compensation(result, config: DensePipelineConfig, camera_records, refs_local, progress_callback=None):
+    """Per-image exposure gains (experimental['gain_compensation']) on the collected cloud, in front of every cloud stage
+    while the per-reference counts are still the loop's: the factors are solved from the run's statistics (core/gains.py),
+    ``<output file>.gains.json`` is written, and every point's colour is multiplied by its reference's factor where the points are - the
+    device tensors of a GPU run through lfd_gain_apply, the host arrays of ``backend='host'`` through the twin.  Returns the result with the
+    new rgb; points, counts, order, xyz and err are the input's.  Off: the result itself, nothing runs."""
+    mode = str(config.exp("gain_compensation"))
+    if mode == "off":
+        return result
+    import json
+    import torch
+    from .core import hip_backend as hb
+    from .core.gains import solve_gains
+    from .core.sinks import PipelineResult
+    if result.streamed_path is not None or result.gain_rows is None:
+        raise RuntimeError("experimental['gain_compensation'] needs the cloud held as arrays and the run's statistics: this result has neither")
+    counts = np.asarray(result.points_per_reference, np.int64)
+    pts = result.device_points
+    if pts is None:
+        pts = tuple(torch.from_numpy(np.ascontiguousarray(a)) for a in (result.xyz, result.rgb, result.err))
+    n_in = int(pts[0].shape[0])
+    if counts.size != len(refs_local) or int(counts.sum()) != n_in:
+        raise RuntimeError(f"experimental['gain_compensation'] needs the whole cloud with its per-reference counts: this result holds {n_in:,} "
+                           f"points in {counts.size} counts that add up to {int(counts.sum()):,}, the run has {len(refs_local)} references")
+    if progress_callback:
+        progress_callback(91.0, "Applying gain compensation...")
+    uids = [int(c.uid) for c in camera_records]
+    sol = solve_gains(result.gain_rows, uids, mode, warn=log.warn)
+    by_uid = sol.factor_of()
+    factors = np.stack([by_uid[int(camera_records[int(ci)].uid)] for ci in refs_local]).astype(np.float32)
+    names = {int(c.uid): os.path.basename(str(c.image_path)) for c in camera_records}
+    with open(str(config.output_path) + ".gains.json", "w") as f:
+        json.dump(sol.to_json(names), f, indent=1)
+    on_gpu = bool(pts[0].is_cuda)
+    dens = hb.HipDensifier(pts[0].device) if on_gpu else hb.HostDensifier(int(config.exp("host_threads")))
+    try:
+        rgb = dens.gain_apply(pts[1], counts, factors)
+    finally:
+        dens.close()
+    used = factors[counts > 0] if (counts > 0).any() else np.ones((1, 3), np.float32)       # (an empty cloud: nothing was multiplied)
+    log.info(f"Gain compensation ({mode}): {int(sol.pairs.sum()) // 2} pairs in {sol.n_components} component(s), {sol.rows_ignored} rows ignored, "
+             f"factors of the references {float(used.min()):.4f} .. {float(used.max()):.4f}, {len(sol.clamped)} clamped")
+    new_pts = (pts[0], rgb, pts[2])
+    if on_gpu:
+        clock = result._clock
+
+        def loader(p=new_pts, clk=clock):
+            if hasattr(clk, "stage"):
+                with clk.stage("d2h"):
+                    return tuple(t.cpu().numpy() for t in p)
+            return tuple(t.cpu().numpy() for t in p)
+        arrays = (None, None, None)
+    else:
+        loader, arrays = None, tuple(t.numpy() for t in new_pts)
+    out = PipelineResult(xyz=arrays[0], rgb=arrays[1], err=arrays[2], elapsed_seconds=result.elapsed_seconds, pairs_processed=result.pairs_processed,
+                         pairs_matched=result.pairs_matched, points_per_reference=result.points_per_reference, device_points=new_pts,
+                         streamed_path=None, clock=result._clock, loader=loader, device_normals=result.device_normals, match_grid=result.match_grid)
+    out.gain_rows = result.gain_rows
+    return out
+
+
 def _apply_consensus_filter(result, config: DensePipelineConfig, progress_callback=None):
     """The cross-reference consensus filter on the finished cloud (lfd_consensus_filter), where the points are: the device
     tensors of a GPU run through the device call, the host arrays of ``backend='host'`` through the twin.  Returns the result with the kept
@@ -674,6 +735,7 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
         if progress_callback:
             progress_callback(0.0, "Cancelled")
         return 2
+    result = _apply_gain_compensation(result, config, records, refs_local, progress_callback)      # (while the counts are still the loop's)
     result = _apply_consensus_filter(result, config, progress_callback)      # (in front of the point cap: it has to see the whole cloud)
     result = _apply_freespace_filter(result, config, records, refs_local, progress_callback)      # (behind it: what it removed cannot "see through" a surface)
     _write_depth_maps(result, config, records, progress_callback)      # (a side output of the densest filtered cloud, in front of cap, fusion and voxel filter)
@@ -736,6 +798,7 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
     if _was_cancelled(cancel_requested):
         return 2, "Cancelled"
     try:
+        result = _apply_gain_compensation(result, config, records, refs_local, progress_callback)      # (while the counts are still the loop's)
         result = _apply_consensus_filter(result, config, progress_callback)  # (in front of the point cap and the voxel filter: it has to see the whole cloud)
         result = _apply_freespace_filter(result, config, records, refs_local, progress_callback)   # (behind it, in front of cap and voxel filter)
         _write_depth_maps(result, config, records, progress_callback)      # (a side output of that cloud)
@@ -867,6 +930,8 @@ def _experimental_from_args(args) -> dict:
         exp["fused_refiner_head"] = True
     if str(getattr(args, "multiview_colour", None) or "off") != "off":
         exp["multiview_colour"] = str(args.multiview_colour)
+    if str(getattr(args, "gain_compensation", None) or "off") != "off":
+        exp["gain_compensation"] = str(args.gain_compensation)
     if bool(getattr(args, "estimate_normals", False)):
         exp["estimate_normals"] = True
     if getattr(args, "normal_radius_cells", None) is not None:
@@ -976,6 +1041,10 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--multiview_colour", choices=("off", "mean", "median"), default="off",
                     help="colour every point by the mean or the median, per channel, over the views that see it (its reference, the neighbour "
                          "that made it and every other neighbour that confirms it within the support threshold) instead of the reference alone")
+    ap.add_argument("--gain_compensation", choices=("off", "luma", "rgb"), default="off",
+                    help="bring the whole cloud to one exposure: solve one factor per image (luma) or per image and channel (rgb) from the "
+                         "colours the confirming views have at the same points, multiply every point's colour by its reference's factor and "
+                         "write <out_name>.gains.json")
     ap.add_argument("--estimate_normals", action="store_true",
                     help="give every point a unit surface normal, fitted to its winning neighbour's warp around its grid cell and oriented towards "
                          "its reference's camera: the PLY then has x y z nx ny nz red green blue vertices (needs a .ply --out_name)")
