@@ -759,6 +759,34 @@ int lfd_cap_spatial(lfd_context* ctx, const float* xyz, const float* err, int64_
 int lfd_cap_spatial_host(lfd_context* ctx, const float* xyz, const float* err, int64_t n, int64_t budget, int64_t* keep_out, int64_t* n_keep_host,
                          double* stats_host);
 
+/* Footprint-adaptive thinning (no upstream counterpart): keep at most one point per cell of a linear octree over the cloud, every
+ * point at the level that the footprint of its own reference camera selects, so the kept density is constant in that camera's image and not in
+ * world space.  xyz: f32 [n][3]; err: f32 [n] or NULL; ref_offsets_host: i64 [n_refs + 1], ascending from 0 to n (point i belongs to the
+ * reference r with offsets[r] <= i < offsets[r + 1]); ref_rows_host: f64 [n_refs][5] = r3x r3y r3z t3 (the third row of the reference's
+ * world-to-camera [R | t]) and tan_cell (the tangent of one match-grid cell, max(cam_w / (fx grid_w), cam_h / (fy grid_h))); keep_out: i64 [n],
+ * the kept INPUT INDICES in ascending order - the kept cloud is the input under a mask, in input order.  The rule (csrc/lfd_thin.hpp; integers
+ * and single IEEE f64 operations, no FMA), exact: device, twin and a reference written from these lines agree element for element.
+ *   box, key   lfd_cap_spatial's: o_c the f32 minimum per axis, L the longest side, the 63-bit Morton key of 21 bits per axis
+ *   depth      z = ((r3x x + r3y y) + r3z z_c) + t3 in f64 from the f32 coordinates
+ *   footprint  g = (z tan_cell) thin_cells
+ *   level      20 where !(g > 0), g is infinite or !(L > 0); else with q = L / g: 0 where q < 1, else min(the unbiased binary exponent of q, 20) -
+ *              the cell side L / 2^level is at least g and, unless clamped, below 2 g
+ *   code       (1 << 3 level) | (key >> 3 (21 - level)): unique across levels, below 2^61
+ *   kept       of the points of equal code the one of smallest error by the monotone integer image of its f32 bits (-0 < +0, NaNs by their
+ *              bits), the lowest input index on ties and with err NULL
+ * There is no suppression across levels: a surface seen from two distances keeps a point per cell of each level.
+ * *n_keep_host: the number of kept points; ref_offsets_out_host: i64 [n_refs + 1], the offsets of the kept cloud; stats_host: NULL, or f64 [43] =
+ * points per level 0 .. 20, cells per level 0 .. 20, L.  Synchronous, deterministic; the workspace belongs to the context and is reused.
+ * LFD_ERR_INVALID: a null required pointer, n < 0 or > 2^31 - 1, n_refs < 1, offsets that do not start at 0, end at n or that decrease, thin_cells
+ * or a tan_cell that is not finite and > 0, keep_out overlapping xyz or err, a "non-finite coordinate" in the input (decided before anything is
+ * sorted).  n == 0 is valid: zero outputs.  lfd_thin_footprint_host: the same over host pointers on a host context, whatever its thread count. */
+int lfd_thin_footprint(lfd_context* ctx, const float* xyz, const float* err, int64_t n, const int64_t* ref_offsets_host, int32_t n_refs,
+                       const double* ref_rows_host, double thin_cells, int64_t* keep_out, int64_t* n_keep_host, int64_t* ref_offsets_out_host,
+                       double* stats_host);
+int lfd_thin_footprint_host(lfd_context* ctx, const float* xyz, const float* err, int64_t n, const int64_t* ref_offsets_host, int32_t n_refs,
+                            const double* ref_rows_host, double thin_cells, int64_t* keep_out, int64_t* n_keep_host, int64_t* ref_offsets_out_host,
+                            double* stats_host);
+
 /* (e) multi-GPU exchange, placement step (no upstream counterpart - upstream has no multi-GPU code): n copies
  * dst[dst_offset .. +nbytes) = src[src_offset .. +nbytes) in ONE launch on `hip_stream` of device `device_index` (offsets and lengths in
  * bytes, no alignment required: 15-byte PLY records).  The overlapped exchange receives every rank's records of a round as one padded block

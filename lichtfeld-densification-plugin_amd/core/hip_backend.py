@@ -61,6 +61,11 @@ class CapInputRefused(HipBackendError):
     knob (densify.py does)."""
 
 
+class ThinInputRefused(HipBackendError):
+    """lfd_thin_footprint refused the cloud - a non-finite coordinate - before sorting anything.  Nothing stands in for it: the caller reports the
+    knob (densify.py does)."""
+
+
 class lfd_params(C.Structure):
     _fields_ = [("sampson_thresh", C.c_double), ("certainty_thresh", C.c_float), ("sample_cap", C.c_float),
                 ("reproj_thresh", C.c_float), ("min_parallax_deg", C.c_float), ("no_filter", C.c_int32),
@@ -244,6 +249,9 @@ def load_library() -> C.CDLL:
     lib.lfd_pack_gaussians_host.argtypes = list(lib.lfd_pack_gaussians.argtypes)
     lib.lfd_cap_spatial.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     lib.lfd_cap_spatial_host.argtypes = list(lib.lfd_cap_spatial.argtypes)
+    lib.lfd_thin_footprint.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_double), C.c_double,
+                                       C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    lib.lfd_thin_footprint_host.argtypes = list(lib.lfd_thin_footprint.argtypes)
     lib.lfd_copy_segments.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.lfd_launch_status.argtypes = [ctxp, C.POINTER(C.c_int32)]
     lib.lfd_get_pair_fundamental.argtypes = [ctxp, C.c_int32, C.POINTER(C.c_double)]
@@ -283,7 +291,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_refiner_head", "lfd_refiner_head_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_colour_multiview", "lfd_colour_multiview_host", "lfd_gain_accumulate", "lfd_gain_accumulate_host", "lfd_gain_apply", "lfd_gain_apply_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_render_depth", "lfd_render_depth_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_cap_spatial", "lfd_cap_spatial_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_refiner_head", "lfd_refiner_head_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_colour_multiview", "lfd_colour_multiview_host", "lfd_gain_accumulate", "lfd_gain_accumulate_host", "lfd_gain_apply", "lfd_gain_apply_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_render_depth", "lfd_render_depth_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_cap_spatial", "lfd_cap_spatial_host", "lfd_thin_footprint", "lfd_thin_footprint_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -1332,6 +1340,49 @@ def _cap_call(fn, ctx, what, xyz, err, budget, device, last_error):
     return keep[:int(n_keep.value)], (int(stats[0]), int(stats[1]), int(stats[2]), float(stats[3]))
 
 
+THIN_LEVELS = 21     # octree levels 0 .. 20 of lfd_thin_footprint (csrc/lfd_thin.hpp)
+
+
+def _thin_call(fn, ctx, what, xyz, err, ref_counts, ref_rows, thin_cells, device, last_error):
+    """One lfd_thin_footprint[_host] call.  ``xyz``: (n, 3) float32 tensor on ``device``; ``err``: (n,) float32 tensor there, or None;
+    ``ref_counts``: points per reference, in the order of the cloud; ``ref_rows``: (n_refs, 5) float64 host array, per reference the third row of
+    its world-to-camera [R | t] and the tangent of one match-grid cell.  Returns ``(keep, counts, stats)``: the int64 tensor of the kept input
+    indices, ascending, on ``device``, the kept points per reference (int64 array) and ``(points per level, cells per level, longest side of the
+    bounding box)`` with two int64 arrays of THIN_LEVELS entries.  Raises ``ThinInputRefused`` for a non-finite coordinate."""
+    if not isinstance(xyz, torch.Tensor) or xyz.dtype != torch.float32 or xyz.device != device or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"{what}: xyz must be a float32 tensor of n rows x 3 on {device}")
+    n = int(xyz.shape[0])
+    if err is not None and (not isinstance(err, torch.Tensor) or err.dtype != torch.float32 or err.device != device or err.dim() != 1
+                            or int(err.shape[0]) != n):
+        raise ValueError(f"{what}: err must be None or a float32 tensor of {n} values on {device}")
+    counts = np.ascontiguousarray(np.asarray(ref_counts, np.int64).reshape(-1))
+    if counts.size < 1 or (counts < 0).any() or int(counts.sum()) != n:
+        raise ValueError(f"{what}: ref_counts must be non-negative counts, one per reference, that add up to the {n} points")
+    rows = np.ascontiguousarray(np.asarray(ref_rows, np.float64).reshape(-1, 5))
+    if rows.shape[0] != counts.size:
+        raise ValueError(f"{what}: ref_rows must hold five values per reference ({counts.size}), not {rows.shape[0]} rows")
+    xyz = xyz.contiguous()
+    err = err.contiguous() if err is not None else None
+    offs = np.zeros(counts.size + 1, np.int64)
+    np.cumsum(counts, out=offs[1:])
+    offs_out = np.zeros_like(offs)
+    keep = torch.empty((max(n, 1),), dtype=torch.int64, device=device)
+    n_keep = C.c_int64(0)
+    stats = (C.c_double * (2 * THIN_LEVELS + 1))()
+    i64p = C.POINTER(C.c_int64)
+    rc = fn(ctx, xyz.data_ptr() if n > 0 else None, err.data_ptr() if err is not None and n > 0 else None, n, offs.ctypes.data_as(i64p),
+            int(counts.size), rows.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(float(thin_cells)), keep.data_ptr() if n > 0 else None,
+            C.byref(n_keep), offs_out.ctypes.data_as(i64p), stats)
+    if rc != 0:
+        msg = last_error()
+        if "non-finite coordinate" in msg:
+            raise ThinInputRefused(f"{what} refused its input ({rc}): {msg}")
+        raise HipBackendError(f"{what} failed ({rc}): {msg}")
+    values = np.asarray(list(stats), np.float64)
+    return (keep[:int(n_keep.value)], np.diff(offs_out),
+            (values[:THIN_LEVELS].astype(np.int64), values[THIN_LEVELS:2 * THIN_LEVELS].astype(np.int64), float(values[2 * THIN_LEVELS])))
+
+
 def gaussian_pack_arguments(opacity: float, flatten: float, max_scale: float):
     """``(opacity_logit, log_flatten, max_scale)`` as lfd_pack_gaussians takes them: the f32 logit of the initial opacity and log(flatten), each
     computed once in f64."""
@@ -1463,6 +1514,7 @@ class HipDensifier:
         self.fuse_voxels = 0           # occupied voxels of the last fuse_oriented call
         self.knn_stats = (0.0, 0, 0, 0)       # (cell size, occupied cells, fullest cell, brute-forced points) of the last knn_dist2 call
         self.cap_stats = (0, 0, 0, 0.0)       # (level, cells at it, cells one level up, longest side of the box) of the last cap_spatial call
+        self.thin_stats = (np.zeros(THIN_LEVELS, np.int64), np.zeros(THIN_LEVELS, np.int64), 0.0)   # (points, cells per level, box side) of the last thin_footprint call
 
     def close(self) -> None:
         if getattr(self, "_ctx", None) is not None and self._ctx.value:
@@ -1800,6 +1852,17 @@ class HipDensifier:
             keep, self.cap_stats = _cap_call(self._lib.lfd_cap_spatial, self._ctx, "lfd_cap_spatial", xyz, err, budget, self.device,
                                              lambda: self._lib.lfd_last_error(self._ctx).decode())
         return keep
+
+    def thin_footprint(self, xyz: torch.Tensor, err: Optional[torch.Tensor], ref_counts, ref_rows, thin_cells: float):
+        """Footprint-adaptive thinning (lfd_thin_footprint): one point per cell of an octree over the cloud, every point at the
+        level whose cell is ``thin_cells`` match-grid cells of its own reference camera at its depth, each cell's point of smallest ``err``
+        (lowest index on ties and with ``err`` None).  Returns ``(keep, counts)``: the int64 device tensor of the kept input indices, ascending,
+        so ``xyz[keep]`` is the input under a mask, and the kept points per reference.  ``self.thin_stats`` then holds (points per level, cells
+        per level, longest side of the bounding box).  Synchronous.  Raises ``ThinInputRefused`` for a non-finite coordinate."""
+        with torch.cuda.stream(self.stream):
+            keep, counts, self.thin_stats = _thin_call(self._lib.lfd_thin_footprint, self._ctx, "lfd_thin_footprint", xyz, err, ref_counts, ref_rows,
+                                                       thin_cells, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
+        return keep, counts
 
     def pack_gaussians(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor, dist2: torch.Tensor, opacity: float = 0.1,
                        flatten: float = 1.0, max_scale: float = 0.0) -> torch.Tensor:
@@ -2144,6 +2207,7 @@ class HostDensifier:
         self.fuse_voxels = 0           # occupied voxels of the last fuse_oriented call
         self.knn_stats = (0.0, 0, 0, 0)       # (cell size, occupied cells, fullest cell, brute-forced points) of the last knn_dist2 call
         self.cap_stats = (0, 0, 0, 0.0)       # (level, cells at it, cells one level up, longest side of the box) of the last cap_spatial call
+        self.thin_stats = (np.zeros(THIN_LEVELS, np.int64), np.zeros(THIN_LEVELS, np.int64), 0.0)   # (points, cells per level, box side) of the last thin_footprint call
 
     close = HipDensifier.close
     __del__ = HipDensifier.__del__
@@ -2288,6 +2352,13 @@ class HostDensifier:
         keep, self.cap_stats = _cap_call(self._lib.lfd_cap_spatial_host, self._ctx, "lfd_cap_spatial_host", xyz, err, budget, self.device,
                                          lambda: self._lib.lfd_last_error(self._ctx).decode())
         return keep
+
+    def thin_footprint(self, xyz: torch.Tensor, err: Optional[torch.Tensor], ref_counts, ref_rows, thin_cells: float):
+        """HipDensifier.thin_footprint over CPU tensors (lfd_thin_footprint_host): the same indices, counts and ``thin_stats``, whatever the thread
+        count."""
+        keep, counts, self.thin_stats = _thin_call(self._lib.lfd_thin_footprint_host, self._ctx, "lfd_thin_footprint_host", xyz, err, ref_counts,
+                                                   ref_rows, thin_cells, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
+        return keep, counts
 
     def pack_gaussians(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor, dist2: torch.Tensor, opacity: float = 0.1,
                        flatten: float = 1.0, max_scale: float = 0.0) -> torch.Tensor:

@@ -166,6 +166,14 @@ EXPERIMENTAL_DEFAULTS = {
     # ... "nearer" meaning by more than this fraction of the nearer depth, in (0, 1).  The free-space filter's default and, like it, a
     # judgement, not a measurement; a surface whose depth changes by more across the window loses its far side.
     "depth_map_tol_rel": 0.02,
+    # footprint-adaptive thinning of the final cloud (lfd_thin_footprint): at most one point per cell of an octree over the cloud,
+    # where the cell a point falls into is this many match-grid cells of its OWN reference camera wide at the point's depth (rounded up to the
+    # next octree level, so up to twice that): constant density in image space instead of world space - the table at 2 units and the trees at
+    # 50 are both thinned to what their cameras resolved.  A cell keeps its point of smallest reprojection error; the kept points stay in
+    # input order with their bits.  Runs once, behind the consensus and free-space filters and the depth maps, in front of max_points, fusion,
+    # the Gaussian output and the voxel filter.  0.5 removes little more than the duplicates between references; 2 keeps about a third of a
+    # lone reference's samples.  0 = off: no new code runs and every output stays byte-identical.
+    "footprint_thin_cells": 0.0,
 }
 CAP_MODES = ("random", "spatial")
 COLOUR_MODES = ("off", "mean", "median")
@@ -536,6 +544,19 @@ class DensePipelineConfig:
             if self.exp("dense_tile_segments"):
                 return ("experimental['depth_maps_dir'] needs the cloud as arrays; dense mode with experimental['dense_tile_segments'] retires tiles "
                         "into the file's records")
+        thin = self.exp("footprint_thin_cells")
+        if isinstance(thin, (bool, np.bool_)) or not isinstance(thin, (int, float, np.integer, np.floating)) or not np.isfinite(float(thin)) or float(thin) < 0.0:
+            return ("experimental['footprint_thin_cells'] must be a finite number >= 0 (the cell of the thinning in match-grid cells of a point's own "
+                    "reference camera; 0 = off)")
+        if float(thin) > 0.0:
+            if self.stream_output:
+                return ("experimental['footprint_thin_cells'] has to see the whole cloud before anything is written; stream_output writes the file "
+                        "while the run proceeds")
+            if self.exchange_record_format() == "ply":
+                return "experimental['footprint_thin_cells'] thins f32 rows; experimental['exchange_records'] must be 'f32' with it"
+            if self.exp("dense_tile_segments"):
+                return ("experimental['footprint_thin_cells'] needs the cloud as arrays with per-reference counts; dense mode with "
+                        "experimental['dense_tile_segments'] retires tiles unordered")
         gain = self.exp("gain_compensation")
         if not isinstance(gain, str) or gain not in GAIN_MODES:
             return ("experimental['gain_compensation'] must be 'off', 'luma' (one exposure factor per image) or 'rgb' (one per image and "

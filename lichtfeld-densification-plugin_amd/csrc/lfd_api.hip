@@ -31,6 +31,7 @@
 #include "lfd_fuse.hpp"
 #include "lfd_knn.hpp"
 #include "lfd_cap.hpp"
+#include "lfd_thin.hpp"
 
 extern "C" __global__ void lfd_aggregate_kernel(LfdLaunch L, float* best_cert, uint8_t* best_slot);
 extern "C" __global__ void lfd_dense_kernel(LfdLaunch L);
@@ -114,6 +115,9 @@ extern "C" __global__ void lfd_cap_rep_kernel(const unsigned* sorted_idx, const 
                                               unsigned long long budget, unsigned long long* rep);
 extern "C" __global__ void lfd_cap_mark_kernel(const unsigned long long* rep, const unsigned* nc_p, long long n, unsigned long long budget, uint8_t* keep);
 extern "C" __global__ void lfd_cap_index_kernel(const uint8_t* keep, const unsigned* wg_kept, long long n, long long capacity, long long* keep_out);
+extern "C" __global__ void lfd_thin_keys_kernel(const float* xyz, long long n, const long long* offs, int n_refs, const double* rows, double thin_cells,
+                                                LfdCapBox box, unsigned long long* keys, unsigned* idx, unsigned* hist);
+extern "C" __global__ void lfd_thin_cells_kernel(const unsigned long long* keys, const unsigned* vstart, const unsigned* nc_p, long long n, unsigned* hist);
 extern "C" __global__ void lfd_freespace_fill_kernel(uint32_t* zbuf, long long n_words);
 extern "C" __global__ void lfd_freespace_splat_kernel(const float* xyz, long long n, const long long* offs, int n_refs, const LfdFreespaceCam* cams, int pw,
                                                       int ph, uint32_t* zbuf);
@@ -1933,6 +1937,72 @@ int lfd_cap_spatial(lfd_context* ctx, const float* xyz, const float* err, int64_
     LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, c.wg_kept + p.n_wg, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     LFD_HIP(ctx, hipStreamSynchronize(st));
     *n_keep_host = (int64_t)(unsigned)ctx->pinned_words[0];
+    return LFD_OK;
+}
+
+// ---- footprint-adaptive thinning of the final cloud (lfd_thin.hip; the representatives are the cap's kernels, the rest is the shared driver) ------------
+int lfd_thin_footprint(lfd_context* ctx, const float* xyz, const float* err, int64_t n, const int64_t* ref_offsets_host, int32_t n_refs,
+                       const double* ref_rows_host, double thin_cells, int64_t* keep_out, int64_t* n_keep_host, int64_t* ref_offsets_out_host,
+                       double* stats_host) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_thin_check(xyz, err, n, ref_offsets_host, n_refs, ref_rows_host, thin_cells, keep_out, n_keep_host, ref_offsets_out_host))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_thin_footprint: ") + why);
+    for (int32_t r = 0; r <= n_refs; ++r) ref_offsets_out_host[r] = 0;
+    *n_keep_host = 0;
+    if (stats_host)
+        for (int k = 0; k < LFD_THIN_STATS; ++k) stats_host[k] = 0.0;
+    if (n == 0) return LFD_OK;
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const CloudPlan p = cloud_plan(n);
+    CloudSort w;                                                       // counters: cell count, then points per level and cells per level
+    unsigned long long* rep = nullptr;                                 // (rank, index) minimum of every cell
+    double* rows = nullptr;                                            // the references' five values
+    CloudCompact c;
+    if (int rc = carve_cloud_ws(ctx, [&](Bump& b) {
+            w = carve_sort(b, p.n, 1 + 2 * LFD_THIN_LEVELS, true);
+            rep = b.take<unsigned long long>((size_t)n);
+            rows = b.take<double>(LFD_THIN_ROW * (size_t)n_refs);
+            c = carve_compact(b, p, n_refs);
+        }))
+        return rc;
+    unsigned *nc_dev = w.counters, *hist_dev = w.counters + 1;
+
+    // the refusal is decided before anything is sorted (the read-back of the statistics also ends the two uploads)
+    LFD_HIP(ctx, hipMemcpyAsync(c.offs, ref_offsets_host, ((size_t)n_refs + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    LFD_HIP(ctx, hipMemcpyAsync(rows, ref_rows_host, LFD_THIN_ROW * (size_t)n_refs * sizeof(double), hipMemcpyHostToDevice, st));
+    LfdVoxStats s;
+    if (int rc = cloud_stats(ctx, p, w, xyz, nullptr, s)) return rc;
+    if (s.flags & LFD_VOX_NONFINITE) return fail(ctx, LFD_ERR_INVALID, "lfd_thin_footprint: " LFD_THIN_NONFINITE);
+    const LfdCapBox box = lfd_cap_box(s.lo, s.hi);
+
+    LFD_HIP(ctx, hipMemsetAsync(hist_dev, 0, 2 * LFD_THIN_LEVELS * sizeof(unsigned), st));
+    hipLaunchKernelGGL(lfd_thin_keys_kernel, dim3(p.grid), dim3(256), 0, st, xyz, p.n, c.offs, (int)n_refs, rows, thin_cells, box, w.keys[0],
+                       w.idx[0], hist_dev);
+    const int cur = cloud_sort(st, p, w, LFD_THIN_CODE_BITS);
+    cloud_heads_count(st, p, w, cur);
+    cloud_heads_scatter(st, p, w, cur);
+    hipLaunchKernelGGL(lfd_thin_cells_kernel, dim3(p.grid), dim3(256), 0, st, w.keys[cur], w.vstart, nc_dev, p.n, hist_dev + LFD_THIN_LEVELS);
+    LFD_HIP(ctx, hipMemsetAsync(rep, 0xff, (size_t)n * sizeof(unsigned long long), st));
+    LFD_HIP(ctx, hipMemsetAsync(c.keep, 0, (size_t)n, st));
+    const unsigned long long all = (unsigned long long)n;              // a budget of n >= the cell count: lfd_cap_pick takes every cell
+    hipLaunchKernelGGL(lfd_cap_rep_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, st, w.idx[cur], w.vstart, nc_dev, err, p.n, all, rep);
+    hipLaunchKernelGGL(lfd_cap_mark_kernel, dim3(p.grid), dim3(256), 0, st, rep, nc_dev, p.n, all, c.keep);
+    cloud_compact_prefix(st, p, c);
+    hipLaunchKernelGGL(lfd_consensus_offsets_kernel, dim3((unsigned)std::min<long long>(((long long)n_refs + 256) / 256, 1024)), dim3(256), 0, st, c.offs,
+                       (int)n_refs, c.keep, c.wg_kept, c.offs_out);
+    hipLaunchKernelGGL(lfd_cap_index_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, st, c.keep, c.wg_kept, p.n, p.n, reinterpret_cast<long long*>(keep_out));
+    LFD_HIP(ctx, hipGetLastError());
+    unsigned hist[2 * LFD_THIN_LEVELS];
+    LFD_HIP(ctx, hipMemcpyAsync(hist, hist_dev, sizeof(hist), hipMemcpyDeviceToHost, st));
+    LFD_HIP(ctx, hipMemcpyAsync(ref_offsets_out_host, c.offs_out, ((size_t)n_refs + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));
+    *n_keep_host = ref_offsets_out_host[n_refs];
+    if (stats_host) {
+        for (int k = 0; k < 2 * LFD_THIN_LEVELS; ++k) stats_host[k] = (double)hist[k];
+        stats_host[2 * LFD_THIN_LEVELS] = box.L;
+    }
     return LFD_OK;
 }
 

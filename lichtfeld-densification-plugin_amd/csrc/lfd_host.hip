@@ -34,6 +34,7 @@
 #include "lfd_fuse.hpp"
 #include "lfd_knn.hpp"
 #include "lfd_cap.hpp"
+#include "lfd_thin.hpp"
 
 void lfd_fill_kernel_params(const lfd_batch* b, const lfd_params* p, LfdKernelParams& kp);   // lfd_api.hip
 
@@ -1270,6 +1271,26 @@ int lfd_cap_spatial_host(lfd_context* ctx, const float* xyz, const float* err, i
     const long long capacity = std::min<long long>(budget, n);
     for (long long i = 0; i < n; ++i)
         if (keep[(size_t)i] && kept < capacity) keep_out[kept++] = i;
+    *n_keep_host = kept;
+    return LFD_OK;
+}
+
+// The twin of lfd_thin_footprint: lfd_thin.hpp's walk - the same box, levels, codes and error ranks over a stable sort of
+// (code, index) pairs, one ordered pass, so the result does not depend on the thread count.
+int lfd_thin_footprint_host(lfd_context* ctx, const float* xyz, const float* err, int64_t n, const int64_t* ref_offsets_host, int32_t n_refs,
+                            const double* ref_rows_host, double thin_cells, int64_t* keep_out, int64_t* n_keep_host, int64_t* ref_offsets_out_host,
+                            double* stats_host) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    if (const char* why = lfd_thin_check(xyz, err, n, ref_offsets_host, n_refs, ref_rows_host, thin_cells, keep_out, n_keep_host, ref_offsets_out_host))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_thin_footprint_host: ") + why);
+    for (int32_t r = 0; r <= n_refs; ++r) ref_offsets_out_host[r] = 0;
+    *n_keep_host = 0;
+    if (stats_host)
+        for (int k = 0; k < LFD_THIN_STATS; ++k) stats_host[k] = 0.0;
+    if (n == 0) return LFD_OK;
+    const long long kept = lfd_thin_walk(xyz, err, (long long)n, ref_offsets_host, n_refs, ref_rows_host, thin_cells, keep_out, ref_offsets_out_host, stats_host);
+    if (kept < 0) return lfd_fail(ctx, LFD_ERR_INVALID, "lfd_thin_footprint_host: " LFD_THIN_NONFINITE);
     *n_keep_host = kept;
     return LFD_OK;
 }

@@ -473,6 +473,75 @@ def _apply_freespace_filter(result, config: DensePipelineConfig, camera_records,
                           clock=result._clock, loader=loader, device_normals=normals, match_grid=result.match_grid)
 
 
+def footprint_rows(camera_records, refs_local, match_grid) -> np.ndarray:
+    """(n_refs, 5) f64, one row per reference as lfd_thin_footprint takes it: the third row of its world-to-camera [R | t] and the tangent of one
+    cell of the matcher's grid (``match_grid`` = (H, W)), max(width / (fx W), height / (fy H))."""
+    grid_h, grid_w = int(match_grid[0]), int(match_grid[1])
+    rows = np.zeros((len(refs_local), 5), np.float64)
+    for i, r in enumerate(refs_local):
+        cam = camera_records[int(r)]
+        K, R, t = (np.asarray(a, np.float64) for a in (cam.K, cam.R, cam.t))
+        rows[i, :3] = R.reshape(3, 3)[2]
+        rows[i, 3] = t.reshape(3)[2]
+        rows[i, 4] = max(float(cam.width) / (K.reshape(3, 3)[0, 0] * grid_w), float(cam.height) / (K.reshape(3, 3)[1, 1] * grid_h))
+    return rows
+
+
+def _apply_footprint_thin(result, config: DensePipelineConfig, camera_records, refs_local, progress_callback=None):
+    """Footprint-adaptive thinning of the finished cloud (lfd_thin_footprint), where the points are, behind the consensus and
+    free-space filters and the depth maps, in front of the point cap, the fusion, the Gaussian output and the voxel filter.  Entry i of
+    ``result.points_per_reference`` is reference ``refs_local[i]``, whose camera is ``camera_records[refs_local[i]]``.  Returns the result with
+    the kept points (input order, same bits), their normals and their per-reference counts in place of the cloud.  Off
+    (experimental['footprint_thin_cells'] = 0): the result itself, nothing runs."""
+    thin_cells = float(config.exp("footprint_thin_cells"))
+    if thin_cells <= 0.0 or result.streamed_path is not None:
+        return result
+    from .core import hip_backend as hb
+    from .core.sinks import PipelineResult
+    import torch
+    if result.match_grid is None:
+        raise RuntimeError("experimental['footprint_thin_cells'] sizes its cells by the matcher's grid, and this result does not record one")
+    pts = result.device_points
+    if pts is None:
+        pts = tuple(torch.from_numpy(np.ascontiguousarray(a)) for a in (result.xyz, result.rgb, result.err))
+    counts = np.asarray(result.points_per_reference, np.int64)
+    n_in = int(pts[0].shape[0])
+    if int(counts.sum()) != n_in or counts.size != len(refs_local):
+        raise RuntimeError(f"experimental['footprint_thin_cells'] needs the whole cloud with its per-reference counts: this result holds {n_in:,} "
+                           f"points, the counts of {counts.size} of {len(refs_local)} references add up to {int(counts.sum()):,} (a rank of a "
+                           "gather_to_root run that is not the root)")
+    rows = footprint_rows(camera_records, refs_local, result.match_grid)
+    if progress_callback:
+        progress_callback(94.0, "Thinning by camera footprint...")
+    on_gpu = bool(pts[0].is_cuda)
+    dens = hb.HipDensifier(pts[0].device) if on_gpu else hb.HostDensifier(int(config.exp("host_threads")))
+    try:
+        keep, kept = dens.thin_footprint(pts[0], pts[2], counts, rows, thin_cells)
+        points_per_level, cells_per_level, _side = dens.thin_stats
+    except hb.HipBackendError as exc:
+        raise RuntimeError(f"experimental['footprint_thin_cells']: {exc}") from exc
+    finally:
+        dens.close()
+    new_pts = tuple(t[keep] for t in pts)               # (the index of the device route is a device tensor: it never leaves the GPU)
+    normals = _take_rows(result.device_normals, keep)
+    levels = ", ".join(f"level {l}: {int(points_per_level[l]):,} points in {int(cells_per_level[l]):,} cells" for l in np.flatnonzero(points_per_level))
+    log.info(f"Footprint thinning ({thin_cells:g} cells): {n_in:,} points in, {int(keep.shape[0]):,} kept; {levels}")
+    if on_gpu:
+        clock = result._clock
+
+        def loader(p=new_pts, clk=clock):
+            if hasattr(clk, "stage"):
+                with clk.stage("d2h"):
+                    return tuple(t.cpu().numpy() for t in p)
+            return tuple(t.cpu().numpy() for t in p)
+        arrays = (None, None, None)
+    else:
+        loader, arrays = None, tuple(t.numpy() for t in new_pts)
+    return PipelineResult(xyz=arrays[0], rgb=arrays[1], err=arrays[2], elapsed_seconds=result.elapsed_seconds, pairs_processed=result.pairs_processed,
+                          pairs_matched=result.pairs_matched, points_per_reference=kept, device_points=new_pts, streamed_path=None,
+                          clock=result._clock, loader=loader, device_normals=normals, match_grid=result.match_grid)
+
+
 class OrientedFusionRefused(RuntimeError):
     """experimental['fuse_voxel_size']: the library refused the cloud (a non-finite coordinate, a voxel key range beyond 63 bits)."""
 
@@ -739,6 +808,7 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
     result = _apply_consensus_filter(result, config, progress_callback)      # (in front of the point cap: it has to see the whole cloud)
     result = _apply_freespace_filter(result, config, records, refs_local, progress_callback)      # (behind it: what it removed cannot "see through" a surface)
     _write_depth_maps(result, config, records, progress_callback)      # (a side output of the densest filtered cloud, in front of cap, fusion and voxel filter)
+    result = _apply_footprint_thin(result, config, records, refs_local, progress_callback)      # (in front of cap, fusion, Gaussian output and voxel filter)
     if progress_callback:
         progress_callback(95.0, "Writing output...")
     if result.streamed_path == config.output_path:      # config.stream_output: the file is already complete (and no cap applies to it)
@@ -802,6 +872,7 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
         result = _apply_consensus_filter(result, config, progress_callback)  # (in front of the point cap and the voxel filter: it has to see the whole cloud)
         result = _apply_freespace_filter(result, config, records, refs_local, progress_callback)   # (behind it, in front of cap and voxel filter)
         _write_depth_maps(result, config, records, progress_callback)      # (a side output of that cloud)
+        result = _apply_footprint_thin(result, config, records, refs_local, progress_callback)   # (in front of cap, fusion, Gaussian output and voxel filter)
     except RuntimeError as exc:
         return 1, str(exc)
     if result.streamed_path == config.output_path:      # config.stream_output: the PLY is complete; neither a cap nor a voxel filter applies to it
@@ -917,6 +988,8 @@ def _experimental_from_args(args) -> dict:
         exp["freespace_depth_tol_rel"] = float(args.freespace_depth_tol_rel)
     if int(getattr(args, "freespace_plane_cells", 0)) != 0:
         exp["freespace_plane_cells"] = int(args.freespace_plane_cells)
+    if float(getattr(args, "footprint_thin_cells", 0.0) or 0.0) != 0.0:
+        exp["footprint_thin_cells"] = float(args.footprint_thin_cells)
     if str(getattr(args, "depth_maps_dir", "") or "") != "":
         exp["depth_maps_dir"] = str(args.depth_maps_dir)
     for key, cast in (("depth_map_cells", int), ("depth_map_splat_cells", int), ("depth_map_window_cells", int), ("depth_map_tol_rel", float)):
@@ -1015,6 +1088,10 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--freespace_plane_cells", type=int, default=0,
                     help="... on z-buffers of this many cells along the longer image side (8 .. 4096; 0 = automatic: ceil(sqrt(matches_per_ref)) in "
                          "sampled mode, the matcher's grid in dense mode; needs --min_freespace_violations)")
+    ap.add_argument("--footprint_thin_cells", type=float, default=0.0,
+                    help="footprint-adaptive thinning of the final cloud (DESIGN.md 4.24): at most one point per octree cell, the cell sized to this "
+                         "many match-grid cells of the point's own reference camera at its depth - constant density in image space, in front of "
+                         "--max_points, fusion, the Gaussian output and the voxel filter (0 = off)")
     ap.add_argument("--depth_maps_dir", type=str, default="",
                     help="write a depth map - and with --estimate_normals a normal map - of the filtered cloud for EVERY loaded camera into this "
                          "directory (relative: to the output file's), <image stem>.npy / <image stem>_normal.npy and depth_maps.json; the point file "
