@@ -598,6 +598,39 @@ int lfd_gain_apply(lfd_context* ctx, const float* rgb, int64_t n, const int64_t*
 int lfd_gain_apply_host(lfd_context* ctx, const float* rgb, int64_t n, const int64_t* ref_offsets, int32_t n_refs, const float* factors,
                         float* rgb_out);
 
+/* Photo-consistency gate on triangulated points (no upstream counterpart - every other gate is geometric).  The test concerns
+ * the MATCH that made a point, not X: xyz is carried along and never read.  Per input point of reference r made by winning slot s on cell
+ * (y, x) of the H x W grid (csrc/lfd_photo.hpp, exact integers, every rounding written out):
+ *   guard        kept with status 0 where the cell lies outside the grid or s >= n_slots[r] (no address is formed from the cell or the slot)
+ *   window       the cells (y + dy, x + dx), |dy|, |dx| <= window_cells (1..3), inside the grid.  A window cell PARTICIPATES iff it is live
+ *                in slot s as lfd_support_filter defines it (raw certainty > 0, the mask_b pixel its warp points at non-zero), its
+ *                observation (xb, yb) - the last two warp channels of slot s there - is finite and -1 <= xb, yb <= 1, and the reference's
+ *                mask_a pixel of the cell is non-zero
+ *   samples      reference: the four-tap f32 blend lfd_triangulate_* use, of batch->image[r] at the match pixel of the cell's reference
+ *                position (warp channels 0, 1 of a 4-channel warp, else axis_x / axis_y); neighbour: lfd_colour_multiview's sample of
+ *                nbr_image[r * k + s] at (xb, yb).  Each channel c, clamped to [0, 1] (NaN -> 0), is quantised as (uint32_t)(c * 4096.0f);
+ *                a, b: the sums of the three channels
+ *   sums         n, Sa, Sb, Saa, Sbb, Sab over the participating cells; va = n Saa - Sa Sa, vb = n Sbb - Sb Sb, cov = n Sab - Sa Sb in i64
+ *   verdict      in this order - status 1, kept: 2 n < (2 window_cells + 1)^2 + 1; status 2, kept: va < n n T or vb < n n T with the
+ *                integer T = ceil((min_texture * 12288 / 255)^2) (min_texture: a standard deviation in 8-bit grey levels); status 3, kept:
+ *                cov > 0 and (double)cov * (double)cov >= ((double)min_ncc * (double)min_ncc) * ((double)va * (double)vb); status 4, DROPPED
+ *                otherwise.  No division and no root takes part: the device and the twin agree on every decision
+ * Compaction, `in`, `out`, ref_offsets_in, ref_offsets_out (always written, stays on the device), seg_counts_out (optional), the batch
+ * preparation and the two launches behind the gate's own are lfd_support_filter's.  nbr_image and its table: as lfd_colour_multiview.
+ * status: NULL or u8 [in->capacity]; ncc: NULL or f32 [in->capacity], (float)(cov / sqrt(va vb)) for status 3 or 4 and NaN otherwise, within
+ * one f32 ulp of the twin's (the host divides and takes an IEEE root where the device refines its reciprocal instructions); both hold one
+ * value per INPUT point.  counters: NULL or device i64 [5], ADDED to: the number of points per status 0..4.  LFD_ERR_INVALID: what the two
+ * siblings refuse, window_cells outside [1, 3], min_ncc outside (0, 1], min_texture negative or not finite, a null image in a valid slot, a
+ * null batch->image[r], status / ncc / counters overlapping `in`, `out` or each other; LFD_ERR_CAPACITY: out->capacity < in->capacity.
+ * lfd_photo_gate_host: the same routine over host pointers (host images, counters: host i64 [5]) on a host context's threads, the same
+ * decisions.  A host context is served by _host only, a device context refuses _host (LFD_ERR_STATE). */
+int lfd_photo_gate(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets_in,
+                   const uint8_t* const* nbr_image, int32_t window_cells, float min_ncc, float min_texture, const lfd_points* out,
+                   int64_t* ref_offsets_out, int32_t* seg_counts_out, uint8_t* status, float* ncc, int64_t* counters);
+int lfd_photo_gate_host(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets_in,
+                        const uint8_t* const* nbr_image, int32_t window_cells, float min_ncc, float min_texture, const lfd_points* out,
+                        int64_t* ref_offsets_out, int32_t* seg_counts_out, uint8_t* status, float* ncc, int64_t* counters);
+
 /* Cross-reference consensus filter on the final cloud (no upstream counterpart - the cloud upstream writes is the plain union of what
  * every reference triangulated on its own).  The cloud is the concatenation of n_refs references' points; a point is kept iff at least min_refs
  * OTHER references own a point within `radius` of it - the fusion rule of multi-view stereo, one level above lfd_support_filter, which only sees
@@ -878,7 +911,7 @@ int lfd_host_eval_correspondence(const float* cam1, const float* cam2, float xa_
  * The per-cell arithmetic is the host build of the very source the kernels compile (csrc/lfd_geometry.hpp; IEEE
  * division / square root where the device uses the 1-ulp v_rcp / v_sqrt), spread over n_threads std::threads
  * (<= 0: all hardware threads).  A host context accepts lfd_upload_cameras, lfd_last_error, lfd_destroy and the
- * *_host calls (the three below, lfd_local_corr_host, lfd_refiner_block_host, lfd_refiner_head_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host, lfd_consensus_filter_host, lfd_freespace_filter_host, lfd_render_depth_host, lfd_fuse_oriented_host, lfd_knn_dist2_host, lfd_pack_gaussians_host and lfd_cap_spatial_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
+ * *_host calls (the three below, lfd_local_corr_host, lfd_refiner_block_host, lfd_refiner_head_host, lfd_cycle_gate_host, lfd_support_filter_host, lfd_refine_multiview_host, lfd_refine_multiview_weighted_host, lfd_depth_sigma_filter_host, lfd_consensus_filter_host, lfd_freespace_filter_host, lfd_render_depth_host, lfd_fuse_oriented_host, lfd_knn_dist2_host, lfd_pack_gaussians_host, lfd_cap_spatial_host and lfd_photo_gate_host); every device entry point refuses it with LFD_ERR_STATE, and the *_host calls refuse a device
  * context: neither side ever stands in for the other.  Semantics (orders, counts, optional outputs, LFD_ERR_CAPACITY
  * with valid counts) are those of lfd_aggregate / lfd_triangulate_dense / lfd_triangulate_indexed. */
 int lfd_create_host(int32_t n_threads, lfd_context** out);

@@ -225,6 +225,9 @@ def load_library() -> C.CDLL:
     lib.lfd_colour_multiview.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_points), C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p,
                                          C.c_void_p, C.c_void_p]
     lib.lfd_colour_multiview_host.argtypes = list(lib.lfd_colour_multiview.argtypes)
+    lib.lfd_photo_gate.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_points), C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float,
+                                   C.POINTER(lfd_points), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lfd_photo_gate_host.argtypes = list(lib.lfd_photo_gate.argtypes)
     lib.lfd_gain_accumulate.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_points), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
     lib.lfd_gain_accumulate_host.argtypes = list(lib.lfd_gain_accumulate.argtypes)
     lib.lfd_gain_apply.argtypes = [ctxp, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
@@ -291,7 +294,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_refiner_head", "lfd_refiner_head_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_colour_multiview", "lfd_colour_multiview_host", "lfd_gain_accumulate", "lfd_gain_accumulate_host", "lfd_gain_apply", "lfd_gain_apply_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_render_depth", "lfd_render_depth_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_cap_spatial", "lfd_cap_spatial_host", "lfd_thin_footprint", "lfd_thin_footprint_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_refiner_head", "lfd_refiner_head_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_colour_multiview", "lfd_photo_gate", "lfd_photo_gate_host", "lfd_colour_multiview_host", "lfd_gain_accumulate", "lfd_gain_accumulate_host", "lfd_gain_apply", "lfd_gain_apply_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_render_depth", "lfd_render_depth_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_cap_spatial", "lfd_cap_spatial_host", "lfd_thin_footprint", "lfd_thin_footprint_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -519,6 +522,8 @@ class TriangulationOutput:
     support_in: Optional[int] = None         # buffers lfd_support_filter filled: the points that reached the filter (``count`` of them were kept)
     sigma_in: Optional[int] = None           # buffers lfd_depth_sigma_filter filled: the points that reached the gate (``count`` of them were kept;
                                              # with both, the support filter kept ``sigma_in``)
+    photo_in: Optional[int] = None           # buffers lfd_photo_gate filled: the points that reached it (``count`` of them were kept; the stage in
+                                             # front of it kept ``photo_in``)
     _packed: Optional[torch.Tensor] = None   # the one float buffer xyz / rgb / err are views of
     _cap: int = 0
     normals: Optional[torch.Tensor] = None   # (n,3) f32 where the points live: what estimate_normals wrote for these points
@@ -716,18 +721,21 @@ class OutputBuffers:
         # ... [sel_info i32 x 2R+1] [pad to 8 bytes] [support_in i64]: the points that reached lfd_support_filter, written by HipDensifier.support_filter
         n_info = 2 * n_refs + 2
         # ... [sigma_in i64]: the points that reached lfd_depth_sigma_filter, written by HipDensifier.depth_sigma_filter
-        self._meta = torch.zeros((n_off + 2 * n_seg + n_info + 4,), dtype=torch.int32, device=device)
+        # ... [photo_in i64]: the points that reached lfd_photo_gate, written by HipDensifier.photo_gate
+        self._meta = torch.zeros((n_off + 2 * n_seg + n_info + 6,), dtype=torch.int32, device=device)
         self._meta[n_off + n_seg:n_off + 2 * n_seg].fill_(-1)
         self.ref_offsets = self._meta[:n_off].view(torch.int64)
         self.seg_counts = self._meta[n_off:n_off + n_seg].view(n_refs, k)
         self.seg_order = self._meta[n_off + n_seg:n_off + 2 * n_seg].view(n_refs, k)
         self.support_in = self._meta[n_off + 2 * n_seg + n_info:n_off + 2 * n_seg + n_info + 2].view(torch.int64)
-        self.sigma_in = self._meta[n_off + 2 * n_seg + n_info + 2:].view(torch.int64)
+        self.sigma_in = self._meta[n_off + 2 * n_seg + n_info + 2:n_off + 2 * n_seg + n_info + 4].view(torch.int64)
+        self.photo_in = self._meta[n_off + 2 * n_seg + n_info + 4:].view(torch.int64)
         self.normals: Optional[torch.Tensor] = None              # (cap,3) f32, allocated by the first estimate_normals over these buffers
         self.normals_valid = False                               # True: ``normals`` was written for the points the buffers hold NOW (collect
                                                                  # hands them out); whatever refills the buffers or moves their points clears it
         self.filtered = False                                    # True: these buffers are a support filter's destination (collect reports support_in)
         self.sigma_filtered = False                              # True: ... a depth-uncertainty gate's (collect reports sigma_in)
+        self.photo_filtered = False                              # True: ... a photo-consistency gate's (collect reports photo_in)
         self.sel_info = self._meta[n_off + 2 * n_seg:n_off + 2 * n_seg + 2 * n_refs + 1]           # lfd_triangulate_sampled[_multi]: {cells selected, selection status} per reference, then the launch status
         self._n_refs, self._k = n_refs, k
         self.c = lfd_points(xyz=self.xyz.data_ptr(), rgb=self.rgb.data_ptr(), err=self.err.data_ptr(),
@@ -788,7 +796,8 @@ class OutputBuffers:
             sel_status=meta[n_off + 2 * n_seg + 1:n_off + 2 * n_seg + 2 * self._n_refs:2].copy(),
             launch_status=int(meta[n_off + 2 * n_seg + 2 * self._n_refs]),
             support_in=int(meta[n_off + 2 * n_seg + 2 * self._n_refs + 2:].view(np.int64)[0]) if self.filtered else None,
-            sigma_in=int(meta[n_off + 2 * n_seg + 2 * self._n_refs + 2:].view(np.int64)[1]) if self.sigma_filtered else None, _packed=self._f,
+            sigma_in=int(meta[n_off + 2 * n_seg + 2 * self._n_refs + 2:].view(np.int64)[1]) if self.sigma_filtered else None,
+            photo_in=int(meta[n_off + 2 * n_seg + 2 * self._n_refs + 2:].view(np.int64)[2]) if self.photo_filtered else None, _packed=self._f,
             _cap=max(self.capacity, 1), normals=self.normals[:n] if (self.normals is not None and self.normals_valid) else None)
 
 
@@ -1228,6 +1237,70 @@ def _depth_sigma_call(fn, ctx, batch, src, max_rel_sigma, iso_sigma_px, refine_s
     res.seg_order = None
     res.n_selected, res.sel_status, res.launch_status = src.n_selected, src.sel_status, src.launch_status
     return rc, res, sigma, (sigma_out[:res.count] if with_sigma else None)
+
+
+PHOTO_STATUSES = 5                           # LFD_PHOTO_STATUSES of csrc/lfd_photo.hpp: guarded, sparse window, untextured, consistent, refuted
+
+
+def _photo_gate_call(fn, ctx, batch, src, window_cells, min_ncc, min_texture, with_status, with_ncc, counters, into, device):
+    """One lfd_photo_gate[_host] call.  ``src``, ``into`` and the result: as in ``_support_filter_call``.  ``counters``: None, or an int64 [5]
+    tensor on the context's device that is added to (points per status 0..4).  Returns (rc, result or None, uint8 status of the input points
+    or None, f32 ncc of the input points or None)."""
+    if not isinstance(window_cells, (int, np.integer)) or isinstance(window_cells, bool):
+        raise ValueError("photo_gate: window_cells must be an integer")
+    if batch.nbr_images is None:
+        raise ValueError("photo_gate: the batch's references carry no neighbour images (ReferenceInputs.nbr_images)")
+    collected = isinstance(src, TriangulationOutput)
+    if src.cell is None or src.slot is None:
+        raise ValueError("photo_gate: the source buffers need the cell / slot outputs (with_cell=True)")
+    if counters is not None and (counters.dtype != torch.int64 or counters.numel() != PHOTO_STATUSES or counters.device != device
+                                 or not counters.is_contiguous()):
+        raise ValueError(f"photo_gate: counters must be a contiguous int64 tensor of five elements on {device}")
+    if collected:
+        n = int(src.xyz.shape[0])
+        keep = [src.xyz.contiguous(), src.rgb.contiguous(), src.err.contiguous(), src.cell.contiguous(), src.slot.contiguous()]
+        if n == 0:                            # (an empty tensor may have no address at all; the library wants its arrays)
+            keep = [torch.zeros((1, 3) if t.dim() == 2 else (1,), dtype=t.dtype, device=t.device) for t in keep]
+        if any(t.device != device for t in keep):
+            raise ValueError(f"photo_gate: the points live on {keep[0].device}, this context computes on {device}")
+        offs_in = torch.from_numpy(np.ascontiguousarray(src.ref_offsets, np.int64)).to(device)
+        pts_in = lfd_points(xyz=keep[0].data_ptr(), rgb=keep[1].data_ptr(), err=keep[2].data_ptr(), cell=keep[3].data_ptr(), slot=keep[4].data_ptr(),
+                            capacity=n)
+        n_refs, k, cap = int(len(src.ref_offsets)) - 1, int(src.seg_counts.shape[1]), n
+    else:
+        if src.xyz.device != device:
+            raise ValueError(f"photo_gate: the points live on {src.xyz.device}, this context computes on {device}")
+        keep, offs_in, pts_in, n_refs, k, cap = [], src.ref_offsets, src.c, src._n_refs, src._k, src.capacity
+    if n_refs != batch.n_refs or k != batch.k:
+        raise ValueError(f"photo_gate: the points were made for {n_refs} references x {k} slots, the batch has {batch.n_refs} x {batch.k}")
+    dst = into if into is not None else OutputBuffers(cap, n_refs, k, device, True, True if collected else src.with_segments)
+    if dst.capacity < cap or dst._n_refs != n_refs or dst._k != k or dst.xyz.device != device:
+        raise ValueError("photo_gate: `into` must have the source's capacity, references and slots, on this context's device")
+    dst.normals_valid = False                 # (refilled: normals an earlier estimate wrote there belong to other points)
+    if not collected:
+        dst._meta.copy_(src._meta)            # group order, selection and launch status and the earlier filters' counts travel with the points
+        dst.photo_in.copy_(src.ref_offsets[-1:])
+        dst.filtered, dst.sigma_filtered, dst.photo_filtered = bool(src.filtered), bool(src.sigma_filtered), True
+    status = torch.zeros((max(cap, 1),), dtype=torch.uint8, device=device) if with_status else None
+    ncc = torch.full((max(cap, 1),), float("nan"), dtype=torch.float32, device=device) if with_ncc else None
+    rc = fn(ctx, C.byref(batch.c), C.byref(pts_in), offs_in.data_ptr(), C.cast(batch.nbr_images, C.c_void_p), int(window_cells),
+            C.c_float(float(min_ncc)), C.c_float(float(min_texture)), C.byref(dst.c), dst.ref_offsets.data_ptr(),
+            dst.seg_counts.data_ptr() if dst.with_segments else None, status.data_ptr() if with_status else None,
+            ncc.data_ptr() if with_ncc else None, counters.data_ptr() if counters is not None else None)
+    del keep
+    if rc != 0:
+        return rc, None, None, None
+    if with_status:
+        status = status[:cap]
+    if with_ncc:
+        ncc = ncc[:cap]
+    if not collected:
+        return rc, dst, status, ncc
+    res = dst.collect()
+    res.support_in, res.sigma_in, res.photo_in = src.support_in, src.sigma_in, n
+    res.seg_order = None
+    res.n_selected, res.sel_status, res.launch_status = src.n_selected, src.sel_status, src.launch_status
+    return rc, res, status, ncc
 
 
 def _consensus_call(fn, ctx, what, xyz, rgb, err, ref_counts, radius, min_refs, with_consensus, device, last_error):
@@ -1770,6 +1843,25 @@ class HipDensifier:
         self._check(rc, "lfd_depth_sigma_filter")
         return (res, sigma, sigma_out) if with_sigma else res
 
+    def photo_gate(self, batch: PreparedBatch, out_buffers, window_cells: int, min_ncc: float, min_texture: float, with_status: bool = False,
+                   with_ncc: bool = False, counters: Optional[torch.Tensor] = None, into: Optional[OutputBuffers] = None):
+        """Photo-consistency gate behind a triangulation call (lfd_photo_gate): of the points ``out_buffers`` holds for ``batch``
+        (an OutputBuffers a launch or a post-stage wrote, or a collected TriangulationOutput; with_cell=True), those whose MATCH the images do
+        not refute, compacted in order.  The test is the ZNCC of the reference's patch - the (2 ``window_cells`` + 1)^2 grid cells around the
+        point's cell - and the winning neighbour's patch where the dense warp sends those cells, sampled from ``ReferenceInputs.nbr_images``;
+        a point is dropped only where at least half the window takes part, both patches have a standard deviation of ``min_texture`` grey
+        levels (8-bit) and the ZNCC is below ``min_ncc``.  ``counters``: int64 [5] on the device, added to (points guarded, with a sparse
+        window, untextured, consistent, refuted).  Returns buffers of the same kind (asynchronous on the context's stream for OutputBuffers;
+        ``into``: the buffers to fill instead of new ones); with ``with_status`` and / or ``with_ncc`` a tuple (result[, uint8 status of every
+        INPUT point][, f32 ZNCC of every INPUT point, NaN where none was decided on])."""
+        self._same_device(batch)
+        with torch.cuda.stream(self.stream):
+            rc, res, status, ncc = _photo_gate_call(self._lib.lfd_photo_gate, self._ctx, batch, out_buffers, window_cells, min_ncc, min_texture,
+                                                    with_status, with_ncc, counters, into, self.device)
+        self._check(rc, "lfd_photo_gate")
+        extra = ((status,) if with_status else ()) + ((ncc,) if with_ncc else ())
+        return (res,) + extra if extra else res
+
     def estimate_normals(self, batch: PreparedBatch, out_buffers, radius: int, depth_step_rel: float, reproj_thresh: float,
                          with_status: bool = False, counters: Optional[torch.Tensor] = None):
         """Per-point surface normals from the resident warps (lfd_estimate_normals): for every point ``out_buffers`` holds for
@@ -2278,6 +2370,16 @@ class HostDensifier:
                                                       iso_sigma_px, refine_status, support_thresh_px, with_sigma, into, self.device)
         self._check(rc, "lfd_depth_sigma_filter_host")
         return (res, sigma, sigma_out) if with_sigma else res
+
+    def photo_gate(self, batch: PreparedBatch, out_buffers, window_cells: int, min_ncc: float, min_texture: float, with_status: bool = False,
+                   with_ncc: bool = False, counters: Optional[torch.Tensor] = None, into: Optional[OutputBuffers] = None):
+        """HipDensifier.photo_gate over CPU tensors (lfd_photo_gate_host): the same per-point routine, the same decisions."""
+        self._same_device(batch)
+        rc, res, status, ncc = _photo_gate_call(self._lib.lfd_photo_gate_host, self._ctx, batch, out_buffers, window_cells, min_ncc, min_texture,
+                                                with_status, with_ncc, counters, into, self.device)
+        self._check(rc, "lfd_photo_gate_host")
+        extra = ((status,) if with_status else ()) + ((ncc,) if with_ncc else ())
+        return (res,) + extra if extra else res
 
     def estimate_normals(self, batch: PreparedBatch, out_buffers, radius: int, depth_step_rel: float, reproj_thresh: float,
                          with_status: bool = False, counters: Optional[torch.Tensor] = None):

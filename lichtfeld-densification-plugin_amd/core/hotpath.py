@@ -38,8 +38,9 @@ def _upload_u8(a, dev) -> torch.Tensor:
 
 def _pool_kind(out: hb.OutputBuffers) -> int:
     """Which of the recycled buffers ``out`` belongs to: 0 a launch's own, 1 a support filter's destination, 2 / 3 a depth-uncertainty gate's
-    (behind no / a support filter) - ``collect`` reports the points that went into a stage only for that stage's destinations."""
-    return int(bool(out.filtered)) | (2 if getattr(out, "sigma_filtered", False) else 0)
+    (behind no / a support filter), + 4 a photo-consistency gate's - ``collect`` reports the points that went into a stage only for that
+    stage's destinations."""
+    return int(bool(out.filtered)) | (2 if getattr(out, "sigma_filtered", False) else 0) | (4 if getattr(out, "photo_filtered", False) else 0)
 
 
 class HotPath:
@@ -103,6 +104,14 @@ class HotPath:
         # per-image exposure gains (lfd_gain_accumulate): statistics where the colour stage would run; reads only
         self.gain_mode = str(config.exp("gain_compensation"))
         self.gain = self.gain_mode != "off"
+        # photo-consistency gate (lfd_photo_gate): behind the depth-uncertainty gate - it then sees the fewest points - and in
+        # front of everything that reads the survivors' colours or cells
+        self.photo_ncc = float(config.exp("min_photo_ncc"))
+        self.photo = self.photo_ncc > 0.0
+        self.photo_window = int(config.exp("photo_window_cells"))
+        self.photo_texture = float(config.exp("photo_min_texture"))
+        self._photo_counter: Optional[torch.Tensor] = None      # int64 [5] where the kernels run: points per status, added to
+        self.nbr_images = self.colour or self.gain or self.photo   # the neighbours' match-size images travel with the reference's
         self._uids = [int(c.uid) for c in cams]
         self._gain_parts: list = []                             # (table where the kernels run, reference uids, neighbour uids) per launch the run used
         on = bool(config.exp("undistort_images"))
@@ -155,6 +164,9 @@ class HotPath:
             with self.clock.stage("kernel"):
                 res = self._sigma_gated(batch, res, status)
             self._support_count(res)
+        if self.photo:
+            with self.clock.stage("kernel"):
+                res = self._photo_gated(batch, res)
         if self.colour:
             with self.clock.stage("kernel"):
                 res = self._recoloured(batch, res)
@@ -230,12 +242,14 @@ class HotPath:
         """The run's totals, from the integers a result brings along anyway (no read-back of their own)."""
         if res is None or self._support_void:
             return
-        if res.support_in is not None:             # (with the gate behind the filter, what the filter kept is what reached the gate)
+        # (what a stage kept is what reached the stage behind it: the depth gate behind the filter, the photo-consistency gate behind both)
+        behind = int(res.count if getattr(res, "photo_in", None) is None else res.photo_in)
+        if res.support_in is not None:
             self.support_in += int(res.support_in)
-            self.support_kept += int(res.count if res.sigma_in is None else res.sigma_in)
+            self.support_kept += int(behind if res.sigma_in is None else res.sigma_in)
         if res.sigma_in is not None:
             self.sigma_in += int(res.sigma_in)
-            self.sigma_kept += int(res.count)
+            self.sigma_kept += behind
 
     def sigma_totals(self) -> Tuple[int, int]:
         """(points that reached the depth-uncertainty gate, points it kept) of the run so far."""
@@ -246,6 +260,21 @@ class HotPath:
         that just ran over ``out`` on the same stream, or None: the winning slot alone placed every point."""
         return self.dens.depth_sigma_filter(batch, out, self.max_sigma, iso_sigma_px=self.iso_sigma_px, refine_status=status,
                                             support_thresh_px=self.support_thresh_px if status is not None else 0.0, into=into)
+
+    # -- photo-consistency gate (lfd_photo_gate, DESIGN.md 4.25) ---------------------------------------------------------------------------------
+    def _photo_gated(self, batch: hb.PreparedBatch, out, into=None):
+        """``out`` (buffers on the stream, or a collected result) through lfd_photo_gate: one call on the stream that made the points.  The five
+        counters stay where the kernels run until ``photo_totals``; like the re-triangulation's they count every launch issued."""
+        if self._photo_counter is None:
+            self._photo_counter = torch.zeros(hb.PHOTO_STATUSES, dtype=torch.int64, device=self.dev)
+        return self.dens.photo_gate(batch, out, self.photo_window, self.photo_ncc, self.photo_texture, counters=self._photo_counter, into=into)
+
+    def photo_totals(self) -> Tuple[int, int, int, int, int]:
+        """Points per verdict of the photo-consistency gate over the launches of the run - guarded, under half a window, untextured, consistent,
+        refuted (the dropped ones): the one read of the counters."""
+        if self._photo_counter is None:
+            return 0, 0, 0, 0, 0
+        return tuple(int(v) for v in self._photo_counter.cpu())
 
     def support_totals(self) -> Tuple[int, int]:
         """(points that reached the filter, points it dropped) of the run so far."""
@@ -270,6 +299,13 @@ class HotPath:
             into = self._take_buffers(out.capacity, out._n_refs, out._k, filtered=_pool_kind(out) | 2)
             try:
                 self._sigma_gated(batch, out, status, into=into)
+            finally:
+                self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, _pool_kind(out)), []).append(out)
+            out = into
+        if self.photo:
+            into = self._take_buffers(out.capacity, out._n_refs, out._k, filtered=_pool_kind(out) | 4)  # (the source's counts travel along)
+            try:
+                self._photo_gated(batch, out, into=into)
             finally:
                 self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, _pool_kind(out)), []).append(out)
             out = into
@@ -394,7 +430,7 @@ class HotPath:
             use_masks = d["mask_a"] is not None or any(m is not None for m in d["nbr_masks"])
             return hb.ReferenceInputs(ref_cam=packed.ref_index, nbr_cams=list(packed.nbr_indices), cert=certs, warp=warps,
                                       image=d["image"], mask_a=d["mask_a"], mask_b=list(d["nbr_masks"]) if use_masks else None,
-                                      precision=precision, nbr_images=list(d["nbr_images"]) if (self.colour or self.gain) else None)
+                                      precision=precision, nbr_images=list(d["nbr_images"]) if self.nbr_images else None)
         use_masks = packed.mask_a is not None or any(m is not None for m in packed.nbr_masks)
         mask_b = None
         with self.clock.stage("prepare"):        # the host-prepared image and masks cross to where the kernels run
@@ -403,7 +439,7 @@ class HotPath:
             image = _upload_u8(packed.image, dev)
             mask_a = _upload_u8(packed.mask_a, dev) if packed.mask_a is not None else None
             # (multi-view colour: the neighbours' match-size images cross beside the reference's)
-            nbr_images = [_upload_u8(im, dev) for im in packed.nbr_images] if (self.colour or self.gain) else None
+            nbr_images = [_upload_u8(im, dev) for im in packed.nbr_images] if self.nbr_images else None
         return hb.ReferenceInputs(ref_cam=packed.ref_index, nbr_cams=list(packed.nbr_indices), cert=certs, warp=warps, image=image,
                                   mask_a=mask_a, mask_b=mask_b, precision=precision, nbr_images=nbr_images)
 
@@ -697,7 +733,7 @@ class HotPath:
             if bool(self.config.exp("dense_tile_segments")):
                 # unordered retirement (no look-back), raster order restored from the tile table: the same result, bit for bit
                 return self.dens.order_segments(self.dens.triangulate_dense_segments(batch, self.params))
-            if (self.min_support > 0 or self.refine or self.max_sigma > 0.0 or self.colour or self.gain or self.normals) and not self.on_host:
+            if (self.min_support > 0 or self.refine or self.max_sigma > 0.0 or self.photo or self.colour or self.gain or self.normals) and not self.on_host:
                 # the launch, the filter, the re-triangulation and / or the gate behind it on the same stream, then the one read-back of the offsets
                 cap = batch.n_refs * batch.H * batch.W
                 out = hb.OutputBuffers(cap, batch.n_refs, batch.k, self.dev)
@@ -709,6 +745,8 @@ class HotPath:
                     out, status = self._refined(batch, out, self.max_sigma > 0.0)
                 if self.max_sigma > 0.0:
                     out = self._sigma_gated(batch, out, status)
+                if self.photo:
+                    out = self._photo_gated(batch, out)
                 if self.colour:
                     out = self._recoloured(batch, out)
                 if self.gain:

@@ -246,6 +246,9 @@ def run_dense_pipeline(
     if world > 1 and str(config.exp("multiview_colour")) != "off":
         raise ValueError("experimental['multiview_colour'] cannot run sharded over several GPUs: like the normals it is a stage of the single-GPU "
                          "run, and the sharded schedules have not been taken through it")
+    if world > 1 and float(config.exp("min_photo_ncc")) > 0.0:
+        raise ValueError("experimental['min_photo_ncc'] cannot run sharded over several GPUs: like the multi-view colour it is a stage of the "
+                         "single-GPU run, and the sharded schedules have not been taken through it")
     if world > 1 and str(config.exp("gain_compensation")) != "off":
         raise ValueError("experimental['gain_compensation'] cannot run sharded over several GPUs: like the multi-view colour it is a stage of the "
                          "single-GPU run, and the exchange of a sharded run does not carry the statistics")
@@ -365,6 +368,11 @@ def run_dense_pipeline(
             n_in, n_kept = hot.sigma_totals()
             noise = f"isotropic match noise {hot.iso_sigma_px:g} px" if hot.iso_sigma_px > 0.0 else "the matcher's precision planes"
             log.info(f"Depth-uncertainty gate: relative depth sigma at most {hot.max_sigma:g} ({noise}), {n_in} points in, {n_kept} kept")
+        if hot.photo:
+            n_guard, n_sparse, n_flat, n_ok, n_refuted = hot.photo_totals()
+            log.info(f"Photo-consistency gate: ZNCC at least {hot.photo_ncc:g} over {2 * hot.photo_window + 1} x {2 * hot.photo_window + 1} cells, "
+                     f"texture floor {hot.photo_texture:g} grey levels: {n_guard} points guarded, {n_sparse} with under half a window, {n_flat} "
+                     f"untextured, {n_ok} consistent, {n_refuted} refuted and dropped")
         if hot.colour:
             n_col, n_views = hot.colour_totals()
             log.info(f"Multi-view colour: {hot.colour_mode} over the confirming views (within {hot.support_thresh_px:g} px), {n_col} points blended, "

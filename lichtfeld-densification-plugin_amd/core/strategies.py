@@ -332,6 +332,7 @@ class DenseBatcher:
         n = int(self.config.refs_per_launch)
         if self.auto_group:               # 33 bytes per cell: xyz, rgb, err + the cell and slot columns of the C-ABI (once more with the support filter's copy)
             copies = 1 + (int(self.config.exp("min_support_views")) > 0) + (float(self.config.exp("max_depth_sigma_rel")) > 0.0)     # (... and the gate's)
+            copies += float(self.config.exp("min_photo_ncc")) > 0.0     # (... and the photo-consistency gate's)
             n = bounded_group(n, m.H * m.W, 33 * copies, 0)
         if len(self.pending) >= n:
             self.drain()

@@ -149,6 +149,18 @@ EXPERIMENTAL_DEFAULTS = {
     # and every point's colour is multiplied by its reference's factor: the cloud comes out at one exposure, and <output>.gains.json lists the
     # factors.  Rewrites rgb only, once, in front of the consensus filter.  "off" = no new code runs and every output stays byte-identical.
     "gain_compensation": "off",
+    # photo-consistency gate behind triangulation (lfd_photo_gate): the one gate that looks at the pixels.  A point is dropped
+    # when the zero-mean normalised cross-correlation of the two patches its match joins - the reference's around the point's cell, the winning
+    # neighbour's where the dense warp sends those cells - is below this, provided at least half the window takes part and both patches are
+    # textured.  Refutes gross mismatches of a few match pixels on textured surfaces (a match that slid along its epipolar line passes every
+    # geometric gate); it does not refute sub-pixel error.  Behind the depth-uncertainty gate, in front of colour, gains and normals.
+    # In (0, 1]; 0.0 = off: no new code runs and every output stays byte-identical.
+    "min_photo_ncc": 0.0,
+    # ... over the (2 r + 1)^2 window of this radius, 1 .. 3 grid cells.  Refused with the gate off unless left at the default.
+    "photo_window_cells": 2,
+    # ... a patch whose standard deviation is below this many 8-bit grey levels is no evidence either way: the point is kept.  >= 0.  A design
+    # default, not a measurement.  Refused with the gate off unless left at the default.
+    "photo_min_texture": 2.0,
     # per-camera depth and normal maps rendered from the final cloud (lfd_render_depth): a directory - relative to the output
     # file's own - that receives <image stem>.npy (f32 (ph, pw): depth along the camera's z axis in scene units, 0 = no data), with
     # estimate_normals <image stem>_normal.npy (f32 (ph, pw, 3): world frame, the PLY's normals, 0 0 0 = no data) and depth_maps.json, for EVERY
@@ -513,6 +525,36 @@ class DensePipelineConfig:
                 return "experimental['multiview_colour'] needs the ordered dense result; experimental['dense_tile_segments'] retires tiles unordered"
             if self.exchange_record_format() == "ply":
                 return "experimental['multiview_colour'] rewrites f32 rows; experimental['exchange_records'] must be 'f32' with it"
+        try:
+            photo_ncc = float(self.exp("min_photo_ncc"))
+        except (TypeError, ValueError):
+            return "experimental['min_photo_ncc'] must be a number (the ZNCC below which a match is refuted, in (0, 1]; 0 = off)"
+        if not (0.0 <= photo_ncc <= 1.0):
+            return "experimental['min_photo_ncc'] must be 0 (off) or in (0, 1] (the ZNCC below which a match is refuted)"
+        photo_r = self.exp("photo_window_cells")
+        if isinstance(photo_r, (bool, np.bool_)) or not isinstance(photo_r, (int, np.integer)) or not 1 <= int(photo_r) <= 3:
+            return "experimental['photo_window_cells'] must be an integer in 1 .. 3 (radius of the photo-consistency window in grid cells)"
+        try:
+            photo_tex = float(self.exp("photo_min_texture"))
+        except (TypeError, ValueError):
+            return "experimental['photo_min_texture'] must be a number (standard deviation in 8-bit grey levels below which a patch is no evidence)"
+        if not (0.0 <= photo_tex < float("inf")):
+            return "experimental['photo_min_texture'] must be finite and >= 0 (standard deviation in 8-bit grey levels below which a patch is no evidence)"
+        if not photo_ncc > 0.0:
+            if int(photo_r) != int(EXPERIMENTAL_DEFAULTS["photo_window_cells"]):
+                return "experimental['photo_window_cells'] is the window of the photo-consistency gate: it needs experimental['min_photo_ncc'] > 0"
+            if photo_tex != float(EXPERIMENTAL_DEFAULTS["photo_min_texture"]):
+                return "experimental['photo_min_texture'] is the texture floor of the photo-consistency gate: it needs experimental['min_photo_ncc'] > 0"
+        else:
+            if self.no_filter:
+                return "experimental['min_photo_ncc'] is a filter: it cannot run with no_filter"
+            if self.stream_output:
+                return ("experimental['min_photo_ncc'] filters points held as arrays (xyz, rgb, cell, slot); stream_output writes 15-byte records "
+                        "while the run proceeds")
+            if self.exp("dense_tile_segments"):
+                return "experimental['min_photo_ncc'] needs the ordered dense result; experimental['dense_tile_segments'] retires tiles unordered"
+            if self.exchange_record_format() == "ply":
+                return "experimental['min_photo_ncc'] filters f32 rows; experimental['exchange_records'] must be 'f32' with it"
         maps_dir = self.exp("depth_maps_dir")
         if not isinstance(maps_dir, str):
             return "experimental['depth_maps_dir'] must be a string (a directory for the per-camera depth maps; '' = off)"

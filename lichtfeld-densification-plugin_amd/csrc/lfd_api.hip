@@ -22,6 +22,7 @@
 #include "lfd_refine.hpp"
 #include "lfd_normals.hpp"
 #include "lfd_colour.hpp"
+#include "lfd_photo.hpp"
 #include "lfd_gain.hpp"
 #include "lfd_sigma.hpp"
 #include "lfd_consensus.hpp"
@@ -138,6 +139,7 @@ hipError_t lfd_refine_launch(const LfdRefineArgs& p, hipStream_t stream);     //
 hipError_t lfd_sigma_launch(const LfdSigmaArgs& p, hipStream_t stream);       // lfd_sigma.hip
 hipError_t lfd_normals_launch(const LfdNormalArgs& p, hipStream_t stream);    // lfd_normals.hip
 hipError_t lfd_colour_launch(const LfdColourArgs& p, hipStream_t stream);     // lfd_colour.hip
+hipError_t lfd_photo_launch(const LfdPhotoArgs& p, const LfdSupportArgs& sup, hipStream_t stream);   // lfd_photo.hip
 hipError_t lfd_gain_launch(const LfdGainArgs& p, hipStream_t stream);         // lfd_gain.hip
 hipError_t lfd_gain_apply_launch(const LfdGainApplyArgs& p, hipStream_t stream);
 extern "C" __global__ void lfd_pack_ply_normals_kernel(const float* xyz, const float* normals, const float* rgb, long long n, unsigned char* out);
@@ -2310,6 +2312,55 @@ int lfd_gain_apply(lfd_context* ctx, const float* rgb, int64_t n, const int64_t*
     p.offs = reinterpret_cast<const long long*>(ref_offsets);
     p.factors = factors; p.rgb = rgb; p.o_rgb = rgb_out; p.n = n; p.n_refs = n_refs;
     LFD_HIP(ctx, lfd_gain_apply_launch(p, ctx->stream));
+    return LFD_OK;
+}
+
+// ---- photo-consistency gate (lfd_photo.hip) -----------------------------------------------------------------------------------------------------
+int lfd_photo_gate(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets_in,
+                   const uint8_t* const* nbr_image, int32_t window_cells, float min_ncc, float min_texture, const lfd_points* out,
+                   int64_t* ref_offsets_out, int32_t* seg_counts_out, uint8_t* status, float* ncc, int64_t* counters) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    int code = LFD_ERR_INVALID;
+    if (const char* why = lfd_photo_check(in, ref_offsets_in, nbr_image, window_cells, min_ncc, min_texture, out, ref_offsets_out, status, ncc,
+                                          counters, &code))
+        return fail(ctx, code, std::string("lfd_photo_gate: ") + why);
+    LfdLaunch L;
+    int rc = batch_launch(ctx, batch, L);
+    if (rc != LFD_OK) return rc;
+    if (const char* why = lfd_colour_check_images(batch, nbr_image)) return fail(ctx, LFD_ERR_INVALID, std::string("lfd_photo_gate: ") + why);
+    LfdPhotoArgs p;
+    std::memset(&p, 0, sizeof(p));
+    // (the image table is the colour stage's: the cache compares content, and the stages of one configuration hand over the same images)
+    rc = upload_pointer_table(ctx, ctx->colour_img, batch, reinterpret_cast<const void* const*>(nbr_image),
+                              reinterpret_cast<const void* const**>(&p.img));
+    if (rc != LFD_OK) return rc;
+    p.n_wg = (int32_t)((in->capacity + 255) / 256);
+    const size_t keep_bytes = ((size_t)p.n_wg * 256 + 255) & ~size_t(255);   // the support filter's layout: its counts are the keep bytes
+    rc = ensure(ctx, ctx->support_ws, keep_bytes + ((size_t)p.n_wg + 1) * sizeof(unsigned));
+    if (rc != LFD_OK) return rc;
+    p.refs = L.refs; p.slots = L.slots; p.axis_x = L.axis_x; p.axis_y = L.axis_y;
+    p.offs_in = reinterpret_cast<const long long*>(ref_offsets_in);
+    p.cell = in->cell; p.slot = in->slot;
+    p.seg_counts = seg_counts_out; p.status = status; p.ncc = ncc;
+    p.counters = reinterpret_cast<unsigned long long*>(counters);
+    p.keep = static_cast<uint8_t*>(ctx->support_ws.ptr);
+    p.wg_kept = reinterpret_cast<unsigned*>(static_cast<unsigned char*>(ctx->support_ws.ptr) + keep_bytes);
+    p.capacity = in->capacity;
+    p.n_refs = batch->n_refs; p.k = batch->k; p.radius = window_cells;
+    p.th = lfd_photo_thresholds(min_ncc, min_texture);
+    p.g = launch_geom(batch, L, 0.0f, 0.0f);
+    LfdSupportArgs q;
+    std::memset(&q, 0, sizeof(q));
+    q.offs_in = p.offs_in;
+    q.xyz = in->xyz; q.rgb = in->rgb; q.err = in->err; q.cell = in->cell; q.slot = in->slot;
+    q.o_xyz = out->xyz; q.o_rgb = out->rgb; q.o_err = out->err; q.o_cell = out->cell; q.o_slot = out->slot;
+    q.offs_out = reinterpret_cast<long long*>(ref_offsets_out);
+    q.counts = p.keep; q.wg_kept = p.wg_kept;
+    q.capacity = in->capacity;
+    q.n_refs = batch->n_refs; q.k = batch->k; q.min_support = 1; q.n_wg = p.n_wg;
+    if (seg_counts_out) LFD_HIP(ctx, hipMemsetAsync(seg_counts_out, 0, sizeof(int32_t) * (size_t)batch->n_refs * batch->k, ctx->stream));
+    LFD_HIP(ctx, lfd_photo_launch(p, q, ctx->stream));
     return LFD_OK;
 }
 

@@ -26,6 +26,7 @@
 #include "lfd_sigma.hpp"
 #include "lfd_normals.hpp"
 #include "lfd_colour.hpp"
+#include "lfd_photo.hpp"
 #include "lfd_gain.hpp"
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
@@ -255,6 +256,30 @@ int check_host_points(lfd_context* ctx, const lfd_points* out, const int64_t* re
 
 constexpr int kChunk = 4096;     // cells per work item
 
+// The stable compaction behind a per-point verdict (the support filter's, the photo-consistency gate's): the points i < total with kept(i), in
+// the input order inside and across references; ref_offsets_out and the optional per-(reference, winning slot) counts with them.
+template <class Kept>
+void compact_points(const lfd_batch* b, const lfd_points* in, const long long* offs, long long cap, long long total, Kept kept,
+                    const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out) {
+    if (seg_counts_out) std::memset(seg_counts_out, 0, sizeof(int32_t) * (size_t)b->n_refs * b->k);
+    long long o = 0;
+    int r_next = 0;
+    for (long long i = 0; i <= total; ++i) {
+        while (r_next <= b->n_refs && std::min(lfd_support_clamp(offs[r_next], cap), total) <= i) ref_offsets_out[r_next++] = o;
+        if (i == total || !kept(i)) continue;
+        for (int e = 0; e < 3; ++e) { out->xyz[3 * o + e] = in->xyz[3 * i + e]; out->rgb[3 * o + e] = in->rgb[3 * i + e]; }
+        out->err[o] = in->err[i];
+        if (out->cell) out->cell[o] = in->cell[i];
+        if (out->slot) out->slot[o] = in->slot[i];
+        if (seg_counts_out) {
+            const int r = lfd_support_ref_of(offs, b->n_refs, cap, i), s = (int)in->slot[i];
+            if (s < b->n_slots[r]) seg_counts_out[(size_t)r * b->k + s] += 1;
+        }
+        ++o;
+    }
+    while (r_next <= b->n_refs) ref_offsets_out[r_next++] = o;       // (offsets that do not ascend: whatever is left counts from the end)
+}
+
 }  // namespace
 
 extern "C" {
@@ -440,24 +465,8 @@ int lfd_support_filter_host(lfd_context* ctx, const lfd_batch* b, const lfd_poin
             if (support) support[i] = (uint8_t)n;
         }
     });
-    // stable compaction: the input order inside and across references
-    if (seg_counts_out) std::memset(seg_counts_out, 0, sizeof(int32_t) * (size_t)b->n_refs * b->k);
-    long long o = 0;
-    int r_next = 0;
-    for (long long i = 0; i <= total; ++i) {
-        while (r_next <= b->n_refs && std::min(lfd_support_clamp(offs[r_next], cap), total) <= i) ref_offsets_out[r_next++] = o;
-        if (i == total || (int)counts[(size_t)i] < min_support) continue;
-        for (int e = 0; e < 3; ++e) { out->xyz[3 * o + e] = in->xyz[3 * i + e]; out->rgb[3 * o + e] = in->rgb[3 * i + e]; }
-        out->err[o] = in->err[i];
-        if (out->cell) out->cell[o] = in->cell[i];
-        if (out->slot) out->slot[o] = in->slot[i];
-        if (seg_counts_out) {
-            const int r = lfd_support_ref_of(offs, b->n_refs, cap, i), s = (int)in->slot[i];
-            if (s < b->n_slots[r]) seg_counts_out[(size_t)r * b->k + s] += 1;
-        }
-        ++o;
-    }
-    while (r_next <= b->n_refs) ref_offsets_out[r_next++] = o;       // (offsets that do not ascend: whatever is left counts from the end)
+    compact_points(b, in, offs, cap, total, [&](long long i) { return (int)counts[(size_t)i] >= min_support; }, out, ref_offsets_out,
+                   seg_counts_out);
     return LFD_OK;
 }
 
@@ -748,6 +757,58 @@ int lfd_gain_apply_host(lfd_context* ctx, const float* rgb, int64_t n, const int
             }
         }
     });
+    return LFD_OK;
+}
+
+// The twin of lfd_photo_gate: lfd_photo_point per point over host pointers on the context's threads, then the support filter's
+// stable compaction.
+int lfd_photo_gate_host(lfd_context* ctx, const lfd_batch* b, const lfd_points* in, const int64_t* ref_offsets_in,
+                        const uint8_t* const* nbr_image, int32_t window_cells, float min_ncc, float min_texture, const lfd_points* out,
+                        int64_t* ref_offsets_out, int32_t* seg_counts_out, uint8_t* status, float* ncc, int64_t* counters) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    int code = LFD_ERR_INVALID;
+    if (const char* why = lfd_photo_check(in, ref_offsets_in, nbr_image, window_cells, min_ncc, min_texture, out, ref_offsets_out, status, ncc,
+                                          counters, &code))
+        return lfd_fail(ctx, code, std::string("lfd_photo_gate_host: ") + why);
+    lfd_params none;
+    std::memset(&none, 0, sizeof(none));
+    int rc = validate_host(ctx, b, &none);
+    if (rc != LFD_OK) return rc;
+    if (const char* why = lfd_colour_check_images(b, nbr_image)) return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_photo_gate_host: ") + why);
+    HostLaunch L;
+    prepare_host(b, &none, L);
+    std::vector<LfdPhotoSlot> slot((size_t)b->n_refs * LFD_MAX_SLOTS);
+    for (int r = 0; r < b->n_refs; ++r)
+        for (int j = 0; j < b->n_slots[r]; ++j) {
+            const size_t sj = (size_t)r * b->k + j;
+            slot[(size_t)r * LFD_MAX_SLOTS + j] = {b->cert[sj], b->warp[sj], b->mask_b ? b->mask_b[sj] : nullptr, nbr_image[sj]};
+        }
+    const LfdSupportGeom g = make_geom(L, 0.0f, 0.0f);
+    const LfdPhotoThresh th = lfd_photo_thresholds(min_ncc, min_texture);
+    const long long cap = in->capacity;
+    const long long* offs = reinterpret_cast<const long long*>(ref_offsets_in);
+    const long long total = lfd_support_clamp(offs[b->n_refs], cap);
+    const int n_chunks = (int)((total + kChunk - 1) / kChunk);
+    std::vector<uint8_t> st((size_t)total);
+    std::vector<long long> count((size_t)n_chunks * LFD_PHOTO_STATUSES, 0);
+    parallel_chunks(ctx, n_chunks, [&](int c) {
+        const long long i1 = std::min<long long>(total, (long long)(c + 1) * kChunk);
+        for (long long i = (long long)c * kChunk; i < i1; ++i) {
+            const int r = lfd_support_ref_of(offs, b->n_refs, cap, i);
+            float v;
+            const unsigned s = lfd_photo_point(&slot[(size_t)r * LFD_MAX_SLOTS], b->n_slots[r], b->image[r], b->mask_a ? b->mask_a[r] : nullptr,
+                                               L.ax, L.ay, g, window_cells, th, in->cell[i], (int)in->slot[i], &v);
+            st[(size_t)i] = (uint8_t)s;
+            if (status) status[i] = (uint8_t)s;
+            if (ncc) ncc[i] = v;
+            ++count[(size_t)c * LFD_PHOTO_STATUSES + s];
+        }
+    });
+    if (counters)
+        for (int c = 0; c < n_chunks; ++c)
+            for (int e = 0; e < LFD_PHOTO_STATUSES; ++e) counters[e] += count[(size_t)c * LFD_PHOTO_STATUSES + e];
+    compact_points(b, in, offs, cap, total, [&](long long i) { return st[(size_t)i] != LFD_PHOTO_REFUTED; }, out, ref_offsets_out, seg_counts_out);
     return LFD_OK;
 }
 

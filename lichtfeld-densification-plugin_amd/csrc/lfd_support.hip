@@ -155,6 +155,19 @@ __global__ void __launch_bounds__(256) lfd_support_scatter_kernel(const LfdSuppo
     if (p.o_slot) p.o_slot[o] = p.slot[i];
 }
 
+// The compaction behind a per-point verdict: scan, then scatter, of the points whose byte in p.counts is >= p.min_support.  The support filter's
+// own tail, and the photo-consistency gate's (lfd_photo.hip: a keep byte against a min_support of 1).
+hipError_t lfd_support_compact_launch(const LfdSupportArgs& p, hipStream_t stream) {
+    hipLaunchKernelGGL(lfd_support_scan_kernel, dim3(1), dim3(1024), 0, stream, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (p.n_wg > 0) {
+        hipLaunchKernelGGL(lfd_support_scatter_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, stream, p);
+        e = hipGetLastError();
+    }
+    return e;
+}
+
 // lfd_api.hip's lfd_support_filter: the arguments were validated there (capacity <= 2^31 - 1: at most 2^23 workgroups)
 hipError_t lfd_support_launch(const LfdSupportArgs& p, hipStream_t stream) {
     if (p.n_wg > 0) {
@@ -165,12 +178,5 @@ hipError_t lfd_support_launch(const LfdSupportArgs& p, hipStream_t stream) {
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(lfd_support_scan_kernel, dim3(1), dim3(1024), 0, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (p.n_wg > 0) {
-        hipLaunchKernelGGL(lfd_support_scatter_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, stream, p);
-        e = hipGetLastError();
-    }
-    return e;
+    return lfd_support_compact_launch(p, stream);
 }

@@ -1005,6 +1005,11 @@ def _experimental_from_args(args) -> dict:
         exp["multiview_colour"] = str(args.multiview_colour)
     if str(getattr(args, "gain_compensation", None) or "off") != "off":
         exp["gain_compensation"] = str(args.gain_compensation)
+    if float(getattr(args, "min_photo_ncc", 0.0) or 0.0) != 0.0:
+        exp["min_photo_ncc"] = float(args.min_photo_ncc)
+    for key, cast in (("photo_window_cells", int), ("photo_min_texture", float)):
+        if getattr(args, key, None) is not None:
+            exp[key] = cast(getattr(args, key))
     if bool(getattr(args, "estimate_normals", False)):
         exp["estimate_normals"] = True
     if getattr(args, "normal_radius_cells", None) is not None:
@@ -1122,6 +1127,14 @@ def build_argparser() -> argparse.ArgumentParser:
                     help="bring the whole cloud to one exposure: solve one factor per image (luma) or per image and channel (rgb) from the "
                          "colours the confirming views have at the same points, multiply every point's colour by its reference's factor and "
                          "write <out_name>.gains.json")
+    ap.add_argument("--min_photo_ncc", type=float, default=0.0,
+                    help="photo-consistency gate: drop a triangulated point when the normalised cross-correlation of the two image patches its "
+                         "match joins is below this (e.g. 0.8; in (0, 1], 0 = off).  Refutes mismatches of a few match pixels on textured "
+                         "surfaces, not sub-pixel error")
+    ap.add_argument("--photo_window_cells", type=int, default=None,
+                    help="... over the (2 r + 1)^2 grid cells of this radius around the point's cell (1 .. 3; default 2)")
+    ap.add_argument("--photo_min_texture", type=float, default=None,
+                    help="... keeping points whose patches have a standard deviation below this many 8-bit grey levels (no evidence; default 2)")
     ap.add_argument("--estimate_normals", action="store_true",
                     help="give every point a unit surface normal, fitted to its winning neighbour's warp around its grid cell and oriented towards "
                          "its reference's camera: the PLY then has x y z nx ny nz red green blue vertices (needs a .ply --out_name)")
