@@ -598,6 +598,51 @@ int lfd_gain_apply(lfd_context* ctx, const float* rgb, int64_t n, const int64_t*
 int lfd_gain_apply_host(lfd_context* ctx, const float* rgb, int64_t n, const int64_t* ref_offsets, int32_t n_refs, const float* factors,
                         float* rgb_out);
 
+/* Far-field shell, the statistics (no upstream counterpart).  Reads the batch only; independent of the point stages.  Per grid cell
+ * c of reference r (csrc/lfd_far.hpp, every rounding written out):
+ *   d        the f32 world direction of the cell's ray: M (u, v, 1), M = R^T K^-1 of the reference's camera as forward fused chains, (u, v) the
+ *            cell's A-coordinate in camera px - warp channels 0 / 1 of slot 0 with four-channel warps, axis_x / axis_y (or the matcher's grid)
+ *            with two;
+ *   slot s < n_slots[r] is CONFIDENT iff its raw certainty is >= far_certainty (a NaN is not), its observation lies inside the neighbour's grid
+ *            (lfd_grid_nearest >= 0 on both axes) and mask_b, where present, is set at the pixel the support filter looks at; it AGREES with
+ *            infinity iff lfd_support_filter's comparison, with the homogeneous point (d, 0) in place of (X, 1), holds at far_thresh_px [px of
+ *            the neighbour's camera image]: pz > 0 and d2 <= (tau pz)^2, a NaN anywhere rejects;
+ *   the cell is FAR iff mask_a, where present, is set at the cell, n_conf >= min(far_min_views, n_slots[r]), n_agree == n_conf, and d is finite
+ *            and not zero.
+ * A far cell adds to row `key` of table, u64 [6 S S][7], S = shell_cells: in f64 with IEEE division and root, face = 2 m + (d_m < 0), m the
+ * index of the largest |d_i| (lowest on ties); (u, v) the two other components, ascending, over |d_m|; cell = floor((u + 1) / 2 S) clamped to
+ * [0, S - 1]; key = (face S + cell_v) S + cell_u.  Columns 0..2 += rint(d_i / |d| 2^30) as i64 (two's complement), 3..5 += the reference image's
+ * colour at the cell (the dense kernel's f32 four-tap blend, quantised as the writers do), 6 += 1.  counters: NULL or i64 [n_refs], far cells per
+ * reference.  Both are ADDED to, never cleared; integer additions only (no-return 64-bit atomics behind a reduction over runs of equal keys
+ * inside a wave), so the content does not depend on launch geometry and the device and the twin agree on every element.  A column overflows
+ * after 2^33 samples in one direction cell.  One launch on the context's stream, asynchronous.  LFD_ERR_INVALID: a null table, far_thresh_px or
+ * far_certainty not finite or <= 0, far_min_views outside [1, 8], shell_cells outside [8, 512], a table or counters overlapping the batch's
+ * planes or each other, more than 65535 references.  lfd_far_accumulate_host: the same routines over host pointers on a host context's threads.
+ * A host context is served by _host only, a device context refuses _host (LFD_ERR_STATE). */
+int lfd_far_accumulate(lfd_context* ctx, const lfd_batch* batch, float far_thresh_px, float far_certainty, int32_t far_min_views,
+                       int32_t shell_cells, uint64_t* table, int64_t* counters);
+int lfd_far_accumulate_host(lfd_context* ctx, const lfd_batch* batch, float far_thresh_px, float far_certainty, int32_t far_min_views,
+                            int32_t shell_cells, uint64_t* table, int64_t* counters);
+
+/* lfd_far_accumulate that also reports WHICH cells were far: flags, u8 [n_refs * H * W] where the context computes (NULL: lfd_far_accumulate
+ * itself), is written - not added to - 1 at [r * H * W + cell] for every far cell and 0 elsewhere.  It must overlap neither the table, the
+ * counters nor the batch (LFD_ERR_INVALID).  What the driver counts the far cells that also produced a point with. */
+int lfd_far_accumulate_flags(lfd_context* ctx, const lfd_batch* batch, float far_thresh_px, float far_certainty, int32_t far_min_views,
+                             int32_t shell_cells, uint64_t* table, int64_t* counters, uint8_t* flags);
+int lfd_far_accumulate_flags_host(lfd_context* ctx, const lfd_batch* batch, float far_thresh_px, float far_certainty, int32_t far_min_views,
+                                  int32_t shell_cells, uint64_t* table, int64_t* counters, uint8_t* flags);
+
+/* Far-field shell, the points.  The direction cells of `table` with count >= min_samples and a non-zero direction sum, in key
+ * order; per cell in f64: d_hat = sum / |sum|, xyz = (float)(centre + radius d_hat), rgb = (float)(sum_c / (255 count)), normal = (float)(-d_hat)
+ * (NULL: not written), samples = count saturated to i32 (NULL: not written).  table and the outputs where the context computes; centre (f64 [3],
+ * finite) and n_out on the host.  Synchronous.  *n_out is the number of cells that qualify; at most `capacity` records are written, and
+ * LFD_ERR_CAPACITY is returned when there are more.  LFD_ERR_INVALID: a null required pointer, shell_cells outside [8, 512], min_samples < 1,
+ * radius not finite or <= 0, capacity outside [0, 2^31 - 1], outputs overlapping the table or each other. */
+int lfd_far_emit(lfd_context* ctx, const uint64_t* table, int32_t shell_cells, int64_t min_samples, const double* centre, double radius,
+                 float* xyz, float* rgb, float* normal, int32_t* samples, int64_t capacity, int64_t* n_out);
+int lfd_far_emit_host(lfd_context* ctx, const uint64_t* table, int32_t shell_cells, int64_t min_samples, const double* centre, double radius,
+                      float* xyz, float* rgb, float* normal, int32_t* samples, int64_t capacity, int64_t* n_out);
+
 /* Photo-consistency gate on triangulated points (no upstream counterpart - every other gate is geometric).  The test concerns
  * the MATCH that made a point, not X: xyz is carried along and never read.  Per input point of reference r made by winning slot s on cell
  * (y, x) of the H x W grid (csrc/lfd_photo.hpp, exact integers, every rounding written out):

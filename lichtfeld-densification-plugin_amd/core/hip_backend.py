@@ -232,6 +232,13 @@ def load_library() -> C.CDLL:
     lib.lfd_gain_accumulate_host.argtypes = list(lib.lfd_gain_accumulate.argtypes)
     lib.lfd_gain_apply.argtypes = [ctxp, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.lfd_gain_apply_host.argtypes = list(lib.lfd_gain_apply.argtypes)
+    lib.lfd_far_accumulate.argtypes = [ctxp, C.POINTER(lfd_batch), C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.lfd_far_accumulate_host.argtypes = list(lib.lfd_far_accumulate.argtypes)
+    lib.lfd_far_accumulate_flags.argtypes = list(lib.lfd_far_accumulate.argtypes) + [C.c_void_p]
+    lib.lfd_far_accumulate_flags_host.argtypes = list(lib.lfd_far_accumulate_flags.argtypes)
+    lib.lfd_far_emit.argtypes = [ctxp, C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    lib.lfd_far_emit_host.argtypes = list(lib.lfd_far_emit.argtypes)
     lib.lfd_pack_ply_normals.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.lfd_consensus_filter.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_float, C.c_int32,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)]
@@ -294,7 +301,7 @@ def load_library() -> C.CDLL:
                  "lfd_triangulate_dense_ply", "lfd_triangulate_dense_ply_segments", "lfd_dense_tiles_per_ref", "lfd_triangulate_dense_segments", "lfd_order_segments", "lfd_pack_ply_segments", "lfd_pack_points3d_segments",
                  "lfd_triangulate_indexed", "lfd_triangulate_sampled", "lfd_triangulate_sampled_multi", "lfd_triangulate_sampled_chain", "lfd_launch_status", "lfd_rng_seed", "lfd_rng_get_state", "lfd_rng_set_state",
                  "lfd_rng_checkpoint", "lfd_rng_rollback",
-                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_refiner_head", "lfd_refiner_head_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_colour_multiview", "lfd_photo_gate", "lfd_photo_gate_host", "lfd_colour_multiview_host", "lfd_gain_accumulate", "lfd_gain_accumulate_host", "lfd_gain_apply", "lfd_gain_apply_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_render_depth", "lfd_render_depth_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_cap_spatial", "lfd_cap_spatial_host", "lfd_thin_footprint", "lfd_thin_footprint_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
+                 "lfd_select_samples", "lfd_select_top_m", "lfd_pack_ply", "lfd_pack_points3d", "lfd_voxel_downsample", "lfd_local_corr", "lfd_local_corr_host", "lfd_refiner_block", "lfd_refiner_block_host", "lfd_refiner_head", "lfd_refiner_head_host", "lfd_cycle_gate", "lfd_cycle_gate_host", "lfd_support_filter", "lfd_support_filter_host", "lfd_refine_multiview", "lfd_refine_multiview_host", "lfd_refine_multiview_weighted", "lfd_refine_multiview_weighted_host", "lfd_depth_sigma_filter", "lfd_depth_sigma_filter_host", "lfd_estimate_normals", "lfd_estimate_normals_host", "lfd_colour_multiview", "lfd_photo_gate", "lfd_photo_gate_host", "lfd_colour_multiview_host", "lfd_gain_accumulate", "lfd_gain_accumulate_host", "lfd_gain_apply", "lfd_gain_apply_host", "lfd_far_accumulate", "lfd_far_accumulate_host", "lfd_far_accumulate_flags", "lfd_far_accumulate_flags_host", "lfd_far_emit", "lfd_far_emit_host", "lfd_pack_ply_normals", "lfd_consensus_filter", "lfd_consensus_filter_host", "lfd_freespace_filter", "lfd_freespace_filter_host", "lfd_render_depth", "lfd_render_depth_host", "lfd_fuse_oriented", "lfd_fuse_oriented_host", "lfd_knn_dist2", "lfd_knn_dist2_host", "lfd_pack_gaussians", "lfd_pack_gaussians_host", "lfd_cap_spatial", "lfd_cap_spatial_host", "lfd_thin_footprint", "lfd_thin_footprint_host", "lfd_quantise_rgb", "lfd_copy_segments", "lfd_identity_axis",
                  "lfd_host_fundamental", "lfd_get_pair_fundamental", "lfd_create_host", "lfd_aggregate_host",
                  "lfd_triangulate_dense_host", "lfd_triangulate_indexed_host", "lfd_prepare_image", "lfd_prepare_mask",
                  "lfd_host_resize_tables", "lfd_host_nearest_indices",
@@ -1159,6 +1166,57 @@ def _gain_accumulate_call(fn, ctx, batch, src, support_thresh_px, table, device)
     return rc, table
 
 
+FAR_QUANTITIES = 7                           # LFD_FAR_QUANTITIES of csrc/lfd_far.hpp: direction sum [3], colour sum [3], count per direction cell
+
+
+def far_table(shell_cells: int, device) -> torch.Tensor:
+    """A zeroed table of the far-field shell: int64 (6 * S * S, 7) - the library's u64 sums, the direction columns two's complement."""
+    return torch.zeros((6 * int(shell_cells) * int(shell_cells), FAR_QUANTITIES), dtype=torch.int64, device=device)
+
+
+def _far_accumulate_call(fn, ctx, batch, far_thresh_px, far_certainty, far_min_views, shell_cells, table, counters, device, flags=None):
+    """One lfd_far_accumulate[_flags][_host] call.  ``table``: None (a zeroed one is made) or a contiguous int64 (6 S S, 7) tensor where the
+    context computes, ADDED to; ``counters``: None or a contiguous int64 (n_refs,) tensor there, added to; ``flags`` (the _flags calls): a
+    contiguous uint8 (n_refs, H * W) tensor there, written.  Returns (rc, table)."""
+    S = int(shell_cells)
+    rows = 6 * S * S
+    if table is None:
+        table = far_table(S, device)
+    elif table.dtype != torch.int64 or tuple(table.shape) != (rows, FAR_QUANTITIES) or table.device != device or not table.is_contiguous():
+        raise ValueError(f"far_accumulate: table must be a contiguous int64 ({rows}, {FAR_QUANTITIES}) tensor on {device}")
+    if counters is not None and (counters.dtype != torch.int64 or tuple(counters.shape) != (batch.n_refs,) or counters.device != device
+                                 or not counters.is_contiguous()):
+        raise ValueError(f"far_accumulate: counters must be a contiguous int64 ({batch.n_refs},) tensor on {device}")
+    args = [ctx, C.byref(batch.c), C.c_float(float(far_thresh_px)), C.c_float(float(far_certainty)), int(far_min_views), S, table.data_ptr(),
+            counters.data_ptr() if counters is not None else None]
+    if flags is not None:
+        if flags.dtype != torch.uint8 or tuple(flags.shape) != (batch.n_refs, batch.H * batch.W) or flags.device != device or not flags.is_contiguous():
+            raise ValueError(f"far_accumulate: flags must be a contiguous uint8 ({batch.n_refs}, {batch.H * batch.W}) tensor on {device}")
+        args.append(flags.data_ptr())
+    rc = fn(*args)
+    return rc, table
+
+
+def _far_emit_call(fn, ctx, table, shell_cells, min_samples, centre, radius, with_normals, capacity, device):
+    """One lfd_far_emit[_host] call.  Returns (rc, n_out, xyz, rgb, normals or None, samples): the tensors hold min(n_out, capacity) records.
+    ``capacity`` None: the number of direction cells that reach ``min_samples`` (an upper bound of what is emitted)."""
+    S = int(shell_cells)
+    if table.dtype != torch.int64 or tuple(table.shape) != (6 * S * S, FAR_QUANTITIES) or table.device != device or not table.is_contiguous():
+        raise ValueError(f"far_emit: table must be a contiguous int64 ({6 * S * S}, {FAR_QUANTITIES}) tensor on {device}")
+    cap = int((table[:, 6] >= int(min_samples)).sum().item()) if capacity is None else int(capacity)
+    alloc = max(cap, 1)
+    xyz = torch.empty((alloc, 3), dtype=torch.float32, device=device)
+    rgb = torch.empty((alloc, 3), dtype=torch.float32, device=device)
+    nrm = torch.empty((alloc, 3), dtype=torch.float32, device=device) if with_normals else None
+    smp = torch.empty((alloc,), dtype=torch.int32, device=device)
+    c3 = (C.c_double * 3)(*[float(v) for v in np.asarray(centre, np.float64).reshape(3)])
+    n_out = C.c_int64(0)
+    rc = fn(ctx, table.data_ptr(), S, int(min_samples), c3, C.c_double(float(radius)), xyz.data_ptr(), rgb.data_ptr(),
+            nrm.data_ptr() if nrm is not None else None, smp.data_ptr(), cap, C.byref(n_out))
+    n = min(int(n_out.value), cap)
+    return rc, int(n_out.value), xyz[:n], rgb[:n], (nrm[:n] if nrm is not None else None), smp[:n]
+
+
 def _gain_apply_call(fn, ctx, rgb, ref_counts, factors, device):
     """One lfd_gain_apply[_host] call.  ``rgb`` (n, 3) float32 where the context computes; ``ref_counts``: points per reference, in the order
     of the cloud; ``factors`` (n_refs, 3) float32 (array or tensor).  Returns (rc, a new (n, 3) tensor)."""
@@ -1913,6 +1971,31 @@ class HipDensifier:
         self._check(rc, "lfd_gain_apply")
         return out
 
+    def far_accumulate(self, batch: PreparedBatch, far_thresh_px: float, far_certainty: float, far_min_views: int, shell_cells: int,
+                       table: Optional[torch.Tensor] = None, counters: Optional[torch.Tensor] = None,
+                       flags: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The statistics of the far-field shell (lfd_far_accumulate): every grid cell of ``batch`` that all its confident
+        neighbours see at infinity adds its direction, its colour and a count to its direction cell's row of ``table``: int64 (6 S S, 7) on
+        the device, ADDED to (None: a zeroed one is made); ``counters``: int64 (n_refs,) far cells per reference, added to; ``flags``: uint8
+        (n_refs, H * W), written 1 for the far cells (lfd_far_accumulate_flags).  One launch on the context's stream, asynchronous; returns
+        the table."""
+        self._same_device(batch, None, table, counters, flags)
+        with torch.cuda.stream(self.stream):
+            fn = self._lib.lfd_far_accumulate if flags is None else self._lib.lfd_far_accumulate_flags
+            rc, table = _far_accumulate_call(fn, self._ctx, batch, far_thresh_px, far_certainty, far_min_views, shell_cells, table, counters,
+                                             self.device, flags)
+        self._check(rc, "lfd_far_accumulate")
+        return table
+
+    def far_emit(self, table: torch.Tensor, shell_cells: int, min_samples: int, centre, radius: float, with_normals: bool = False):
+        """The shell's points (lfd_far_emit) from ``table``: (xyz, rgb, normals or None, samples) device tensors, one record per
+        direction cell with at least ``min_samples`` samples, in key order, at ``centre + radius * d_hat``.  Synchronous."""
+        with torch.cuda.stream(self.stream):
+            rc, _n, xyz, rgb, nrm, smp = _far_emit_call(self._lib.lfd_far_emit, self._ctx, table, shell_cells, min_samples, centre, radius,
+                                                        with_normals, None, self.device)
+        self._check(rc, "lfd_far_emit")
+        return xyz, rgb, nrm, smp
+
     def pack_ply_normals(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
         """(n*27,) u8 device tensor: the body of a PLY whose header lists x y z nx ny nz red green blue."""
         xyz, normals, rgb = self._pts(xyz, 3, "xyz"), self._pts(normals, 3, "normals"), self._pts(rgb, 3, "rgb")
@@ -2411,6 +2494,24 @@ class HostDensifier:
         rc, out = _gain_apply_call(self._lib.lfd_gain_apply_host, self._ctx, rgb, ref_counts, factors, self.device)
         self._check(rc, "lfd_gain_apply_host")
         return out
+
+    def far_accumulate(self, batch: PreparedBatch, far_thresh_px: float, far_certainty: float, far_min_views: int, shell_cells: int,
+                       table: Optional[torch.Tensor] = None, counters: Optional[torch.Tensor] = None,
+                       flags: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """HipDensifier.far_accumulate over CPU tensors (lfd_far_accumulate[_flags]_host): the same routines, the same integers."""
+        self._same_device(batch, None, table, counters, flags)
+        fn = self._lib.lfd_far_accumulate_host if flags is None else self._lib.lfd_far_accumulate_flags_host
+        rc, table = _far_accumulate_call(fn, self._ctx, batch, far_thresh_px, far_certainty, far_min_views, shell_cells, table, counters,
+                                         self.device, flags)
+        self._check(rc, "lfd_far_accumulate_host")
+        return table
+
+    def far_emit(self, table: torch.Tensor, shell_cells: int, min_samples: int, centre, radius: float, with_normals: bool = False):
+        """HipDensifier.far_emit over CPU tensors (lfd_far_emit_host): the same bits."""
+        rc, _n, xyz, rgb, nrm, smp = _far_emit_call(self._lib.lfd_far_emit_host, self._ctx, table, shell_cells, min_samples, centre, radius,
+                                                    with_normals, None, self.device)
+        self._check(rc, "lfd_far_emit_host")
+        return xyz, rgb, nrm, smp
 
     def pack_ply_normals(self, xyz: torch.Tensor, normals: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
         """HipDensifier.pack_ply_normals over CPU tensors: the host writer's records (core/writers.py), the same bytes."""

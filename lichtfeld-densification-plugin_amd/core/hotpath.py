@@ -112,6 +112,15 @@ class HotPath:
         self.photo_texture = float(config.exp("photo_min_texture"))
         self._photo_counter: Optional[torch.Tensor] = None      # int64 [5] where the kernels run: points per status, added to
         self.nbr_images = self.colour or self.gain or self.photo   # the neighbours' match-size images travel with the reference's
+        # far-field shell (lfd_far_accumulate): once per launch on the stream that holds the batch, beside the point stages
+        self.far_mode = str(config.exp("far_shell"))
+        self.far = self.far_mode != "off"
+        self.far_thresh_px = float(config.far_threshold())
+        self.far_certainty = float(config.exp("far_certainty"))
+        self.far_min_views = int(config.exp("far_min_views"))
+        self.far_cells = int(config.exp("far_shell_cells"))
+        self._far_table: Optional[torch.Tensor] = None          # the run's table, int64 (6 S S, 7) where the kernels run
+        self._far_parts: list = []                              # (far cells per reference, reference uids, overlap or None) per launch the run used
         self._uids = [int(c.uid) for c in cams]
         self._gain_parts: list = []                             # (table where the kernels run, reference uids, neighbour uids) per launch the run used
         on = bool(config.exp("undistort_images"))
@@ -148,7 +157,12 @@ class HotPath:
     # -- multi-view support filter (lfd_support_filter) --------------------------------------------------------------------------
     def support_filter_collected(self, batch: hb.PreparedBatch, res: hb.TriangulationOutput) -> hb.TriangulationOutput:
         """A collected result through the filter (the synchronous schedules, the host backend)."""
+        far_part = None
+        if self.far:
+            with self.clock.stage("kernel"):
+                far_part = self._far_launch(batch, pending=False)
         if res is None:
+            self._far_commit(far_part, None)
             return res
         if self.min_support > 0:
             self._support_void = False
@@ -176,7 +190,53 @@ class HotPath:
         if self.normals:
             with self.clock.stage("kernel"):
                 res = self._with_normals(batch, res)
+        self._far_commit(far_part, res)
         return res
+
+    # -- far-field shell (lfd_far_accumulate) ------------------------------------------------------------------------------------
+    def _far_launch(self, batch: hb.PreparedBatch, pending: bool):
+        """One launch of lfd_far_accumulate over ``batch`` on the stream that holds it; nothing is read back here.  ``pending``: into a zeroed
+        table of the launch's own, which ``_far_commit`` adds to the run's when the launch's result is one the run uses (``finish_sampled``) and
+        drops otherwise - the gain statistics' rule: a grouped call that is void as a whole and redone reference by reference counts once.
+        Otherwise straight into the run's table.  Returns (pending table or None, far cells per reference, reference uids, far flags)."""
+        if self._far_table is None:
+            self._far_table = hb.far_table(self.far_cells, self.dev)
+        table = hb.far_table(self.far_cells, self.dev) if pending else self._far_table
+        counters = torch.zeros(batch.n_refs, dtype=torch.int64, device=self.dev)
+        flags = torch.empty((batch.n_refs, batch.H * batch.W), dtype=torch.uint8, device=self.dev)
+        self.dens.far_accumulate(batch, self.far_thresh_px, self.far_certainty, self.far_min_views, self.far_cells, table=table, counters=counters,
+                                 flags=flags)
+        uids = np.array([self._uids[int(r.ref_cam)] for r in batch.refs], np.int64)
+        return (table if pending else None), counters, uids, flags
+
+    def _far_commit(self, part, res) -> None:
+        """The launch's statistics join the run's.  ``res``: the launch's collected result (or None): the far cells that also produced one of
+        its points are counted where the flags are."""
+        if part is None:
+            return
+        table, counters, uids, flags = part
+        if table is not None:
+            self._far_table += table
+        overlap = None
+        if res is not None and getattr(res, "cell", None) is not None and int(res.count) > 0:
+            per_ref = torch.from_numpy(np.diff(np.asarray(res.ref_offsets, np.int64))).to(flags.device)
+            ref_of = torch.repeat_interleave(torch.arange(per_ref.numel(), device=flags.device), per_ref)
+            cell = res.cell.to(flags.device).long()
+            ok = (cell >= 0) & (cell < flags.shape[1])
+            overlap = flags.reshape(-1)[(ref_of * flags.shape[1] + cell.clamp(0, flags.shape[1] - 1))[ok]].sum()
+        self._far_parts.append((counters, uids, overlap))
+
+    def far_result(self) -> dict:
+        """The run's far-field statistics: ``table`` (where the kernels run), ``far_cells`` {camera uid: far cells of its references},
+        ``overlap`` (far cells that also produced a point of their launch's result)."""
+        table = self._far_table if self._far_table is not None else hb.far_table(self.far_cells, self.dev)
+        cells: dict = {}
+        overlap = 0
+        for counters, uids, ov in self._far_parts:
+            for uid, n in zip(uids.tolist(), counters.cpu().tolist()):
+                cells[int(uid)] = cells.get(int(uid), 0) + int(n)
+            overlap += int(ov.item()) if ov is not None else 0
+        return dict(table=table, far_cells=cells, overlap=overlap)
 
     # -- per-image exposure gains (lfd_gain_accumulate, DESIGN.md 4.23) -------------------------------------------------------------------------
     def _gain_launch(self, batch: hb.PreparedBatch, out):
@@ -315,6 +375,8 @@ class HotPath:
             out.gain_pending = self._gain_launch(batch, out)       # (committed in finish_sampled, when the result is one the run uses)
         if self.normals:
             out = self._with_normals(batch, out)
+        if self.far:
+            out.far_pending = self._far_launch(batch, pending=True)    # (committed in finish_sampled, like the gain statistics)
         return out
 
     # -- multi-view re-triangulation of supported points (lfd_refine_multiview) ---------------------------------------------------
@@ -542,6 +604,7 @@ class HotPath:
         out = free.pop() if free else hb.OutputBuffers(int(capacity), int(n_refs), int(k), self.dev)
         out.normals_valid = False              # (whatever fills them next has not had its normals estimated)
         out.gain_pending = None
+        out.far_pending = None
         return out
 
     # -- upstream's normaliser without stalling the launch stream ---------------------------------------------------------------
@@ -704,6 +767,7 @@ class HotPath:
             # an exception above keeps nothing, and a caller that drops the result clears ``gain_pending`` first (SampledLoop._recover)
             if not void:
                 self._gain_commit(getattr(out, "gain_pending", None))
+                self._far_commit(getattr(out, "far_pending", None), res)
             if not res.count and check_selection:
                 return None
             return dataclasses.replace(res, xyz=res.xyz.clone(), rgb=res.rgb.clone(), err=res.err.clone(),
@@ -712,6 +776,7 @@ class HotPath:
                                        normals=res.normals.clone() if res.normals is not None else None)
         finally:
             out.gain_pending = None
+            out.far_pending = None
             self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, _pool_kind(out)), []).append(out)
 
     def pack_ply_tensor(self, xyz: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
@@ -753,10 +818,12 @@ class HotPath:
                     self._gain_commit(self._gain_launch(batch, out))
                 if self.normals:
                     out = self._with_normals(batch, out)
+                far_part = self._far_launch(batch, pending=False) if self.far else None
                 self.dens.check_launches()
                 res = out.collect()
                 self._support_void = False
                 self._support_count(res)
+                self._far_commit(far_part, res)
                 return res
             res = self.dens.triangulate_dense(batch, self.params)
         return self.support_filter_collected(batch, res)

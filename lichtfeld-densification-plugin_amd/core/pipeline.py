@@ -252,6 +252,9 @@ def run_dense_pipeline(
     if world > 1 and str(config.exp("gain_compensation")) != "off":
         raise ValueError("experimental['gain_compensation'] cannot run sharded over several GPUs: like the multi-view colour it is a stage of the "
                          "single-GPU run, and the exchange of a sharded run does not carry the statistics")
+    if world > 1 and str(config.exp("far_shell")) != "off":
+        raise ValueError("experimental['far_shell'] cannot run sharded over several GPUs: the direction table is a statistic of the single-GPU "
+                         "run, and the exchange of a sharded run does not carry it")
     if world > 1 and str(config.exp("depth_maps_dir")) != "":
         raise ValueError("experimental['depth_maps_dir'] cannot run sharded over several GPUs: the maps are a stage of the single-GPU run, and with "
                          "gather_to_root only one rank would hold the cloud they are rendered from")
@@ -278,7 +281,7 @@ def run_dense_pipeline(
                          cancel_requested=cancel_requested, total_pairs_est=total_pairs_est)
     t0 = time.time()
     own_matcher = matcher is None
-    prefetch = hot = feat_cache = strategy = gain_rows = None
+    prefetch = hot = feat_cache = strategy = gain_rows = far_shell = None
     rank_status, rank_error = 0, None         # 0 fine, 1 cancelled, 2 failed: agreed on by all ranks before the exchange step (core/distributed.py)
     try:
         if own_matcher:
@@ -381,6 +384,12 @@ def run_dense_pipeline(
             gain_rows = hot.gain_rows()
             log.info(f"Gain compensation: {int(gain_rows.table[:, 0].sum())} samples in {int((gain_rows.table[:, 0] > 0).sum())} of "
                      f"{gain_rows.table.shape[0]} (reference, neighbour) rows (within {hot.support_thresh_px:g} px)")
+        if hot.far:
+            far_shell = hot.far_result()
+            t6 = far_shell["table"][:, 6]
+            log.info(f"Far-field shell: {sum(far_shell['far_cells'].values())} far cells (every confident neighbour within {hot.far_thresh_px:g} px of "
+                     f"the rotation-only transfer, certainty >= {hot.far_certainty:g}) in {int((t6 > 0).sum())} of {t6.numel()} direction cells, "
+                     f"{far_shell['overlap']} of them also produced a point")
         if hot.normals:
             n_fit, n_fell = hot.normal_totals()
             log.info(f"Surface normals: window radius {hot.normal_radius} cell(s), depth step {hot.normal_depth_step:g}, {n_fit} points fitted, "
@@ -409,6 +418,7 @@ def run_dense_pipeline(
         progress_callback(90.0, "Finalizing triangulation...")
     result = outputs.result(t0, clock)
     result.gain_rows = gain_rows          # experimental['gain_compensation']: the run's statistics, for the solve (densify.py)
+    result.far_shell = far_shell          # experimental['far_shell']: the run's direction table, for the shell (densify.py)
     return result
 
 

@@ -272,6 +272,8 @@ class SampledLoop:
             try:
                 if getattr(handle[1], "gain_pending", None) is not None:
                     handle[1].gain_pending = None       # (experimental['gain_compensation']: its statistics go with its results)
+                if getattr(handle[1], "far_pending", None) is not None:
+                    handle[1].far_pending = None        # (experimental['far_shell']: likewise)
                 self.hot.finish_sampled(handle, check_selection=False)       # waited for, its buffers back in the pool, its results dropped
             except Exception:
                 pass

@@ -186,7 +186,28 @@ EXPERIMENTAL_DEFAULTS = {
     # the Gaussian output and the voxel filter.  0.5 removes little more than the duplicates between references; 2 keeps about a third of a
     # lone reference's samples.  0 = off: no new code runs and every output stays byte-identical.
     "footprint_thin_cells": 0.0,
+    # far-field shell (lfd_far_accumulate / lfd_far_emit): points at infinity for sky, skyline and distant background - the
+    # cells every filter rightly drops because their depth is unknown.  A grid cell is FAR when every neighbour that matched it confidently
+    # sees it where the rotation-only transfer predicts; far cells are summed into a cube map of direction cells, and at the end of the run
+    # every occupied direction cell becomes one point on a sphere around the cameras, coloured by the mean of its samples.  "file" writes them
+    # to <output stem>_shell.ply beside an unchanged main file, "merge" appends them behind the cloud's records in the main PLY; both write
+    # <output file>.shell.json.  The positions are a convention, not depth.  "off" = no new code runs and every output stays byte-identical.
+    "far_shell": "off",
+    # ... a neighbour agrees with infinity within this many px of ITS camera image, as support_thresh_px; 0 = reproj_thresh
+    "far_thresh_px": 0.0,
+    # ... a neighbour is confident at a cell when its raw certainty is at least this, in (0, 1].  A design default, not a measurement.
+    "far_certainty": 0.5,
+    # ... at least min(this, the reference's neighbours) confident neighbours, all of which must agree, 1 .. 8
+    "far_min_views": 2,
+    # ... direction cells along a cube face's side, 8 .. 512 (6 S^2 cells in all)
+    "far_shell_cells": 256,
+    # ... a direction cell becomes a point when it holds at least this many samples, >= 1
+    "far_min_samples": 2,
+    # ... radius of the sphere in scene units; 0 = automatic: max(10 x the cameras' spread, 1.25 x the cloud's) around the cameras' mean centre
+    "far_shell_radius": 0.0,
 }
+FAR_MODES = ("off", "file", "merge")
+FAR_KNOBS = ("far_thresh_px", "far_certainty", "far_min_views", "far_shell_cells", "far_min_samples", "far_shell_radius")
 CAP_MODES = ("random", "spatial")
 COLOUR_MODES = ("off", "mean", "median")
 GAIN_MODES = ("off", "luma", "rgb")
@@ -271,6 +292,11 @@ class DensePipelineConfig:
         """Threshold of the multi-view support filter in px of the neighbour's camera image (experimental['support_thresh_px'], 0 = 2 * reproj_thresh)."""
         tau = float(self.exp("support_thresh_px"))
         return tau if tau > 0.0 else 2.0 * float(self.reproj_thresh)
+
+    def far_threshold(self) -> float:
+        """Threshold of the far-field shell's agreement test in px of the neighbour's camera image (experimental['far_thresh_px'], 0 = reproj_thresh)."""
+        tau = float(self.exp("far_thresh_px"))
+        return tau if tau > 0.0 else float(self.reproj_thresh)
 
     def exchange_record_format(self) -> str:
         rec = str(self.exp("exchange_records"))
@@ -617,6 +643,51 @@ class DensePipelineConfig:
                 return "experimental['gain_compensation'] needs the ordered dense result; experimental['dense_tile_segments'] retires tiles unordered"
             if self.exchange_record_format() == "ply":
                 return "experimental['gain_compensation'] rewrites f32 rows; experimental['exchange_records'] must be 'f32' with it"
+        far = self.exp("far_shell")
+        if not isinstance(far, str) or far not in FAR_MODES:
+            return ("experimental['far_shell'] must be 'off', 'file' (the shell in <output stem>_shell.ply) or 'merge' (its records behind the "
+                    "cloud's in the main PLY)")
+        number = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(float(v))  # noqa: E731
+        whole = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer))      # noqa: E731
+        if not number(self.exp("far_thresh_px")) or float(self.exp("far_thresh_px")) < 0.0:
+            return "experimental['far_thresh_px'] must be a finite number >= 0 (px of the neighbour's camera image; 0 = reproj_thresh)"
+        if not number(self.exp("far_certainty")) or not (0.0 < float(self.exp("far_certainty")) <= 1.0):
+            return "experimental['far_certainty'] must be in (0, 1] (the raw certainty from which a neighbour is confident)"
+        if not whole(self.exp("far_min_views")) or not 1 <= int(self.exp("far_min_views")) <= 8:
+            return "experimental['far_min_views'] must be an integer in 1 .. 8 (confident neighbours a far cell needs)"
+        if not whole(self.exp("far_shell_cells")) or not 8 <= int(self.exp("far_shell_cells")) <= 512:
+            return "experimental['far_shell_cells'] must be an integer in 8 .. 512 (direction cells along a cube face's side)"
+        if not whole(self.exp("far_min_samples")) or int(self.exp("far_min_samples")) < 1:
+            return "experimental['far_min_samples'] must be an integer >= 1 (samples a direction cell needs to become a point)"
+        if not number(self.exp("far_shell_radius")) or float(self.exp("far_shell_radius")) < 0.0:
+            return "experimental['far_shell_radius'] must be a finite number >= 0 (scene units; 0 = automatic)"
+        if far == "off":
+            for key in FAR_KNOBS:
+                if float(self.exp(key)) != float(EXPERIMENTAL_DEFAULTS[key]):
+                    return f"experimental['{key}'] is a knob of the far-field shell: it needs experimental['far_shell'] = 'file' or 'merge'"
+        else:
+            if self.no_filter:
+                return ("experimental['far_shell'] collects the cells the filters drop for want of parallax: with no_filter they are triangulated "
+                        "and emitted at arbitrary depths already")
+            if not (float(self.min_parallax_deg) > 0.0):
+                return ("experimental['far_shell'] needs min_parallax_deg > 0: without the parallax gate the far cells also reach the cloud, at "
+                        "depths nothing supports")
+            if not (self.far_threshold() > 0.0):
+                return "experimental['far_shell'] compares in pixels: experimental['far_thresh_px'] or, for its default, reproj_thresh must be > 0"
+            if self.stream_output:
+                return ("experimental['far_shell'] is placed around the finished cloud; stream_output writes the file while the run proceeds and "
+                        "keeps no cloud")
+            if self.exp("dense_tile_segments"):
+                return ("experimental['far_shell'] needs the cloud as arrays; dense mode with experimental['dense_tile_segments'] retires tiles "
+                        "into the file's records")
+            if self.exchange_record_format() == "ply":
+                return "experimental['far_shell'] measures the cloud's f32 rows; experimental['exchange_records'] must be 'f32' with it"
+            if far == "merge":
+                if self.exp("gaussian_init"):
+                    return ("experimental['far_shell'] = 'merge' cannot run with experimental['gaussian_init']: a shell point has no neighbour "
+                            "distance to take a scale from; use 'file'")
+                if not str(self.output_path).lower().endswith(".ply"):
+                    return "experimental['far_shell'] = 'merge' appends PLY records: output_path must end in .ply (use 'file' with other formats)"
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):
                 return "stream_output writes a PLY while the run proceeds: output_path must end in .ply"

@@ -24,6 +24,7 @@
 #include "lfd_colour.hpp"
 #include "lfd_photo.hpp"
 #include "lfd_gain.hpp"
+#include "lfd_far.hpp"
 #include "lfd_sigma.hpp"
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
@@ -142,6 +143,9 @@ hipError_t lfd_colour_launch(const LfdColourArgs& p, hipStream_t stream);     //
 hipError_t lfd_photo_launch(const LfdPhotoArgs& p, const LfdSupportArgs& sup, hipStream_t stream);   // lfd_photo.hip
 hipError_t lfd_gain_launch(const LfdGainArgs& p, hipStream_t stream);         // lfd_gain.hip
 hipError_t lfd_gain_apply_launch(const LfdGainApplyArgs& p, hipStream_t stream);
+hipError_t lfd_far_launch(const LfdFarArgs& p, bool reduce, hipStream_t stream);   // lfd_far.hip
+hipError_t lfd_far_mark_launch(const unsigned long long* table, long long n_cells, long long min_samples, uint8_t* keep, hipStream_t stream);
+hipError_t lfd_far_emit_launch(const LfdFarEmitArgs& p, hipStream_t stream);
 extern "C" __global__ void lfd_pack_ply_normals_kernel(const float* xyz, const float* normals, const float* rgb, long long n, unsigned char* out);
 extern "C" __global__ void lfd_select_topm_kernel(LfdSelectArgs A);
 extern "C" __global__ void lfd_select_filter_mw_kernel(LfdSelectArgs A, LfdSelectNorms norms);
@@ -2312,6 +2316,70 @@ int lfd_gain_apply(lfd_context* ctx, const float* rgb, int64_t n, const int64_t*
     p.offs = reinterpret_cast<const long long*>(ref_offsets);
     p.factors = factors; p.rgb = rgb; p.o_rgb = rgb_out; p.n = n; p.n_refs = n_refs;
     LFD_HIP(ctx, lfd_gain_apply_launch(p, ctx->stream));
+    return LFD_OK;
+}
+
+// ---- far-field shell (lfd_far.hip) -----------------------------------------------------------------------------------------------------------------
+int lfd_far_accumulate(lfd_context* ctx, const lfd_batch* batch, float far_thresh_px, float far_certainty, int32_t far_min_views,
+                       int32_t shell_cells, uint64_t* table, int64_t* counters) {
+    return lfd_far_accumulate_flags(ctx, batch, far_thresh_px, far_certainty, far_min_views, shell_cells, table, counters, nullptr);
+}
+
+int lfd_far_accumulate_flags(lfd_context* ctx, const lfd_batch* batch, float far_thresh_px, float far_certainty, int32_t far_min_views,
+                             int32_t shell_cells, uint64_t* table, int64_t* counters, uint8_t* flags) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_far_check(far_thresh_px, far_certainty, far_min_views, shell_cells, table))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_far_accumulate: ") + why);
+    LfdLaunch L;
+    int rc = batch_launch(ctx, batch, L);
+    if (rc != LFD_OK) return rc;
+    if (const char* why = lfd_far_check_batch(batch, shell_cells, table, counters, flags))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_far_accumulate: ") + why);
+    if (batch->n_refs > 65535) return fail(ctx, LFD_ERR_INVALID, "lfd_far_accumulate: at most 65535 references per batch");
+    LfdFarArgs p;
+    std::memset(&p, 0, sizeof(p));
+    p.cams = L.cams; p.refs = L.refs; p.slots = L.slots; p.ref_const = L.ref_const; p.pair_const = L.pair_const;
+    p.axis_x = L.axis_x; p.axis_y = L.axis_y;
+    p.table = reinterpret_cast<unsigned long long*>(table);
+    p.counters = reinterpret_cast<unsigned long long*>(counters);
+    p.flags = flags;
+    if (flags) LFD_HIP(ctx, hipMemsetAsync(flags, 0, (size_t)batch->n_refs * batch->H * batch->W, ctx->stream));
+    p.n_refs = batch->n_refs; p.k = batch->k; p.S = shell_cells; p.min_views = far_min_views;
+    p.far_certainty = far_certainty;
+    p.g = launch_geom(batch, L, far_thresh_px, 0.0f);
+    const char* e = std::getenv("LFD_FAR_NO_REDUCE");                  // profiling: every far lane issues its own adds (the same table)
+    LFD_HIP(ctx, lfd_far_launch(p, !(e && std::atoi(e) != 0), ctx->stream));
+    return LFD_OK;
+}
+
+int lfd_far_emit(lfd_context* ctx, const uint64_t* table, int32_t shell_cells, int64_t min_samples, const double* centre, double radius,
+                 float* xyz, float* rgb, float* normal, int32_t* samples, int64_t capacity, int64_t* n_out) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_far_emit_check(table, shell_cells, min_samples, centre, radius, xyz, rgb, normal, samples, capacity, n_out))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_far_emit: ") + why);
+    *n_out = 0;
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const long long n_cells = 6LL * shell_cells * shell_cells;
+    const CloudPlan p = cloud_plan(n_cells);
+    CloudCompact c;
+    if (int rc = carve_cloud_ws(ctx, [&](Bump& b) { c = carve_compact(b, p, 0); })) return rc;
+    LFD_HIP(ctx, lfd_far_mark_launch(reinterpret_cast<const unsigned long long*>(table), n_cells, (long long)min_samples, c.keep, st));
+    cloud_compact_prefix(st, p, c);
+    LfdFarEmitArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.table = reinterpret_cast<const unsigned long long*>(table); a.keep = c.keep; a.wg_kept = c.wg_kept;
+    for (int i = 0; i < 3; ++i) a.centre[i] = centre[i];
+    a.radius = radius;
+    a.xyz = xyz; a.rgb = rgb; a.normal = normal; a.samples = samples;
+    a.n_cells = n_cells; a.capacity = capacity; a.min_samples = min_samples;
+    LFD_HIP(ctx, lfd_far_emit_launch(a, st));
+    LFD_HIP(ctx, hipMemcpyAsync(ctx->pinned_words, c.wg_kept + p.n_wg, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    LFD_HIP(ctx, hipStreamSynchronize(st));                            // the workspace is free for the next stage on return
+    *n_out = (int64_t)(unsigned)ctx->pinned_words[0];
+    if (*n_out > capacity) return fail(ctx, LFD_ERR_CAPACITY, "lfd_far_emit: the shell has more points than capacity (n_out holds the number)");
     return LFD_OK;
 }
 

@@ -28,6 +28,7 @@
 #include "lfd_colour.hpp"
 #include "lfd_photo.hpp"
 #include "lfd_gain.hpp"
+#include "lfd_far.hpp"
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
 #include "lfd_freespace.hpp"
@@ -757,6 +758,96 @@ int lfd_gain_apply_host(lfd_context* ctx, const float* rgb, int64_t n, const int
             }
         }
     });
+    return LFD_OK;
+}
+
+// The twin of lfd_far_accumulate: the routines of lfd_far.hpp per cell over host pointers, on the context's threads.  A chunk adds
+// each far cell's seven integers to the table with relaxed atomic adds: integer additions, order-free.
+int lfd_far_accumulate_host(lfd_context* ctx, const lfd_batch* b, float far_thresh_px, float far_certainty, int32_t far_min_views,
+                            int32_t shell_cells, uint64_t* table, int64_t* counters) {
+    return lfd_far_accumulate_flags_host(ctx, b, far_thresh_px, far_certainty, far_min_views, shell_cells, table, counters, nullptr);
+}
+
+int lfd_far_accumulate_flags_host(lfd_context* ctx, const lfd_batch* b, float far_thresh_px, float far_certainty, int32_t far_min_views,
+                                  int32_t shell_cells, uint64_t* table, int64_t* counters, uint8_t* flags) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    if (const char* why = lfd_far_check(far_thresh_px, far_certainty, far_min_views, shell_cells, table))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_far_accumulate_host: ") + why);
+    lfd_params none;
+    std::memset(&none, 0, sizeof(none));
+    int rc = validate_host(ctx, b, &none);
+    if (rc != LFD_OK) return rc;
+    if (const char* why = lfd_far_check_batch(b, shell_cells, table, counters, flags))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_far_accumulate_host: ") + why);
+    if (b->n_refs > 65535) return lfd_fail(ctx, LFD_ERR_INVALID, "lfd_far_accumulate_host: at most 65535 references per batch");
+    HostLaunch L;
+    prepare_host(b, &none, L);
+    std::vector<LfdSlot> slot;
+    make_slot_table(ctx, L, slot, nullptr);
+    const LfdSupportGeom g = make_geom(L, far_thresh_px, 0.0f);
+    const int chunks_per_ref = (L.HW + kChunk - 1) / kChunk;
+    if (flags) std::memset(flags, 0, (size_t)b->n_refs * L.HW);
+    parallel_chunks(ctx, b->n_refs * chunks_per_ref, [&](int c) {
+        const int r = c / chunks_per_ref, c0 = (c - r * chunks_per_ref) * kChunk, c1 = std::min(L.HW, c0 + kChunk);
+        const LfdCam& cam = ctx->host_cams[(size_t)b->ref_cam[r]];
+        LfdRefConst rcst;
+        lfd_make_ref_const(cam, b->w_match, b->h_match, rcst);
+        float M[9];
+        lfd_far_dir_matrix(cam, M);
+        const int ns = b->n_slots[r];
+        const LfdSlot* sl = &slot[(size_t)r * LFD_MAX_SLOTS];
+        const uint8_t* ma = b->mask_a ? b->mask_a[r] : nullptr;
+        long long n_far = 0;
+        for (int cell = c0; cell < c1; ++cell) {
+            const int y = cell / b->W, x = cell - y * b->W;
+            if (ma && ma[(size_t)lfd_nearest_src(y, g.mask_sy, g.h_match) * g.w_match + lfd_nearest_src(x, g.mask_sx, g.w_match)] == 0) continue;
+            float xan, yan, d[3];
+            if (g.C == 4) { const float* a = sl[0].warp + (size_t)cell * 4; xan = a[0]; yan = a[1]; }
+            else { xan = L.ax[x]; yan = L.ay[y]; }
+            lfd_far_direction(M, rcst.sx, rcst.sy, xan, yan, g.wm1, g.hm1, d);
+            int n_conf = 0, n_agree = 0;
+            for (int j = 0; j < ns; ++j) {
+                const float* wv = sl[j].warp + (size_t)cell * g.C + (g.C - 2);
+                const int v = lfd_far_slot(sl[j], g, far_certainty, sl[j].cert[cell], wv[0], wv[1], d[0], d[1], d[2]);
+                n_conf += v & 1; n_agree += v >> 1;
+            }
+            if (!lfd_far_verdict(n_conf, n_agree, far_min_views, ns)) continue;
+            long long key, q[3];
+            if (!lfd_far_key(d[0], d[1], d[2], shell_cells, &key, q)) continue;
+            float rgb[3];
+            lfd_bilinear_rgb_f32(b->image[r], b->w_match, b->h_match, lfd_match_px(xan, g.wm1), lfd_match_px(yan, g.hm1), rgb);
+            uint64_t* row = table + (size_t)key * LFD_FAR_QUANTITIES;
+            for (int e = 0; e < 3; ++e) {
+                __atomic_fetch_add(row + e, (uint64_t)q[e], __ATOMIC_RELAXED);
+                __atomic_fetch_add(row + 3 + e, (uint64_t)lfd_quantise_u8(rgb[e]), __ATOMIC_RELAXED);
+            }
+            __atomic_fetch_add(row + 6, (uint64_t)1, __ATOMIC_RELAXED);
+            if (flags) flags[(size_t)r * L.HW + cell] = 1;
+            ++n_far;
+        }
+        if (counters && n_far) __atomic_fetch_add(counters + r, (int64_t)n_far, __ATOMIC_RELAXED);
+    });
+    return LFD_OK;
+}
+
+// The twin of lfd_far_emit: lfd_far_kept / lfd_far_record per direction cell in key order, the same bits.
+int lfd_far_emit_host(lfd_context* ctx, const uint64_t* table, int32_t shell_cells, int64_t min_samples, const double* centre, double radius,
+                      float* xyz, float* rgb, float* normal, int32_t* samples, int64_t capacity, int64_t* n_out) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    if (const char* why = lfd_far_emit_check(table, shell_cells, min_samples, centre, radius, xyz, rgb, normal, samples, capacity, n_out))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_far_emit_host: ") + why);
+    const long long n_cells = 6LL * shell_cells * shell_cells;
+    long long o = 0;
+    for (long long i = 0; i < n_cells; ++i) {
+        const uint64_t* row = table + i * LFD_FAR_QUANTITIES;
+        if (!lfd_far_kept(row, (long long)min_samples)) continue;
+        if (o < capacity) lfd_far_record(row, centre, radius, xyz + 3 * o, rgb + 3 * o, normal ? normal + 3 * o : nullptr, samples ? samples + o : nullptr);
+        ++o;
+    }
+    *n_out = o;
+    if (o > capacity) return lfd_fail(ctx, LFD_ERR_CAPACITY, "lfd_far_emit_host: the shell has more points than capacity (n_out holds the number)");
     return LFD_OK;
 }
 

@@ -204,7 +204,7 @@ def _cap_args(config) -> dict:
     return {} if config is None else {"cap_mode": str(config.exp("cap_mode")), "host_threads": int(config.exp("host_threads"))}
 
 
-def _finish_on_device(result, path: str, max_points: int, seed: int, clock=None, config=None, progress_callback=None) -> Optional[int]:
+def _finish_on_device(result, path: str, max_points: int, seed: int, clock=None, config=None, progress_callback=None, shell=None) -> Optional[int]:
     """Point cap + output file for a result whose points are still on the GPU, without ever bringing the f32 cloud to the host: the same subset
     ``_apply_point_cap`` picks (the same generator, the same call), applied to the device tensors, then the file payload packed on the device
     (``_write_output``).  Returns the number of points written, or None when the result is not on a GPU (the host path applies)."""
@@ -220,8 +220,10 @@ def _finish_on_device(result, path: str, max_points: int, seed: int, clock=None,
     n = int(pts[0].shape[0])
     if config is not None and bool(config.exp("gaussian_init")):              # (the last stage: it replaces the 27-byte packing)
         _write_gaussians(config, path, pts[0], normals, pts[1], clock=clock, progress_callback=progress_callback)
+        if shell is not None:
+            shell.write_file(pts[0], normals is not None, clock)
         return n
-    _write_output(path, np.empty((n, 0), np.float32), None, None, pts, clock=clock, normals=normals)
+    _write_final(shell, path, np.empty((n, 0), np.float32), None, None, pts, clock=clock, normals=normals)
     return n
 
 
@@ -323,6 +325,89 @@ def _apply_gain_compensation(result, config: DensePipelineConfig, camera_records
                          streamed_path=None, clock=result._clock, loader=loader, device_normals=result.device_normals, match_grid=result.match_grid)
     out.gain_rows = result.gain_rows
     return out
+
+
+class FarShell:
+    """The far-field shell of a run (experimental['far_shell']) between the pipeline and the writers: the run's direction
+    table and what ``emit`` needs to place it around the final cloud - behind every filter, thinning, cap and fusion, in front of packing.
+    Centre: the f64 mean of the loaded cameras' centres; automatic radius: max(10 x the largest distance of a camera from the centre,
+    1.25 x the largest distance of a point of the final cloud), the cloud's taken where the cloud lives - squares and sums as separate f64
+    operations, the same bits on either route."""
+
+    def __init__(self, stats: dict, config: DensePipelineConfig, camera_records):
+        self.config, self.stats, self.mode = config, stats, str(config.exp("far_shell"))
+        self.table = stats["table"]
+        self.names = {int(c.uid): os.path.basename(str(c.image_path)) for c in camera_records}
+        centres = np.stack([np.asarray(c.C, np.float64).reshape(3) for c in camera_records])
+        self.centre = centres.mean(axis=0)
+        d = centres - self.centre
+        sq = d * d
+        self.r_cams = float(np.sqrt(((sq[:, 0] + sq[:, 1]) + sq[:, 2]).max()))
+        self.shell_path = os.path.splitext(str(config.output_path))[0] + "_shell.ply"
+
+    def radius(self, xyz) -> float:
+        import torch
+        fixed = float(self.config.exp("far_shell_radius"))
+        if fixed > 0.0:
+            return fixed
+        r_cloud = 0.0
+        if xyz is not None and int(xyz.shape[0]) > 0:
+            t = xyz if isinstance(xyz, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(xyz))
+            d = t.to(torch.float64) - torch.from_numpy(self.centre).to(t.device)
+            sq = d * d
+            r_cloud = float(torch.sqrt(((sq[:, 0] + sq[:, 1]) + sq[:, 2]).max()).item())
+        r = max(10.0 * self.r_cams, 1.25 * r_cloud)
+        return r if r > 0.0 else 1.0                    # (one camera and no cloud: any positive radius is as good as another)
+
+    def emit(self, xyz, with_normals: bool):
+        """The shell around the final cloud ``xyz`` (array or tensor, where it lives): (xyz, rgb, normals or None) tensors where the table
+        lives, and ``<output file>.shell.json`` beside the output."""
+        import json
+        from .core import hip_backend as hb
+        cfg = self.config
+        S, min_samples = int(cfg.exp("far_shell_cells")), int(cfg.exp("far_min_samples"))
+        radius = self.radius(xyz)
+        dens = hb.HipDensifier(self.table.device) if self.table.is_cuda else hb.HostDensifier(int(cfg.exp("host_threads")))
+        try:
+            sx, srgb, snrm, samples = dens.far_emit(self.table, S, min_samples, self.centre, radius, with_normals=with_normals)
+        finally:
+            dens.close()
+        count = self.table[:, 6]
+        report = {"mode": self.mode, "far_thresh_px": float(cfg.far_threshold()), "far_certainty": float(cfg.exp("far_certainty")),
+                  "far_min_views": int(cfg.exp("far_min_views")), "far_shell_cells": S, "far_min_samples": min_samples,
+                  "far_shell_radius": float(cfg.exp("far_shell_radius")), "centre": [float(v) for v in self.centre], "radius": float(radius),
+                  "direction_cells": 6 * S * S, "cells_occupied": int((count > 0).sum()), "cells_kept": int(sx.shape[0]),
+                  "samples": int(count.sum()), "samples_kept": int(samples.sum()),
+                  "far_cells": {self.names.get(uid, str(uid)): int(n) for uid, n in sorted(self.stats["far_cells"].items())},
+                  "far_cells_with_a_point": int(self.stats["overlap"])}
+        if _is_writer_rank():
+            with open(str(cfg.output_path) + ".shell.json", "w") as f:
+                json.dump(report, f, indent=1)
+        log.info(f"Far-field shell ({self.mode}): {report['cells_kept']} points from {report['samples_kept']} samples in {report['cells_occupied']} "
+                 f"occupied direction cells (S = {S}, at least {min_samples} samples), radius {radius:.4g} around the cameras' centre")
+        return sx, srgb, snrm
+
+    def write_file(self, xyz, with_normals: bool, clock=None) -> None:
+        """'file' mode beside an output this module does not pack itself (the Gaussian file, a PLY under another name)."""
+        sx, srgb, snrm = self.emit(xyz, with_normals)
+        _write_shell_file(self.shell_path, sx, srgb, snrm, clock)
+
+
+def _write_shell_file(path: str, sx, srgb, snrm, clock=None) -> None:
+    n = int(sx.shape[0])
+    if sx.is_cuda:
+        _write_output(path, np.empty((n, 0), np.float32), None, None, (sx, srgb), clock=clock, as_ply=True, normals=snrm)
+    else:
+        _write_output(path, sx.numpy(), srgb.numpy(), None, None, as_ply=True, normals=snrm.numpy() if snrm is not None else None)
+
+
+def _far_shell_of(result, config: DensePipelineConfig, camera_records):
+    """The run's FarShell, or None with the knob off (nothing runs)."""
+    if str(config.exp("far_shell")) == "off":
+        return None
+    if result.streamed_path is not None or getattr(result, "far_shell", None) is None:
+        raise RuntimeError("experimental['far_shell'] needs the cloud held as arrays and the run's direction table: this result has neither")
+    return FarShell(result.far_shell, config, camera_records)
 
 
 def _apply_consensus_filter(result, config: DensePipelineConfig, progress_callback=None):
@@ -739,6 +824,32 @@ def _write_output(path: str, xyz, rgb, err, device_points=None, clock=None, as_p
         write_points3D_bin(path, xyz, rgb8, err)
 
 
+def _write_final(shell, path: str, xyz, rgb, err, device_points=None, normals=None, **kw) -> None:
+    """``_write_output`` with the far-field shell (experimental['far_shell'], ``FarShell`` or None) placed around the cloud as it is written, in
+    front of packing: 'file' writes the shell beside an untouched main file, 'merge' appends its records behind the cloud's."""
+    if shell is None:
+        _write_output(path, xyz, rgb, err, device_points, normals=normals, **kw)
+        return
+    import torch
+    on_dev = device_points is not None and device_points[0].is_cuda and int(device_points[0].shape[0]) == int(xyz.shape[0])
+    sx, srgb, snrm = shell.emit(device_points[0] if on_dev else xyz, normals is not None)
+    if shell.mode == "file":
+        _write_output(path, xyz, rgb, err, device_points, normals=normals, **kw)
+        _write_shell_file(shell.shell_path, sx, srgb, snrm, kw.get("clock"))
+        return
+    if on_dev:
+        dev = device_points[0].device
+        device_points = (torch.cat([device_points[0], sx.to(dev)]), torch.cat([device_points[1], srgb.to(dev)]))
+        normals = torch.cat([normals.to(dev), snrm.to(dev)]) if normals is not None else None
+        xyz = np.empty((int(device_points[0].shape[0]), 0), np.float32)
+    else:
+        host = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)      # noqa: E731
+        xyz, rgb = np.concatenate([host(xyz), host(sx)]), np.concatenate([host(rgb), host(srgb)])
+        normals = np.concatenate([host(normals), host(snrm)]) if normals is not None else None
+        err, device_points = None, None
+    _write_output(path, xyz, rgb, err, device_points, normals=normals, **kw)
+
+
 def _cap_device_points(device_points, keep):
     """The GPU copy under the cap's index (``_cap_keep``)."""
     if device_points is None or keep is None:
@@ -804,6 +915,7 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
         if progress_callback:
             progress_callback(0.0, "Cancelled")
         return 2
+    shell = _far_shell_of(result, config, records)      # (experimental['far_shell']: placed around the final cloud, where it is written)
     result = _apply_gain_compensation(result, config, records, refs_local, progress_callback)      # (while the counts are still the loop's)
     result = _apply_consensus_filter(result, config, progress_callback)      # (in front of the point cap: it has to see the whole cloud)
     result = _apply_freespace_filter(result, config, records, refs_local, progress_callback)      # (behind it: what it removed cannot "see through" a surface)
@@ -815,7 +927,7 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
         n_points = result.n_points
     else:
         n_points = _finish_on_device(result, config.output_path, args.max_points, args.seed, clock=pipeline_kwargs.get("stage_clock"), config=config,
-                                     progress_callback=progress_callback)
+                                     progress_callback=progress_callback, shell=shell)
         if n_points is None:
             keep = _cap_keep(result.xyz, result.err, args.max_points, args.seed, progress_callback=progress_callback, **_cap_args(config))
             normals = _take_rows(result.normals, keep)
@@ -825,8 +937,10 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
                 err = None
             if bool(config.exp("gaussian_init")):
                 _write_gaussians(config, config.output_path, xyz, normals, rgb, clock=pipeline_kwargs.get("stage_clock"), progress_callback=progress_callback)
+                if shell is not None:
+                    shell.write_file(xyz, normals is not None)
             else:
-                _write_output(config.output_path, xyz, rgb, err, None, normals=normals)
+                _write_final(shell, config.output_path, xyz, rgb, err, None, normals=normals)
             n_points = int(xyz.shape[0])
     log.info(f"Dense reconstruction finished: {n_points:,} points -> {config.output_path}")
     if progress_callback:
@@ -868,6 +982,7 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
     if _was_cancelled(cancel_requested):
         return 2, "Cancelled"
     try:
+        shell = _far_shell_of(result, config, records)      # (experimental['far_shell']: placed around the final cloud, where it is written)
         result = _apply_gain_compensation(result, config, records, refs_local, progress_callback)      # (while the counts are still the loop's)
         result = _apply_consensus_filter(result, config, progress_callback)  # (in front of the point cap and the voxel filter: it has to see the whole cloud)
         result = _apply_freespace_filter(result, config, records, refs_local, progress_callback)   # (behind it, in front of cap and voxel filter)
@@ -888,7 +1003,7 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
             progress_callback(95.0, "Writing output PLY...")
         try:
             n_written = _finish_on_device(result, config.output_path, config.max_points, config.seed, clock=pipeline_kwargs.get("stage_clock"),
-                                          config=config, progress_callback=progress_callback)
+                                          config=config, progress_callback=progress_callback, shell=shell)
         except (SpatialCapRefused, OrientedFusionRefused, GaussianInitRefused) as exc:
             return 1, str(exc)
         log.info(f"Dense point cloud saved to {config.output_path} ({n_written:,} points)")
@@ -913,7 +1028,8 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
             if progress_callback:
                 progress_callback(95.0, "Writing output PLY...")
             # upstream always writes a PLY here, whatever the name
-            _write_output(config.output_path, np.empty((n_vox, 0), np.float32), None, None, voxels, clock=pipeline_kwargs.get("stage_clock"), as_ply=True)
+            _write_final(shell, config.output_path, np.empty((n_vox, 0), np.float32), None, None, voxels, clock=pipeline_kwargs.get("stage_clock"),
+                         as_ply=True)
             log.info(f"Dense point cloud saved to {config.output_path} ({n_vox:,} points)")
             if progress_callback:
                 progress_callback(100.0, f"Done! {n_vox:,} points")
@@ -948,13 +1064,17 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
             os.makedirs(d, exist_ok=True)
         if _is_writer_rank():
             write_ply(config.output_path, xyz, to_uint8_rgb(rgb))
+        if shell is not None:                           # ('merge' needs a .ply name: this is 'file')
+            shell.write_file(xyz, False)
     elif bool(config.exp("gaussian_init")):             # (needs estimate_normals, which makes output_path a .ply)
         try:
             _write_gaussians(config, config.output_path, xyz, normals, rgb, clock=pipeline_kwargs.get("stage_clock"), progress_callback=progress_callback)
         except GaussianInitRefused as exc:
             return 1, str(exc)
+        if shell is not None:
+            shell.write_file(xyz, normals is not None)
     else:
-        _write_output(config.output_path, xyz, rgb, err, dev_pts if normals is None else None, normals=normals)
+        _write_final(shell, config.output_path, xyz, rgb, err, dev_pts if normals is None else None, normals=normals)
     log.info(f"Dense point cloud saved to {config.output_path} ({xyz.shape[0]:,} points)")
     if progress_callback:
         progress_callback(100.0, f"Done! {xyz.shape[0]:,} points")
@@ -1005,6 +1125,11 @@ def _experimental_from_args(args) -> dict:
         exp["multiview_colour"] = str(args.multiview_colour)
     if str(getattr(args, "gain_compensation", None) or "off") != "off":
         exp["gain_compensation"] = str(args.gain_compensation)
+    if str(getattr(args, "far_shell", None) or "off") != "off":
+        exp["far_shell"] = str(args.far_shell)
+    for key in ("far_thresh_px", "far_certainty", "far_min_views", "far_shell_cells", "far_min_samples", "far_shell_radius"):
+        if getattr(args, key, None) is not None:
+            exp[key] = getattr(args, key)
     if float(getattr(args, "min_photo_ncc", 0.0) or 0.0) != 0.0:
         exp["min_photo_ncc"] = float(args.min_photo_ncc)
     for key, cast in (("photo_window_cells", int), ("photo_min_texture", float)):
@@ -1135,6 +1260,21 @@ def build_argparser() -> argparse.ArgumentParser:
                     help="... over the (2 r + 1)^2 grid cells of this radius around the point's cell (1 .. 3; default 2)")
     ap.add_argument("--photo_min_texture", type=float, default=None,
                     help="... keeping points whose patches have a standard deviation below this many 8-bit grey levels (no evidence; default 2)")
+    ap.add_argument("--far_shell", choices=("off", "file", "merge"), default="off",
+                    help="points at infinity for sky and distant background: the grid cells every confident neighbour sees where the rotation-only "
+                         "transfer predicts become one point per direction cell on a sphere around the cameras - in <out_name stem>_shell.ply "
+                         "(file) or behind the cloud's records in the main PLY (merge); writes <out_name>.shell.json")
+    ap.add_argument("--far_thresh_px", type=float, default=None,
+                    help="... agreement with infinity in px of the neighbour's camera image (default 0 = reproj_thresh; needs --far_shell)")
+    ap.add_argument("--far_certainty", type=float, default=None,
+                    help="... raw certainty from which a neighbour is confident, in (0, 1] (default 0.5, a design default; needs --far_shell)")
+    ap.add_argument("--far_min_views", type=int, default=None, help="... confident neighbours a far cell needs, 1 .. 8 (default 2; needs --far_shell)")
+    ap.add_argument("--far_shell_cells", type=int, default=None,
+                    help="... direction cells along a cube face's side, 8 .. 512 (default 256; needs --far_shell)")
+    ap.add_argument("--far_min_samples", type=int, default=None,
+                    help="... samples a direction cell needs to become a point (default 2; needs --far_shell)")
+    ap.add_argument("--far_shell_radius", type=float, default=None,
+                    help="... radius of the sphere in scene units (default 0 = automatic; needs --far_shell)")
     ap.add_argument("--estimate_normals", action="store_true",
                     help="give every point a unit surface normal, fitted to its winning neighbour's warp around its grid cell and oriented towards "
                          "its reference's camera: the PLY then has x y z nx ny nz red green blue vertices (needs a .ply --out_name)")
