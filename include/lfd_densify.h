@@ -643,6 +643,30 @@ int lfd_far_emit(lfd_context* ctx, const uint64_t* table, int32_t shell_cells, i
 int lfd_far_emit_host(lfd_context* ctx, const uint64_t* table, int32_t shell_cells, int64_t min_samples, const double* centre, double radius,
                       float* xyz, float* rgb, float* normal, int32_t* samples, int64_t capacity, int64_t* n_out);
 
+/* Epipolar audit: pose health from the matches (no upstream counterpart).  Reads the batch only; independent of the point stages.
+ * Per reference r, per grid cell c whose mask_a, where present, is set, and per slot j < n_slots[r] (csrc/lfd_audit.hpp, every rounding
+ * written out):
+ *   the slot is CONFIDENT exactly as lfd_far_accumulate's is, at audit_certainty: its raw certainty is >= audit_certainty (a NaN is not), its
+ *            observation lies inside the neighbour's grid, and mask_b, where present, is set at the pixel the support filter looks at;
+ *   (ua, va), (ub, vb)  the match in camera px as the dense kernel forms it, f32: ((x + 1) * 0.5) * (w_match - 1) * sx and so on, the A-coordinate
+ *            from warp channels 0 / 1 of slot 0 with four-channel warps, from axis_x / axis_y (or the matcher's grid) with two;
+ *   in f64 from the widened f32 values, every product and sum rounded separately, F the pair's fundamental matrix (f32 values):
+ *            l_i = (F_3i ua + F_3i+1 va) + F_3i+2,  num = (ub l0 + vb l1) + l2,  n2 = l0 l0 + l1 l1,  num2 = num num;
+ *   the sample is USABLE iff num2 and n2 are finite and n2 > 0, else DEGENERATE;
+ *   bin      the number of b in 0 .. 62 with num2 >= RN(((b + 1)^2 / 64) n2): no division, no root.  bin b < 63: the observation lies
+ *            [b / 8, (b + 1) / 8) px of the NEIGHBOUR's camera image (reproj_thresh's unit) off its epipolar line; bin 63: >= 7.875 px.
+ * Row r * k + j of table, u64 [n_refs * k][66]: column 0 += 1 per usable sample, column 1 += 1 per degenerate one, column 2 + bin += 1.  The
+ * table is ADDED to, never cleared; rows of slots >= n_slots[r] are not touched.  Integer additions only (an aggregation inside the wave, one
+ * table per workgroup, then at most one no-return 64-bit atomic per workgroup, slot and non-zero quantity), so the content does not depend on
+ * launch geometry and the device and the twin agree on every element.  best: NULL, or u8 [n_refs * H * W] where the context computes, WRITTEN,
+ * not added to: the smallest bin over the cell's usable confident slots, 255 where there is none or mask_a is unset - the best that any
+ * confident neighbour says about the cell, in the winning slot's camera px.  One launch on the context's stream, asynchronous.
+ * LFD_ERR_INVALID: a null table, audit_certainty not finite or <= 0, a table or best overlapping the batch's planes or each other, more than
+ * 65535 references.  lfd_epipolar_audit_host: the same routine over host pointers on a host context's threads.  A host context is served by
+ * _host only, a device context refuses _host (LFD_ERR_STATE). */
+int lfd_epipolar_audit(lfd_context* ctx, const lfd_batch* batch, float audit_certainty, uint64_t* table, uint8_t* best);
+int lfd_epipolar_audit_host(lfd_context* ctx, const lfd_batch* batch, float audit_certainty, uint64_t* table, uint8_t* best);
+
 /* Photo-consistency gate on triangulated points (no upstream counterpart - every other gate is geometric).  The test concerns
  * the MATCH that made a point, not X: xyz is carried along and never read.  Per input point of reference r made by winning slot s on cell
  * (y, x) of the H x W grid (csrc/lfd_photo.hpp, exact integers, every rounding written out):

@@ -236,6 +236,8 @@ def load_library() -> C.CDLL:
     lib.lfd_far_accumulate_host.argtypes = list(lib.lfd_far_accumulate.argtypes)
     lib.lfd_far_accumulate_flags.argtypes = list(lib.lfd_far_accumulate.argtypes) + [C.c_void_p]
     lib.lfd_far_accumulate_flags_host.argtypes = list(lib.lfd_far_accumulate_flags.argtypes)
+    lib.lfd_epipolar_audit.argtypes = [ctxp, C.POINTER(lfd_batch), C.c_float, C.c_void_p, C.c_void_p]
+    lib.lfd_epipolar_audit_host.argtypes = list(lib.lfd_epipolar_audit.argtypes)
     lib.lfd_far_emit.argtypes = [ctxp, C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     lib.lfd_far_emit_host.argtypes = list(lib.lfd_far_emit.argtypes)
@@ -1197,6 +1199,30 @@ def _far_accumulate_call(fn, ctx, batch, far_thresh_px, far_certainty, far_min_v
     return rc, table
 
 
+AUDIT_QUANTITIES = 66                        # LFD_AUDIT_QUANTITIES of csrc/lfd_audit.hpp: usable, degenerate, 64 bins of 1/8 px per (reference, slot)
+AUDIT_NONE = 255                             # the cell map's "no usable confident slot"
+
+
+def audit_table(n_refs: int, k: int, device) -> torch.Tensor:
+    """A zeroed table of the epipolar audit: int64 (n_refs * k, 66) - the library's u64 counts, far below 2^63."""
+    return torch.zeros((int(n_refs) * int(k), AUDIT_QUANTITIES), dtype=torch.int64, device=device)
+
+
+def _epipolar_audit_call(fn, ctx, batch, audit_certainty, table, best, device):
+    """One lfd_epipolar_audit[_host] call.  ``table``: None (a zeroed one is made) or a contiguous int64 (n_refs * k, 66) tensor where the
+    context computes, ADDED to; ``best``: None or a contiguous uint8 (n_refs, H * W) tensor there, written.  Returns (rc, table)."""
+    rows = batch.n_refs * batch.k
+    if table is None:
+        table = audit_table(batch.n_refs, batch.k, device)
+    elif table.dtype != torch.int64 or tuple(table.shape) != (rows, AUDIT_QUANTITIES) or table.device != device or not table.is_contiguous():
+        raise ValueError(f"epipolar_audit: table must be a contiguous int64 ({rows}, {AUDIT_QUANTITIES}) tensor on {device}")
+    if best is not None and (best.dtype != torch.uint8 or tuple(best.shape) != (batch.n_refs, batch.H * batch.W) or best.device != device
+                             or not best.is_contiguous()):
+        raise ValueError(f"epipolar_audit: best must be a contiguous uint8 ({batch.n_refs}, {batch.H * batch.W}) tensor on {device}")
+    rc = fn(ctx, C.byref(batch.c), C.c_float(float(audit_certainty)), table.data_ptr(), best.data_ptr() if best is not None else None)
+    return rc, table
+
+
 def _far_emit_call(fn, ctx, table, shell_cells, min_samples, centre, radius, with_normals, capacity, device):
     """One lfd_far_emit[_host] call.  Returns (rc, n_out, xyz, rgb, normals or None, samples): the tensors hold min(n_out, capacity) records.
     ``capacity`` None: the number of direction cells that reach ``min_samples`` (an upper bound of what is emitted)."""
@@ -1987,6 +2013,18 @@ class HipDensifier:
         self._check(rc, "lfd_far_accumulate")
         return table
 
+    def epipolar_audit(self, batch: PreparedBatch, audit_certainty: float, table: Optional[torch.Tensor] = None,
+                       best: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The epipolar audit's statistics (lfd_epipolar_audit): every confident match of ``batch`` is measured against its pair's
+        epipolar line and counted in row ``r * k + j`` of ``table``: int64 (n_refs * k, 66) on the device - usable, degenerate, 64 bins of an
+        eighth of a neighbour's camera pixel - ADDED to (None: a zeroed one is made); ``best``: uint8 (n_refs, H * W), written with the smallest
+        bin of each cell (255: none).  One launch on the context's stream, asynchronous; returns the table."""
+        self._same_device(batch, None, table, best)
+        with torch.cuda.stream(self.stream):
+            rc, table = _epipolar_audit_call(self._lib.lfd_epipolar_audit, self._ctx, batch, audit_certainty, table, best, self.device)
+        self._check(rc, "lfd_epipolar_audit")
+        return table
+
     def far_emit(self, table: torch.Tensor, shell_cells: int, min_samples: int, centre, radius: float, with_normals: bool = False):
         """The shell's points (lfd_far_emit) from ``table``: (xyz, rgb, normals or None, samples) device tensors, one record per
         direction cell with at least ``min_samples`` samples, in key order, at ``centre + radius * d_hat``.  Synchronous."""
@@ -2504,6 +2542,14 @@ class HostDensifier:
         rc, table = _far_accumulate_call(fn, self._ctx, batch, far_thresh_px, far_certainty, far_min_views, shell_cells, table, counters,
                                          self.device, flags)
         self._check(rc, "lfd_far_accumulate_host")
+        return table
+
+    def epipolar_audit(self, batch: PreparedBatch, audit_certainty: float, table: Optional[torch.Tensor] = None,
+                       best: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """HipDensifier.epipolar_audit over CPU tensors (lfd_epipolar_audit_host): the same routine, the same integers."""
+        self._same_device(batch, None, table, best)
+        rc, table = _epipolar_audit_call(self._lib.lfd_epipolar_audit_host, self._ctx, batch, audit_certainty, table, best, self.device)
+        self._check(rc, "lfd_epipolar_audit_host")
         return table
 
     def far_emit(self, table: torch.Tensor, shell_cells: int, min_samples: int, centre, radius: float, with_normals: bool = False):

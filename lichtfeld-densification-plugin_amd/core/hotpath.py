@@ -121,6 +121,11 @@ class HotPath:
         self.far_cells = int(config.exp("far_shell_cells"))
         self._far_table: Optional[torch.Tensor] = None          # the run's table, int64 (6 S S, 7) where the kernels run
         self._far_parts: list = []                              # (far cells per reference, reference uids, overlap or None) per launch the run used
+        # epipolar audit (lfd_epipolar_audit): once per launch on the stream that holds the batch, where the far shell's launch is
+        self.audit = str(config.exp("epipolar_audit")) != "off"
+        self.audit_certainty = float(config.exp("audit_certainty"))
+        self.audit_maps = self.audit and str(config.exp("audit_maps_dir")) != ""
+        self._audit_parts: list = []                            # (table, (reference uid, neighbour uid) or None per row, cell map or None, reference uids, (H, W)) per launch the run used
         self._uids = [int(c.uid) for c in cams]
         self._gain_parts: list = []                             # (table where the kernels run, reference uids, neighbour uids) per launch the run used
         on = bool(config.exp("undistort_images"))
@@ -161,6 +166,9 @@ class HotPath:
         if self.far:
             with self.clock.stage("kernel"):
                 far_part = self._far_launch(batch, pending=False)
+        if self.audit:
+            with self.clock.stage("kernel"):
+                self._audit_commit(self._audit_launch(batch))
         if res is None:
             self._far_commit(far_part, None)
             return res
@@ -237,6 +245,39 @@ class HotPath:
                 cells[int(uid)] = cells.get(int(uid), 0) + int(n)
             overlap += int(ov.item()) if ov is not None else 0
         return dict(table=table, far_cells=cells, overlap=overlap)
+
+    # -- epipolar audit (lfd_epipolar_audit) --------------------------------------------------------------------------------------
+    def _audit_launch(self, batch: hb.PreparedBatch):
+        """One launch of lfd_epipolar_audit over ``batch`` on the stream that holds it, into a zeroed table of the launch's own (its rows are
+        the batch's (reference, slot) pairs); nothing is read back here.  ``_audit_commit`` makes it part of the run - at once where the
+        launch's result is the run's, in ``finish_sampled`` for a grouped sampled call (the far shell's rule: a call that is void as a whole
+        and redone reference by reference counts once).  With experimental['audit_maps_dir'] the launch also writes the cell map."""
+        best = torch.empty((batch.n_refs, batch.H * batch.W), dtype=torch.uint8, device=self.dev) if self.audit_maps else None
+        table = self.dens.epipolar_audit(batch, self.audit_certainty, best=best)
+        pairs = []
+        for r in batch.refs:
+            row = [(self._uids[int(r.ref_cam)], self._uids[int(n)]) for n in r.nbr_cams]
+            pairs.extend(row + [None] * (batch.k - len(row)))
+        return table, pairs, best, [self._uids[int(r.ref_cam)] for r in batch.refs], (batch.H, batch.W)
+
+    def _audit_commit(self, part) -> None:
+        if part is not None:
+            self._audit_parts.append(part)
+
+    def audit_result(self) -> dict:
+        """The run's audit: ``rows`` {(reference uid, neighbour uid): the pair's 66 integers summed over the run} and ``maps`` {reference uid:
+        uint8 (H, W) cell map} (None without experimental['audit_maps_dir']).  The one read of the tables."""
+        rows: dict = {}
+        maps = {} if self.audit_maps else None
+        for table, pairs, best, ref_uids, grid in self._audit_parts:
+            for pair, row in zip(pairs, table.cpu().tolist()):
+                if pair is not None:
+                    have = rows.get(pair)
+                    rows[pair] = row if have is None else [a + b for a, b in zip(have, row)]
+            if maps is not None and best is not None:
+                for uid, m in zip(ref_uids, best.cpu().numpy()):
+                    maps[int(uid)] = m.reshape(grid)
+        return dict(rows=rows, maps=maps)
 
     # -- per-image exposure gains (lfd_gain_accumulate, DESIGN.md 4.23) -------------------------------------------------------------------------
     def _gain_launch(self, batch: hb.PreparedBatch, out):
@@ -377,6 +418,8 @@ class HotPath:
             out = self._with_normals(batch, out)
         if self.far:
             out.far_pending = self._far_launch(batch, pending=True)    # (committed in finish_sampled, like the gain statistics)
+        if self.audit:
+            out.audit_pending = self._audit_launch(batch)              # (likewise)
         return out
 
     # -- multi-view re-triangulation of supported points (lfd_refine_multiview) ---------------------------------------------------
@@ -605,6 +648,7 @@ class HotPath:
         out.normals_valid = False              # (whatever fills them next has not had its normals estimated)
         out.gain_pending = None
         out.far_pending = None
+        out.audit_pending = None
         return out
 
     # -- upstream's normaliser without stalling the launch stream ---------------------------------------------------------------
@@ -768,6 +812,7 @@ class HotPath:
             if not void:
                 self._gain_commit(getattr(out, "gain_pending", None))
                 self._far_commit(getattr(out, "far_pending", None), res)
+                self._audit_commit(getattr(out, "audit_pending", None))
             if not res.count and check_selection:
                 return None
             return dataclasses.replace(res, xyz=res.xyz.clone(), rgb=res.rgb.clone(), err=res.err.clone(),
@@ -777,6 +822,7 @@ class HotPath:
         finally:
             out.gain_pending = None
             out.far_pending = None
+            out.audit_pending = None
             self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, _pool_kind(out)), []).append(out)
 
     def pack_ply_tensor(self, xyz: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
@@ -819,6 +865,8 @@ class HotPath:
                 if self.normals:
                     out = self._with_normals(batch, out)
                 far_part = self._far_launch(batch, pending=False) if self.far else None
+                if self.audit:
+                    self._audit_commit(self._audit_launch(batch))
                 self.dens.check_launches()
                 res = out.collect()
                 self._support_void = False

@@ -33,6 +33,7 @@ from __future__ import annotations
 
 import dataclasses
 import gc
+import os
 import time
 from typing import Callable, List, Optional
 
@@ -255,6 +256,9 @@ def run_dense_pipeline(
     if world > 1 and str(config.exp("far_shell")) != "off":
         raise ValueError("experimental['far_shell'] cannot run sharded over several GPUs: the direction table is a statistic of the single-GPU "
                          "run, and the exchange of a sharded run does not carry it")
+    if world > 1 and str(config.exp("epipolar_audit")) != "off":
+        raise ValueError("experimental['epipolar_audit'] cannot run sharded over several GPUs: the histograms are a statistic of the single-GPU "
+                         "run, and the exchange of a sharded run does not carry them")
     if world > 1 and str(config.exp("depth_maps_dir")) != "":
         raise ValueError("experimental['depth_maps_dir'] cannot run sharded over several GPUs: the maps are a stage of the single-GPU run, and with "
                          "gather_to_root only one rank would hold the cloud they are rendered from")
@@ -281,7 +285,7 @@ def run_dense_pipeline(
                          cancel_requested=cancel_requested, total_pairs_est=total_pairs_est)
     t0 = time.time()
     own_matcher = matcher is None
-    prefetch = hot = feat_cache = strategy = gain_rows = far_shell = None
+    prefetch = hot = feat_cache = strategy = gain_rows = far_shell = epipolar_audit = None
     rank_status, rank_error = 0, None         # 0 fine, 1 cancelled, 2 failed: agreed on by all ranks before the exchange step (core/distributed.py)
     try:
         if own_matcher:
@@ -390,6 +394,12 @@ def run_dense_pipeline(
             log.info(f"Far-field shell: {sum(far_shell['far_cells'].values())} far cells (every confident neighbour within {hot.far_thresh_px:g} px of "
                      f"the rotation-only transfer, certainty >= {hot.far_certainty:g}) in {int((t6 > 0).sum())} of {t6.numel()} direction cells, "
                      f"{far_shell['overlap']} of them also produced a point")
+        if hot.audit:
+            from . import audit as audit_report
+            epipolar_audit = hot.audit_result()
+            names = {int(c.uid): os.path.basename(str(c.image_path)) for c in camera_records}
+            epipolar_audit["report"] = audit_report.build_report(epipolar_audit["rows"], names, int(config.exp("audit_min_samples")),
+                                                                 config.audit_warn_threshold(), hot.audit_certainty)
         if hot.normals:
             n_fit, n_fell = hot.normal_totals()
             log.info(f"Surface normals: window radius {hot.normal_radius} cell(s), depth step {hot.normal_depth_step:g}, {n_fit} points fitted, "
@@ -419,6 +429,7 @@ def run_dense_pipeline(
     result = outputs.result(t0, clock)
     result.gain_rows = gain_rows          # experimental['gain_compensation']: the run's statistics, for the solve (densify.py)
     result.far_shell = far_shell          # experimental['far_shell']: the run's direction table, for the shell (densify.py)
+    result.epipolar_audit = epipolar_audit      # experimental['epipolar_audit']: the pairs' histograms, the report and the cell maps (densify.py)
     return result
 
 

@@ -274,6 +274,8 @@ class SampledLoop:
                     handle[1].gain_pending = None       # (experimental['gain_compensation']: its statistics go with its results)
                 if getattr(handle[1], "far_pending", None) is not None:
                     handle[1].far_pending = None        # (experimental['far_shell']: likewise)
+                if getattr(handle[1], "audit_pending", None) is not None:
+                    handle[1].audit_pending = None      # (experimental['epipolar_audit']: likewise)
                 self.hot.finish_sampled(handle, check_selection=False)       # waited for, its buffers back in the pool, its results dropped
             except Exception:
                 pass

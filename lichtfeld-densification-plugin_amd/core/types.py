@@ -205,7 +205,25 @@ EXPERIMENTAL_DEFAULTS = {
     "far_min_samples": 2,
     # ... radius of the sphere in scene units; 0 = automatic: max(10 x the cameras' spread, 1.25 x the cloud's) around the cameras' mean centre
     "far_shell_radius": 0.0,
+    # epipolar audit (lfd_epipolar_audit): a report on the camera poses from the run's own matches.  Every confident match is
+    # measured against its pair's epipolar line as the poses give it, in eighths of a px of the neighbour's camera image, and counted per
+    # (reference, neighbour) pair; at the end of the run <output file>.audit.json holds the histograms, per-pair medians, a score per camera
+    # (the lower median of its pairs' medians) and the cameras whose score exceeds audit_warn_px - each of them is logged as a warning.  The
+    # statistics move no point: cloud, counts and order are the knob-off run's.  It sees only the error ACROSS the epipolar lines, cannot tell
+    # a pose from intrinsics or distortion (see undistort_images), and contains the matcher's own error.  "off" = no new code runs.
+    "epipolar_audit": "off",
+    # ... a neighbour is confident at a cell when its raw certainty is at least this, in (0, 1].  far_certainty's design default, not a measurement.
+    "audit_certainty": 0.5,
+    # ... a pair is judged when it has at least this many confident matches, >= 1.  A design default.
+    "audit_min_samples": 256,
+    # ... a camera is suspect when its score exceeds this many px of a camera image; 0 = reproj_thresh
+    "audit_warn_px": 0.0,
+    # ... directory (relative to the output file's) for one <image stem>_epi.npy per reference: f32 (H, W), the smallest distance any confident
+    # neighbour reports for the cell in px of that neighbour's camera image, NaN where there is none - what moved between the photographs
+    "audit_maps_dir": "",
 }
+AUDIT_MODES = ("off", "report")
+AUDIT_KNOBS = ("audit_certainty", "audit_min_samples", "audit_warn_px", "audit_maps_dir")
 FAR_MODES = ("off", "file", "merge")
 FAR_KNOBS = ("far_thresh_px", "far_certainty", "far_min_views", "far_shell_cells", "far_min_samples", "far_shell_radius")
 CAP_MODES = ("random", "spatial")
@@ -292,6 +310,11 @@ class DensePipelineConfig:
         """Threshold of the multi-view support filter in px of the neighbour's camera image (experimental['support_thresh_px'], 0 = 2 * reproj_thresh)."""
         tau = float(self.exp("support_thresh_px"))
         return tau if tau > 0.0 else 2.0 * float(self.reproj_thresh)
+
+    def audit_warn_threshold(self) -> float:
+        """The score above which the epipolar audit calls a camera suspect, in px (experimental['audit_warn_px'], 0 = reproj_thresh)."""
+        tau = float(self.exp("audit_warn_px"))
+        return tau if tau > 0.0 else float(self.reproj_thresh)
 
     def far_threshold(self) -> float:
         """Threshold of the far-field shell's agreement test in px of the neighbour's camera image (experimental['far_thresh_px'], 0 = reproj_thresh)."""
@@ -688,6 +711,32 @@ class DensePipelineConfig:
                             "distance to take a scale from; use 'file'")
                 if not str(self.output_path).lower().endswith(".ply"):
                     return "experimental['far_shell'] = 'merge' appends PLY records: output_path must end in .ply (use 'file' with other formats)"
+        audit = self.exp("epipolar_audit")
+        if not isinstance(audit, str) or audit not in AUDIT_MODES:
+            return "experimental['epipolar_audit'] must be 'off' or 'report' (<output file>.audit.json and a warning per suspect camera)"
+        if not number(self.exp("audit_certainty")) or not (0.0 < float(self.exp("audit_certainty")) <= 1.0):
+            return "experimental['audit_certainty'] must be in (0, 1] (the raw certainty from which a match is counted)"
+        if not whole(self.exp("audit_min_samples")) or int(self.exp("audit_min_samples")) < 1:
+            return "experimental['audit_min_samples'] must be an integer >= 1 (confident matches a pair needs to be judged)"
+        if not number(self.exp("audit_warn_px")) or float(self.exp("audit_warn_px")) < 0.0:
+            return "experimental['audit_warn_px'] must be a finite number >= 0 (px of a camera image; 0 = reproj_thresh)"
+        if not isinstance(self.exp("audit_maps_dir"), str):
+            return "experimental['audit_maps_dir'] must be a string (a directory, relative to the output file's; '' = no maps)"
+        if audit == "off":
+            for key in AUDIT_KNOBS:
+                if self.exp(key) != EXPERIMENTAL_DEFAULTS[key]:
+                    return f"experimental['{key}'] is a knob of the epipolar audit: it needs experimental['epipolar_audit'] = 'report'"
+        else:
+            if not (self.audit_warn_threshold() > 0.0):
+                return "experimental['epipolar_audit'] warns in pixels: experimental['audit_warn_px'] or, for its default, reproj_thresh must be > 0"
+            if self.stream_output:
+                return ("experimental['epipolar_audit'] is launched beside the point stages of a collected result; stream_output writes records "
+                        "while the run proceeds and has no such site")
+            if self.exp("dense_tile_segments"):
+                return ("experimental['epipolar_audit'] is launched beside the ordered dense result; dense mode with "
+                        "experimental['dense_tile_segments'] retires tiles into the file's records")
+            if self.exchange_record_format() == "ply":
+                return "experimental['epipolar_audit'] is launched beside f32 rows; experimental['exchange_records'] must be 'f32' with it"
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):
                 return "stream_output writes a PLY while the run proceeds: output_path must end in .ply"

@@ -25,6 +25,7 @@
 #include "lfd_photo.hpp"
 #include "lfd_gain.hpp"
 #include "lfd_far.hpp"
+#include "lfd_audit.hpp"
 #include "lfd_sigma.hpp"
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
@@ -146,6 +147,7 @@ hipError_t lfd_gain_apply_launch(const LfdGainApplyArgs& p, hipStream_t stream);
 hipError_t lfd_far_launch(const LfdFarArgs& p, bool reduce, hipStream_t stream);   // lfd_far.hip
 hipError_t lfd_far_mark_launch(const unsigned long long* table, long long n_cells, long long min_samples, uint8_t* keep, hipStream_t stream);
 hipError_t lfd_far_emit_launch(const LfdFarEmitArgs& p, hipStream_t stream);
+hipError_t lfd_audit_launch(const LfdAuditArgs& p, bool aggregate, hipStream_t stream);   // lfd_audit.hip
 extern "C" __global__ void lfd_pack_ply_normals_kernel(const float* xyz, const float* normals, const float* rgb, long long n, unsigned char* out);
 extern "C" __global__ void lfd_select_topm_kernel(LfdSelectArgs A);
 extern "C" __global__ void lfd_select_filter_mw_kernel(LfdSelectArgs A, LfdSelectNorms norms);
@@ -2316,6 +2318,29 @@ int lfd_gain_apply(lfd_context* ctx, const float* rgb, int64_t n, const int64_t*
     p.offs = reinterpret_cast<const long long*>(ref_offsets);
     p.factors = factors; p.rgb = rgb; p.o_rgb = rgb_out; p.n = n; p.n_refs = n_refs;
     LFD_HIP(ctx, lfd_gain_apply_launch(p, ctx->stream));
+    return LFD_OK;
+}
+
+// ---- epipolar audit (lfd_audit.hip) -----------------------------------------------------------------------------------------------------------------
+int lfd_epipolar_audit(lfd_context* ctx, const lfd_batch* batch, float audit_certainty, uint64_t* table, uint8_t* best) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_audit_check(audit_certainty, table)) return fail(ctx, LFD_ERR_INVALID, std::string("lfd_epipolar_audit: ") + why);
+    LfdLaunch L;
+    int rc = batch_launch(ctx, batch, L);
+    if (rc != LFD_OK) return rc;
+    if (const char* why = lfd_audit_check_batch(batch, table, best)) return fail(ctx, LFD_ERR_INVALID, std::string("lfd_epipolar_audit: ") + why);
+    LfdAuditArgs p;
+    std::memset(&p, 0, sizeof(p));
+    p.refs = L.refs; p.slots = L.slots; p.ref_const = L.ref_const; p.pair_const = L.pair_const;
+    p.axis_x = L.axis_x; p.axis_y = L.axis_y;
+    p.table = reinterpret_cast<unsigned long long*>(table);
+    p.best = best;
+    p.n_refs = batch->n_refs; p.k = batch->k;
+    p.audit_certainty = audit_certainty;
+    p.g = launch_geom(batch, L, 0.0f, 0.0f);
+    const char* e = std::getenv("LFD_AUDIT_NO_AGGREGATE");             // profiling: every confident lane issues its own LDS adds (the same table)
+    LFD_HIP(ctx, lfd_audit_launch(p, !(e && std::atoi(e) != 0), ctx->stream));
     return LFD_OK;
 }
 

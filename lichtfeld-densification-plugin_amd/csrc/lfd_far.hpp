@@ -51,15 +51,21 @@ LFD_HD bool lfd_far_agree(const float* Pi, float sx, float sy, float d0, float d
     return pz > 0.0f && d2s <= t2;         // a NaN anywhere rejects
 }
 
-// Slot `sl` at a cell whose raw certainty and observation are cert and (wx, wy): confident (bit 0), confident and agreeing with infinity (bit 1)
-LFD_HD int lfd_far_slot(const LfdSlot& sl, const LfdSupportGeom& g, float far_certainty, float cert, float wx, float wy, float d0, float d1,
-                        float d2) {
+// Slot `sl` at a cell whose raw certainty and observation are cert and (wx, wy) is CONFIDENT: bit 0 of lfd_far_slot, and what the epipolar
+// audit (lfd_audit.hpp) counts
+LFD_HD bool lfd_far_confident(const LfdSlot& sl, const LfdSupportGeom& g, float far_certainty, float cert, float wx, float wy) {
     bool conf = cert >= far_certainty;     // a NaN is not confident
     if (conf) {
         const long long m = lfd_support_mask_index(wx, wy, g.W, g.H, g.mask_sx, g.mask_sy, g.w_match, g.h_match);   // -1: outside the neighbour
         conf = m >= 0 && (!sl.mask_b || sl.mask_b[m] != 0);
     }
-    if (!conf) return 0;
+    return conf;
+}
+
+// ... confident (bit 0), confident and agreeing with infinity (bit 1)
+LFD_HD int lfd_far_slot(const LfdSlot& sl, const LfdSupportGeom& g, float far_certainty, float cert, float wx, float wy, float d0, float d1,
+                        float d2) {
+    if (!lfd_far_confident(sl, g, far_certainty, cert, wx, wy)) return 0;
     return lfd_far_agree(sl.P, sl.sx, sl.sy, d0, d1, d2, wx, wy, g.wm1, g.hm1, g.tau) ? 3 : 1;
 }
 

@@ -401,6 +401,57 @@ def _write_shell_file(path: str, sx, srgb, snrm, clock=None) -> None:
         _write_output(path, sx.numpy(), srgb.numpy(), None, None, as_ply=True, normals=snrm.numpy() if snrm is not None else None)
 
 
+def _check_audit_maps(config: DensePipelineConfig, camera_records) -> None:
+    """experimental['audit_maps_dir'] names a reference's map after its image file, as the depth maps do: refused before the run when two image
+    files share a stem."""
+    if str(config.exp("epipolar_audit")) == "off" or str(config.exp("audit_maps_dir")) == "":
+        return
+    stems = {}
+    for rec in camera_records:
+        stem = os.path.splitext(os.path.basename(str(rec.image_path)))[0]
+        if stem == "" or stem in stems:
+            raise RuntimeError(f"experimental['audit_maps_dir'] names a camera's maps after its image file: {stems.get(stem, rec).image_path!r} and "
+                               f"{rec.image_path!r} both give {stem!r}")
+        stems[stem] = rec
+
+
+def _write_audit(result, config: DensePipelineConfig, camera_records) -> None:
+    """The epipolar audit of a run (experimental['epipolar_audit']): ``<output file>.audit.json`` - the knobs, every pair's
+    histogram and quantiles, every camera's score, the scene summary; no timing, so a device run and a host run write the same bytes - one
+    summary line, and one warning per suspect camera (one in all when more than half of them are).  With experimental['audit_maps_dir'] every
+    REFERENCE also gets ``<image stem>_epi.npy``: f32 (H, W), the smallest distance from the epipolar line any confident neighbour reports for
+    the cell, in px of that neighbour's camera image (bin / 8), NaN where there is none.  A side output: ``result`` is not changed."""
+    if str(config.exp("epipolar_audit")) == "off" or not _is_writer_rank():
+        return
+    from .core import audit as audit_report
+    got = getattr(result, "epipolar_audit", None)
+    if got is None:
+        raise RuntimeError("experimental['epipolar_audit'] needs the run's histograms: this result has none")
+    report = dict(got["report"])
+    maps_dir = str(config.exp("audit_maps_dir"))
+    if maps_dir != "":
+        _check_audit_maps(config, camera_records)
+        rel = maps_dir
+        if not os.path.isabs(maps_dir):
+            maps_dir = os.path.join(os.path.dirname(os.path.abspath(config.output_path)), maps_dir)
+        os.makedirs(maps_dir, exist_ok=True)
+        by_uid = {int(c.uid): c for c in camera_records}
+        entries = []
+        for uid in sorted(got["maps"] or {}):
+            m = got["maps"][uid]
+            stem = os.path.splitext(os.path.basename(str(by_uid[uid].image_path)))[0]
+            px = np.where(m == 255, np.float32(np.nan), m.astype(np.float32) / np.float32(8.0)).astype(np.float32)
+            np.save(os.path.join(maps_dir, stem + "_epi.npy"), px)
+            entries.append({"uid": uid, "image": os.path.basename(str(by_uid[uid].image_path)), "map": stem + "_epi.npy",
+                            "height": int(m.shape[0]), "width": int(m.shape[1]), "cells_with_data": int((m != 255).sum())})
+        report["maps"] = {"dir": rel, "unit": "px of the winning neighbour's camera image, lower edge of the bin", "references": entries}
+    with open(str(config.output_path) + ".audit.json", "w") as f:
+        f.write(audit_report.to_json(report))
+    log.info(audit_report.summary_line(report))
+    for line in audit_report.warnings(report):
+        log.warn(line)
+
+
 def _far_shell_of(result, config: DensePipelineConfig, camera_records):
     """The run's FarShell, or None with the knob off (nothing runs)."""
     if str(config.exp("far_shell")) == "off":
@@ -904,6 +955,7 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
         refs_per_launch=getattr(args, "refs_per_launch", 0), backend=getattr(args, "backend", "device"),
         stream_output=bool(getattr(args, "stream_output", False)), device_image_prep=bool(getattr(args, "device_image_prep", False)),
         experimental=_experimental_from_args(args))
+    _check_audit_maps(config, records)
     try:
         result = run_dense_pipeline(records, refs_local, nn_table, config, progress_callback=progress_callback,
                                     on_sequential_viz=None, debug_state=debug_state, cancel_requested=cancel_requested, **pipeline_kwargs)
@@ -915,6 +967,7 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
         if progress_callback:
             progress_callback(0.0, "Cancelled")
         return 2
+    _write_audit(result, config, records)               # (experimental['epipolar_audit']: a side output about the poses; moves nothing)
     shell = _far_shell_of(result, config, records)      # (experimental['far_shell']: placed around the final cloud, where it is written)
     result = _apply_gain_compensation(result, config, records, refs_local, progress_callback)      # (while the counts are still the loop's)
     result = _apply_consensus_filter(result, config, progress_callback)      # (in front of the point cap: it has to see the whole cloud)
@@ -972,6 +1025,7 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
     nn_table = nearest_neighbors(flat, nns)
     log.info(f"Prepared {len(records)} cameras (refs={len(refs_local)})")
     try:
+        _check_audit_maps(config, records)
         result = run_dense_pipeline(records, refs_local, nn_table, config, progress_callback=progress_callback,
                                     on_sequential_viz=on_sequential_viz, debug_state=debug_state,
                                     cancel_requested=cancel_requested, **pipeline_kwargs)
@@ -982,6 +1036,7 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
     if _was_cancelled(cancel_requested):
         return 2, "Cancelled"
     try:
+        _write_audit(result, config, records)               # (experimental['epipolar_audit']: a side output about the poses; moves nothing)
         shell = _far_shell_of(result, config, records)      # (experimental['far_shell']: placed around the final cloud, where it is written)
         result = _apply_gain_compensation(result, config, records, refs_local, progress_callback)      # (while the counts are still the loop's)
         result = _apply_consensus_filter(result, config, progress_callback)  # (in front of the point cap and the voxel filter: it has to see the whole cloud)
@@ -1125,6 +1180,13 @@ def _experimental_from_args(args) -> dict:
         exp["multiview_colour"] = str(args.multiview_colour)
     if str(getattr(args, "gain_compensation", None) or "off") != "off":
         exp["gain_compensation"] = str(args.gain_compensation)
+    if str(getattr(args, "epipolar_audit", None) or "off") != "off":
+        exp["epipolar_audit"] = str(args.epipolar_audit)
+    for key in ("audit_certainty", "audit_min_samples", "audit_warn_px"):
+        if getattr(args, key, None) is not None:
+            exp[key] = getattr(args, key)
+    if str(getattr(args, "audit_maps_dir", "") or "") != "":
+        exp["audit_maps_dir"] = str(args.audit_maps_dir)
     if str(getattr(args, "far_shell", None) or "off") != "off":
         exp["far_shell"] = str(args.far_shell)
     for key in ("far_thresh_px", "far_certainty", "far_min_views", "far_shell_cells", "far_min_samples", "far_shell_radius"):
@@ -1260,6 +1322,19 @@ def build_argparser() -> argparse.ArgumentParser:
                     help="... over the (2 r + 1)^2 grid cells of this radius around the point's cell (1 .. 3; default 2)")
     ap.add_argument("--photo_min_texture", type=float, default=None,
                     help="... keeping points whose patches have a standard deviation below this many 8-bit grey levels (no evidence; default 2)")
+    ap.add_argument("--epipolar_audit", choices=("off", "report"), default="off",
+                    help="report on the camera poses from the run's own matches: every confident match is measured against its pair's epipolar "
+                         "line; <output file>.audit.json holds per-pair medians and a score per camera, and every camera whose score exceeds "
+                         "--audit_warn_px is logged as suspect.  Sees only the error across the epipolar lines; moves no point")
+    ap.add_argument("--audit_certainty", type=float, default=None,
+                    help="... raw certainty from which a match is counted, in (0, 1] (default 0.5, a design default; needs --epipolar_audit)")
+    ap.add_argument("--audit_min_samples", type=int, default=None,
+                    help="... confident matches a pair needs to be judged (default 256, a design default; needs --epipolar_audit)")
+    ap.add_argument("--audit_warn_px", type=float, default=None,
+                    help="... a camera is suspect above this many px (default 0 = reproj_thresh; needs --epipolar_audit)")
+    ap.add_argument("--audit_maps_dir", type=str, default="",
+                    help="... directory (relative: to the output file's) for one <image stem>_epi.npy per reference: the smallest distance any "
+                         "confident neighbour reports per cell, NaN where none (needs --epipolar_audit)")
     ap.add_argument("--far_shell", choices=("off", "file", "merge"), default="off",
                     help="points at infinity for sky and distant background: the grid cells every confident neighbour sees where the rotation-only "
                          "transfer predicts become one point per direction cell on a sphere around the cameras - in <out_name stem>_shell.ply "
