@@ -667,6 +667,31 @@ int lfd_far_emit_host(lfd_context* ctx, const uint64_t* table, int32_t shell_cel
 int lfd_epipolar_audit(lfd_context* ctx, const lfd_batch* batch, float audit_certainty, uint64_t* table, uint8_t* best);
 int lfd_epipolar_audit_host(lfd_context* ctx, const lfd_batch* batch, float audit_certainty, uint64_t* table, uint8_t* best);
 
+/* Pose corrections from the matches: the normal equations of one Gauss-Newton step on the epipolar error (no upstream
+ * counterpart).  Reads the batch and the uploaded camera table only; batch->fundamental is NOT used (a caller's F says nothing about R and t).
+ * Per pair (reference A = ref_cam[r], neighbour B = nbr_cam[r * k + j]), once per launch on the host, in f64 from the table's f32 values with
+ * every operation rounded separately:  R = R_B R_A^T,  t = t_B - R t_A,  tn = |t|,  th = t / tn (tn not finite or 0: every sample of the pair
+ * is degenerate),  K_A^-1 and K_B^-1 the closed-form inverses the library's own F uses.
+ * Per grid cell whose mask_a, where present, is set and per slot that is CONFIDENT exactly as lfd_epipolar_audit's is, at pose_certainty, with
+ * (ua, va), (ub, vb) the match in camera px formed as there (csrc/lfd_pose.hpp, f64, IEEE division and root, no contraction):
+ *   yA = K_A^-1 (ua, va, 1),  p = R yA,  n = th x p,  l = K_B^-T n,  num = (ub l0 + vb l1) + l2,  d2 = l0 l0 + l1 l1,  d = sqrt(d2),
+ *   r = num / d  (the signed distance from the epipolar line in px of B's camera image);
+ *   the foot point  ub' = ub - (r l0) / d,  vb' = vb - (r l1) / d,  yB = K_B^-1 (ub', vb', 1);
+ *   J[0..2] = (n x yB) / d,  J[3..5] = (p x yB) / d:  the derivative of r with respect to a left twist (omega, tau) of the RELATIVE pose
+ *   T_B T_A^-1, tau in units of tn, in px per radian;
+ *   DEGENERATE iff num, d2, num num or any later value is not finite, or d2 <= 0, or some |J_i| >= 2^16; otherwise OUTLIER iff
+ *   num num >= (c c) d2, c = pose_inlier_px (no division in the decision); otherwise INLIER with Jq_i = rint(8 J_i), rq = rint(1024 r).
+ * Row r * k + j of table, i64 [n_refs * k][32], is ADDED to (two's complement), never cleared: column 0 inliers, 1 outliers, 2 degenerate,
+ * 3 the sum of rq rq, 4..9 of Jq_i rq, 10..30 of Jq_i Jq_j for i <= j row-major; column 31 and rows of slots >= n_slots[r] are not touched.
+ * |Jq| <= 2^19, |rq| <= 2^16 and H W <= 2^24, so a launch adds less than 2^63 to a column.  Integer additions only (sums inside the wave, one
+ * table per workgroup, then at most one no-return 64-bit atomic per workgroup, slot and non-zero quantity): the content does not depend on
+ * launch geometry, and the device and the twin agree on every element.  One launch on the context's stream, asynchronous.
+ * LFD_ERR_INVALID: a null table, pose_certainty not in (0, 3.4e38], pose_inlier_px not in (0, 64], a table overlapping the batch's planes,
+ * more than 65535 references, H W > 2^24.  lfd_pose_accumulate_host: the same routine over host pointers on a host context's threads.  A host
+ * context is served by _host only, a device context refuses _host (LFD_ERR_STATE). */
+int lfd_pose_accumulate(lfd_context* ctx, const lfd_batch* batch, float pose_certainty, float pose_inlier_px, int64_t* table);
+int lfd_pose_accumulate_host(lfd_context* ctx, const lfd_batch* batch, float pose_certainty, float pose_inlier_px, int64_t* table);
+
 /* Photo-consistency gate on triangulated points (no upstream counterpart - every other gate is geometric).  The test concerns
  * the MATCH that made a point, not X: xyz is carried along and never read.  Per input point of reference r made by winning slot s on cell
  * (y, x) of the H x W grid (csrc/lfd_photo.hpp, exact integers, every rounding written out):

@@ -238,6 +238,8 @@ def load_library() -> C.CDLL:
     lib.lfd_far_accumulate_flags_host.argtypes = list(lib.lfd_far_accumulate_flags.argtypes)
     lib.lfd_epipolar_audit.argtypes = [ctxp, C.POINTER(lfd_batch), C.c_float, C.c_void_p, C.c_void_p]
     lib.lfd_epipolar_audit_host.argtypes = list(lib.lfd_epipolar_audit.argtypes)
+    lib.lfd_pose_accumulate.argtypes = [ctxp, C.POINTER(lfd_batch), C.c_float, C.c_float, C.c_void_p]
+    lib.lfd_pose_accumulate_host.argtypes = list(lib.lfd_pose_accumulate.argtypes)
     lib.lfd_far_emit.argtypes = [ctxp, C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     lib.lfd_far_emit_host.argtypes = list(lib.lfd_far_emit.argtypes)
@@ -1223,6 +1225,26 @@ def _epipolar_audit_call(fn, ctx, batch, audit_certainty, table, best, device):
     return rc, table
 
 
+POSE_QUANTITIES = 32                         # LFD_POSE_QUANTITIES of csrc/lfd_pose.hpp: inliers, outliers, degenerate, 28 signed sums, one unused, per (reference, slot)
+
+
+def pose_table(n_refs: int, k: int, device) -> torch.Tensor:
+    """A zeroed table of the pose refinement: int64 (n_refs * k, 32) - the normal equations of one Gauss-Newton step per pair, as integers."""
+    return torch.zeros((int(n_refs) * int(k), POSE_QUANTITIES), dtype=torch.int64, device=device)
+
+
+def _pose_accumulate_call(fn, ctx, batch, pose_certainty, pose_inlier_px, table, device):
+    """One lfd_pose_accumulate[_host] call.  ``table``: None (a zeroed one is made) or a contiguous int64 (n_refs * k, 32) tensor where the
+    context computes, ADDED to.  Returns (rc, table)."""
+    rows = batch.n_refs * batch.k
+    if table is None:
+        table = pose_table(batch.n_refs, batch.k, device)
+    elif table.dtype != torch.int64 or tuple(table.shape) != (rows, POSE_QUANTITIES) or table.device != device or not table.is_contiguous():
+        raise ValueError(f"pose_accumulate: table must be a contiguous int64 ({rows}, {POSE_QUANTITIES}) tensor on {device}")
+    rc = fn(ctx, C.byref(batch.c), C.c_float(float(pose_certainty)), C.c_float(float(pose_inlier_px)), table.data_ptr())
+    return rc, table
+
+
 def _far_emit_call(fn, ctx, table, shell_cells, min_samples, centre, radius, with_normals, capacity, device):
     """One lfd_far_emit[_host] call.  Returns (rc, n_out, xyz, rgb, normals or None, samples): the tensors hold min(n_out, capacity) records.
     ``capacity`` None: the number of direction cells that reach ``min_samples`` (an upper bound of what is emitted)."""
@@ -2025,6 +2047,17 @@ class HipDensifier:
         self._check(rc, "lfd_epipolar_audit")
         return table
 
+    def pose_accumulate(self, batch: PreparedBatch, pose_certainty: float, pose_inlier_px: float,
+                        table: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The pose refinement's statistics (lfd_pose_accumulate): every confident match of ``batch`` adds its row of the
+        Gauss-Newton normal equations of the epipolar error, as quantised integers, to row ``r * k + j`` of ``table``: int64 (n_refs * k, 32) on
+        the device, ADDED to (None: a zeroed one is made).  One launch on the context's stream, asynchronous; returns the table."""
+        self._same_device(batch, None, table)
+        with torch.cuda.stream(self.stream):
+            rc, table = _pose_accumulate_call(self._lib.lfd_pose_accumulate, self._ctx, batch, pose_certainty, pose_inlier_px, table, self.device)
+        self._check(rc, "lfd_pose_accumulate")
+        return table
+
     def far_emit(self, table: torch.Tensor, shell_cells: int, min_samples: int, centre, radius: float, with_normals: bool = False):
         """The shell's points (lfd_far_emit) from ``table``: (xyz, rgb, normals or None, samples) device tensors, one record per
         direction cell with at least ``min_samples`` samples, in key order, at ``centre + radius * d_hat``.  Synchronous."""
@@ -2550,6 +2583,14 @@ class HostDensifier:
         self._same_device(batch, None, table, best)
         rc, table = _epipolar_audit_call(self._lib.lfd_epipolar_audit_host, self._ctx, batch, audit_certainty, table, best, self.device)
         self._check(rc, "lfd_epipolar_audit_host")
+        return table
+
+    def pose_accumulate(self, batch: PreparedBatch, pose_certainty: float, pose_inlier_px: float,
+                        table: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """HipDensifier.pose_accumulate over CPU tensors (lfd_pose_accumulate_host): the same routine, the same integers."""
+        self._same_device(batch, None, table)
+        rc, table = _pose_accumulate_call(self._lib.lfd_pose_accumulate_host, self._ctx, batch, pose_certainty, pose_inlier_px, table, self.device)
+        self._check(rc, "lfd_pose_accumulate_host")
         return table
 
     def far_emit(self, table: torch.Tensor, shell_cells: int, min_samples: int, centre, radius: float, with_normals: bool = False):

@@ -126,6 +126,11 @@ class HotPath:
         self.audit_certainty = float(config.exp("audit_certainty"))
         self.audit_maps = self.audit and str(config.exp("audit_maps_dir")) != ""
         self._audit_parts: list = []                            # (table, (reference uid, neighbour uid) or None per row, cell map or None, reference uids, (H, W)) per launch the run used
+        # pose refinement (lfd_pose_accumulate): once per launch beside the audit's, with the audit's pending / commit rule
+        self.pose = str(config.exp("pose_refine")) != "off"
+        self.pose_certainty = float(config.exp("pose_certainty"))
+        self.pose_inlier_px = float(config.exp("pose_inlier_px"))
+        self._pose_parts: list = []                             # (table, (reference uid, neighbour uid) or None per row) per launch the run used
         self._uids = [int(c.uid) for c in cams]
         self._gain_parts: list = []                             # (table where the kernels run, reference uids, neighbour uids) per launch the run used
         on = bool(config.exp("undistort_images"))
@@ -169,6 +174,9 @@ class HotPath:
         if self.audit:
             with self.clock.stage("kernel"):
                 self._audit_commit(self._audit_launch(batch))
+        if self.pose:
+            with self.clock.stage("kernel"):
+                self._pose_commit(self._pose_launch(batch))
         if res is None:
             self._far_commit(far_part, None)
             return res
@@ -278,6 +286,32 @@ class HotPath:
                 for uid, m in zip(ref_uids, best.cpu().numpy()):
                     maps[int(uid)] = m.reshape(grid)
         return dict(rows=rows, maps=maps)
+
+    # -- pose refinement (lfd_pose_accumulate) ---------------------------------------------------------------------------------------
+    def _pose_launch(self, batch: hb.PreparedBatch):
+        """One launch of lfd_pose_accumulate over ``batch`` on the stream that holds it, into a zeroed table of the launch's own; nothing is
+        read back here.  ``_pose_commit`` makes it part of the run, by the audit's rule."""
+        table = self.dens.pose_accumulate(batch, self.pose_certainty, self.pose_inlier_px)
+        pairs = []
+        for r in batch.refs:
+            row = [(self._uids[int(r.ref_cam)], self._uids[int(n)]) for n in r.nbr_cams]
+            pairs.extend(row + [None] * (batch.k - len(row)))
+        return table, pairs
+
+    def _pose_commit(self, part) -> None:
+        if part is not None:
+            self._pose_parts.append(part)
+
+    def pose_result(self) -> dict:
+        """The run's normal equations: ``rows`` {(reference uid, neighbour uid): the pair's 32 integers summed over the run}.  The one read of
+        the tables."""
+        rows: dict = {}
+        for table, pairs in self._pose_parts:
+            for pair, row in zip(pairs, table.cpu().tolist()):
+                if pair is not None:
+                    have = rows.get(pair)
+                    rows[pair] = row if have is None else [a + b for a, b in zip(have, row)]
+        return dict(rows=rows)
 
     # -- per-image exposure gains (lfd_gain_accumulate, DESIGN.md 4.23) -------------------------------------------------------------------------
     def _gain_launch(self, batch: hb.PreparedBatch, out):
@@ -420,6 +454,8 @@ class HotPath:
             out.far_pending = self._far_launch(batch, pending=True)    # (committed in finish_sampled, like the gain statistics)
         if self.audit:
             out.audit_pending = self._audit_launch(batch)              # (likewise)
+        if self.pose:
+            out.pose_pending = self._pose_launch(batch)                # (likewise)
         return out
 
     # -- multi-view re-triangulation of supported points (lfd_refine_multiview) ---------------------------------------------------
@@ -649,6 +685,7 @@ class HotPath:
         out.gain_pending = None
         out.far_pending = None
         out.audit_pending = None
+        out.pose_pending = None
         return out
 
     # -- upstream's normaliser without stalling the launch stream ---------------------------------------------------------------
@@ -813,6 +850,7 @@ class HotPath:
                 self._gain_commit(getattr(out, "gain_pending", None))
                 self._far_commit(getattr(out, "far_pending", None), res)
                 self._audit_commit(getattr(out, "audit_pending", None))
+                self._pose_commit(getattr(out, "pose_pending", None))
             if not res.count and check_selection:
                 return None
             return dataclasses.replace(res, xyz=res.xyz.clone(), rgb=res.rgb.clone(), err=res.err.clone(),
@@ -823,6 +861,7 @@ class HotPath:
             out.gain_pending = None
             out.far_pending = None
             out.audit_pending = None
+            out.pose_pending = None
             self._buf_pool.setdefault((out.capacity, out._n_refs, out._k, _pool_kind(out)), []).append(out)
 
     def pack_ply_tensor(self, xyz: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
@@ -867,6 +906,8 @@ class HotPath:
                 far_part = self._far_launch(batch, pending=False) if self.far else None
                 if self.audit:
                     self._audit_commit(self._audit_launch(batch))
+                if self.pose:
+                    self._pose_commit(self._pose_launch(batch))
                 self.dens.check_launches()
                 res = out.collect()
                 self._support_void = False

@@ -259,6 +259,9 @@ def run_dense_pipeline(
     if world > 1 and str(config.exp("epipolar_audit")) != "off":
         raise ValueError("experimental['epipolar_audit'] cannot run sharded over several GPUs: the histograms are a statistic of the single-GPU "
                          "run, and the exchange of a sharded run does not carry them")
+    if world > 1 and str(config.exp("pose_refine")) != "off":
+        raise ValueError("experimental['pose_refine'] cannot run sharded over several GPUs: the normal equations are a statistic of the single-GPU "
+                         "run, and the exchange of a sharded run does not carry them")
     if world > 1 and str(config.exp("depth_maps_dir")) != "":
         raise ValueError("experimental['depth_maps_dir'] cannot run sharded over several GPUs: the maps are a stage of the single-GPU run, and with "
                          "gather_to_root only one rank would hold the cloud they are rendered from")
@@ -285,7 +288,7 @@ def run_dense_pipeline(
                          cancel_requested=cancel_requested, total_pairs_est=total_pairs_est)
     t0 = time.time()
     own_matcher = matcher is None
-    prefetch = hot = feat_cache = strategy = gain_rows = far_shell = epipolar_audit = None
+    prefetch = hot = feat_cache = strategy = gain_rows = far_shell = epipolar_audit = pose_refine = None
     rank_status, rank_error = 0, None         # 0 fine, 1 cancelled, 2 failed: agreed on by all ranks before the exchange step (core/distributed.py)
     try:
         if own_matcher:
@@ -400,6 +403,12 @@ def run_dense_pipeline(
             names = {int(c.uid): os.path.basename(str(c.image_path)) for c in camera_records}
             epipolar_audit["report"] = audit_report.build_report(epipolar_audit["rows"], names, int(config.exp("audit_min_samples")),
                                                                  config.audit_warn_threshold(), hot.audit_certainty)
+        if hot.pose:
+            from . import poses as pose_report
+            pose_refine = hot.pose_result()
+            names = {int(c.uid): os.path.basename(str(c.image_path)) for c in camera_records}
+            pose_refine["report"] = pose_report.build_report(pose_refine["rows"], camera_records, int(config.exp("pose_min_samples")),
+                                                             hot.pose_certainty, hot.pose_inlier_px, names)
         if hot.normals:
             n_fit, n_fell = hot.normal_totals()
             log.info(f"Surface normals: window radius {hot.normal_radius} cell(s), depth step {hot.normal_depth_step:g}, {n_fit} points fitted, "
@@ -430,6 +439,7 @@ def run_dense_pipeline(
     result.gain_rows = gain_rows          # experimental['gain_compensation']: the run's statistics, for the solve (densify.py)
     result.far_shell = far_shell          # experimental['far_shell']: the run's direction table, for the shell (densify.py)
     result.epipolar_audit = epipolar_audit      # experimental['epipolar_audit']: the pairs' histograms, the report and the cell maps (densify.py)
+    result.pose_refine = pose_refine            # experimental['pose_refine']: the pairs' normal equations and the report (densify.py)
     return result
 
 

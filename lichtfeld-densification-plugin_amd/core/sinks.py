@@ -41,6 +41,7 @@ class PipelineResult:
         self.match_grid = match_grid                          # (H, W) of the matcher's grid, when a reference was matched in this process
         self.gain_rows = None                                 # experimental['gain_compensation']: core.gains.GainRows of the run, else None
         self.far_shell = None                                 # experimental['far_shell']: HotPath.far_result() of the run, else None
+        self.pose_refine = None                               # experimental['pose_refine']: {"rows", "report"} of the run, else None
         self.epipolar_audit = None                            # experimental['epipolar_audit']: {"rows", "report", "maps"} of the run, else None
         self._loader = loader
         self.elapsed_seconds = float(elapsed_seconds)

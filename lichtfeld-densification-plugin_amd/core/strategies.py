@@ -276,6 +276,8 @@ class SampledLoop:
                     handle[1].far_pending = None        # (experimental['far_shell']: likewise)
                 if getattr(handle[1], "audit_pending", None) is not None:
                     handle[1].audit_pending = None      # (experimental['epipolar_audit']: likewise)
+                if getattr(handle[1], "pose_pending", None) is not None:
+                    handle[1].pose_pending = None       # (experimental['pose_refine']: likewise)
                 self.hot.finish_sampled(handle, check_selection=False)       # waited for, its buffers back in the pool, its results dropped
             except Exception:
                 pass

@@ -221,7 +221,25 @@ EXPERIMENTAL_DEFAULTS = {
     # ... directory (relative to the output file's) for one <image stem>_epi.npy per reference: f32 (H, W), the smallest distance any confident
     # neighbour reports for the cell in px of that neighbour's camera image, NaN where there is none - what moved between the photographs
     "audit_maps_dir": "",
+    # pose corrections from the matches (lfd_pose_accumulate): one Gauss-Newton step on the epipolar error.  Every confident
+    # match adds its row of the normal equations with respect to its pair's relative pose, as quantised integers, per (reference, neighbour)
+    # pair; at the end of the run core/poses.py projects the gauge out, solves, and <output file>.poses.json holds one corrected
+    # world-to-camera pose per camera.  The statistics move no point: cloud, counts and order are the knob-off run's; a SECOND run takes the
+    # file through pose_corrections.  One linear step; sees only the error ACROSS the epipolar lines; cannot tell a pose from intrinsics;
+    # contains the matcher's own error.  "off" = no new code runs.
+    "pose_refine": "off",
+    # ... a neighbour is confident at a cell when its raw certainty is at least this, in (0, 1].  audit_certainty's design default.
+    "pose_certainty": 0.5,
+    # ... a confident match further than this many px of the neighbour's camera image from its epipolar line is an outlier, in (0, 64].  The
+    # audit's histogram range, a design default.
+    "pose_inlier_px": 8.0,
+    # ... a pair enters the solve when it has at least this many inliers, >= 1.  A design default.
+    "pose_min_samples": 256,
+    # a poses.json of an earlier run (path; "" = none): its poses replace the camera records' before anything else runs
+    "pose_corrections": "",
 }
+POSE_MODES = ("off", "report")
+POSE_KNOBS = ("pose_certainty", "pose_inlier_px", "pose_min_samples")
 AUDIT_MODES = ("off", "report")
 AUDIT_KNOBS = ("audit_certainty", "audit_min_samples", "audit_warn_px", "audit_maps_dir")
 FAR_MODES = ("off", "file", "merge")
@@ -737,6 +755,30 @@ class DensePipelineConfig:
                         "experimental['dense_tile_segments'] retires tiles into the file's records")
             if self.exchange_record_format() == "ply":
                 return "experimental['epipolar_audit'] is launched beside f32 rows; experimental['exchange_records'] must be 'f32' with it"
+        pose = self.exp("pose_refine")
+        if not isinstance(pose, str) or pose not in POSE_MODES:
+            return "experimental['pose_refine'] must be 'off' or 'report' (<output file>.poses.json: one corrected pose per camera)"
+        if not number(self.exp("pose_certainty")) or not (0.0 < float(self.exp("pose_certainty")) <= 1.0):
+            return "experimental['pose_certainty'] must be in (0, 1] (the raw certainty from which a match is counted)"
+        if not number(self.exp("pose_inlier_px")) or not (0.0 < float(self.exp("pose_inlier_px")) <= 64.0):
+            return "experimental['pose_inlier_px'] must be in (0, 64] (px of the neighbour's camera image from the epipolar line)"
+        if not whole(self.exp("pose_min_samples")) or int(self.exp("pose_min_samples")) < 1:
+            return "experimental['pose_min_samples'] must be an integer >= 1 (inliers a pair needs to enter the solve)"
+        if not isinstance(self.exp("pose_corrections"), str):
+            return "experimental['pose_corrections'] must be a string (the path of a poses.json; '' = none)"
+        if pose == "off":
+            for key in POSE_KNOBS:
+                if self.exp(key) != EXPERIMENTAL_DEFAULTS[key]:
+                    return f"experimental['{key}'] is a knob of the pose refinement: it needs experimental['pose_refine'] = 'report'"
+        else:
+            if self.stream_output:
+                return ("experimental['pose_refine'] is launched beside the point stages of a collected result; stream_output writes records "
+                        "while the run proceeds and has no such site")
+            if self.exp("dense_tile_segments"):
+                return ("experimental['pose_refine'] is launched beside the ordered dense result; dense mode with "
+                        "experimental['dense_tile_segments'] retires tiles into the file's records")
+            if self.exchange_record_format() == "ply":
+                return "experimental['pose_refine'] is launched beside f32 rows; experimental['exchange_records'] must be 'f32' with it"
         if self.stream_output:
             if not str(self.output_path).lower().endswith(".ply"):
                 return "stream_output writes a PLY while the run proceeds: output_path must end in .ply"

@@ -14,8 +14,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(os.path.dirname(HERE), "liblfd_densify.so")
-SOURCES = ["lfd_api.hip", "lfd_kernels.hip", "lfd_select.hip", "lfd_writer.hip", "lfd_host.hip", "lfd_image.hip", "lfd_voxel.hip", "lfd_corr.hip", "lfd_cycle.hip", "lfd_support.hip", "lfd_refine.hip", "lfd_sigma.hip", "lfd_normals.hip", "lfd_colour.hip", "lfd_gain.hip", "lfd_far.hip", "lfd_audit.hip", "lfd_consensus.hip", "lfd_undistort.hip", "lfd_freespace.hip", "lfd_depth.hip", "lfd_fuse.hip", "lfd_knn.hip", "lfd_block.hip", "lfd_cap.hip", "lfd_head.hip", "lfd_thin.hip", "lfd_photo.hip"]
-HEADERS = ["lfd_device.hpp", "lfd_geometry.hpp", "lfd_context.hpp", "lfd_corr.hpp", "lfd_cycle.hpp", "lfd_support.hpp", "lfd_refine.hpp", "lfd_sigma.hpp", "lfd_normals.hpp", "lfd_colour.hpp", "lfd_gain.hpp", "lfd_far.hpp", "lfd_audit.hpp", "lfd_consensus.hpp", "lfd_undistort.hpp", "lfd_freespace.hpp", "lfd_depth.hpp", "lfd_fuse.hpp", "lfd_knn.hpp", "lfd_block.hpp", "lfd_cap.hpp", "lfd_head.hpp", "lfd_thin.hpp", "lfd_photo.hpp", os.path.join("..", "..", "include", "lfd_densify.h")]
+SOURCES = ["lfd_api.hip", "lfd_kernels.hip", "lfd_select.hip", "lfd_writer.hip", "lfd_host.hip", "lfd_image.hip", "lfd_voxel.hip", "lfd_corr.hip", "lfd_cycle.hip", "lfd_support.hip", "lfd_refine.hip", "lfd_sigma.hip", "lfd_normals.hip", "lfd_colour.hip", "lfd_gain.hip", "lfd_far.hip", "lfd_audit.hip", "lfd_pose.hip", "lfd_consensus.hip", "lfd_undistort.hip", "lfd_freespace.hip", "lfd_depth.hip", "lfd_fuse.hip", "lfd_knn.hip", "lfd_block.hip", "lfd_cap.hip", "lfd_head.hip", "lfd_thin.hip", "lfd_photo.hip"]
+HEADERS = ["lfd_device.hpp", "lfd_geometry.hpp", "lfd_context.hpp", "lfd_corr.hpp", "lfd_cycle.hpp", "lfd_support.hpp", "lfd_refine.hpp", "lfd_sigma.hpp", "lfd_normals.hpp", "lfd_colour.hpp", "lfd_gain.hpp", "lfd_far.hpp", "lfd_audit.hpp", "lfd_pose.hpp", "lfd_consensus.hpp", "lfd_undistort.hpp", "lfd_freespace.hpp", "lfd_depth.hpp", "lfd_fuse.hpp", "lfd_knn.hpp", "lfd_block.hpp", "lfd_cap.hpp", "lfd_head.hpp", "lfd_thin.hpp", "lfd_photo.hpp", os.path.join("..", "..", "include", "lfd_densify.h")]
 # -amdgpu-sched-strategy=max-ilp: the dense kernel is bound by its vector arithmetic (long dependent f64 chains); the
 # ILP-first machine scheduler is worth 3.5 % on it (profiles/history.md (r1/ablation.txt)), instruction semantics are unchanged
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
@@ -25,7 +25,9 @@ SCHED_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 # wave-uniform weights held in SGPRs; hoisting every scalar load to the top spills 40 and 46 SGPRs there, the default scheduler none.
 # The refiner-head kernel (lfd_head.hip) streams z once and is bound by memory; max-ilp lifts its loads and the two f64 softplus evaluations per pixel
 # over each other and costs 64 / 98 .. 108 VGPRs (2- / 4-pixel lanes) against 50 .. 52 / 96: one wave per SIMD less for the 4-pixel kernels.
-DEFAULT_SCHED = ("lfd_block.hip", "lfd_head.hip")
+# The pose kernel (lfd_pose.hip) holds up to 32 64-bit products for its folding reduction; max-ilp forms them all at once (179 .. 195 VGPRs, two
+# waves per SIMD) where the default scheduler needs 138 .. 158 (three).
+DEFAULT_SCHED = ("lfd_block.hip", "lfd_head.hip", "lfd_pose.hip")
 # Flags of one source only.  lfd_kernels.hip without the SLP vectoriser: a v_pk_*_f32 is cheaper per operation than two scalar instructions only
 # when both halves already sit in a register pair (profiles/r7/fma_f32_packing.txt); in the dense kernels the pairing costs more than it saves - moves to
 # assemble the pairs, scalar instructions, SGPR spill reloads inside the geometry loop.  Same arithmetic, same bits; -1.7 % of the dense kernel's time

@@ -26,6 +26,7 @@
 #include "lfd_gain.hpp"
 #include "lfd_far.hpp"
 #include "lfd_audit.hpp"
+#include "lfd_pose.hpp"
 #include "lfd_sigma.hpp"
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
@@ -148,6 +149,7 @@ hipError_t lfd_far_launch(const LfdFarArgs& p, bool reduce, hipStream_t stream);
 hipError_t lfd_far_mark_launch(const unsigned long long* table, long long n_cells, long long min_samples, uint8_t* keep, hipStream_t stream);
 hipError_t lfd_far_emit_launch(const LfdFarEmitArgs& p, hipStream_t stream);
 hipError_t lfd_audit_launch(const LfdAuditArgs& p, bool aggregate, hipStream_t stream);   // lfd_audit.hip
+hipError_t lfd_pose_launch(const LfdPoseArgs& p, hipStream_t stream);   // lfd_pose.hip
 extern "C" __global__ void lfd_pack_ply_normals_kernel(const float* xyz, const float* normals, const float* rgb, long long n, unsigned char* out);
 extern "C" __global__ void lfd_select_topm_kernel(LfdSelectArgs A);
 extern "C" __global__ void lfd_select_filter_mw_kernel(LfdSelectArgs A, LfdSelectNorms norms);
@@ -771,10 +773,10 @@ void lfd_destroy(lfd_context* ctx) {
     }
     for (hipEvent_t ev : ctx->kt_start) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->kt_stop) (void)hipEventDestroy(ev);
-    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->cloud_ws, &ctx->support_ws, &ctx->prec.tab, &ctx->colour_img.tab, &ctx->undist_cnt})
+    for (DeviceBuffer* b : {&ctx->cams, &ctx->ws, &ctx->axes, &ctx->scratch, &ctx->codes, &ctx->idx_tab, &ctx->agg, &ctx->sel_buf, &ctx->colour_tab, &ctx->mt, &ctx->mt_ckpt, &ctx->mt_batch, &ctx->sel_scratch, &ctx->sel_chain, &ctx->stamps, &ctx->img_tab, &ctx->msk_tab, &ctx->seg_scan, &ctx->cloud_ws, &ctx->support_ws, &ctx->prec.tab, &ctx->colour_img.tab, &ctx->pose_const.tab, &ctx->undist_cnt})
         if (b->ptr) (void)hipFree(b->ptr);
     if (ctx->pinned_words) (void)hipHostFree(ctx->pinned_words);
-    for (lfd_context::PointerTable* t : {&ctx->prec, &ctx->colour_img}) {
+    for (lfd_context::PointerTable* t : {&ctx->prec, &ctx->colour_img, &ctx->pose_const}) {
         if (t->pinned) (void)hipHostFree(t->pinned);
         if (t->free_ev) (void)hipEventDestroy(t->free_ev);
     }
@@ -892,6 +894,7 @@ int lfd_upload_cameras(lfd_context* ctx, int32_t n, const float* K, const float*
     LFD_HIP(ctx, hipMemcpyAsync(ctx->cams.ptr, cams.data(), cams.size() * sizeof(LfdCam), hipMemcpyHostToDevice, ctx->stream));
     LFD_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->prep_stream) LFD_HIP(ctx, hipStreamSynchronize(ctx->prep_stream));
+    ctx->host_cams.swap(cams);
     ctx->n_cams = n;
     for (LfdBatchSlot& sl : ctx->slot) sl.consts_valid = false;      // every constant block derives from the camera table
     return LFD_OK;
@@ -2144,12 +2147,8 @@ int lfd_support_filter(lfd_context* ctx, const lfd_batch* batch, const lfd_point
 // descriptor tables it is compared with what the device already holds and uploaded only when it differs, on the launch stream (an earlier
 // launch still reading the old table precedes the copy in it), from a pinned staging buffer that is waited for only while its last upload is
 // still on its way.  Entries of slots the batch does not use are null.
-static int upload_pointer_table(lfd_context* ctx, lfd_context::PointerTable& t, const lfd_batch* b, const void* const* ptrs, const void* const** d_tab) {
-    const size_t n = (size_t)b->n_refs * b->k, bytes = n * sizeof(const void*);
-    std::vector<unsigned char> blob(bytes, 0);
-    const void** tab = reinterpret_cast<const void**>(blob.data());
-    for (int r = 0; r < b->n_refs; ++r)
-        for (int j = 0; j < b->n_slots[r]; ++j) tab[(size_t)r * b->k + j] = ptrs[(size_t)r * b->k + j];
+static int upload_blob_table(lfd_context* ctx, lfd_context::PointerTable& t, std::vector<unsigned char>& blob, const void** d_tab) {
+    const size_t bytes = blob.size();
     if (!t.tab.ptr || t.cache != blob) {
         int rc = ensure(ctx, t.tab, bytes);
         if (rc != LFD_OK) return rc;
@@ -2167,7 +2166,20 @@ static int upload_pointer_table(lfd_context* ctx, lfd_context::PointerTable& t, 
         t.in_flight = true;
         t.cache.swap(blob);
     }
-    *d_tab = static_cast<const void* const*>(t.tab.ptr);
+    *d_tab = t.tab.ptr;
+    return LFD_OK;
+}
+
+static int upload_pointer_table(lfd_context* ctx, lfd_context::PointerTable& t, const lfd_batch* b, const void* const* ptrs, const void* const** d_tab) {
+    const size_t n = (size_t)b->n_refs * b->k, bytes = n * sizeof(const void*);
+    std::vector<unsigned char> blob(bytes, 0);
+    const void** tab = reinterpret_cast<const void**>(blob.data());
+    for (int r = 0; r < b->n_refs; ++r)
+        for (int j = 0; j < b->n_slots[r]; ++j) tab[(size_t)r * b->k + j] = ptrs[(size_t)r * b->k + j];
+    const void* d = nullptr;
+    int rc = upload_blob_table(ctx, t, blob, &d);
+    if (rc != LFD_OK) return rc;
+    *d_tab = static_cast<const void* const*>(d);
     return LFD_OK;
 }
 
@@ -2341,6 +2353,42 @@ int lfd_epipolar_audit(lfd_context* ctx, const lfd_batch* batch, float audit_cer
     p.g = launch_geom(batch, L, 0.0f, 0.0f);
     const char* e = std::getenv("LFD_AUDIT_NO_AGGREGATE");             // profiling: every confident lane issues its own LDS adds (the same table)
     LFD_HIP(ctx, lfd_audit_launch(p, !(e && std::atoi(e) != 0), ctx->stream));
+    return LFD_OK;
+}
+
+// ---- pose corrections from the matches (lfd_pose.hip) -------------------------------------------------------------------------------------------
+// The pairs' constants are derived here, once per launch, from the camera table as it was uploaded (f64 from its f32 values; batch->fundamental
+// is not used), and travel to the device like the pointer tables: compared with what the device holds, uploaded on the launch stream when they
+// differ.
+int lfd_pose_accumulate(lfd_context* ctx, const lfd_batch* batch, float pose_certainty, float pose_inlier_px, int64_t* table) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_pose_check(pose_certainty, pose_inlier_px, table)) return fail(ctx, LFD_ERR_INVALID, std::string("lfd_pose_accumulate: ") + why);
+    LfdLaunch L;
+    int rc = batch_launch(ctx, batch, L);
+    if (rc != LFD_OK) return rc;
+    if (const char* why = lfd_pose_check_batch(batch, table)) return fail(ctx, LFD_ERR_INVALID, std::string("lfd_pose_accumulate: ") + why);
+    std::vector<unsigned char> blob((size_t)batch->n_refs * batch->k * sizeof(LfdPoseConst), 0);
+    LfdPoseConst* pc = reinterpret_cast<LfdPoseConst*>(blob.data());
+    for (int r = 0; r < batch->n_refs; ++r)
+        for (int j = 0; j < batch->n_slots[r]; ++j) {
+            const size_t s = (size_t)r * batch->k + j;
+            lfd_pose_make_const(ctx->host_cams[(size_t)batch->ref_cam[r]], ctx->host_cams[(size_t)batch->nbr_cam[s]], pc[s]);
+        }
+    const void* d_pc = nullptr;
+    rc = upload_blob_table(ctx, ctx->pose_const, blob, &d_pc);
+    if (rc != LFD_OK) return rc;
+    LfdPoseArgs p;
+    std::memset(&p, 0, sizeof(p));
+    p.refs = L.refs; p.slots = L.slots; p.ref_const = L.ref_const; p.pair_const = L.pair_const;
+    p.pose_const = static_cast<const LfdPoseConst*>(d_pc);
+    p.axis_x = L.axis_x; p.axis_y = L.axis_y;
+    p.table = reinterpret_cast<unsigned long long*>(table);
+    p.n_refs = batch->n_refs; p.k = batch->k;
+    p.pose_certainty = pose_certainty;
+    p.c2 = (double)pose_inlier_px * (double)pose_inlier_px;
+    p.g = launch_geom(batch, L, 0.0f, 0.0f);
+    LFD_HIP(ctx, lfd_pose_launch(p, ctx->stream));
     return LFD_OK;
 }
 

@@ -57,7 +57,7 @@ struct lfd_context {
     int host_threads = 1;
     LfdHostPool* host_pool = nullptr;            // created with the context, joined by lfd_destroy
     std::vector<unsigned char> host_stage;       // survivors of the chunks in flight (lfd_triangulate_dense_host), kept across calls
-    std::vector<LfdCam> host_cams;
+    std::vector<LfdCam> host_cams;              // the uploaded camera table as the host holds it (both kinds of context: lfd_pose_accumulate derives the pairs' constants from it)
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
@@ -108,6 +108,7 @@ struct lfd_context {
         bool in_flight = false;
     };
     PointerTable prec, colour_img;
+    PointerTable pose_const;       // lfd_pose_accumulate: the pairs' LfdPoseConst of the last batch, uploaded the same way
     // N3 image preparation: coefficient / index tables of the last size pair
     DeviceBuffer img_tab, msk_tab;
     int img_key[4] = {0, 0, 0, 0}, img_ks[2] = {0, 0};

@@ -30,6 +30,7 @@
 #include "lfd_gain.hpp"
 #include "lfd_far.hpp"
 #include "lfd_audit.hpp"
+#include "lfd_pose.hpp"
 #include "lfd_consensus.hpp"
 #include "lfd_undistort.hpp"
 #include "lfd_freespace.hpp"
@@ -819,6 +820,66 @@ int lfd_epipolar_audit_host(lfd_context* ctx, const lfd_batch* b, float audit_ce
         }
         for (int i = 0; i < ns * LFD_AUDIT_QUANTITIES; ++i)
             if (local[i]) __atomic_fetch_add(table + (size_t)r * b->k * LFD_AUDIT_QUANTITIES + i, local[i], __ATOMIC_RELAXED);
+    });
+    return LFD_OK;
+}
+
+// The twin of lfd_pose_accumulate: lfd_pose_sample per confident (cell, slot) over host pointers, on the context's threads.  A
+// chunk sums into a table of its own and adds the non-zero entries with relaxed atomic adds: integer additions, order-free.
+int lfd_pose_accumulate_host(lfd_context* ctx, const lfd_batch* b, float pose_certainty, float pose_inlier_px, int64_t* table) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    if (const char* why = lfd_pose_check(pose_certainty, pose_inlier_px, table))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_pose_accumulate_host: ") + why);
+    lfd_params none;
+    std::memset(&none, 0, sizeof(none));
+    int rc = validate_host(ctx, b, &none);
+    if (rc != LFD_OK) return rc;
+    if (const char* why = lfd_pose_check_batch(b, table)) return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_pose_accumulate_host: ") + why);
+    HostLaunch L;
+    prepare_host(b, &none, L);
+    std::vector<LfdSlot> slot;
+    make_slot_table(ctx, L, slot, nullptr);
+    std::vector<LfdPoseConst> pcs((size_t)b->n_refs * LFD_MAX_SLOTS);
+    for (int r = 0; r < b->n_refs; ++r)
+        for (int j = 0; j < b->n_slots[r]; ++j)
+            lfd_pose_make_const(ctx->host_cams[(size_t)b->ref_cam[r]], ctx->host_cams[(size_t)b->nbr_cam[(size_t)r * b->k + j]],
+                                pcs[(size_t)r * LFD_MAX_SLOTS + j]);
+    const LfdSupportGeom g = make_geom(L, 0.0f, 0.0f);
+    const double c2 = (double)pose_inlier_px * (double)pose_inlier_px;
+    const int chunks_per_ref = (L.HW + kChunk - 1) / kChunk;
+    uint64_t* utable = reinterpret_cast<uint64_t*>(table);
+    parallel_chunks(ctx, b->n_refs * chunks_per_ref, [&](int c) {
+        const int r = c / chunks_per_ref, c0 = (c - r * chunks_per_ref) * kChunk, c1 = std::min(L.HW, c0 + kChunk);
+        const LfdCam& cam = ctx->host_cams[(size_t)b->ref_cam[r]];
+        LfdRefConst rcst;
+        lfd_make_ref_const(cam, b->w_match, b->h_match, rcst);
+        const int ns = b->n_slots[r];
+        const LfdSlot* sl = &slot[(size_t)r * LFD_MAX_SLOTS];
+        const uint8_t* ma = b->mask_a ? b->mask_a[r] : nullptr;
+        uint64_t local[LFD_MAX_SLOTS * LFD_POSE_QUANTITIES];
+        std::memset(local, 0, sizeof(local));
+        for (int cell = c0; cell < c1; ++cell) {
+            const int y = cell / b->W, x = cell - y * b->W;
+            const bool ok = !ma || ma[(size_t)lfd_nearest_src(y, g.mask_sy, g.h_match) * g.w_match + lfd_nearest_src(x, g.mask_sx, g.w_match)] != 0;
+            if (!ok || ns <= 0) continue;
+            float xan, yan;
+            if (g.C == 4) { const float* a = sl[0].warp + (size_t)cell * 4; xan = a[0]; yan = a[1]; }
+            else { xan = L.ax[x]; yan = L.ay[y]; }
+            for (int j = 0; j < ns; ++j) {
+                const float* wv = sl[j].warp + (size_t)cell * g.C + (g.C - 2);
+                if (!lfd_far_confident(sl[j], g, pose_certainty, sl[j].cert[cell], wv[0], wv[1])) continue;
+                int32_t q[7];
+                const int kind = lfd_pose_sample(pcs[(size_t)r * LFD_MAX_SLOTS + j], rcst.sx, rcst.sy, sl[j].sx, sl[j].sy, xan, yan, wv[0], wv[1], g.wm1,
+                                                 g.hm1, c2, q);
+                uint64_t* row = local + (size_t)j * LFD_POSE_QUANTITIES;
+                ++row[kind];                                           // columns 0 / 1 / 2: inliers, outliers, degenerate
+                if (kind != LFD_POSE_INLIER) continue;
+                for (int e = 0; e < LFD_POSE_SUMS; ++e) row[3 + e] += (uint64_t)lfd_pose_term(q, e);      // (two's complement)
+            }
+        }
+        for (int i = 0; i < ns * LFD_POSE_QUANTITIES; ++i)
+            if (local[i]) __atomic_fetch_add(utable + (size_t)r * b->k * LFD_POSE_QUANTITIES + i, local[i], __ATOMIC_RELAXED);
     });
     return LFD_OK;
 }

@@ -452,6 +452,39 @@ def _write_audit(result, config: DensePipelineConfig, camera_records) -> None:
         log.warn(line)
 
 
+def _load_pose_corrections(config: DensePipelineConfig, camera_records):
+    """experimental['pose_corrections']: the records with the poses of that poses.json (core/poses.py: apply_corrections) - what a second run
+    densifies with.  The reference views and their neighbours were chosen from the input poses, so both runs match the same pairs.  '' = the
+    records as they are."""
+    path = str(config.exp("pose_corrections"))
+    if path == "":
+        return camera_records
+    from .core import poses as pose_report
+    with open(path) as f:
+        report = pose_report.from_json(f.read())
+    out = pose_report.apply_corrections(camera_records, report, log)
+    log.info(f"pose_corrections: {sum(a is not b for a, b in zip(out, camera_records))} camera poses taken from {path}")
+    return out
+
+
+def _write_poses(result, config: DensePipelineConfig) -> None:
+    """The pose refinement of a run (experimental['pose_refine']): ``<output file>.poses.json`` - the knobs, one corrected
+    world-to-camera pose per camera beside its input pose, every pair's counts and rms distance before and (predicted) after the step, the
+    scene totals; no timing, so a device run and a host run write the same bytes - one summary line, and one warning per camera whose step
+    is too large for a linear step.  A side output: ``result`` is not changed."""
+    if str(config.exp("pose_refine")) == "off" or not _is_writer_rank():
+        return
+    from .core import poses as pose_report
+    got = getattr(result, "pose_refine", None)
+    if got is None:
+        raise RuntimeError("experimental['pose_refine'] needs the run's normal equations: this result has none")
+    with open(str(config.output_path) + ".poses.json", "w") as f:
+        f.write(pose_report.to_json(got["report"]))
+    log.info(pose_report.summary_line(got["report"]))
+    for line in pose_report.warnings(got["report"]):
+        log.warn(line)
+
+
 def _far_shell_of(result, config: DensePipelineConfig, camera_records):
     """The run's FarShell, or None with the knob off (nothing runs)."""
     if str(config.exp("far_shell")) == "off":
@@ -956,6 +989,7 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
         stream_output=bool(getattr(args, "stream_output", False)), device_image_prep=bool(getattr(args, "device_image_prep", False)),
         experimental=_experimental_from_args(args))
     _check_audit_maps(config, records)
+    records = _load_pose_corrections(config, records)      # (experimental['pose_corrections']: the poses of an earlier run's poses.json)
     try:
         result = run_dense_pipeline(records, refs_local, nn_table, config, progress_callback=progress_callback,
                                     on_sequential_viz=None, debug_state=debug_state, cancel_requested=cancel_requested, **pipeline_kwargs)
@@ -968,6 +1002,7 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
             progress_callback(0.0, "Cancelled")
         return 2
     _write_audit(result, config, records)               # (experimental['epipolar_audit']: a side output about the poses; moves nothing)
+    _write_poses(result, config)                        # (experimental['pose_refine']: likewise)
     shell = _far_shell_of(result, config, records)      # (experimental['far_shell']: placed around the final cloud, where it is written)
     result = _apply_gain_compensation(result, config, records, refs_local, progress_callback)      # (while the counts are still the loop's)
     result = _apply_consensus_filter(result, config, progress_callback)      # (in front of the point cap: it has to see the whole cloud)
@@ -1025,6 +1060,10 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
     nn_table = nearest_neighbors(flat, nns)
     log.info(f"Prepared {len(records)} cameras (refs={len(refs_local)})")
     try:
+        records = _load_pose_corrections(config, records)      # (experimental['pose_corrections']: the poses of an earlier run's poses.json)
+    except (OSError, ValueError) as exc:
+        return 1, str(exc)
+    try:
         _check_audit_maps(config, records)
         result = run_dense_pipeline(records, refs_local, nn_table, config, progress_callback=progress_callback,
                                     on_sequential_viz=on_sequential_viz, debug_state=debug_state,
@@ -1037,6 +1076,7 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
         return 2, "Cancelled"
     try:
         _write_audit(result, config, records)               # (experimental['epipolar_audit']: a side output about the poses; moves nothing)
+        _write_poses(result, config)                        # (experimental['pose_refine']: likewise)
         shell = _far_shell_of(result, config, records)      # (experimental['far_shell']: placed around the final cloud, where it is written)
         result = _apply_gain_compensation(result, config, records, refs_local, progress_callback)      # (while the counts are still the loop's)
         result = _apply_consensus_filter(result, config, progress_callback)  # (in front of the point cap and the voxel filter: it has to see the whole cloud)
@@ -1187,6 +1227,13 @@ def _experimental_from_args(args) -> dict:
             exp[key] = getattr(args, key)
     if str(getattr(args, "audit_maps_dir", "") or "") != "":
         exp["audit_maps_dir"] = str(args.audit_maps_dir)
+    if str(getattr(args, "pose_refine", None) or "off") != "off":
+        exp["pose_refine"] = str(args.pose_refine)
+    for key in ("pose_certainty", "pose_inlier_px", "pose_min_samples"):
+        if getattr(args, key, None) is not None:
+            exp[key] = getattr(args, key)
+    if str(getattr(args, "pose_corrections", "") or "") != "":
+        exp["pose_corrections"] = str(args.pose_corrections)
     if str(getattr(args, "far_shell", None) or "off") != "off":
         exp["far_shell"] = str(args.far_shell)
     for key in ("far_thresh_px", "far_certainty", "far_min_views", "far_shell_cells", "far_min_samples", "far_shell_radius"):
@@ -1335,6 +1382,19 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--audit_maps_dir", type=str, default="",
                     help="... directory (relative: to the output file's) for one <image stem>_epi.npy per reference: the smallest distance any "
                          "confident neighbour reports per cell, NaN where none (needs --epipolar_audit)")
+    ap.add_argument("--pose_refine", choices=("off", "report"), default="off",
+                    help="corrected camera poses from the run's own matches: one Gauss-Newton step on the epipolar error of every confident match; "
+                         "<output file>.poses.json holds one corrected world-to-camera pose per camera.  Moves no point of this run: hand the file "
+                         "to a second run with --pose_corrections")
+    ap.add_argument("--pose_certainty", type=float, default=None,
+                    help="... raw certainty from which a match is counted, in (0, 1] (default 0.5, a design default; needs --pose_refine)")
+    ap.add_argument("--pose_inlier_px", type=float, default=None,
+                    help="... a match further than this many px from its epipolar line is an outlier, in (0, 64] (default 8, a design default; "
+                         "needs --pose_refine)")
+    ap.add_argument("--pose_min_samples", type=int, default=None,
+                    help="... inliers a pair needs to enter the solve (default 256, a design default; needs --pose_refine)")
+    ap.add_argument("--pose_corrections", type=str, default="",
+                    help="a poses.json written by an earlier run with --pose_refine: its poses replace the cameras' before the run starts")
     ap.add_argument("--far_shell", choices=("off", "file", "merge"), default="off",
                     help="points at infinity for sky and distant background: the grid cells every confident neighbour sees where the rotation-only "
                          "transfer predicts become one point per direction cell on a sphere around the cameras - in <out_name stem>_shell.ply "
