@@ -105,7 +105,7 @@ int lfd_abi_version(void);
 int lfd_create(int device_index, void* hip_stream, lfd_context** out);
 void lfd_destroy(lfd_context* ctx);
 int lfd_set_stream(lfd_context* ctx, void* hip_stream);
-/* The profiling / A-B switches of the environment (LFD_DENSE_EXTRA_LDS, LFD_INDEXED_SPLIT, LFD_SELECT_WORKGROUPS, LFD_SELECT_TIMING,
+/* The profiling / A-B switches of the environment (LFD_DENSE_EXTRA_LDS, LFD_DENSE_GENERIC, LFD_INDEXED_SPLIT, LFD_SELECT_WORKGROUPS, LFD_SELECT_TIMING,
  * LFD_DENSE_TIMING) are read when a context is created, never on a launch path; a test or profiling script that changes them for a
  * live context calls this to have them read again. */
 int lfd_reload_env(lfd_context* ctx);
@@ -153,6 +153,13 @@ int lfd_aggregate(lfd_context* ctx, const lfd_batch* batch, const lfd_params* pa
  * last = total); seg_counts: device i32 [n_refs*k] survivors per (reference, slot) or NULL. */
 int lfd_triangulate_dense(lfd_context* ctx, const lfd_batch* batch, const lfd_params* params,
                           const lfd_points* out, int64_t* ref_offsets, int32_t* seg_counts);
+
+/* Host helper, no context and no device: which instantiation of the fused kernel lfd_triangulate_dense runs for these arguments.  1: the
+ * production-shape kernel - the same code compiled for H*W a multiple of the 1024-cell tile and W % 4 == 0, no masks, certainty_thresh > 0,
+ * warp_channels == 2 on the default axes (axis_x == axis_y == NULL), the default f32 colour, no_filter off with sampson_thresh > 0 and
+ * min_parallax_deg > 0, and seg_counts, out->cell and out->slot all NULL; 0: the generic kernel (any violated condition, and every launch of a
+ * context created with LFD_DENSE_GENERIC=1 in the environment).  The two produce the same bytes (tests/test_gpu_dense_prod.py). */
+int lfd_dense_variant(const lfd_batch* batch, const lfd_params* params, const lfd_points* out, const int32_t* seg_counts);
 
 /* The same kernel writing the FILE PAYLOAD itself: survivors leave as 15-byte PLY vertex records (x y z f32 LE, r g b u8 quantised like
  * upstream's to_uint8_rgb - what lfd_pack_ply makes of lfd_triangulate_dense's arrays, byte for byte) in raster order per reference, so a run

@@ -173,6 +173,8 @@ def load_library() -> C.CDLL:
     lib.lfd_triangulate_dense_ply.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_params), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p]
     lib.lfd_dense_tiles_per_ref.argtypes = [C.c_int32, C.c_int32]
+    lib.lfd_dense_variant.argtypes = [C.POINTER(lfd_batch), C.POINTER(lfd_params), C.POINTER(lfd_points), C.c_void_p]
+    lib.lfd_dense_variant.restype = C.c_int
     lib.lfd_triangulate_dense_segments.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_params), C.POINTER(lfd_points),
                                                    C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lfd_triangulate_dense_ply_segments.argtypes = [ctxp, C.POINTER(lfd_batch), C.POINTER(lfd_params), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -330,6 +332,13 @@ def make_params(config: DensePipelineConfig, sample_cap: float = 0.9, exact_colo
                       sample_cap=float(sample_cap), reproj_thresh=float(config.reproj_thresh),
                       min_parallax_deg=float(config.min_parallax_deg), no_filter=1 if config.no_filter else 0,
                       flags=LFD_FLAG_EXACT_COLOUR if exact_colour else 0)
+
+
+def dense_variant(batch: lfd_batch, params: lfd_params, out: lfd_points, seg_counts: Optional[int] = None) -> int:
+    """lfd_dense_variant: which instantiation of the fused kernel lfd_triangulate_dense runs for these ctypes structures (``PreparedBatch.c``,
+    ``make_params``, ``OutputBuffers.c``) and this ``seg_counts`` address - 1 the production-shape kernel, 0 the generic one.  A host
+    function: needs no context and no GPU.  (LFD_DENSE_GENERIC=1 in the environment of a context forces the generic kernel regardless.)"""
+    return int(load_library().lfd_dense_variant(C.byref(batch), C.byref(params), C.byref(out), seg_counts))
 
 
 def _f32(a) -> np.ndarray:

@@ -40,6 +40,7 @@
 extern "C" __global__ void lfd_aggregate_kernel(LfdLaunch L, float* best_cert, uint8_t* best_slot);
 extern "C" __global__ void lfd_dense_kernel(LfdLaunch L);
 extern "C" __global__ void lfd_dense_exact_kernel(LfdLaunch L);
+extern "C" __global__ void lfd_dense_prod_kernel(LfdLaunch L);
 extern "C" __global__ void lfd_dense_ply_kernel(LfdLaunch L);
 extern "C" __global__ void lfd_dense_ply_exact_kernel(LfdLaunch L);
 extern "C" __global__ void lfd_dense_segments_kernel(LfdLaunch L);
@@ -229,10 +230,18 @@ int validate_batch(lfd_context* ctx, const lfd_batch* b, const lfd_params* p) {
     return LFD_OK;
 }
 
+// The events of this file order work on ONE device; none of them publishes device writes to the host, so none needs the release to system
+// scope that an event carries by default (after the dense kernel: behind 400 MB of stores).  A host read of results goes through a copy or a
+// stream synchronisation of the caller's, which release on their own.
+constexpr unsigned kOrderOnly = hipEventDisableTiming | hipEventDisableSystemFence;
+
 int slot_events(lfd_context* ctx, LfdBatchSlot& sl) {
-    if (!sl.pinned_free) LFD_HIP(ctx, hipEventCreateWithFlags(&sl.pinned_free, hipEventDisableTiming));
-    if (!sl.ready) LFD_HIP(ctx, hipEventCreateWithFlags(&sl.ready, hipEventDisableTiming));
-    if (!sl.idle) LFD_HIP(ctx, hipEventCreateWithFlags(&sl.idle, hipEventDisableTiming));
+    // pinned_free: the host waits on it (hipEventSynchronize) before it overwrites `pinned`, host memory the device only READS
+    if (!sl.pinned_free) LFD_HIP(ctx, hipEventCreateWithFlags(&sl.pinned_free, kOrderOnly));
+    // ready: the launch stream waits on it (hipStreamWaitEvent) and then reads the tables and constants the preparation stream wrote - same device
+    if (!sl.ready) LFD_HIP(ctx, hipEventCreateWithFlags(&sl.ready, kOrderOnly));
+    // idle: the preparation stream waits on it (hipStreamWaitEvent) before it OVERWRITES the slot's tables - same device, nothing is read
+    if (!sl.idle) LFD_HIP(ctx, hipEventCreateWithFlags(&sl.idle, kOrderOnly));
     return LFD_OK;
 }
 
@@ -338,7 +347,8 @@ int upload_tables(lfd_context* ctx, const lfd_batch* b, const long long* extra, 
             sl.pinned_x_bytes = std::max<size_t>(extra_room * 2, 4096);
             LFD_HIP(ctx, hipHostMalloc(&sl.pinned_x, sl.pinned_x_bytes, hipHostMallocDefault));
         }
-        if (!sl.x_free) LFD_HIP(ctx, hipEventCreateWithFlags(&sl.x_free, hipEventDisableTiming));
+        // x_free: the host waits on it before it overwrites `pinned_x`, host memory the device only reads
+        if (!sl.x_free) LFD_HIP(ctx, hipEventCreateWithFlags(&sl.x_free, kOrderOnly));
         std::memcpy(sl.pinned_x, extra, n_extra * sizeof(long long));
         LFD_HIP(ctx, hipMemcpyAsync(static_cast<unsigned char*>(sl.desc.ptr) + off_extra, sl.pinned_x, n_extra * sizeof(long long), hipMemcpyHostToDevice,
                                     ctx->stream));
@@ -525,6 +535,7 @@ void read_env_switches(lfd_context* ctx) {
     ctx->env = LfdEnvSwitches();
     if (const char* e = std::getenv("LFD_DENSE_EXTRA_LDS")) ctx->env.dense_extra_lds = (size_t)std::atol(e);
     if (const char* e = std::getenv("LFD_DENSE_TIMING")) ctx->env.dense_timing_path = e;
+    if (const char* e = std::getenv("LFD_DENSE_GENERIC")) ctx->env.dense_generic = std::atoi(e) != 0;
     if (const char* e = std::getenv("LFD_INDEXED_SPLIT")) ctx->env.indexed_split = std::atoi(e) != 0;
     if (const char* e = std::getenv("LFD_SELECT_TIMING")) ctx->env.select_timing = std::max(1, std::atoi(e));
     if (const char* e = std::getenv("LFD_SELECT_WORKGROUPS")) ctx->env.select_workgroups = std::atoi(e);
@@ -796,9 +807,11 @@ int lfd_kernel_timing(lfd_context* ctx, int32_t n_launches) {
         ctx->kt_start.pop_back(); ctx->kt_stop.pop_back();
     }
     while (ctx->kt_start.size() < (size_t)n_launches) {
+        // kt_start / kt_stop: read for their time stamps (hipEventElapsedTime; lfd_kernel_timing_read waits for the last stop only to know the
+        // stamps are there), and a stop event doubles as the slot's `idle` marker above - nobody reads device results on their strength
         hipEvent_t a = nullptr, b = nullptr;
-        LFD_HIP(ctx, hipEventCreate(&a));
-        hipError_t e = hipEventCreate(&b);
+        LFD_HIP(ctx, hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
+        hipError_t e = hipEventCreateWithFlags(&b, hipEventDisableSystemFence);
         if (e != hipSuccess) { (void)hipEventDestroy(a); return fail(ctx, LFD_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e)); }
         ctx->kt_start.push_back(a); ctx->kt_stop.push_back(b);
     }
@@ -919,6 +932,29 @@ int lfd_aggregate(lfd_context* ctx, const lfd_batch* batch, const lfd_params* pa
     return LFD_OK;
 }
 
+// Which instantiation of the ordered dense kernel a launch of lfd_triangulate_dense may run: 1 = the production-shape one (lfd_dense_prod_kernel,
+// lfd_kernels.hip: every question below is compiled into it as answered), 0 = the generic one.  A pure function of its arguments - no context, no
+// device - and the ONLY place the conditions are written down: every line is an assumption the kernel makes and does not test again.
+int lfd_dense_variant(const lfd_batch* b, const lfd_params* p, const lfd_points* out, const int32_t* seg_counts) {
+    if (!b || !p || !out) return 0;
+    const long long tile = LFD_DENSE_BLOCK * LFD_DENSE_CPT;
+    if (b->n_refs <= 0 || b->H <= 0 || b->W <= 0 || (b->W & 3) != 0 || ((long long)b->H * b->W) % tile != 0) return 0;      // whole tiles, rows of whole threads
+    if (b->warp_channels != 2 || b->axis_x || b->axis_y) return 0;                     // [xB, yB] warps on the identity axes (and with them the colour tables)
+    if ((p->flags & LFD_FLAG_EXACT_COLOUR) != 0) return 0;                             // f32 colour blend
+    if (!(p->certainty_thresh > 0.0f)) return 0;                                       // a positive floor: no cell of an unmasked reference is dead
+    if (p->no_filter || !(p->sampson_thresh > 0.0) || !(p->min_parallax_deg > 0.0f)) return 0;      // all three gates on
+    if (seg_counts || out->cell || out->slot) return 0;                                // xyz / rgb / err / ref_offsets only
+    if (b->mask_a || b->mask_b) {                                                      // no mask on any reference (what upload_tables calls any_mask)
+        if (!b->n_slots) return 0;
+        for (int r = 0; r < b->n_refs; ++r) {
+            if (b->mask_a && b->mask_a[r]) return 0;
+            for (int j = 0; b->mask_b && j < b->n_slots[r] && j < b->k; ++j)
+                if (b->mask_b[(size_t)r * b->k + j]) return 0;
+        }
+    }
+    return 1;
+}
+
 // the dense launch in its two forms: ordered (ref_offsets; ref_counts / table null) and unordered retirement (ref_counts + table)
 static int dense_launch(lfd_context* ctx, const lfd_batch* batch, const lfd_params* params, const lfd_points* out,
                         int64_t* ref_offsets, int32_t* seg_counts, int64_t* ref_counts, lfd_tile_segment* table, uint8_t* ply = nullptr) {
@@ -976,7 +1012,10 @@ static int dense_launch(lfd_context* ctx, const lfd_batch* batch, const lfd_para
     if (rc != LFD_OK) return rc;
     hipEvent_t t_start = nullptr, t_stop = used_slot.idle;
     if (ctx->kt_used < ctx->kt_start.size()) { t_start = ctx->kt_start[ctx->kt_used]; t_stop = ctx->kt_stop[ctx->kt_used]; ++ctx->kt_used; }
-    auto kernel = (ply && unordered) ? (exact_colour ? lfd_dense_ply_segments_exact_kernel : lfd_dense_ply_segments_kernel)
+    // (the colour tables exist whenever the predicate holds; LFD_DENSE_GENERIC=1 keeps the generic kernel for tests and A/B runs)
+    const bool prod = !ply && !unordered && !exact_colour && !ctx->env.dense_generic && L.colour_cols && lfd_dense_variant(batch, params, out, seg_counts) == 1;
+    auto kernel = prod ? lfd_dense_prod_kernel
+                : (ply && unordered) ? (exact_colour ? lfd_dense_ply_segments_exact_kernel : lfd_dense_ply_segments_kernel)
                 : ply ? (exact_colour ? lfd_dense_ply_exact_kernel : lfd_dense_ply_kernel)
                 : unordered ? (exact_colour ? lfd_dense_segments_exact_kernel : lfd_dense_segments_kernel)
                             : (exact_colour ? lfd_dense_exact_kernel : lfd_dense_kernel);

@@ -45,6 +45,7 @@ struct LfdBatchSlot {
 struct LfdEnvSwitches {          // profiling / A-B switches of the environment, read once by lfd_create
     size_t dense_extra_lds = 0;           // LFD_DENSE_EXTRA_LDS: dynamic LDS per dense workgroup (lowers the resident workgroups per CU)
     std::string dense_timing_path;        // LFD_DENSE_TIMING (profiling builds): file the per-tile phase stamps are dumped to
+    bool dense_generic = false;           // LFD_DENSE_GENERIC=1: lfd_triangulate_dense never picks the production-shape kernel (tests, A/B runs)
     bool indexed_split = true;            // LFD_INDEXED_SPLIT=0: indexed mode in one kernel
     int select_timing = 0;                // LFD_SELECT_TIMING: 1 phase stamps of the selection kernel, 2 of the multi-workgroup one
     int select_workgroups = -1;           // LFD_SELECT_WORKGROUPS: compute workgroups of the selection (-1: default)

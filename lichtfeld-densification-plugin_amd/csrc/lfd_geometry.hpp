@@ -595,8 +595,11 @@ LFD_HD float lfd_reproj_sq(const float* P, float X0, float X1, float X2, float X
 
 LFD_HD bool lfd_finite(float x) { return fabsf(x) <= 3.402823466e+38f; }   // false for NaN/Inf
 
-LFD_HD void lfd_eval_correspondence(const LfdRefConst& rc, const LfdPairConst& pc, float xan, float yan,
-                                    float xbn, float ybn, const LfdKernelParams& kp, LfdCellResult& o) {
+// kAllGates: the caller knows that kp.use_sampson and kp.use_parallax are set and kp.no_filter is not (the production-shape dense kernel:
+// lfd_dense_variant), so the three scalar tests per cell are decided when the code is compiled.  The arithmetic is the same code either way.
+template <bool kAllGates>
+LFD_HD void lfd_eval_correspondence_as(const LfdRefConst& rc, const LfdPairConst& pc, float xan, float yan,
+                                       float xbn, float ybn, const LfdKernelParams& kp, LfdCellResult& o) {
     const float xa = lfd_match_px(xan, kp.wm1), ya = lfd_match_px(yan, kp.hm1);
     const float xb = lfd_match_px(xbn, kp.wm1), yb = lfd_match_px(ybn, kp.hm1);
     const float ua = xa * rc.sx, va = ya * rc.sy;
@@ -604,7 +607,7 @@ LFD_HD void lfd_eval_correspondence(const LfdRefConst& rc, const LfdPairConst& p
     o.xa_px = xa; o.ya_px = ya;
     o.x = o.y = o.z = 0.0f; o.err = 0.0f; o.keep = 0;
 
-    if (kp.use_sampson) {     // f64 throughout (core/geometry.py:133-141)
+    if (kAllGates || kp.use_sampson) {     // f64 throughout (core/geometry.py:133-141)
         const double x1 = (double)ua, y1 = (double)va, x2 = (double)ub, y2 = (double)vb;
         const double* F = pc.F;
         // fused multiply-adds: upstream's NumPy expression rounds every product and sum separately, which moves the
@@ -694,12 +697,12 @@ LFD_HD void lfd_eval_correspondence(const LfdRefConst& rc, const LfdPairConst& p
     const float err = lfd_sqrt_f32(qm);
     o.x = X0; o.y = X1; o.z = X2; o.err = err;
 
-    if (kp.no_filter) {       // core/pipeline.py:739-743
+    if (!kAllGates && kp.no_filter) {       // core/pipeline.py:739-743
         o.keep = (lfd_finite(X0) && lfd_finite(X1) && lfd_finite(X2) && lfd_finite(X3) && lfd_finite(err)) ? 1 : 0;
         return;
     }
     bool keep = (err <= kp.reproj_thresh) && (z1 > 0.0f) && (z2 > 0.0f);
-    if (keep && kp.use_parallax) {
+    if (keep && (kAllGates || kp.use_parallax)) {
         const float a0 = X0 - rc.C[0], a1 = X1 - rc.C[1], a2 = X2 - rc.C[2];
         const float b0 = X0 - pc.C[0], b1 = X1 - pc.C[1], b2 = X2 - pc.C[2];
 #if LFD_PARALLAX_EXACT
@@ -767,6 +770,11 @@ LFD_HD void lfd_eval_correspondence(const LfdRefConst& rc, const LfdPairConst& p
 #endif
     }
     o.keep = keep ? 1 : 0;
+}
+
+LFD_HD void lfd_eval_correspondence(const LfdRefConst& rc, const LfdPairConst& pc, float xan, float yan,
+                                    float xbn, float ybn, const LfdKernelParams& kp, LfdCellResult& o) {
+    lfd_eval_correspondence_as<false>(rc, pc, xan, yan, xbn, ybn, kp, o);
 }
 
 // ---- colour (core/pipeline.py:661-679) -------------------------------------------------------

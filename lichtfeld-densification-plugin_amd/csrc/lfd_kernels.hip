@@ -503,8 +503,14 @@ constexpr int kCopyThreadsOrdered = kBlock - 64;
 // walk the table and emit raster order.  Everything up to the retirement is the same code.
 // kPly (lfd_triangulate_dense_ply): the survivors leave as 15-byte PLY vertex records (xyz f32 LE + the colour quantised like upstream's
 // to_uint8_rgb) instead of the 28-byte structure of arrays: the packer's pass over the cloud disappears for streamed / exchanged output.
-template <bool kExactColour, bool kUnordered = false, bool kPly = false>
+// kProd (lfd_dense_prod_kernel): the ordered kernel for the shape production launches, with every question a launch already answers decided
+// when the code is compiled - what lfd_dense_variant (lfd_api.hip) checks on the host before it picks this entry: the grid is whole tiles and
+// W % 4 == 0, no masks and a positive certainty floor, two-channel warps on the identity axes, table colours, all three gates on, no
+// seg_counts / cell / slot.  The cells' arithmetic, the look-back, the capacity clamp and the wrong-guess re-fetch are the generic kernel's.
+template <bool kExactColour, bool kUnordered = false, bool kPly = false, bool kProd = false>
 __device__ __forceinline__ void lfd_dense_body(const LfdLaunch& L) {
+    static_assert(!kProd || (!kExactColour && !kUnordered && !kPly), "the production-shape kernel is the ordered f32-colour one");
+    static_assert(!kProd || (LFD_WARP_BY_LANE && !LFD_DENSE_ALL_WARPS && kCpt == 4), "the production-shape kernel parks by lane (see kProdBuild)");
     // one LDS block, the per-pair constants first: S.pc[slot] is then addressed as slot * sizeof(LfdPairConst) + an instruction offset,
     // with no base to keep in a vector register across the geometry loop
     struct DenseShared {
@@ -571,12 +577,12 @@ __device__ __forceinline__ void lfd_dense_body(const LfdLaunch& L) {
         const unsigned long long k = atomicAdd(L.ticket_lanes + (size_t)seq * 16, 1ull) - L.ticket_base_lane[seq];
         s_ticket = (unsigned)k * LFD_TICKET_LANES + seq;
     }
-    if (tid < LFD_MAX_SLOTS) s_slot_cnt[tid] = 0;
+    if (!kProd && tid < LFD_MAX_SLOTS) s_slot_cnt[tid] = 0;
     if (tile_guess < n_tiles) prologue_commit(L, pro, S);             // ... and into LDS
     __syncthreads();
     LFD_STAMP(1);
     const unsigned tile = s_ticket;
-    if (tile == 0 && (L.seg_counts || kUnordered)) {         // zero the per-(reference, slot) counters (and the references' cursors) for this launch, then raise the flag
+    if (!kProd && tile == 0 && (L.seg_counts || kUnordered)) {         // zero the per-(reference, slot) counters (and the references' cursors) for this launch, then raise the flag
         if (L.seg_counts) for (int i = tid; i < L.n_refs * L.k; i += kBlock) L.seg_counts[i] = 0;
         if (kUnordered) for (int i = tid; i < L.n_refs; i += kBlock) L.ref_cursor[i] = 0ull;
         __threadfence();
@@ -608,7 +614,7 @@ __device__ __forceinline__ void lfd_dense_body(const LfdLaunch& L) {
         }
 #endif
         const int ns = S.ref.n_slots;
-        const bool any_mask = S.ref.any_mask != 0;
+        const bool any_mask = !kProd && S.ref.any_mask != 0;
         const int tile_cell0 = tile_in_ref * kTile;
         const int cell0 = tile_cell0 + tid * kCpt;
         int tile_y0, tile_x0;                    // (row, column) of the tile's first cell: uniform, kept in SGPRs
@@ -664,7 +670,7 @@ __device__ __forceinline__ void lfd_dense_body(const LfdLaunch& L) {
                 dead = (unsigned)(best.x <= 0.0f) | ((unsigned)(best.y <= 0.0f) << 1) | ((unsigned)(best.z <= 0.0f) << 2) | ((unsigned)(best.w <= 0.0f) << 3);
         } else
 #endif
-        if (!any_mask && (HW & 3) == 0 && kCpt == 4 && cell0 + 3 < HW) {
+        if (kProd || (!any_mask && (HW & 3) == 0 && kCpt == 4 && cell0 + 3 < HW)) {
             const float th = L.kp.certainty_thresh;
             float4 best;
             bj[0] = bj[1] = bj[2] = bj[3] = 0;
@@ -689,7 +695,7 @@ __device__ __forceinline__ void lfd_dense_body(const LfdLaunch& L) {
                     }
                 }
             }
-            if (!(th > 0.0f))
+            if (!kProd && !(th > 0.0f))
                 dead = (unsigned)(best.x <= 0.0f) | ((unsigned)(best.y <= 0.0f) << 1) | ((unsigned)(best.z <= 0.0f) << 2) | ((unsigned)(best.w <= 0.0f) << 3);
         } else if ((L.W & 3) == 0 && (HW & 3) == 0 && kCpt == 4 && cell0 + 3 < HW) {      // masks present
             int dy, x0;
@@ -718,7 +724,7 @@ __device__ __forceinline__ void lfd_dense_body(const LfdLaunch& L) {
         // winners' slots go through LDS to the lanes of the SAME wave and lane l fetches the cells l, l + 64, l + 128, l + 192 of the wave's 256:
         // consecutive lanes, consecutive cells - four lines per plane and load - and parks the coordinates in THOSE cells' slots (word stride 3 and 1
         // instead of 12 and 4).  LDS operations of one wave complete in order: no barrier.  Same bits.
-        const bool wave_whole = kCpt == 4 && (L.W & 3) == 0 && tile_cell0 + (wave + 1) * 64 * kCpt <= HW;
+        const bool wave_whole = kProd || (kCpt == 4 && (L.W & 3) == 0 && tile_cell0 + (wave + 1) * 64 * kCpt <= HW);
 #if LFD_DENSE_ALL_WARPS
         const bool by_lane = wave_whole && !have_warps;
 #else
@@ -733,12 +739,12 @@ __device__ __forceinline__ void lfd_dense_body(const LfdLaunch& L) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) bj_packed |= (unsigned)bj[e] << (8 * e);
             *reinterpret_cast<unsigned*>(&stage.slot[t2 * kCpt]) = bj_packed;
-            if (L.warp_channels != 4) {          // the A-grid coordinates of the thread's own cells: computed (or two small loads), parked at once
+            if (kProd || L.warp_channels != 4) {          // the A-grid coordinates of the thread's own cells: computed (or two small loads), parked at once
                 int dy, x0;
                 lfd_divmod_local(tile_x0 + t2 * kCpt, L.W, L.inv_w, L.w_log2, dy, x0);
                 const int y0 = tile_y0 + dy;
                 float xa[4], ya;
-                if (L.axis_identity) {
+                if (kProd || L.axis_identity) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) xa[e] = lfd_axis_value(L.ax, x0 + e);
                     ya = lfd_axis_value(L.ay, y0);
@@ -757,7 +763,7 @@ __device__ __forceinline__ void lfd_dense_body(const LfdLaunch& L) {
             int sj[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) sj[e] = (int)stage.slot[wbase + 64 * e];
-            if (L.warp_channels == 4) {          // upstream's concatenated [xA, yA, xB, yB]: 16 bytes per cell, consecutive lanes read one contiguous KB per plane
+            if (!kProd && L.warp_channels == 4) {          // upstream's concatenated [xA, yA, xB, yB]: 16 bytes per cell, consecutive lanes read one contiguous KB per plane
                 float4 v[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = load_f32x4(S.slot[sj[e]].warp + (size_t)(unsigned)(tile_cell0 + wbase + 64 * e) * 4);
@@ -782,7 +788,9 @@ __device__ __forceinline__ void lfd_dense_body(const LfdLaunch& L) {
             __builtin_amdgcn_wave_barrier();
         } else
 #endif
-        if (kCpt == 4 && (L.W & 3) == 0 && cell0 + 3 < HW) {
+        if (kProd) {
+            // (never reached: a production-shape tile is whole waves, parked by lane above)
+        } else if (kCpt == 4 && (L.W & 3) == 0 && cell0 + 3 < HW) {
             // W % 4 == 0: the four cells share a row, so one cell -> (row, column) conversion serves all
             float xa[4] = {0.0f, 0.0f, 0.0f, 0.0f}, ya = 0.0f;
             if (L.warp_channels != 4) {
@@ -830,12 +838,12 @@ __device__ __forceinline__ void lfd_dense_body(const LfdLaunch& L) {
                 bj_packed |= (unsigned)bj[e] << (8 * e);
             }
         }
-        if (dead) {                               // (rare: masks, or a floor of 0)
+        if (!kProd && dead) {                               // (rare: masks, or a floor of 0)
 #pragma unroll
             for (int e = 0; e < kCpt; ++e)
                 if ((dead >> e) & 1u) stage.xyz[3 * (tid * kCpt + e) + 2] = __builtin_nanf("");
         }
-        *reinterpret_cast<unsigned*>(&stage.slot[tid * kCpt]) = bj_packed;
+        if (!kProd) *reinterpret_cast<unsigned*>(&stage.slot[tid * kCpt]) = bj_packed;      // (parked by lane: already there, and nothing reads it afterwards)
 
         LFD_STAMP(4);
 #if LFD_FRONT_PRIO > 0
@@ -858,7 +866,8 @@ __device__ __forceinline__ void lfd_dense_body(const LfdLaunch& L) {
 #if defined(LFD_ABLATE_EVAL)
             if (cell0 + e < HW) { res.keep = xbn > -0.9f; res.x = xan; res.y = yan; res.z = xbn; res.err = ybn; res.xa_px = 1.0f; res.ya_px = 1.0f; }
 #else
-            if (cell0 + e < HW) lfd_eval_correspondence(rc, S.pc[bje], xan, yan, xbn, ybn, L.kp, res);
+            if (kProd) lfd_eval_correspondence_as<true>(rc, S.pc[bje], xan, yan, xbn, ybn, L.kp, res);       // (whole tiles: every cell is inside the grid)
+            else if (cell0 + e < HW) lfd_eval_correspondence(rc, S.pc[bje], xan, yan, xbn, ybn, L.kp, res);
 #endif
             if (res.keep) {
                 sxyz[0] = res.x; sxyz[1] = res.y; sxyz[2] = res.z;
@@ -871,7 +880,7 @@ __device__ __forceinline__ void lfd_dense_body(const LfdLaunch& L) {
         __builtin_amdgcn_s_setprio(LFD_BACK_PRIO);
 #endif
         // survivors per neighbour slot (outside the divergent loop): ballots over the kept cells of each slot
-        if (L.seg_counts) {
+        if (!kProd && L.seg_counts) {
             for (int j = 0; j < ns; ++j) {
                 unsigned c = 0;
 #pragma unroll
@@ -909,7 +918,7 @@ __device__ __forceinline__ void lfd_dense_body(const LfdLaunch& L) {
         }
         __syncthreads();                          // the order map is complete
         LFD_STAMP(7);
-        if (L.seg_counts && tid < ns && s_slot_cnt[tid]) {
+        if (!kProd && L.seg_counts && tid < ns && s_slot_cnt[tid]) {
             // the workgroup of tile 0 zeroed the array and raised seg_ready when the launch began (no memset launch)
             // (only the first few workgroups of a launch ever have to poll.  The counters are only touched by device-scope
             // atomics, so a relaxed read of the flag is enough.)
@@ -966,7 +975,7 @@ __device__ __forceinline__ void lfd_dense_body(const LfdLaunch& L) {
 #if !defined(LFD_ABLATE_STORES)
             const uint8_t* image = S.ref.image;
             const int n_loc = (int)block_total;
-            if (!kExactColour && L.colour_cols) {
+            if (kProd || (!kExactColour && L.colour_cols)) {
                 // analytic A-grid, f32 blend: a cell's reference position, first-tap offset and weight factors come from the
                 // column / row tables (two 16-byte loads instead of ~60 instructions of axis, floor, clamp and offset arithmetic)
                 const unsigned n_bytes = __umul24((unsigned)L.w_match, (unsigned)L.h_match) * 3u;
@@ -1111,8 +1120,8 @@ __device__ __forceinline__ void lfd_dense_body(const LfdLaunch& L) {
                     *reinterpret_cast<LfdF3*>(gc + o12) = c;
                     *reinterpret_cast<float*>(ge + o4) = stage.err[sl];
 #endif
-                    if (L.cell) L.cell[base + i] = tile_cell0 + sl;
-                    if (L.slot) L.slot[base + i] = stage.slot[sl];
+                    if (!kProd && L.cell) L.cell[base + i] = tile_cell0 + sl;
+                    if (!kProd && L.slot) L.slot[base + i] = stage.slot[sl];
                 }
             }
         }
@@ -1131,6 +1140,10 @@ __device__ __forceinline__ void lfd_dense_body(const LfdLaunch& L) {
 extern "C" __global__ void __launch_bounds__(kBlock, LFD_DENSE_WAVES_PER_SIMD) lfd_dense_kernel(LfdLaunch L) { lfd_dense_body<false>(L); }
 // the same kernel with upstream's f64 colour arithmetic (bit-identical rgb; lfd_params.flags & LFD_FLAG_EXACT_COLOUR)
 extern "C" __global__ void __launch_bounds__(kBlock, LFD_DENSE_WAVES_PER_SIMD) lfd_dense_exact_kernel(LfdLaunch L) { lfd_dense_body<true>(L); }
+// the ordered f32-colour kernel instantiated for the production shape (lfd_dense_variant decides on the host; same bits as lfd_dense_kernel)
+// (a profiling build that switches the by-lane parking off or the all-warps front end on gets the generic body under this name)
+constexpr bool kProdBuild = LFD_WARP_BY_LANE && !LFD_DENSE_ALL_WARPS && kCpt == 4;
+extern "C" __global__ void __launch_bounds__(kBlock, LFD_DENSE_WAVES_PER_SIMD) lfd_dense_prod_kernel(LfdLaunch L) { lfd_dense_body<false, false, false, kProdBuild>(L); }
 // unordered retirement (lfd_triangulate_dense_segments), both colour forms
 // file-payload output (lfd_triangulate_dense_ply), both colour forms
 extern "C" __global__ void __launch_bounds__(kBlock, LFD_DENSE_WAVES_PER_SIMD) lfd_dense_ply_kernel(LfdLaunch L) { lfd_dense_body<false, false, true>(L); }
