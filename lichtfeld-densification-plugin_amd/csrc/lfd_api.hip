@@ -138,12 +138,12 @@ hipError_t lfd_corr_launch(const LfdCorrArgs& p, hipStream_t stream);     // lfd
 hipError_t lfd_block_launch(const LfdBlockArgs& p, hipStream_t stream);   // lfd_block.hip
 hipError_t lfd_head_launch(const LfdHeadArgs& p, hipStream_t stream);     // lfd_head.hip
 hipError_t lfd_cycle_launch(const LfdCycleArgs& p, hipStream_t stream);   // lfd_cycle.hip
-hipError_t lfd_support_launch(const LfdSupportArgs& p, hipStream_t stream);   // lfd_support.hip
+hipError_t lfd_support_launch(const LfdSupportArgs& p, const LfdCompactArgs& tail, hipStream_t stream);   // lfd_support.hip
 hipError_t lfd_refine_launch(const LfdRefineArgs& p, hipStream_t stream);     // lfd_refine.hip
-hipError_t lfd_sigma_launch(const LfdSigmaArgs& p, hipStream_t stream);       // lfd_sigma.hip
+hipError_t lfd_sigma_launch(const LfdSigmaArgs& p, const LfdCompactArgs& tail, hipStream_t stream);   // lfd_sigma.hip
 hipError_t lfd_normals_launch(const LfdNormalArgs& p, hipStream_t stream);    // lfd_normals.hip
 hipError_t lfd_colour_launch(const LfdColourArgs& p, hipStream_t stream);     // lfd_colour.hip
-hipError_t lfd_photo_launch(const LfdPhotoArgs& p, const LfdSupportArgs& sup, hipStream_t stream);   // lfd_photo.hip
+hipError_t lfd_photo_launch(const LfdPhotoArgs& p, const LfdCompactArgs& tail, hipStream_t stream);   // lfd_photo.hip
 hipError_t lfd_gain_launch(const LfdGainArgs& p, hipStream_t stream);         // lfd_gain.hip
 hipError_t lfd_gain_apply_launch(const LfdGainApplyArgs& p, hipStream_t stream);
 hipError_t lfd_far_launch(const LfdFarArgs& p, bool reduce, hipStream_t stream);   // lfd_far.hip
@@ -2140,44 +2140,75 @@ int lfd_cycle_gate(lfd_context* ctx, int32_t n_pairs, const float* const* cert, 
     return LFD_OK;
 }
 
-// ---- multi-view support filter (lfd_support.hip) -------------------------------------------------------------------------------------------
-static LfdSupportGeom launch_geom(const lfd_batch* batch, const LfdLaunch& L, float support_thresh_px, float reproj_thresh) {
-    LfdSupportGeom g;
-    g.H = batch->H; g.W = batch->W; g.C = batch->warp_channels; g.w_match = batch->w_match; g.h_match = batch->h_match;
-    g.wm1 = L.kp.wm1; g.hm1 = L.kp.hm1; g.mask_sx = L.mask_sx; g.mask_sy = L.mask_sy;
-    g.tau = support_thresh_px; g.reproj_thresh = reproj_thresh;
-    return g;
-}
-
-int lfd_support_filter(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets_in, int32_t min_support,
-                       float support_thresh_px, const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out, uint8_t* support) {
+// ---- the per-point stages behind triangulation: what their entry points share ---------------------------------------------------------------
+static int device_guard(lfd_context* ctx) {
     if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
     if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
-    int code = LFD_ERR_INVALID;
-    if (const char* why = lfd_support_check(in, ref_offsets_in, min_support, support_thresh_px, out, ref_offsets_out, &code))
-        return fail(ctx, code, std::string("lfd_support_filter: ") + why);
+    return LFD_OK;
+}
+
+static LfdSupportGeom launch_geom(const lfd_batch* batch, const LfdLaunch& L, float support_thresh_px, float reproj_thresh) {
+    return lfd_support_geom(batch, L.kp.wm1, L.kp.hm1, L.mask_sx, L.mask_sy, support_thresh_px, reproj_thresh);
+}
+
+// The header of a stage's arguments: the batch's tables (batch_launch), the input points and the launch geometry.
+static int fill_stage(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets, float support_thresh_px,
+                      float reproj_thresh, LfdPointStage& st) {
     LfdLaunch L;
     int rc = batch_launch(ctx, batch, L);
     if (rc != LFD_OK) return rc;
-    LfdSupportArgs p;
-    std::memset(&p, 0, sizeof(p));
-    p.n_wg = (int32_t)((in->capacity + 255) / 256);
-    const size_t counts_bytes = ((size_t)p.n_wg * 256 + 255) & ~size_t(255);
-    rc = ensure(ctx, ctx->support_ws, counts_bytes + ((size_t)p.n_wg + 1) * sizeof(unsigned));
+    st.refs = L.refs; st.slots = L.slots; st.ref_const = L.ref_const; st.pair_const = L.pair_const;
+    st.axis_x = L.axis_x; st.axis_y = L.axis_y;
+    st.offs = reinterpret_cast<const long long*>(ref_offsets);
+    st.xyz = in->xyz; st.rgb = in->rgb; st.err = in->err; st.cell = in->cell; st.slot = in->slot;
+    st.capacity = in->capacity;
+    st.n_refs = batch->n_refs; st.k = batch->k; st.n_wg = (int32_t)((in->capacity + 255) / 256);
+    st.g = launch_geom(batch, L, support_thresh_px, reproj_thresh);
+    return LFD_OK;
+}
+
+// The workspace of the three gates (support filter, depth-uncertainty gate, photo-consistency gate), one layout: a keep byte per point of the
+// covering workgroups, the workgroups' counts and one word for the total, then - when a plane moves with the points - an f32 per point.  Also
+// zeroes the caller's seg_counts, which the gates' kernels add to.
+struct GateWs { uint8_t* keep; unsigned* wg_kept; float* extra; };
+
+static int carve_gate_ws(lfd_context* ctx, const LfdPointStage& st, bool extra, int32_t* seg_counts_out, GateWs& w) {
+    const size_t n_pad = (size_t)st.n_wg * 256, words = ((size_t)st.n_wg + 1) * sizeof(unsigned);
+    int rc = ensure(ctx, ctx->support_ws, n_pad + words + (extra ? n_pad * sizeof(float) : 0));
     if (rc != LFD_OK) return rc;
-    p.refs = L.refs; p.slots = L.slots; p.pair_const = L.pair_const;
-    p.offs_in = reinterpret_cast<const long long*>(ref_offsets_in);
-    p.xyz = in->xyz; p.rgb = in->rgb; p.err = in->err; p.cell = in->cell; p.slot = in->slot;
-    p.o_xyz = out->xyz; p.o_rgb = out->rgb; p.o_err = out->err; p.o_cell = out->cell; p.o_slot = out->slot;
-    p.offs_out = reinterpret_cast<long long*>(ref_offsets_out);
-    p.seg_counts = seg_counts_out; p.support = support;
-    p.counts = static_cast<uint8_t*>(ctx->support_ws.ptr);
-    p.wg_kept = reinterpret_cast<unsigned*>(static_cast<unsigned char*>(ctx->support_ws.ptr) + counts_bytes);
-    p.capacity = in->capacity;
-    p.n_refs = batch->n_refs; p.k = batch->k; p.min_support = min_support;
-    p.g = launch_geom(batch, L, support_thresh_px, 0.0f);
-    if (seg_counts_out) LFD_HIP(ctx, hipMemsetAsync(seg_counts_out, 0, sizeof(int32_t) * (size_t)batch->n_refs * batch->k, ctx->stream));
-    LFD_HIP(ctx, lfd_support_launch(p, ctx->stream));
+    unsigned char* ws = static_cast<unsigned char*>(ctx->support_ws.ptr);
+    w.keep = ws;
+    w.wg_kept = reinterpret_cast<unsigned*>(ws + n_pad);
+    w.extra = extra ? reinterpret_cast<float*>(ws + n_pad + words) : nullptr;
+    if (seg_counts_out) LFD_HIP(ctx, hipMemsetAsync(seg_counts_out, 0, sizeof(int32_t) * (size_t)st.n_refs * st.k, ctx->stream));
+    return LFD_OK;
+}
+
+static LfdCompactArgs compact_args(const LfdPointStage& st, const GateWs& w, const lfd_points* out, int64_t* ref_offsets_out, float* extra_out) {
+    LfdCompactArgs c = {};
+    c.offs_in = st.offs; c.offs_out = reinterpret_cast<long long*>(ref_offsets_out);
+    c.xyz = st.xyz; c.rgb = st.rgb; c.err = st.err; c.cell = st.cell; c.slot = st.slot;
+    c.o_xyz = out->xyz; c.o_rgb = out->rgb; c.o_err = out->err; c.o_cell = out->cell; c.o_slot = out->slot;
+    c.keep = w.keep; c.wg_kept = w.wg_kept; c.extra_in = w.extra; c.extra_out = extra_out;
+    c.capacity = st.capacity; c.n_refs = st.n_refs; c.n_wg = st.n_wg;
+    return c;
+}
+
+// ---- multi-view support filter (lfd_support.hip) -------------------------------------------------------------------------------------------
+int lfd_support_filter(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets_in, int32_t min_support,
+                       float support_thresh_px, const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out, uint8_t* support) {
+    if (int rc = device_guard(ctx)) return rc;
+    int code = LFD_ERR_INVALID;
+    if (const char* why = lfd_support_check(in, ref_offsets_in, min_support, support_thresh_px, out, ref_offsets_out, &code))
+        return fail(ctx, code, std::string("lfd_support_filter: ") + why);
+    LfdSupportArgs p = {};
+    int rc = fill_stage(ctx, batch, in, ref_offsets_in, support_thresh_px, 0.0f, p.st);
+    if (rc != LFD_OK) return rc;
+    GateWs w;
+    rc = carve_gate_ws(ctx, p.st, false, seg_counts_out, w);
+    if (rc != LFD_OK) return rc;
+    p.seg_counts = seg_counts_out; p.support = support; p.keep = w.keep; p.wg_kept = w.wg_kept; p.min_support = min_support;
+    LFD_HIP(ctx, lfd_support_launch(p, compact_args(p.st, w, out, ref_offsets_out, nullptr), ctx->stream));
     return LFD_OK;
 }
 
@@ -2226,35 +2257,29 @@ static int upload_precision_table(lfd_context* ctx, const lfd_batch* b, const fl
     return upload_pointer_table(ctx, ctx->prec, b, reinterpret_cast<const void* const*>(precision), reinterpret_cast<const void* const**>(d_tab));
 }
 
+// (one table for the colour, gain and photo stages: the cache compares content, and the stages of one configuration hand over the same images)
+static int upload_image_table(lfd_context* ctx, const lfd_batch* b, const uint8_t* const* nbr_image, const uint8_t* const** d_tab) {
+    return upload_pointer_table(ctx, ctx->colour_img, b, reinterpret_cast<const void* const*>(nbr_image), reinterpret_cast<const void* const**>(d_tab));
+}
+
 // Both re-triangulation calls.  weighted: lfd_refine_multiview_weighted (precision checked behind the batch, its table uploaded, three
 // counters); otherwise lfd_refine_multiview (two).  name: the entry point, for the messages.
 static int refine_impl(lfd_context* ctx, const char* name, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets,
                        float support_thresh_px, float reproj_thresh, float* xyz_out, float* err_out, uint8_t* status, int64_t* counters,
                        const float* const* precision, bool weighted) {
-    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
-    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (int rc = device_guard(ctx)) return rc;
     if (const char* why = lfd_refine_check(in, ref_offsets, support_thresh_px, reproj_thresh, xyz_out, err_out, status))
         return fail(ctx, LFD_ERR_INVALID, std::string(name) + ": " + why);
-    LfdLaunch L;
-    int rc = batch_launch(ctx, batch, L);
+    LfdRefineArgs p = {};
+    int rc = fill_stage(ctx, batch, in, ref_offsets, support_thresh_px, reproj_thresh, p.st);
     if (rc != LFD_OK) return rc;
-    LfdRefineArgs p;
-    std::memset(&p, 0, sizeof(p));
     if (weighted) {
         if (const char* why = lfd_refine_check_precision(batch, precision)) return fail(ctx, LFD_ERR_INVALID, std::string(name) + ": " + why);
         rc = upload_precision_table(ctx, batch, precision, &p.prec);
         if (rc != LFD_OK) return rc;
     }
-    p.n_wg = (int32_t)((in->capacity + 255) / 256);
-    p.refs = L.refs; p.slots = L.slots; p.ref_const = L.ref_const; p.pair_const = L.pair_const;
-    p.axis_x = L.axis_x; p.axis_y = L.axis_y;
-    p.offs = reinterpret_cast<const long long*>(ref_offsets);
-    p.xyz = in->xyz; p.err = in->err; p.cell = in->cell; p.slot = in->slot;
     p.o_xyz = xyz_out; p.o_err = err_out; p.status = status;
     p.counters = reinterpret_cast<unsigned long long*>(counters);
-    p.capacity = in->capacity;
-    p.n_refs = batch->n_refs; p.k = batch->k;
-    p.g = launch_geom(batch, L, support_thresh_px, reproj_thresh);
     LFD_HIP(ctx, lfd_refine_launch(p, ctx->stream));
     return LFD_OK;
 }
@@ -2275,25 +2300,15 @@ int lfd_refine_multiview_weighted(lfd_context* ctx, const lfd_batch* batch, cons
 // ---- per-point surface normals (lfd_normals.hip) ----------------------------------------------------------------------------------------------
 int lfd_estimate_normals(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets, int32_t radius_cells,
                          float depth_step_rel, float reproj_thresh, float* normals_out, uint8_t* status, int64_t* counters) {
-    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
-    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (int rc = device_guard(ctx)) return rc;
     if (const char* why = lfd_normals_check(in, ref_offsets, radius_cells, depth_step_rel, reproj_thresh, normals_out, status))
         return fail(ctx, LFD_ERR_INVALID, std::string("lfd_estimate_normals: ") + why);
-    LfdLaunch L;
-    int rc = batch_launch(ctx, batch, L);
+    LfdNormalArgs p = {};
+    int rc = fill_stage(ctx, batch, in, ref_offsets, 0.0f, reproj_thresh, p.st);
     if (rc != LFD_OK) return rc;
-    LfdNormalArgs p;
-    std::memset(&p, 0, sizeof(p));
-    p.n_wg = (int32_t)((in->capacity + 255) / 256);
-    p.refs = L.refs; p.slots = L.slots; p.ref_const = L.ref_const; p.pair_const = L.pair_const;
-    p.axis_x = L.axis_x; p.axis_y = L.axis_y;
-    p.offs = reinterpret_cast<const long long*>(ref_offsets);
-    p.xyz = in->xyz; p.cell = in->cell; p.slot = in->slot;
     p.normals = normals_out; p.status = status;
     p.counters = reinterpret_cast<unsigned long long*>(counters);
-    p.capacity = in->capacity;
-    p.n_refs = batch->n_refs; p.k = batch->k; p.radius = radius_cells; p.depth_step_rel = depth_step_rel;
-    p.g = launch_geom(batch, L, 0.0f, reproj_thresh);
+    p.radius = radius_cells; p.depth_step_rel = depth_step_rel;
     LFD_HIP(ctx, lfd_normals_launch(p, ctx->stream));
     return LFD_OK;
 }
@@ -2302,28 +2317,18 @@ int lfd_estimate_normals(lfd_context* ctx, const lfd_batch* batch, const lfd_poi
 int lfd_colour_multiview(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets,
                          const uint8_t* const* nbr_image, float support_thresh_px, int32_t mode, float* rgb_out, uint8_t* status,
                          int64_t* counters) {
-    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
-    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (int rc = device_guard(ctx)) return rc;
     if (const char* why = lfd_colour_check(in, ref_offsets, nbr_image, support_thresh_px, mode, rgb_out, status))
         return fail(ctx, LFD_ERR_INVALID, std::string("lfd_colour_multiview: ") + why);
-    LfdLaunch L;
-    int rc = batch_launch(ctx, batch, L);
+    LfdColourArgs p = {};
+    int rc = fill_stage(ctx, batch, in, ref_offsets, support_thresh_px, 0.0f, p.st);
     if (rc != LFD_OK) return rc;
     if (const char* why = lfd_colour_check_images(batch, nbr_image)) return fail(ctx, LFD_ERR_INVALID, std::string("lfd_colour_multiview: ") + why);
-    LfdColourArgs p;
-    std::memset(&p, 0, sizeof(p));
-    rc = upload_pointer_table(ctx, ctx->colour_img, batch, reinterpret_cast<const void* const*>(nbr_image),
-                              reinterpret_cast<const void* const**>(&p.img));
+    rc = upload_image_table(ctx, batch, nbr_image, &p.img);
     if (rc != LFD_OK) return rc;
-    p.n_wg = (int32_t)((in->capacity + 255) / 256);
-    p.refs = L.refs; p.slots = L.slots; p.pair_const = L.pair_const;
-    p.offs = reinterpret_cast<const long long*>(ref_offsets);
-    p.xyz = in->xyz; p.rgb = in->rgb; p.cell = in->cell; p.slot = in->slot;
     p.o_rgb = rgb_out; p.status = status;
     p.counters = reinterpret_cast<unsigned long long*>(counters);
-    p.capacity = in->capacity;
-    p.n_refs = batch->n_refs; p.k = batch->k; p.mode = mode;
-    p.g = launch_geom(batch, L, support_thresh_px, 0.0f);
+    p.mode = mode;
     LFD_HIP(ctx, lfd_colour_launch(p, ctx->stream));
     return LFD_OK;
 }
@@ -2331,30 +2336,18 @@ int lfd_colour_multiview(lfd_context* ctx, const lfd_batch* batch, const lfd_poi
 // ---- per-image exposure gains (lfd_gain.hip) ----------------------------------------------------------------------------------------------------
 int lfd_gain_accumulate(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets,
                         const uint8_t* const* nbr_image, float support_thresh_px, uint64_t* table) {
-    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
-    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (int rc = device_guard(ctx)) return rc;
     if (const char* why = lfd_gain_check(in, ref_offsets, nbr_image, support_thresh_px, table, 0))
         return fail(ctx, LFD_ERR_INVALID, std::string("lfd_gain_accumulate: ") + why);
-    LfdLaunch L;
-    int rc = batch_launch(ctx, batch, L);
+    LfdGainArgs p = {};
+    int rc = fill_stage(ctx, batch, in, ref_offsets, support_thresh_px, 0.0f, p.st);
     if (rc != LFD_OK) return rc;
     if (const char* why = lfd_gain_check(in, ref_offsets, nbr_image, support_thresh_px, table, (long long)batch->n_refs * batch->k))
         return fail(ctx, LFD_ERR_INVALID, std::string("lfd_gain_accumulate: ") + why);
     if (const char* why = lfd_colour_check_images(batch, nbr_image)) return fail(ctx, LFD_ERR_INVALID, std::string("lfd_gain_accumulate: ") + why);
-    LfdGainArgs p;
-    std::memset(&p, 0, sizeof(p));
-    // (the image table is the colour stage's: the two stages never run in one configuration, and the cache compares content anyway)
-    rc = upload_pointer_table(ctx, ctx->colour_img, batch, reinterpret_cast<const void* const*>(nbr_image),
-                              reinterpret_cast<const void* const**>(&p.img));
+    rc = upload_image_table(ctx, batch, nbr_image, &p.img);
     if (rc != LFD_OK) return rc;
-    p.n_wg = (int32_t)((in->capacity + 255) / 256);
-    p.refs = L.refs; p.slots = L.slots; p.pair_const = L.pair_const;
-    p.offs = reinterpret_cast<const long long*>(ref_offsets);
-    p.xyz = in->xyz; p.rgb = in->rgb; p.cell = in->cell; p.slot = in->slot;
     p.table = reinterpret_cast<unsigned long long*>(table);
-    p.capacity = in->capacity;
-    p.n_refs = batch->n_refs; p.k = batch->k;
-    p.g = launch_geom(batch, L, support_thresh_px, 0.0f);
     LFD_HIP(ctx, lfd_gain_launch(p, ctx->stream));
     return LFD_OK;
 }
@@ -2499,48 +2492,26 @@ int lfd_far_emit(lfd_context* ctx, const uint64_t* table, int32_t shell_cells, i
 int lfd_photo_gate(lfd_context* ctx, const lfd_batch* batch, const lfd_points* in, const int64_t* ref_offsets_in,
                    const uint8_t* const* nbr_image, int32_t window_cells, float min_ncc, float min_texture, const lfd_points* out,
                    int64_t* ref_offsets_out, int32_t* seg_counts_out, uint8_t* status, float* ncc, int64_t* counters) {
-    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
-    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (int rc = device_guard(ctx)) return rc;
     int code = LFD_ERR_INVALID;
     if (const char* why = lfd_photo_check(in, ref_offsets_in, nbr_image, window_cells, min_ncc, min_texture, out, ref_offsets_out, status, ncc,
                                           counters, &code))
         return fail(ctx, code, std::string("lfd_photo_gate: ") + why);
-    LfdLaunch L;
-    int rc = batch_launch(ctx, batch, L);
+    LfdPhotoArgs p = {};
+    int rc = fill_stage(ctx, batch, in, ref_offsets_in, 0.0f, 0.0f, p.st);
     if (rc != LFD_OK) return rc;
     if (const char* why = lfd_colour_check_images(batch, nbr_image)) return fail(ctx, LFD_ERR_INVALID, std::string("lfd_photo_gate: ") + why);
-    LfdPhotoArgs p;
-    std::memset(&p, 0, sizeof(p));
-    // (the image table is the colour stage's: the cache compares content, and the stages of one configuration hand over the same images)
-    rc = upload_pointer_table(ctx, ctx->colour_img, batch, reinterpret_cast<const void* const*>(nbr_image),
-                              reinterpret_cast<const void* const**>(&p.img));
+    rc = upload_image_table(ctx, batch, nbr_image, &p.img);
     if (rc != LFD_OK) return rc;
-    p.n_wg = (int32_t)((in->capacity + 255) / 256);
-    const size_t keep_bytes = ((size_t)p.n_wg * 256 + 255) & ~size_t(255);   // the support filter's layout: its counts are the keep bytes
-    rc = ensure(ctx, ctx->support_ws, keep_bytes + ((size_t)p.n_wg + 1) * sizeof(unsigned));
+    GateWs w;
+    rc = carve_gate_ws(ctx, p.st, false, seg_counts_out, w);
     if (rc != LFD_OK) return rc;
-    p.refs = L.refs; p.slots = L.slots; p.axis_x = L.axis_x; p.axis_y = L.axis_y;
-    p.offs_in = reinterpret_cast<const long long*>(ref_offsets_in);
-    p.cell = in->cell; p.slot = in->slot;
     p.seg_counts = seg_counts_out; p.status = status; p.ncc = ncc;
     p.counters = reinterpret_cast<unsigned long long*>(counters);
-    p.keep = static_cast<uint8_t*>(ctx->support_ws.ptr);
-    p.wg_kept = reinterpret_cast<unsigned*>(static_cast<unsigned char*>(ctx->support_ws.ptr) + keep_bytes);
-    p.capacity = in->capacity;
-    p.n_refs = batch->n_refs; p.k = batch->k; p.radius = window_cells;
+    p.keep = w.keep; p.wg_kept = w.wg_kept;
+    p.radius = window_cells;
     p.th = lfd_photo_thresholds(min_ncc, min_texture);
-    p.g = launch_geom(batch, L, 0.0f, 0.0f);
-    LfdSupportArgs q;
-    std::memset(&q, 0, sizeof(q));
-    q.offs_in = p.offs_in;
-    q.xyz = in->xyz; q.rgb = in->rgb; q.err = in->err; q.cell = in->cell; q.slot = in->slot;
-    q.o_xyz = out->xyz; q.o_rgb = out->rgb; q.o_err = out->err; q.o_cell = out->cell; q.o_slot = out->slot;
-    q.offs_out = reinterpret_cast<long long*>(ref_offsets_out);
-    q.counts = p.keep; q.wg_kept = p.wg_kept;
-    q.capacity = in->capacity;
-    q.n_refs = batch->n_refs; q.k = batch->k; q.min_support = 1; q.n_wg = p.n_wg;
-    if (seg_counts_out) LFD_HIP(ctx, hipMemsetAsync(seg_counts_out, 0, sizeof(int32_t) * (size_t)batch->n_refs * batch->k, ctx->stream));
-    LFD_HIP(ctx, lfd_photo_launch(p, q, ctx->stream));
+    LFD_HIP(ctx, lfd_photo_launch(p, compact_args(p.st, w, out, ref_offsets_out, nullptr), ctx->stream));
     return LFD_OK;
 }
 
@@ -2549,17 +2520,14 @@ int lfd_depth_sigma_filter(lfd_context* ctx, const lfd_batch* batch, const lfd_p
                            const float* const* precision, float iso_sigma_px, const uint8_t* refine_status, float support_thresh_px,
                            float max_rel_sigma, const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out, float* sigma_rel,
                            float* sigma_rel_out) {
-    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
-    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (int rc = device_guard(ctx)) return rc;
     int code = LFD_ERR_INVALID;
     if (const char* why = lfd_sigma_check(in, ref_offsets_in, precision, iso_sigma_px, refine_status, support_thresh_px, max_rel_sigma, out,
                                           ref_offsets_out, sigma_rel, sigma_rel_out, &code))
         return fail(ctx, code, std::string("lfd_depth_sigma_filter: ") + why);
-    LfdLaunch L;
-    int rc = batch_launch(ctx, batch, L);
+    LfdSigmaArgs p = {};
+    int rc = fill_stage(ctx, batch, in, ref_offsets_in, refine_status ? support_thresh_px : 0.0f, 0.0f, p.st);
     if (rc != LFD_OK) return rc;
-    LfdSigmaArgs p;
-    std::memset(&p, 0, sizeof(p));
     if (precision) {
         if (const char* why = lfd_refine_check_precision(batch, precision)) return fail(ctx, LFD_ERR_INVALID, std::string("lfd_depth_sigma_filter: ") + why);
         rc = upload_precision_table(ctx, batch, precision, &p.prec);
@@ -2567,26 +2535,13 @@ int lfd_depth_sigma_filter(lfd_context* ctx, const lfd_batch* batch, const lfd_p
     } else {
         p.iso = lfd_recip_refined((double)iso_sigma_px * (double)iso_sigma_px);     // (host build: the IEEE quotient, as in the twin)
     }
-    p.n_wg = (int32_t)((in->capacity + 255) / 256);
-    const size_t n_pad = (size_t)p.n_wg * 256;                          // sigma f32, keep bytes, then the workgroups' counts
-    rc = ensure(ctx, ctx->support_ws, n_pad * 5 + ((size_t)p.n_wg + 1) * sizeof(unsigned));
+    GateWs w;
+    rc = carve_gate_ws(ctx, p.st, sigma_rel_out != nullptr, seg_counts_out, w);
     if (rc != LFD_OK) return rc;
-    p.refs = L.refs; p.slots = L.slots; p.ref_const = L.ref_const; p.pair_const = L.pair_const;
-    p.offs_in = reinterpret_cast<const long long*>(ref_offsets_in);
-    p.xyz = in->xyz; p.rgb = in->rgb; p.err = in->err; p.cell = in->cell; p.slot = in->slot;
-    p.o_xyz = out->xyz; p.o_rgb = out->rgb; p.o_err = out->err; p.o_cell = out->cell; p.o_slot = out->slot;
-    p.offs_out = reinterpret_cast<long long*>(ref_offsets_out);
-    p.seg_counts = seg_counts_out; p.sigma = sigma_rel; p.o_sigma = sigma_rel_out; p.status = refine_status;
-    unsigned char* ws = static_cast<unsigned char*>(ctx->support_ws.ptr);
-    p.ws_sigma = reinterpret_cast<float*>(ws);
-    p.keep = ws + n_pad * 4;
-    p.wg_kept = reinterpret_cast<unsigned*>(ws + n_pad * 5);
-    p.capacity = in->capacity;
+    p.seg_counts = seg_counts_out; p.sigma = sigma_rel; p.status = refine_status;
+    p.ws_sigma = w.extra; p.keep = w.keep; p.wg_kept = w.wg_kept;
     p.max_rel_sigma = max_rel_sigma;
-    p.n_refs = batch->n_refs; p.k = batch->k;
-    p.g = launch_geom(batch, L, refine_status ? support_thresh_px : 0.0f, 0.0f);
-    if (seg_counts_out) LFD_HIP(ctx, hipMemsetAsync(seg_counts_out, 0, sizeof(int32_t) * (size_t)batch->n_refs * batch->k, ctx->stream));
-    LFD_HIP(ctx, lfd_sigma_launch(p, ctx->stream));
+    LFD_HIP(ctx, lfd_sigma_launch(p, compact_args(p.st, w, out, ref_offsets_out, sigma_rel_out), ctx->stream));
     return LFD_OK;
 }
 

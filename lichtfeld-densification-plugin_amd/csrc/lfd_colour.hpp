@@ -130,18 +130,12 @@ LFD_HD unsigned lfd_colour_point(const LfdSlot* sl, const uint8_t* const* img, i
 
 // What a launch works on (device), by value in the kernel arguments.
 struct LfdColourArgs {
-    const void* refs;                  // LfdRefDesc [n_refs]
-    const void* slots;                 // LfdSlotDesc [n_refs * k]
-    const LfdPairConst* pair_const;    // [n_refs * k]
+    LfdPointStage st;                  // (g.reproj_thresh unused)
     const uint8_t* const* img;         // [n_refs * k] the neighbours' match-size images (device table)
-    const long long* offs;             // [n_refs + 1]
-    const float* xyz; const float* rgb; const int32_t* cell; const uint8_t* slot;
-    float* o_rgb;                      // [3 * capacity]; may be `rgb` itself
+    float* o_rgb;                      // [3 * capacity]; may be st.rgb itself
     uint8_t* status;                   // [capacity] or null
     unsigned long long* counters;      // [2] or null: points blended, the sum of their n; added to
-    long long capacity;
-    int32_t n_refs, k, n_wg, mode;
-    LfdSupportGeom g;                  // (reproj_thresh unused)
+    int32_t mode;
 };
 
 // Arguments of lfd_colour_multiview / lfd_colour_multiview_host that do not depend on the batch; what is wrong with them, or null.

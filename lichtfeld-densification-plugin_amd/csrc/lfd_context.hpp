@@ -96,7 +96,7 @@ struct lfd_context {
     // lfd_knn_dist2, lfd_render_depth), grown on demand.  Each call carves it anew (lfd_api.hip: carve_cloud_ws) and writes or clears every word before it reads it;
     // the stages may share it because each of them returns with the stream idle.
     DeviceBuffer cloud_ws;
-    DeviceBuffer support_ws;       // lfd_support_filter: support count of every input point, kept points per workgroup; grown on demand
+    DeviceBuffer support_ws;       // the gates behind triangulation (carve_gate_ws): keep bytes, kept points per workgroup, an optional f32 plane; grown on demand
     DeviceBuffer undist_cnt;       // lfd_undistort_image: the u64 counter of invalid pixels of a call that asks for it
     // A table of device pointers a per-point stage reads (one per (reference, slot)), uploaded on the launch stream when its content differs from
     // the last: lfd_refine_multiview_weighted's / lfd_depth_sigma_filter's precision planes, lfd_colour_multiview's neighbour images

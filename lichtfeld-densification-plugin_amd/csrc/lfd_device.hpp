@@ -255,9 +255,9 @@ struct LfdPointSpan {           // the input points of a 256-lane workgroup: lan
     bool any, mine;             // any: the workgroup has points at all (uniform); mine: this lane has one
 };
 
-__device__ __forceinline__ LfdPointSpan lfd_point_span(const long long* offs, int n_refs, long long capacity) {
+__device__ __forceinline__ LfdPointSpan lfd_point_span(const LfdPointStage& st) {
     LfdPointSpan w;
-    w.total = lfd_support_clamp(offs[n_refs], capacity);
+    w.total = lfd_support_clamp(st.offs[st.n_refs], st.capacity);
     const long long base = (long long)blockIdx.x * 256;
     w.any = base < w.total;
     w.i = base + (int)threadIdx.x;
@@ -275,5 +275,68 @@ __device__ __forceinline__ void lfd_stage_slots(LfdSlot* sh, const void* slots, 
         const LfdSlotDesc& d = static_cast<const LfdSlotDesc*>(slots)[(size_t)rr * k + tid];
         lfd_slot_fill(sh[tid], d.cert, d.warp, d.mask_b, pair_const[(size_t)rr * k + tid]);
     }
+}
+
+// The references a workgroup's points belong to, [r_first, r_last], exchanged through sh_ref behind a barrier; returns the lane's own.  A
+// workgroup whose points straddle references takes them one after the other.  The lane that writes sh_ref[0] also zeroes the workgroup's NZ
+// counters at sh_zero (null when NZ is 0), which the same barrier publishes.
+template <int NZ>
+__device__ __forceinline__ int lfd_ref_range(int (&sh_ref)[2], unsigned* sh_zero, const LfdPointStage& st, const LfdPointSpan& sp, int& r_first,
+                                             int& r_last) {
+    const int r = lfd_support_ref_of(st.offs, st.n_refs, st.capacity, sp.ii);
+    if (threadIdx.x == 0) {
+        sh_ref[0] = r;
+#pragma unroll
+        for (int e = 0; e < NZ; ++e) sh_zero[e] = 0u;
+    }
+    if (sp.i == sp.last) sh_ref[1] = r;
+    __syncthreads();
+    r_first = sh_ref[0]; r_last = sh_ref[1];
+    return r;
+}
+
+// reference rr has no points (uniform): the loop over [r_first, r_last] skips it
+__device__ __forceinline__ bool lfd_ref_empty(const LfdPointStage& st, int rr) {
+    return lfd_support_clamp(st.offs[rr + 1], st.capacity) <= lfd_support_clamp(st.offs[rr], st.capacity);
+}
+
+// the neighbours of reference rr a kernel with room for KMAX looks at
+template <int KMAX>
+__device__ __forceinline__ int lfd_ref_slots(const LfdPointStage& st, int rr) {
+    const int ns = static_cast<const LfdRefDesc*>(st.refs)[rr].n_slots;
+    return ns < KMAX ? ns : KMAX;
+}
+
+// Per-(reference, winning slot) counts of the kept points of a gate: every lane of the workgroup calls lfd_seg_tally (after sh_seg[0 .. KMAX) was
+// zeroed and a barrier), then, behind another barrier, lfd_seg_flush - one integer atomic per workgroup and slot that kept anything.
+template <int KMAX>
+__device__ __forceinline__ void lfd_seg_tally(unsigned* sh_seg, bool kept_here, int s) {
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j) {
+        const unsigned long long m = __ballot(kept_here && s == j);
+        if (m && (threadIdx.x & 63) == 0) atomicAdd(&sh_seg[j], (unsigned)__popcll(m));
+    }
+}
+
+__device__ __forceinline__ void lfd_seg_flush(const unsigned* sh_seg, int32_t* seg_counts, int rr, int k, int ns) {
+    const int tid = (int)threadIdx.x;
+    if (tid < ns && sh_seg[tid]) atomicAdd(seg_counts + (size_t)rr * k + tid, (int)sh_seg[tid]);
+}
+
+// N counters over the lanes of a workgroup: hit[j] says whether the lane counts for counter j.  sh_cnt[0 .. N) was zeroed before a barrier; the
+// caller puts a barrier between the tally and lfd_count_flush, which adds what is not zero to counters (integer adds: order-free).
+template <int N>
+__device__ __forceinline__ void lfd_count_tally(unsigned* sh_cnt, const bool (&hit)[N]) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const unsigned long long m = __ballot(hit[j]);
+        if (m && (threadIdx.x & 63) == 0) atomicAdd(&sh_cnt[j], (unsigned)__popcll(m));
+    }
+}
+
+template <int N>
+__device__ __forceinline__ void lfd_count_flush(const unsigned* sh_cnt, unsigned long long* counters) {
+    const int tid = (int)threadIdx.x;
+    if (tid < N && sh_cnt[tid]) atomicAdd(counters + tid, (unsigned long long)sh_cnt[tid]);
 }
 #endif

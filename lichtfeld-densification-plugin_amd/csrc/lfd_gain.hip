@@ -1,6 +1,6 @@
 // Per-image exposure gains on the device (lfd_gain_accumulate / lfd_gain_apply).
 //
-// lfd_gain_kernel: one launch, a lane per input point, with the front end of lfd_colour_kernel (lfd_colour.hip): coalesced loads of the
+// lfd_gain_kernel: one launch, a lane per input point, with the per-point kernels' common front end (lfd_device.hpp): coalesced loads of the
 // point's own fields, its reference from ref_offsets (device data), the reference's neighbours and their image bases staged in LDS (a
 // workgroup whose points straddle references takes them one after the other).  What a lane has per slot is a flag and six integers below
 // 2^24; what the table wants is their sum.  The reduction, per (reference, slot):
@@ -24,32 +24,28 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) l
     __shared__ int sh_ref[2];
     __shared__ unsigned sh_acc[KMAX * LFD_GAIN_QUANTITIES];
     const int tid = (int)threadIdx.x;
-    const LfdPointSpan sp = lfd_point_span(p.offs, p.n_refs, p.capacity);
+    const LfdPointStage& st = p.st;
+    const LfdPointSpan sp = lfd_point_span(st);
     if (!sp.any) return;                                                // the whole workgroup lies past the last point
-    const long long i = sp.i, ii = sp.ii;
+    const long long ii = sp.ii;
     const bool mine = sp.mine;
-    const int cell = p.cell[ii];
-    const int s = (int)p.slot[ii];
-    const float X0 = p.xyz[3 * ii], X1 = p.xyz[3 * ii + 1], X2 = p.xyz[3 * ii + 2];
-    const float rgb[3] = {p.rgb[3 * ii], p.rgb[3 * ii + 1], p.rgb[3 * ii + 2]};
-    const int r = lfd_support_ref_of(p.offs, p.n_refs, p.capacity, ii);
-    if (tid == 0) sh_ref[0] = r;
-    if (i == sp.last) sh_ref[1] = r;
-    __syncthreads();
-    const int r_first = sh_ref[0], r_last = sh_ref[1];
-    const LfdSupportGeom g = p.g;
+    const int cell = st.cell[ii];
+    const int s = (int)st.slot[ii];
+    const float X0 = st.xyz[3 * ii], X1 = st.xyz[3 * ii + 1], X2 = st.xyz[3 * ii + 2];
+    const float rgb[3] = {st.rgb[3 * ii], st.rgb[3 * ii + 1], st.rgb[3 * ii + 2]};
+    int r_first, r_last;
+    const int r = lfd_ref_range<0>(sh_ref, nullptr, st, sp, r_first, r_last);
+    const LfdSupportGeom g = st.g;
     const long long HW = (long long)g.H * g.W;
-    const LfdRefDesc* refs = static_cast<const LfdRefDesc*>(p.refs);
     const bool ref_ok = lfd_gain_in_range(rgb[0]) && lfd_gain_in_range(rgb[1]) && lfd_gain_in_range(rgb[2]);
     // (a value out of range - NaN included - never reaches the conversion)
     const unsigned qr0 = ref_ok ? lfd_gain_quantise(rgb[0]) : 0u, qr1 = ref_ok ? lfd_gain_quantise(rgb[1]) : 0u,
                    qr2 = ref_ok ? lfd_gain_quantise(rgb[2]) : 0u;
     for (int rr = r_first; rr <= r_last; ++rr) {
-        if (lfd_support_clamp(p.offs[rr + 1], p.capacity) <= lfd_support_clamp(p.offs[rr], p.capacity)) continue;   // uniform: no points
-        int ns = refs[rr].n_slots;
-        ns = ns < KMAX ? ns : KMAX;
-        lfd_stage_slots(sh, p.slots, p.pair_const, rr, p.k, ns);
-        if (tid < ns) sh_img[tid] = p.img[(size_t)rr * p.k + tid];
+        if (lfd_ref_empty(st, rr)) continue;
+        const int ns = lfd_ref_slots<KMAX>(st, rr);
+        lfd_stage_slots(sh, st.slots, st.pair_const, rr, st.k, ns);
+        if (tid < ns) sh_img[tid] = p.img[(size_t)rr * st.k + tid];
         if (tid < KMAX * LFD_GAIN_QUANTITIES) sh_acc[tid] = 0u;
         __syncthreads();
         const bool active = mine && r == rr && !lfd_colour_guarded(X0, X1, X2, rgb[0], rgb[1], rgb[2], cell, HW, s, ns);
@@ -91,7 +87,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) l
         __syncthreads();
         if (tid < ns * LFD_GAIN_QUANTITIES) {
             const unsigned a = sh_acc[tid];                            // row rr * k + tid / 7, quantity tid % 7: consecutive in the table
-            if (a) atomicAdd(p.table + (size_t)rr * p.k * LFD_GAIN_QUANTITIES + tid, (unsigned long long)a);
+            if (a) atomicAdd(p.table + (size_t)rr * st.k * LFD_GAIN_QUANTITIES + tid, (unsigned long long)a);
         }
         __syncthreads();                                               // the next reference's constants replace these
     }
@@ -123,16 +119,16 @@ __global__ void __launch_bounds__(256) lfd_gain_apply_kernel(const LfdGainApplyA
 // (C: the warp's channels, 2 or 4 - a compile-time stride for the observation's address)
 template <int C>
 static void lfd_gain_launch_c(const LfdGainArgs& p, dim3 grid, hipStream_t stream) {
-    if (p.k <= 4) hipLaunchKernelGGL((lfd_gain_kernel<4, C>), grid, dim3(256), 0, stream, p);
-    else if (p.k <= 8) hipLaunchKernelGGL((lfd_gain_kernel<8, C>), grid, dim3(256), 0, stream, p);
+    if (p.st.k <= 4) hipLaunchKernelGGL((lfd_gain_kernel<4, C>), grid, dim3(256), 0, stream, p);
+    else if (p.st.k <= 8) hipLaunchKernelGGL((lfd_gain_kernel<8, C>), grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL((lfd_gain_kernel<LFD_MAX_SLOTS, C>), grid, dim3(256), 0, stream, p);
 }
 
 // lfd_api.hip's lfd_gain_accumulate: the arguments were validated there (capacity <= 2^31 - 1: at most 2^23 workgroups; warp_channels 2 or 4)
 hipError_t lfd_gain_launch(const LfdGainArgs& p, hipStream_t stream) {
-    if (p.n_wg <= 0) return hipSuccess;
-    const dim3 grid((unsigned)p.n_wg);
-    if (p.g.C == 2) lfd_gain_launch_c<2>(p, grid, stream);
+    if (p.st.n_wg <= 0) return hipSuccess;
+    const dim3 grid((unsigned)p.st.n_wg);
+    if (p.st.g.C == 2) lfd_gain_launch_c<2>(p, grid, stream);
     else lfd_gain_launch_c<4>(p, grid, stream);
     return hipGetLastError();
 }

@@ -42,16 +42,9 @@ LFD_HD float lfd_gain_value(float c, float f) {
 
 // What an accumulate launch works on (device), by value in the kernel arguments.
 struct LfdGainArgs {
-    const void* refs;                  // LfdRefDesc [n_refs]
-    const void* slots;                 // LfdSlotDesc [n_refs * k]
-    const LfdPairConst* pair_const;    // [n_refs * k]
+    LfdPointStage st;                  // (g.reproj_thresh unused)
     const uint8_t* const* img;         // [n_refs * k] the neighbours' match-size images (device table)
-    const long long* offs;             // [n_refs + 1]
-    const float* xyz; const float* rgb; const int32_t* cell; const uint8_t* slot;
     unsigned long long* table;         // [n_refs * k][7], added to
-    long long capacity;
-    int32_t n_refs, k, n_wg;
-    LfdSupportGeom g;                  // (reproj_thresh unused)
 };
 
 struct LfdGainApplyArgs {

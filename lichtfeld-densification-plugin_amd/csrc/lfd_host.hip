@@ -259,11 +259,13 @@ int check_host_points(lfd_context* ctx, const lfd_points* out, const int64_t* re
 
 constexpr int kChunk = 4096;     // cells per work item
 
-// The stable compaction behind a per-point verdict (the support filter's, the photo-consistency gate's): the points i < total with kept(i), in
-// the input order inside and across references; ref_offsets_out and the optional per-(reference, winning slot) counts with them.
+// The stable compaction behind a per-point verdict (the three gates' twins): the points i < total with kept(i), in the input order inside and
+// across references; ref_offsets_out and the optional per-(reference, winning slot) counts with them.  extra_out (or null): extra_in[i] moves
+// with point i.
 template <class Kept>
 void compact_points(const lfd_batch* b, const lfd_points* in, const long long* offs, long long cap, long long total, Kept kept,
-                    const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out) {
+                    const lfd_points* out, int64_t* ref_offsets_out, int32_t* seg_counts_out, const float* extra_in = nullptr,
+                    float* extra_out = nullptr) {
     if (seg_counts_out) std::memset(seg_counts_out, 0, sizeof(int32_t) * (size_t)b->n_refs * b->k);
     long long o = 0;
     int r_next = 0;
@@ -274,6 +276,7 @@ void compact_points(const lfd_batch* b, const lfd_points* in, const long long* o
         out->err[o] = in->err[i];
         if (out->cell) out->cell[o] = in->cell[i];
         if (out->slot) out->slot[o] = in->slot[i];
+        if (extra_out) extra_out[o] = extra_in[i];
         if (seg_counts_out) {
             const int r = lfd_support_ref_of(offs, b->n_refs, cap, i), s = (int)in->slot[i];
             if (s < b->n_slots[r]) seg_counts_out[(size_t)r * b->k + s] += 1;
@@ -420,11 +423,7 @@ void make_slot_table(const lfd_context* ctx, const HostLaunch& L, std::vector<Lf
 }
 
 LfdSupportGeom make_geom(const HostLaunch& L, float support_thresh_px, float reproj_thresh) {
-    const lfd_batch* b = L.b;
-    LfdSupportGeom g;
-    g.H = b->H; g.W = b->W; g.C = b->warp_channels; g.w_match = b->w_match; g.h_match = b->h_match;
-    g.wm1 = L.kp.wm1; g.hm1 = L.kp.hm1; g.mask_sx = L.mask_sx; g.mask_sy = L.mask_sy; g.tau = support_thresh_px; g.reproj_thresh = reproj_thresh;
-    return g;
+    return lfd_support_geom(L.b, L.kp.wm1, L.kp.hm1, L.mask_sx, L.mask_sy, support_thresh_px, reproj_thresh);
 }
 
 }  // namespace
@@ -1103,25 +1102,8 @@ int lfd_depth_sigma_filter_host(lfd_context* ctx, const lfd_batch* b, const lfd_
             if (sigma_rel) sigma_rel[i] = sigma;
         }
     });
-    // stable compaction: the input order inside and across references
-    if (seg_counts_out) std::memset(seg_counts_out, 0, sizeof(int32_t) * (size_t)b->n_refs * b->k);
-    long long o = 0;
-    int r_next = 0;
-    for (long long i = 0; i <= total; ++i) {
-        while (r_next <= b->n_refs && std::min(lfd_support_clamp(offs[r_next], cap), total) <= i) ref_offsets_out[r_next++] = o;
-        if (i == total || !lfd_sigma_keep(sig[(size_t)i], max_rel_sigma)) continue;
-        for (int e = 0; e < 3; ++e) { out->xyz[3 * o + e] = in->xyz[3 * i + e]; out->rgb[3 * o + e] = in->rgb[3 * i + e]; }
-        out->err[o] = in->err[i];
-        if (out->cell) out->cell[o] = in->cell[i];
-        if (out->slot) out->slot[o] = in->slot[i];
-        if (sigma_rel_out) sigma_rel_out[o] = sig[(size_t)i];
-        if (seg_counts_out) {
-            const int r = lfd_support_ref_of(offs, b->n_refs, cap, i), s = (int)in->slot[i];
-            if (s < b->n_slots[r]) seg_counts_out[(size_t)r * b->k + s] += 1;
-        }
-        ++o;
-    }
-    while (r_next <= b->n_refs) ref_offsets_out[r_next++] = o;       // (offsets that do not ascend: whatever is left counts from the end)
+    compact_points(b, in, offs, cap, total, [&](long long i) { return lfd_sigma_keep(sig[(size_t)i], max_rel_sigma); }, out, ref_offsets_out,
+                   seg_counts_out, sig.data(), sigma_rel_out);
     return LFD_OK;
 }
 

@@ -1,8 +1,8 @@
 // Per-point surface normals on the device (lfd_estimate_normals): the normal of every point from the winning neighbour's warp in
 // a (2R + 1)^2 window of grid cells around the point's own cell (lfd_normals.hpp).
 //
-// One launch, a lane per input point, nothing waits for another workgroup and nothing is scanned.  The frame is lfd_refine_kernel's
-// (lfd_refine.hip): coalesced loads of the point's own fields, its reference from ref_offsets (device data), the reference's constants and its
+// One launch, a lane per input point, nothing waits for another workgroup and nothing is scanned.  The frame is the per-point kernels' common one
+// (lfd_device.hpp): coalesced loads of the point's own fields, its reference from ref_offsets (device data), the reference's constants and its
 // neighbours' staged in LDS (a workgroup whose points straddle references takes them one after the other).  Inside a lane the window is
 // walked in raster order - the accumulation order is fixed without any cross-lane reduction.  A whole window row's certainty and warp loads
 // are issued before its arithmetic; in dense mode neighbouring lanes hold neighbouring cells, so a row's loads coalesce across the lanes.  The
@@ -37,35 +37,32 @@ __global__ void __launch_bounds__(256) lfd_normals_kernel(const LfdNormalArgs p)
     __shared__ int sh_ref[2];
     __shared__ unsigned sh_cnt[2];
     const int tid = (int)threadIdx.x;
-    const LfdPointSpan sp = lfd_point_span(p.offs, p.n_refs, p.capacity);
+    const LfdPointStage& st = p.st;
+    const LfdPointSpan sp = lfd_point_span(st);
     if (!sp.any) return;                                                // the whole workgroup lies past the last point
     const long long i = sp.i, ii = sp.ii;
     const bool mine = sp.mine;
-    const int cell = p.cell[ii];
-    const int s = (int)p.slot[ii];
-    const float X0 = p.xyz[3 * ii], X1 = p.xyz[3 * ii + 1], X2 = p.xyz[3 * ii + 2];
-    const int r = lfd_support_ref_of(p.offs, p.n_refs, p.capacity, ii);
-    if (tid == 0) { sh_ref[0] = r; sh_cnt[0] = 0u; sh_cnt[1] = 0u; }
-    if (i == sp.last) sh_ref[1] = r;
-    __syncthreads();
-    const int r_first = sh_ref[0], r_last = sh_ref[1];
-    const LfdSupportGeom g = p.g;
+    const int cell = st.cell[ii];
+    const int s = (int)st.slot[ii];
+    const float X0 = st.xyz[3 * ii], X1 = st.xyz[3 * ii + 1], X2 = st.xyz[3 * ii + 2];
+    int r_first, r_last;
+    const int r = lfd_ref_range<2>(sh_ref, sh_cnt, st, sp, r_first, r_last);
+    const LfdSupportGeom g = st.g;
     const long long HW = (long long)g.H * g.W;
     const bool cell_ok = cell >= 0 && (long long)cell < HW;            // no address is formed from a cell outside the grid
-    const LfdRefDesc* refs = static_cast<const LfdRefDesc*>(p.refs);
+    const LfdRefDesc* refs = static_cast<const LfdRefDesc*>(st.refs);
     const LfdKernelParams kp = lfd_normal_params(g);
     unsigned status = 0u;
     float nrm[3] = {0.0f, 0.0f, 0.0f};
     for (int rr = r_first; rr <= r_last; ++rr) {
-        if (lfd_support_clamp(p.offs[rr + 1], p.capacity) <= lfd_support_clamp(p.offs[rr], p.capacity)) continue;   // uniform: no points
-        int ns = refs[rr].n_slots;
-        ns = ns < LFD_MAX_SLOTS ? ns : LFD_MAX_SLOTS;
+        if (lfd_ref_empty(st, rr)) continue;
+        const int ns = lfd_ref_slots<LFD_MAX_SLOTS>(st, rr);
         if (tid < ns) {
-            const LfdSlotDesc& d = static_cast<const LfdSlotDesc*>(p.slots)[(size_t)rr * p.k + tid];
+            const LfdSlotDesc& d = static_cast<const LfdSlotDesc*>(st.slots)[(size_t)rr * st.k + tid];
             sh[tid].cert = d.cert; sh[tid].warp = d.warp; sh[tid].mask_b = d.mask_b;
-            sh_pc[tid] = p.pair_const[(size_t)rr * p.k + tid];
+            sh_pc[tid] = st.pair_const[(size_t)rr * st.k + tid];
         }
-        if (tid == 64) { sh_rc = p.ref_const[rr]; sh_mask_a = refs[rr].mask_a; }
+        if (tid == 64) { sh_rc = st.ref_const[rr]; sh_mask_a = refs[rr].mask_a; }
         __syncthreads();
         if (mine && r == rr) {
             LfdNormalPoint pt;
@@ -84,7 +81,7 @@ __global__ void __launch_bounds__(256) lfd_normals_kernel(const LfdNormalArgs p)
                     if (qy < 0 || qy >= g.H) continue;
                     // the row's loads first (cells outside the grid: nothing is loaded, a certainty of 0), then its arithmetic
                     float c[NW], wax[NW], way[NW], wbx[NW], wby[NW];
-                    const float ya = (g.C == 4) ? 0.0f : p.axis_y[qy];
+                    const float ya = (g.C == 4) ? 0.0f : st.axis_y[qy];
 #pragma unroll
                     for (int e = 0; e < NW; ++e) {
                         const int qx = x + e - R;
@@ -99,7 +96,7 @@ __global__ void __launch_bounds__(256) lfd_normals_kernel(const LfdNormalArgs p)
                                 const float2 wa = *reinterpret_cast<const float2*>(wp);
                                 wax[e] = wa.x; way[e] = wa.y;
                             } else {
-                                wax[e] = p.axis_x[qx];
+                                wax[e] = st.axis_x[qx];
                             }
                         }
                     }
@@ -122,20 +119,16 @@ __global__ void __launch_bounds__(256) lfd_normals_kernel(const LfdNormalArgs p)
     }
     if (p.counters) {                                                  // (uniform)
         const bool fitted = (status & LFD_NORMAL_FITTED) != 0u;
-        const unsigned long long mf = __ballot(mine && fitted), mb = __ballot(mine && !fitted);
-        if ((tid & 63) == 0) {
-            if (mf) atomicAdd(&sh_cnt[0], (unsigned)__popcll(mf));
-            if (mb) atomicAdd(&sh_cnt[1], (unsigned)__popcll(mb));
-        }
+        lfd_count_tally<2>(sh_cnt, {mine && fitted, mine && !fitted});
         __syncthreads();
-        if (tid < 2 && sh_cnt[tid]) atomicAdd(p.counters + tid, (unsigned long long)sh_cnt[tid]);    // integer adds: order-free
+        lfd_count_flush<2>(sh_cnt, p.counters);
     }
 }
 
 // lfd_api.hip's lfd_estimate_normals: the arguments were validated there (capacity <= 2^31 - 1: at most 2^23 workgroups, radius in 1..4)
 hipError_t lfd_normals_launch(const LfdNormalArgs& p, hipStream_t stream) {
-    if (p.n_wg <= 0) return hipSuccess;
-    const dim3 grid((unsigned)p.n_wg);
+    if (p.st.n_wg <= 0) return hipSuccess;
+    const dim3 grid((unsigned)p.st.n_wg);
     switch (p.radius) {
         case 1: hipLaunchKernelGGL((lfd_normals_kernel<1>), grid, dim3(256), 0, stream, p); break;
         case 2: hipLaunchKernelGGL((lfd_normals_kernel<2>), grid, dim3(256), 0, stream, p); break;

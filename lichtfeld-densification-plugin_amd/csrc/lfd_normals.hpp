@@ -162,21 +162,12 @@ inline unsigned lfd_normal_point(const LfdRefConst& rc, const LfdPairConst* pc, 
 
 // What a launch works on (device), by value in the kernel arguments.
 struct LfdNormalArgs {
-    const void* refs;                  // LfdRefDesc [n_refs]
-    const void* slots;                 // LfdSlotDesc [n_refs * k]
-    const LfdRefConst* ref_const;      // [n_refs]
-    const LfdPairConst* pair_const;    // [n_refs * k]
-    const float* axis_x;               // [W], [H]: the A-grid axes (two-channel warps)
-    const float* axis_y;
-    const long long* offs;             // [n_refs + 1]
-    const float* xyz; const int32_t* cell; const uint8_t* slot;
+    LfdPointStage st;                  // (g.tau unused; g.reproj_thresh: the window cells' two-view test)
     float* normals;                    // [3 * capacity]
     uint8_t* status;                   // [capacity] or null
     unsigned long long* counters;      // [2] or null: points fitted, points that fell back; added to
-    long long capacity;
-    int32_t n_refs, k, n_wg, radius;
+    int32_t radius;
     float depth_step_rel;
-    LfdSupportGeom g;                  // (tau unused; reproj_thresh: the window cells' two-view test)
 };
 
 // Arguments of lfd_estimate_normals / lfd_estimate_normals_host that do not depend on the batch; what is wrong with them, or null.

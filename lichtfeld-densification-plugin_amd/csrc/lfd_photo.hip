@@ -8,10 +8,9 @@
 //                               optional status and ncc, and the kept points of the workgroup; per (reference, winning slot) counters and
 //                               the five status counts through LDS, then one integer atomic per workgroup and counter
 //
-// The scan and the scatter are lfd_support_filter's own kernels (lfd_support_compact_launch, lfd_support.hip), not copies: they read the keep
-// byte as a support count against a min_support of 1.
+// The scan and the scatter are the shared tail of the gates (lfd_compact_launch, lfd_support.hip).
 //
-// The frame is lfd_normals_kernel's (lfd_normals.hip): coalesced loads of the point's own fields, its reference from ref_offsets (device
+// The frame is the per-point kernels' common one (lfd_device.hpp: lfd_point_span ... lfd_count_flush): coalesced loads of the point's own fields, its reference from ref_offsets (device
 // data), the reference's image, mask and its neighbours' plane pointers and image bases staged in LDS (a workgroup whose points straddle
 // references takes them one after the other), so that inside a reference every base is uniform across the workgroup but for the winning
 // slot, a run-time index into LDS.  A whole window row's certainty and warp loads are issued before its arithmetic; in dense mode neighbouring
@@ -26,7 +25,7 @@
 #include "lfd_device.hpp"
 #include "lfd_photo.hpp"
 
-hipError_t lfd_support_compact_launch(const LfdSupportArgs& p, hipStream_t stream);   // lfd_support.hip
+hipError_t lfd_compact_launch(const LfdCompactArgs& p, hipStream_t stream);   // lfd_support.hip
 
 // a[e] for a run-time e through compile-time indices: the array stays in registers (lfd_normals.hip has the reason for the empty statement)
 template <int N>
@@ -51,35 +50,32 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) l
     __shared__ int sh_ref[2];
     __shared__ unsigned sh_kept;
     const int tid = (int)threadIdx.x;
-    const LfdPointSpan sp = lfd_point_span(p.offs_in, p.n_refs, p.capacity);
+    const LfdPointStage& st = p.st;
+    const LfdPointSpan sp = lfd_point_span(st);
     if (!sp.any) {                                                      // the whole workgroup lies past the last point
         if (tid == 0) p.wg_kept[blockIdx.x] = 0u;
         return;
     }
     const long long i = sp.i, ii = sp.ii;
     const bool mine = sp.mine;
-    const int cell = p.cell[ii];
-    const int s = (int)p.slot[ii];
-    const int r = lfd_support_ref_of(p.offs_in, p.n_refs, p.capacity, ii);
-    if (tid == 0) { sh_ref[0] = r; sh_kept = 0u; }
+    const int cell = st.cell[ii];
+    const int s = (int)st.slot[ii];
     if (tid < LFD_PHOTO_STATUSES) sh_cnt[tid] = 0u;
-    if (i == sp.last) sh_ref[1] = r;
-    __syncthreads();
-    const int r_first = sh_ref[0], r_last = sh_ref[1];
-    const LfdSupportGeom g = p.g;
+    int r_first, r_last;
+    const int r = lfd_ref_range<1>(sh_ref, &sh_kept, st, sp, r_first, r_last);
+    const LfdSupportGeom g = st.g;
     const long long HW = (long long)g.H * g.W;
-    const LfdRefDesc* refs = static_cast<const LfdRefDesc*>(p.refs);
+    const LfdRefDesc* refs = static_cast<const LfdRefDesc*>(st.refs);
     unsigned status = LFD_PHOTO_GUARDED;
     float ncc = __builtin_nanf("");
     for (int rr = r_first; rr <= r_last; ++rr) {
-        if (lfd_support_clamp(p.offs_in[rr + 1], p.capacity) <= lfd_support_clamp(p.offs_in[rr], p.capacity)) continue;   // uniform: no points
-        int ns = refs[rr].n_slots;
-        ns = ns < LFD_MAX_SLOTS ? ns : LFD_MAX_SLOTS;
+        if (lfd_ref_empty(st, rr)) continue;
+        const int ns = lfd_ref_slots<LFD_MAX_SLOTS>(st, rr);
         if (tid < LFD_MAX_SLOTS) sh_seg[tid] = 0u;
         if (tid < ns) {
-            const LfdSlotDesc& d = static_cast<const LfdSlotDesc*>(p.slots)[(size_t)rr * p.k + tid];
+            const LfdSlotDesc& d = static_cast<const LfdSlotDesc*>(st.slots)[(size_t)rr * st.k + tid];
             sh[tid].cert = d.cert; sh[tid].warp = d.warp; sh[tid].mask_b = d.mask_b;
-            sh[tid].img = p.img[(size_t)rr * p.k + tid];
+            sh[tid].img = p.img[(size_t)rr * st.k + tid];
         }
         if (tid == 64) { sh_img_a = refs[rr].image; sh_mask_a = refs[rr].mask_a; }
         __syncthreads();
@@ -123,23 +119,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) l
                         const float2 wa = *reinterpret_cast<const float2*>(warp + ((size_t)qy * g.W + qx) * 4);
                         xan = wa.x; yan = wa.y;
                     } else {
-                        xan = p.axis_x[qx]; yan = p.axis_y[qy];
+                        xan = st.axis_x[qx]; yan = st.axis_y[qy];
                     }
                     lfd_photo_sample(acc, img_a, img_b, g, xan, yan, xbn, ybn);
                 }
             }
             status = lfd_photo_verdict(acc, R, p.th, &ncc);
         }
-        if (p.seg_counts) {                                            // (uniform)
-            const bool kept_here = here && status != LFD_PHOTO_REFUTED && s < ns;
-#pragma unroll
-            for (int j = 0; j < LFD_MAX_SLOTS; ++j) {
-                const unsigned long long m = __ballot(kept_here && s == j);
-                if (m && (tid & 63) == 0) atomicAdd(&sh_seg[j], (unsigned)__popcll(m));
-            }
-        }
+        if (p.seg_counts) lfd_seg_tally<LFD_MAX_SLOTS>(sh_seg, here && status != LFD_PHOTO_REFUTED && s < ns, s);   // (uniform)
         __syncthreads();                                               // the next reference's constants replace these
-        if (p.seg_counts && tid < ns && sh_seg[tid]) atomicAdd(p.seg_counts + (size_t)rr * p.k + tid, (int)sh_seg[tid]);
+        if (p.seg_counts) lfd_seg_flush(sh_seg, p.seg_counts, rr, st.k, ns);
     }
     const bool keep = mine && status != LFD_PHOTO_REFUTED;
     if (mine) {
@@ -147,25 +136,22 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) l
         if (p.status) p.status[i] = (uint8_t)status;
         if (p.ncc) p.ncc[i] = ncc;
     }
-    const unsigned long long km = __ballot(keep);
-    if ((tid & 63) == 0 && km) atomicAdd(&sh_kept, (unsigned)__popcll(km));
+    lfd_count_tally<1>(&sh_kept, {keep});
     if (p.counters) {                                                  // (uniform)
+        bool hit[LFD_PHOTO_STATUSES];
 #pragma unroll
-        for (int j = 0; j < LFD_PHOTO_STATUSES; ++j) {
-            const unsigned long long m = __ballot(mine && status == (unsigned)j);
-            if (m && (tid & 63) == 0) atomicAdd(&sh_cnt[j], (unsigned)__popcll(m));
-        }
+        for (int j = 0; j < LFD_PHOTO_STATUSES; ++j) hit[j] = mine && status == (unsigned)j;
+        lfd_count_tally<LFD_PHOTO_STATUSES>(sh_cnt, hit);
     }
     __syncthreads();
     if (tid == 0) p.wg_kept[blockIdx.x] = sh_kept;
-    if (p.counters && tid < LFD_PHOTO_STATUSES && sh_cnt[tid]) atomicAdd(p.counters + tid, (unsigned long long)sh_cnt[tid]);   // integer adds: order-free
+    if (p.counters) lfd_count_flush<LFD_PHOTO_STATUSES>(sh_cnt, p.counters);
 }
 
-// lfd_api.hip's lfd_photo_gate: the arguments were validated there (capacity <= 2^31 - 1: at most 2^23 workgroups, radius in 1..3).  sup: the
-// support filter's view of the same call - the compaction's arguments.
-hipError_t lfd_photo_launch(const LfdPhotoArgs& p, const LfdSupportArgs& sup, hipStream_t stream) {
-    if (p.n_wg > 0) {
-        const dim3 grid((unsigned)p.n_wg);
+// lfd_api.hip's lfd_photo_gate: the arguments were validated there (capacity <= 2^31 - 1: at most 2^23 workgroups, radius in 1..3)
+hipError_t lfd_photo_launch(const LfdPhotoArgs& p, const LfdCompactArgs& tail, hipStream_t stream) {
+    if (p.st.n_wg > 0) {
+        const dim3 grid((unsigned)p.st.n_wg);
         switch (p.radius) {
             case 1: hipLaunchKernelGGL((lfd_photo_count_kernel<1>), grid, dim3(256), 0, stream, p); break;
             case 2: hipLaunchKernelGGL((lfd_photo_count_kernel<2>), grid, dim3(256), 0, stream, p); break;
@@ -175,5 +161,5 @@ hipError_t lfd_photo_launch(const LfdPhotoArgs& p, const LfdSupportArgs& sup, hi
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    return lfd_support_compact_launch(sup, stream);
+    return lfd_compact_launch(tail, stream);
 }

@@ -174,26 +174,18 @@ inline unsigned lfd_photo_point(const LfdPhotoSlot* sl, int ns, const uint8_t* i
     return lfd_photo_verdict(acc, R, th, ncc);
 }
 
-// What the gate's own launch works on (device), by value in the kernel arguments.  The compaction behind it is lfd_support_filter's: its
-// LfdSupportArgs travels beside this one, with the keep bytes as its counts and a min_support of 1.
+// What the gate's own launch works on (device), by value in the kernel arguments.
 struct LfdPhotoArgs {
-    const void* refs;                  // LfdRefDesc [n_refs]
-    const void* slots;                 // LfdSlotDesc [n_refs * k]
+    LfdPointStage st;                  // (g.tau, g.reproj_thresh unused)
     const uint8_t* const* img;         // [n_refs * k] the neighbours' match-size images (device table)
-    const float* axis_x;               // [W], [H]: the A-grid axes (two-channel warps)
-    const float* axis_y;
-    const long long* offs_in;          // [n_refs + 1]
-    const int32_t* cell; const uint8_t* slot;
     int32_t* seg_counts;               // [n_refs * k] or null (zeroed before the launch)
     uint8_t* status;                   // [capacity] or null
     float* ncc;                        // [capacity] or null
     unsigned long long* counters;      // [5] or null: points per status; added to
     uint8_t* keep;                     // workspace [n_wg * 256]: 1 kept, 0 dropped
     unsigned* wg_kept;                 // workspace [n_wg + 1]: kept points per workgroup
-    long long capacity;
-    int32_t n_refs, k, n_wg, radius;
+    int32_t radius;
     LfdPhotoThresh th;
-    LfdSupportGeom g;                  // (tau, reproj_thresh unused)
 };
 
 // Arguments of lfd_photo_gate / lfd_photo_gate_host that do not depend on the batch; what is wrong with them (and the status), or null.

@@ -292,21 +292,11 @@ LFD_HD unsigned lfd_refine_point(const LfdRefineRef& ref, const LfdSlot* sl, con
 
 // What a launch works on (device), by value in the kernel arguments.
 struct LfdRefineArgs {
-    const void* refs;                  // LfdRefDesc [n_refs]
-    const void* slots;                 // LfdSlotDesc [n_refs * k]
-    const LfdRefConst* ref_const;      // [n_refs]
-    const LfdPairConst* pair_const;    // [n_refs * k]
-    const float* axis_x;               // [W], [H]: the A-grid axes (two-channel warps)
-    const float* axis_y;
-    const long long* offs;             // [n_refs + 1]
-    const float* xyz; const float* err; const int32_t* cell; const uint8_t* slot;
+    LfdPointStage st;
     float* o_xyz; float* o_err;
     uint8_t* status;                   // [capacity] or null
     unsigned long long* counters;      // [2] or null: points refined, points with a candidate that kept their two-view position; added to
                                        // ([3] when prec is set: + points solved with weighted rows; without prec element 2 is never touched)
-    long long capacity;
-    int32_t n_refs, k, n_wg;
-    LfdSupportGeom g;
     const float* const* prec;          // lfd_refine_multiview_weighted: [n_refs * k] precision planes (device table; entries at j >= n_slots[r]
                                        // are not read); null: lfd_refine_multiview
 };

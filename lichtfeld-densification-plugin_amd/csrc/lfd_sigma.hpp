@@ -98,29 +98,18 @@ LFD_HD float lfd_sigma_point(const LfdSigmaRef& ref, const LfdSlot* sl, const Lf
 // the gate: max_rel_sigma == 0 keeps everything; otherwise a NaN and +inf drop
 LFD_HD bool lfd_sigma_keep(float sigma_rel, float max_rel_sigma) { return max_rel_sigma == 0.0f || sigma_rel <= max_rel_sigma; }
 
-// What a launch works on (device), by value in the kernel arguments.
+// What the gate's own launch works on (device), by value in the kernel arguments.
 struct LfdSigmaArgs {
-    const void* refs;                  // LfdRefDesc [n_refs]
-    const void* slots;                 // LfdSlotDesc [n_refs * k]
-    const LfdRefConst* ref_const;      // [n_refs]
-    const LfdPairConst* pair_const;    // [n_refs * k]
-    const long long* offs_in;          // [n_refs + 1]
-    const float* xyz; const float* rgb; const float* err; const int32_t* cell; const uint8_t* slot;
-    float* o_xyz; float* o_rgb; float* o_err; int32_t* o_cell; uint8_t* o_slot;
-    long long* offs_out;               // [n_refs + 1]
+    LfdPointStage st;
     int32_t* seg_counts;               // [n_refs * k] or null (zeroed before the launch)
     float* sigma;                      // [capacity] or null: sigma_rel of every input point
-    float* o_sigma;                    // [out capacity] or null: compacted with the points
     const uint8_t* status;             // [capacity] or null: the refinement's status (candidates take part where it has LFD_REFINE_ACCEPTED)
     const float* const* prec;          // [n_refs * k] precision planes (device table), or null: the isotropic form
-    float* ws_sigma;                   // workspace [n_wg * 256]: sigma_rel of every input point
+    float* ws_sigma;                   // workspace [n_wg * 256] or null: sigma_rel of every input point, for the compaction to move
     uint8_t* keep;                     // workspace [n_wg * 256]: 1 where the point is kept
-    unsigned* wg_kept;                 // workspace [n_wg + 1]: kept points per workgroup, then their exclusive prefix and the total
-    long long capacity;                // in->capacity
+    unsigned* wg_kept;                 // workspace [n_wg + 1]: kept points per workgroup
     double iso;                        // 1 / iso_sigma_px^2 (the isotropic form)
     float max_rel_sigma;
-    int32_t n_refs, k, n_wg;
-    LfdSupportGeom g;
 };
 
 // Arguments of lfd_depth_sigma_filter / lfd_depth_sigma_filter_host that do not depend on the batch; what is wrong with them (and the status),

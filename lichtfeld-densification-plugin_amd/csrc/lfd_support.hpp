@@ -91,22 +91,51 @@ LFD_HD bool lfd_support_candidate(const LfdSlot& sl, const LfdSupportGeom& g, fl
     return live && agree;
 }
 
-// What a launch works on (device), by value in the kernel arguments.
-struct LfdSupportArgs {
-    const void* refs;                  // LfdRefDesc [n_refs]            (lfd_device.hpp; the twin reads the lfd_batch itself)
+inline LfdSupportGeom lfd_support_geom(const lfd_batch* b, float wm1, float hm1, float mask_sx, float mask_sy, float tau, float reproj_thresh) {
+    LfdSupportGeom g;
+    g.H = b->H; g.W = b->W; g.C = b->warp_channels; g.w_match = b->w_match; g.h_match = b->h_match;
+    g.wm1 = wm1; g.hm1 = hm1; g.mask_sx = mask_sx; g.mask_sy = mask_sy; g.tau = tau; g.reproj_thresh = reproj_thresh;
+    return g;
+}
+
+// What every per-point stage behind triangulation hands its kernel (device): the first member of each stage's Lfd*Args, by value in the kernel
+// arguments.  A stage reads what it needs of it; lfd_api.hip's fill_stage fills all of it.
+struct LfdPointStage {
+    const void* refs;                  // LfdRefDesc [n_refs]            (lfd_device.hpp; the twins read the lfd_batch itself)
     const void* slots;                 // LfdSlotDesc [n_refs * k]
     const LfdPairConst* pair_const;    // [n_refs * k]
+    const long long* offs;             // [n_refs + 1]
+    const float* xyz; const float* rgb; const float* err; const int32_t* cell; const uint8_t* slot;
+    long long capacity;                // in->capacity
+    int32_t n_refs, k, n_wg;           // n_wg: workgroups of 256 points that cover the capacity
+    LfdSupportGeom g;
+    const LfdRefConst* ref_const;      // [n_refs]          (what only some stages read comes last: with these three between the fields every
+    const float* axis_x;               // [W], [H]: the A-grid axes (two-channel warps)    kernel reads, the support and photo kernels spill more)
+    const float* axis_y;
+};
+
+// The compaction behind a per-point verdict (lfd_compact_launch, lfd_support.hip): the points whose keep byte is set move to the output in order.
+struct LfdCompactArgs {
     const long long* offs_in;          // [n_refs + 1]
+    long long* offs_out;               // [n_refs + 1]
     const float* xyz; const float* rgb; const float* err; const int32_t* cell; const uint8_t* slot;
     float* o_xyz; float* o_rgb; float* o_err; int32_t* o_cell; uint8_t* o_slot;
-    long long* offs_out;               // [n_refs + 1]
+    const uint8_t* keep;               // workspace [n_wg * 256]: 1 where the point is kept, else 0
+    unsigned* wg_kept;                 // workspace [n_wg + 1]: kept points per workgroup, then their exclusive prefix and the total
+    const float* extra_in;             // [n_wg * 256] or null: one more f32 per point ...
+    float* extra_out;                  // ... which moves with the points when this is set
+    long long capacity;                // in->capacity
+    int32_t n_refs, n_wg;
+};
+
+// What a launch of the support filter's own kernel works on (device), by value in the kernel arguments.
+struct LfdSupportArgs {
+    LfdPointStage st;
     int32_t* seg_counts;               // [n_refs * k] or null (zeroed before the launch)
     uint8_t* support;                  // [capacity] or null
-    uint8_t* counts;                   // workspace [n_wg * 256]: support count of every input point
-    unsigned* wg_kept;                 // workspace [n_wg + 1]: kept points per workgroup, then their exclusive prefix and the total
-    long long capacity;                // in->capacity
-    int32_t n_refs, k, min_support, n_wg;
-    LfdSupportGeom g;
+    uint8_t* keep;                     // workspace [n_wg * 256]: 1 where support >= min_support
+    unsigned* wg_kept;                 // workspace [n_wg + 1]: kept points per workgroup
+    int32_t min_support;
 };
 
 // Arguments of lfd_support_filter / lfd_support_filter_host that do not depend on the batch; what is wrong with them (and the status), or null.

@@ -45,6 +45,14 @@ def reference_inputs(ref: int, k: int, H: int, W: int, channels: int = 2, masks:
     return s, ri
 
 
+def with_neighbour_images(ri, device="cpu"):
+    """``ri`` with a match-size u8 image per neighbour (ReferenceInputs.nbr_images), what the photo-consistency gate samples: textures of the
+    neighbours' own, unrelated to the warps - the gate then refutes some matches and lets others pass, and whoever is given the same images
+    decides the same."""
+    ri.nbr_images = [syn.synth_image(MATCH, MATCH, 7000 + int(n), device) for n in ri.nbr_cams]
+    return ri
+
+
 def params(**kw):
     return hb.make_params(lfd.DensePipelineConfig(output_path="", **kw))
 
@@ -102,7 +110,8 @@ def on_host(refs):
     """The same ReferenceInputs with every tensor copied to the CPU (what the twin is given when the device is the other side of a comparison)."""
     cpu = lambda t: t.cpu() if t is not None else None
     return [hb.ReferenceInputs(ref_cam=r.ref_cam, nbr_cams=list(r.nbr_cams), cert=[cpu(c) for c in r.cert], warp=[cpu(w) for w in r.warp],
-                               image=cpu(r.image), mask_a=cpu(r.mask_a), mask_b=[cpu(m) for m in r.mask_b] if r.mask_b is not None else None)
+                               image=cpu(r.image), mask_a=cpu(r.mask_a), mask_b=[cpu(m) for m in r.mask_b] if r.mask_b is not None else None,
+                               nbr_images=[cpu(m) for m in r.nbr_images] if r.nbr_images is not None else None)
             for r in refs]
 
 

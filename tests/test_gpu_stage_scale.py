@@ -7,7 +7,7 @@ Stages on the final cloud (voxel, consensus, free-space, fuse, kNN, cap), one Hi
   n = 4 198 401   1026 chunks of 4096: G is capped, the chunk grows to 4608 (nine scatter rounds of 512), G is recomputed to 912
 Stages on a batch's points (support filter, plain and weighted re-triangulation, depth-sigma gate, normals), on the collected points and on the
 launch's own buffers:
-  four references of 288 x 288   capacity 331 776, 1296 workgroups: lfd_support_scan_kernel and lfd_sigma_scan_kernel walk two counts per thread
+  four references of 288 x 288   capacity 331 776, 1296 workgroups: lfd_compact_scan_kernel, the gates' shared scan, walks two counts per thread
   fourteen references of 6 x 8   a workgroup stages the constants of seven references one after the other, a dead reference among them
 
 Every output is held to the rule of the stage's own test file, through that file's helper where it has one: bit-equal to the CPU twin given the
