@@ -760,6 +760,31 @@ int lfd_consensus_filter_host(lfd_context* ctx, const float* xyz, const float* r
                               int32_t n_refs, float radius, int32_t min_refs, float* xyz_out, float* rgb_out, float* err_out,
                               int64_t* ref_offsets_out_host, uint8_t* consensus, int64_t* n_out_host);
 
+/* Connected-component filter on the final cloud (no upstream counterpart): the floater rule that needs no second witness.  The cloud
+ * is the concatenation of n_refs references' points, as for lfd_consensus_filter (csrc/lfd_component.hpp):
+ *   linked(i, j) iff lfd_consensus_filter's agree(i, j) holds at the same r2 = radius radius - that routine itself: f32, every rounding written
+ *                out, symmetric bit for bit, a NaN never agrees
+ *   component    a class of the transitive closure of the links.  A point with a non-finite coordinate links to nothing: a component of size 1
+ *   size(i)      the number of points in i's component;  label(i): the smallest INPUT index in it
+ *   kept         iff size(i) >= min_points.  The kept cloud is the input under that mask, in input order, with the same bits; ref_offsets_out_host
+ *                is rebuilt as lfd_consensus_filter rebuilds it
+ * The partition does not depend on the order in which links are found, nor on the grid that finds them (lfd_consensus_filter's cells of side
+ * 1.000001 radius), so every output is exact: device, twin and an all-pairs reference agree element for element.
+ * xyz, rgb, err, ref_offsets_host, the outputs xyz_out / rgb_out / err_out / ref_offsets_out_host / *n_out_host: as for lfd_consensus_filter.
+ * min_points in 2 .. 2^31 - 1.  Optional outputs (NULL: not written): size, label: u32 [n] at the point's ORIGINAL index (device pointers for
+ * lfd_component_filter); summary_host: HOST i64 [66]: [0] the number of components, [1] the size of the largest, [2 + b] for b = 0 .. 31 the
+ * components with 2^b <= size < 2^(b + 1), [34 + b] the points in those components.  Synchronous, deterministic; the workspace belongs to the
+ * context and is reused.  LFD_ERR_INVALID: lfd_consensus_filter's refusals of cloud, offsets and radius (the "... key range ..." one included),
+ * min_points < 2, any input array overlapping any output array.  n == 0 is valid (the summary is all zero).  The union-find of the device call
+ * cannot hang: no loop in it waits for another workgroup's store (csrc/lfd_component.hpp, TERMINATION).  lfd_component_filter_host: the same over
+ * host pointers with a sequential union-find on a host context; every output equals the device's bit for bit. */
+int lfd_component_filter(lfd_context* ctx, const float* xyz, const float* rgb, const float* err, int64_t n, const int64_t* ref_offsets_host,
+                         int32_t n_refs, float radius, int32_t min_points, float* xyz_out, float* rgb_out, float* err_out,
+                         int64_t* ref_offsets_out_host, uint32_t* size, uint32_t* label, int64_t* summary_host, int64_t* n_out_host);
+int lfd_component_filter_host(lfd_context* ctx, const float* xyz, const float* rgb, const float* err, int64_t n, const int64_t* ref_offsets_host,
+                              int32_t n_refs, float radius, int32_t min_points, float* xyz_out, float* rgb_out, float* err_out,
+                              int64_t* ref_offsets_out_host, uint32_t* size, uint32_t* label, int64_t* summary_host, int64_t* n_out_host);
+
 /* Free-space filter on the final cloud (no upstream counterpart).  Every reference's own points are a sparse depth map of what it
  * saw; a point of ANOTHER reference that lies in front of that depth map on the same ray cannot exist - the reference looked through it.  The
  * cloud is the concatenation of n_refs references' points (ref_offsets_host as for lfd_consensus_filter); cam_P_host: HOST f32 [n_refs][12], the

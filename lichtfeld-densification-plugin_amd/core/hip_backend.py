@@ -249,6 +249,11 @@ def load_library() -> C.CDLL:
     lib.lfd_consensus_filter.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_float, C.c_int32,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)]
     lib.lfd_consensus_filter_host.argtypes = list(lib.lfd_consensus_filter.argtypes)
+    lib.lfd_component_filter.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_float, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64)]
+    lib.lfd_component_filter_host.argtypes = list(lib.lfd_component_filter.argtypes)
+    lib.lfd_component_filter.restype = lib.lfd_component_filter_host.restype = C.c_int
     lib.lfd_freespace_filter.argtypes = [ctxp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_float),
                                          C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
@@ -1456,6 +1461,52 @@ def _consensus_call(fn, ctx, what, xyz, rgb, err, ref_counts, radius, min_refs, 
     return kept[0], kept[1], kept[2], np.diff(offs_out), (cons[:n] if with_consensus else None)
 
 
+COMPONENT_SUMMARY_WORDS = 66     # lfd_component_filter's summary: n_components, largest size, 32 bins of components, 32 bins of their points
+
+
+def _component_call(fn, ctx, what, xyz, rgb, err, ref_counts, radius, min_points, with_sizes, with_labels, device, last_error):
+    """One lfd_component_filter[_host] call.  ``xyz`` (n, 3), ``rgb`` (n, 3) or None, ``err`` (n,) or None: float32 tensors on ``device``;
+    ``ref_counts``: points per reference, in the order of the cloud.  Returns ``(xyz, rgb, err, kept_counts, sizes, labels, summary)``: the kept
+    points in input order (views of n-row tensors; rgb / err None when not given), the kept points per reference (int64 array), - ``with_sizes``
+    / ``with_labels``, else None - every INPUT point's component size and label (the smallest input index of its component) as int32 tensors
+    on ``device`` holding the library's u32 values (both are below 2^31), and the 66 summary words (int64 array).  Raises
+    ``ConsensusInputRefused`` for the key-range refusal, which is the consensus filter's."""
+    counts = np.ascontiguousarray(np.asarray(ref_counts, np.int64).reshape(-1))
+    n = int(xyz.shape[0])
+    if counts.size < 1 or (counts < 0).any() or int(counts.sum()) != n:
+        raise ValueError(f"{what}: ref_counts must be non-negative counts, one per reference, that add up to the {n} points")
+    tensors = []
+    for t, cols, name in ((xyz, 3, "xyz"), (rgb, 3, "rgb"), (err, 0, "err")):
+        if t is None:
+            tensors.append(None)
+            continue
+        if t.dtype != torch.float32 or t.device != device or int(t.shape[0]) != n or (cols and (t.dim() != 2 or t.shape[1] != cols)) or (not cols and t.dim() != 1):
+            raise ValueError(f"{what}: {name} must be a float32 tensor of {n} rows{' x 3' if cols else ''} on {device}")
+        tensors.append(t.contiguous())
+    xyz, rgb, err = tensors
+    offs = np.zeros(counts.size + 1, np.int64)
+    np.cumsum(counts, out=offs[1:])
+    offs_out = np.zeros_like(offs)
+    outs = [torch.empty((max(n, 1),) + tuple(t.shape[1:]), dtype=torch.float32, device=device) if t is not None else None for t in tensors]
+    sizes = torch.empty((max(n, 1),), dtype=torch.int32, device=device) if with_sizes else None
+    labels = torch.empty((max(n, 1),), dtype=torch.int32, device=device) if with_labels else None
+    summary = np.zeros(COMPONENT_SUMMARY_WORDS, np.int64)
+    n_out = C.c_int64(0)
+    ptr = lambda t: t.data_ptr() if t is not None and n > 0 else None       # noqa: E731  (an empty tensor may have no address at all)
+    i64p = C.POINTER(C.c_int64)
+    rc = fn(ctx, ptr(xyz), ptr(rgb), ptr(err), n, offs.ctypes.data_as(i64p), int(counts.size), C.c_float(float(radius)), int(min_points),
+            ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), offs_out.ctypes.data_as(i64p), ptr(sizes), ptr(labels), summary.ctypes.data_as(i64p),
+            C.byref(n_out))
+    if rc != 0:
+        msg = last_error()
+        if "key range" in msg:
+            raise ConsensusInputRefused(f"{what} refused its input ({rc}): {msg}")
+        raise HipBackendError(f"{what} failed ({rc}): {msg}")
+    k = int(n_out.value)
+    kept = [o[:k] if o is not None else None for o in outs]
+    return (kept[0], kept[1], kept[2], np.diff(offs_out), (sizes[:n] if with_sizes else None), (labels[:n] if with_labels else None), summary)
+
+
 def _fuse_call(fn, ctx, what, xyz, normals, rgb, voxel_size, with_counts, device, last_error):
     """One lfd_fuse_oriented[_host] call.  ``xyz``, ``normals``, ``rgb``: (n, 3) float32 tensors on ``device``.  Returns
     ``((xyz, normals, rgb[, counts]), n_voxels)``: the rows - views of n-row tensors, voxels in key order, side 0 before side 1 -, with
@@ -1826,6 +1877,14 @@ class HipDensifier:
         Returns ``(xyz, rgb, err, counts, consensus)`` as ``_consensus_call`` describes.  Synchronous."""
         return _consensus_call(self._lib.lfd_consensus_filter, self._ctx, "lfd_consensus_filter", xyz, rgb, err, ref_counts, radius, min_refs,
                                with_consensus, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
+
+    def component_filter(self, xyz: torch.Tensor, rgb: Optional[torch.Tensor], err: Optional[torch.Tensor], ref_counts, radius: float,
+                         min_points: int, with_sizes: bool = False, with_labels: bool = False):
+        """Connected-component filter on the device (lfd_component_filter): a point of the cloud is kept iff the connected
+        component of the radius graph it belongs to has at least ``min_points`` points.  The points never leave the GPU.  Returns
+        ``(xyz, rgb, err, kept_counts, sizes, labels, summary)`` as ``_component_call`` describes.  Synchronous."""
+        return _component_call(self._lib.lfd_component_filter, self._ctx, "lfd_component_filter", xyz, rgb, err, ref_counts, radius, min_points,
+                               with_sizes, with_labels, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
 
     def freespace_filter(self, xyz: torch.Tensor, rgb: Optional[torch.Tensor], err: Optional[torch.Tensor], ref_counts, cam_P, cam_wh, plane,
                          tol: float, min_violations: int, with_counts: bool = False):
@@ -2621,6 +2680,13 @@ class HostDensifier:
         """HipDensifier.consensus_filter over CPU tensors (lfd_consensus_filter_host): the same per-point routine, the same bits in every output."""
         return _consensus_call(self._lib.lfd_consensus_filter_host, self._ctx, "lfd_consensus_filter_host", xyz, rgb, err, ref_counts, radius,
                                min_refs, with_consensus, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
+
+    def component_filter(self, xyz: torch.Tensor, rgb: Optional[torch.Tensor], err: Optional[torch.Tensor], ref_counts, radius: float,
+                         min_points: int, with_sizes: bool = False, with_labels: bool = False):
+        """HipDensifier.component_filter over CPU tensors (lfd_component_filter_host): a sequential union-find over the same links, the same bits
+        in every output."""
+        return _component_call(self._lib.lfd_component_filter_host, self._ctx, "lfd_component_filter_host", xyz, rgb, err, ref_counts, radius,
+                               min_points, with_sizes, with_labels, self.device, lambda: self._lib.lfd_last_error(self._ctx).decode())
 
     def freespace_filter(self, xyz: torch.Tensor, rgb: Optional[torch.Tensor], err: Optional[torch.Tensor], ref_counts, cam_P, cam_wh, plane,
                          tol: float, min_violations: int, with_counts: bool = False):

@@ -268,6 +268,9 @@ def run_dense_pipeline(
     if world > 1 and float(config.exp("footprint_thin_cells")) > 0.0:
         raise ValueError("experimental['footprint_thin_cells'] cannot run sharded over several GPUs: the thinning is a stage of the single-GPU run, and "
                          "with gather_to_root only one rank would hold the cloud and the per-reference counts it works on")
+    if world > 1 and int(config.exp("min_component_points")) > 0:
+        raise ValueError("experimental['min_component_points'] cannot run sharded over several GPUs: the filter is a stage of the single-GPU run, and "
+                         "with gather_to_root only one rank would hold the cloud and the per-reference counts it works on")
     config, dev = _resolve_backend(config, backend, device)
     per_ref_rng = bool(config.per_reference_rng) or world > 1
     # refs_per_launch = 0 (the default): several references per launch where the results do not depend on it and nobody watches the run proceed

@@ -237,6 +237,16 @@ EXPERIMENTAL_DEFAULTS = {
     "pose_min_samples": 256,
     # a poses.json of an earlier run (path; "" = none): its poses replace the camera records' before anything else runs
     "pose_corrections": "",
+    # connected-component filter on the final cloud (lfd_component_filter): the floater rule that needs no second witness.  Two
+    # points are linked when they are within component_radius of each other; a point is kept only if the connected component it belongs to
+    # has at least this many points - a clump of tens of points hanging in the air goes, a surface stays however few references saw it.
+    # Exact: no statistic, no order dependence.  A floater within the radius of a surface joins it; a legitimately small isolated object
+    # goes.  Runs once, behind the consensus and free-space filters, in front of the depth maps, thinning, cap, fusion, Gaussian output and
+    # voxel filter; writes <output file>.components.json.  >= 2; 0 = off: no new code runs and every output stays byte-identical.
+    "min_component_points": 0,
+    # ... within this distance, in scene units (the unit of voxel_size).  Required > 0 with the filter on, 0 with it off.  One number for the
+    # whole scene: in unbounded scenes far, sparse structure fragments - see footprint_thin_cells and far_shell for that end.
+    "component_radius": 0.0,
 }
 POSE_MODES = ("off", "report")
 POSE_KNOBS = ("pose_certainty", "pose_inlier_px", "pose_min_samples")
@@ -481,6 +491,31 @@ class DensePipelineConfig:
                 return "experimental['min_consensus_refs'] filters f32 rows; experimental['exchange_records'] must be 'f32' with it"
             if dense and self.exp("dense_tile_segments"):
                 return ("experimental['min_consensus_refs'] needs the cloud as arrays with per-reference counts; dense mode with "
+                        "experimental['dense_tile_segments'] retires tiles unordered")
+        m_cmp = self.exp("min_component_points")
+        if isinstance(m_cmp, (bool, np.bool_)) or not isinstance(m_cmp, (int, np.integer)) or not (0 <= int(m_cmp) <= 2 ** 31 - 1):
+            return ("experimental['min_component_points'] must be an integer in 0 .. 2^31 - 1 (points a connected component has to have for its points "
+                    "to stay; 0 = off)")
+        if int(m_cmp) == 1:
+            return "experimental['min_component_points'] = 1 keeps every point (a point is a component of its own): use 0 for off, or at least 2"
+        try:
+            r_cmp = float(self.exp("component_radius"))
+        except (TypeError, ValueError):
+            return "experimental['component_radius'] must be a number (scene units, the unit of voxel_size)"
+        if not (0.0 <= r_cmp < float("inf")):
+            return "experimental['component_radius'] must be finite and >= 0 (scene units, the unit of voxel_size)"
+        if int(m_cmp) > 0 and not r_cmp > 0.0:
+            return "experimental['min_component_points'] needs a distance: experimental['component_radius'] must be > 0 (scene units, the unit of voxel_size)"
+        if r_cmp > 0.0 and int(m_cmp) == 0:
+            return "experimental['component_radius'] is the link distance of the component filter: it needs experimental['min_component_points'] >= 2"
+        if int(m_cmp) > 0:
+            if self.stream_output:
+                return ("experimental['min_component_points'] has to see the whole cloud before anything is written; stream_output writes the file "
+                        "while the run proceeds")
+            if self.exchange_record_format() == "ply":
+                return "experimental['min_component_points'] filters f32 rows; experimental['exchange_records'] must be 'f32' with it"
+            if self.exp("dense_tile_segments"):
+                return ("experimental['min_component_points'] needs the cloud as arrays with per-reference counts; dense mode with "
                         "experimental['dense_tile_segments'] retires tiles unordered")
         m_fs = self.exp("min_freespace_violations")
         if isinstance(m_fs, bool) or not isinstance(m_fs, (int, np.integer)) or int(m_fs) < 0:

@@ -14,8 +14,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(os.path.dirname(HERE), "liblfd_densify.so")
-SOURCES = ["lfd_api.hip", "lfd_kernels.hip", "lfd_select.hip", "lfd_writer.hip", "lfd_host.hip", "lfd_image.hip", "lfd_voxel.hip", "lfd_corr.hip", "lfd_cycle.hip", "lfd_support.hip", "lfd_refine.hip", "lfd_sigma.hip", "lfd_normals.hip", "lfd_colour.hip", "lfd_gain.hip", "lfd_far.hip", "lfd_audit.hip", "lfd_pose.hip", "lfd_consensus.hip", "lfd_undistort.hip", "lfd_freespace.hip", "lfd_depth.hip", "lfd_fuse.hip", "lfd_knn.hip", "lfd_block.hip", "lfd_cap.hip", "lfd_head.hip", "lfd_thin.hip", "lfd_photo.hip"]
-HEADERS = ["lfd_device.hpp", "lfd_geometry.hpp", "lfd_context.hpp", "lfd_corr.hpp", "lfd_cycle.hpp", "lfd_support.hpp", "lfd_refine.hpp", "lfd_sigma.hpp", "lfd_normals.hpp", "lfd_colour.hpp", "lfd_gain.hpp", "lfd_far.hpp", "lfd_audit.hpp", "lfd_pose.hpp", "lfd_consensus.hpp", "lfd_undistort.hpp", "lfd_freespace.hpp", "lfd_depth.hpp", "lfd_fuse.hpp", "lfd_knn.hpp", "lfd_block.hpp", "lfd_cap.hpp", "lfd_head.hpp", "lfd_thin.hpp", "lfd_photo.hpp", os.path.join("..", "..", "include", "lfd_densify.h")]
+SOURCES = ["lfd_api.hip", "lfd_kernels.hip", "lfd_select.hip", "lfd_writer.hip", "lfd_host.hip", "lfd_image.hip", "lfd_voxel.hip", "lfd_corr.hip", "lfd_cycle.hip", "lfd_support.hip", "lfd_refine.hip", "lfd_sigma.hip", "lfd_normals.hip", "lfd_colour.hip", "lfd_gain.hip", "lfd_far.hip", "lfd_audit.hip", "lfd_pose.hip", "lfd_consensus.hip", "lfd_component.hip", "lfd_undistort.hip", "lfd_freespace.hip", "lfd_depth.hip", "lfd_fuse.hip", "lfd_knn.hip", "lfd_block.hip", "lfd_cap.hip", "lfd_head.hip", "lfd_thin.hip", "lfd_photo.hip"]
+HEADERS = ["lfd_device.hpp", "lfd_geometry.hpp", "lfd_context.hpp", "lfd_corr.hpp", "lfd_cycle.hpp", "lfd_support.hpp", "lfd_refine.hpp", "lfd_sigma.hpp", "lfd_normals.hpp", "lfd_colour.hpp", "lfd_gain.hpp", "lfd_far.hpp", "lfd_audit.hpp", "lfd_pose.hpp", "lfd_consensus.hpp", "lfd_component.hpp", "lfd_undistort.hpp", "lfd_freespace.hpp", "lfd_depth.hpp", "lfd_fuse.hpp", "lfd_knn.hpp", "lfd_block.hpp", "lfd_cap.hpp", "lfd_head.hpp", "lfd_thin.hpp", "lfd_photo.hpp", os.path.join("..", "..", "include", "lfd_densify.h")]
 # -amdgpu-sched-strategy=max-ilp: the dense kernel is bound by its vector arithmetic (long dependent f64 chains); the
 # ILP-first machine scheduler is worth 3.5 % on it (profiles/history.md (r1/ablation.txt)), instruction semantics are unchanged
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",

@@ -29,6 +29,7 @@
 #include "lfd_pose.hpp"
 #include "lfd_sigma.hpp"
 #include "lfd_consensus.hpp"
+#include "lfd_component.hpp"
 #include "lfd_undistort.hpp"
 #include "lfd_freespace.hpp"
 #include "lfd_depth.hpp"
@@ -92,6 +93,16 @@ extern "C" __global__ void lfd_consensus_wgcount_kernel(const uint8_t* keep, lon
 extern "C" __global__ void lfd_consensus_offsets_kernel(const long long* offs, int n_refs, const uint8_t* keep, const unsigned* wg_kept, long long* offs_out);
 extern "C" __global__ void lfd_consensus_scatter_kernel(const float* xyz, const float* rgb, const float* err, long long n, const uint8_t* keep,
                                                         const unsigned* wg_kept, float* o_xyz, float* o_rgb, float* o_err);
+extern "C" __global__ void lfd_component_gather_kernel(const float* xyz, const unsigned* sorted_idx, long long n, LfdComponentPt* spt, uint32_t* parent,
+                                                       uint32_t* count, uint32_t* first, unsigned long long* summary);
+extern "C" __global__ void lfd_component_link_kernel(const unsigned long long* skey, const LfdComponentPt* spt, long long n, unsigned long long e1,
+                                                     unsigned long long e2, unsigned long long sentinel, float r2, uint32_t* parent);
+extern "C" __global__ void lfd_component_flatten_kernel(const uint32_t* parent, long long n, uint32_t* root);
+extern "C" __global__ void lfd_component_size_kernel(const uint32_t* root, const LfdComponentPt* spt, long long n, int aggregate, uint32_t* count,
+                                                     uint32_t* first);
+extern "C" __global__ void lfd_component_mark_kernel(const uint32_t* root, const LfdComponentPt* spt, const uint32_t* count, const uint32_t* first,
+                                                     long long n, uint32_t min_points, uint8_t* keep, uint32_t* size, uint32_t* label,
+                                                     unsigned long long* summary);
 extern "C" __global__ void lfd_fuse_side_kernel(const float* normals, long long n, const unsigned* sorted_idx, const unsigned* vstart, const unsigned* nv_p,
                                                 uint8_t* flag, unsigned* rows, unsigned* big, unsigned* n_big);
 extern "C" __global__ void lfd_fuse_side_big_kernel(const float* normals, long long n, const unsigned* sorted_idx, const unsigned* vstart, const unsigned* nv_p,
@@ -539,6 +550,7 @@ void read_env_switches(lfd_context* ctx) {
     if (const char* e = std::getenv("LFD_INDEXED_SPLIT")) ctx->env.indexed_split = std::atoi(e) != 0;
     if (const char* e = std::getenv("LFD_SELECT_TIMING")) ctx->env.select_timing = std::max(1, std::atoi(e));
     if (const char* e = std::getenv("LFD_SELECT_WORKGROUPS")) ctx->env.select_workgroups = std::atoi(e);
+    if (const char* e = std::getenv("LFD_COMPONENT_PLAIN_SIZE")) ctx->env.component_plain_size = std::atoi(e) != 0;
 }
 
 int check_points(lfd_context* ctx, const lfd_points* out, const long long* ref_offsets) {
@@ -1707,6 +1719,64 @@ int lfd_consensus_filter(lfd_context* ctx, const float* xyz, const float* rgb, c
     hipLaunchKernelGGL(lfd_consensus_gather_kernel, dim3(p.grid), dim3(256), 0, st, xyz, w.idx[cur], c.offs, (int)n_refs, p.n, spt);
     hipLaunchKernelGGL(lfd_consensus_count_kernel, dim3((unsigned)p.n_wg), dim3(256), 0, st, w.keys[cur], spt, w.idx[cur], p.n, g.e[1], g.e[2],
                        g.sentinel, lfd_consensus_r2(radius), (int)min_refs, consensus ? LFD_CONSENSUS_CAP : (int)min_refs, c.keep, consensus);
+    return cloud_compact(ctx, p, c, xyz, rgb, err, n_refs, xyz_out, rgb_out, err_out, ref_offsets_out_host, n_out_host);
+}
+
+// ---- connected-component filter on the final cloud (lfd_component.hip) ---------------------------------------------------------------------------
+int lfd_component_filter(lfd_context* ctx, const float* xyz, const float* rgb, const float* err, int64_t n, const int64_t* ref_offsets_host,
+                         int32_t n_refs, float radius, int32_t min_points, float* xyz_out, float* rgb_out, float* err_out,
+                         int64_t* ref_offsets_out_host, uint32_t* size, uint32_t* label, int64_t* summary_host, int64_t* n_out_host) {
+    if (!ctx) return fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (ctx->is_host) return fail(ctx, LFD_ERR_STATE, "device entry point called on a host context");
+    if (const char* why = lfd_component_check(xyz, rgb, err, n, ref_offsets_host, n_refs, radius, min_points, xyz_out, rgb_out, err_out,
+                                              ref_offsets_out_host, size, label, n_out_host))
+        return fail(ctx, LFD_ERR_INVALID, std::string("lfd_component_filter: ") + why);
+    for (int32_t r = 0; r <= n_refs; ++r) ref_offsets_out_host[r] = 0;
+    *n_out_host = 0;
+    if (summary_host) std::memset(summary_host, 0, LFD_COMPONENT_SUMMARY * sizeof(int64_t));
+    if (n == 0) return LFD_OK;
+    LFD_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const CloudPlan p = cloud_plan(n);
+    CloudSort w;
+    LfdComponentPt* spt = nullptr;                                     // sorted points
+    uint32_t *parent = nullptr, *root = nullptr, *count = nullptr, *first = nullptr;      // per sorted position
+    unsigned long long* summary = nullptr;
+    CloudCompact c;
+    if (int rc = carve_cloud_ws(ctx, [&](Bump& b) {
+            w = carve_sort(b, p.n, 0, false);
+            spt = b.take<LfdComponentPt>((size_t)n);
+            parent = b.take<uint32_t>((size_t)n);
+            root = b.take<uint32_t>((size_t)n);
+            count = b.take<uint32_t>((size_t)n);
+            first = b.take<uint32_t>((size_t)n);
+            summary = b.take<unsigned long long>(LFD_COMPONENT_SUMMARY);
+            c = carve_compact(b, p, n_refs);
+        }))
+        return rc;
+
+    // min / max over the finite points; the key-range refusal is decided before anything is sorted
+    LFD_HIP(ctx, hipMemcpyAsync(c.offs, ref_offsets_host, ((size_t)n_refs + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    LfdVoxStats s;
+    if (int rc = cloud_stats(ctx, p, w, xyz, nullptr, s)) return rc;
+    LfdConsensusGrid g;
+    if (!lfd_component_grid(s.lo, s.hi, radius, g))
+        return fail(ctx, LFD_ERR_INVALID, "lfd_component_filter: key range: more than 2^30 cells along an axis or a linear cell key beyond 63 bits");
+
+    hipLaunchKernelGGL(lfd_consensus_keys_kernel, dim3(p.grid), dim3(256), 0, st, xyz, p.n, g.origin[0], g.origin[1], g.origin[2], g.h, g.e[1],
+                       g.e[2], g.sentinel, w.keys[0], w.idx[0]);
+    const int cur = cloud_sort(st, p, w, g.bits);
+    const dim3 wgs((unsigned)p.n_wg);
+    hipLaunchKernelGGL(lfd_component_gather_kernel, dim3(p.grid), dim3(256), 0, st, xyz, w.idx[cur], p.n, spt, parent, count, first, summary);
+    hipLaunchKernelGGL(lfd_component_link_kernel, wgs, dim3(256), 0, st, w.keys[cur], spt, p.n, g.e[1], g.e[2], g.sentinel, lfd_consensus_r2(radius),
+                       parent);
+    hipLaunchKernelGGL(lfd_component_flatten_kernel, wgs, dim3(256), 0, st, parent, p.n, root);
+    hipLaunchKernelGGL(lfd_component_size_kernel, wgs, dim3(256), 0, st, root, spt, p.n, ctx->env.component_plain_size ? 0 : 1, count, first);
+    hipLaunchKernelGGL(lfd_component_mark_kernel, wgs, dim3(256), 0, st, root, spt, count, first, p.n, (uint32_t)min_points, c.keep, size, label,
+                       summary);
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the summary is copied word for word");
+    if (summary_host)                                                  // (every word is below 2^63; cloud_compact waits for the stream)
+        LFD_HIP(ctx, hipMemcpyAsync(summary_host, summary, LFD_COMPONENT_SUMMARY * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     return cloud_compact(ctx, p, c, xyz, rgb, err, n_refs, xyz_out, rgb_out, err_out, ref_offsets_out_host, n_out_host);
 }
 

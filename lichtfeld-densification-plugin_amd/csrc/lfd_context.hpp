@@ -49,6 +49,7 @@ struct LfdEnvSwitches {          // profiling / A-B switches of the environment,
     bool indexed_split = true;            // LFD_INDEXED_SPLIT=0: indexed mode in one kernel
     int select_timing = 0;                // LFD_SELECT_TIMING: 1 phase stamps of the selection kernel, 2 of the multi-workgroup one
     int select_workgroups = -1;           // LFD_SELECT_WORKGROUPS: compute workgroups of the selection (-1: default)
+    bool component_plain_size = false;    // LFD_COMPONENT_PLAIN_SIZE=1: lfd_component_size_kernel without its aggregation (the A/B run of DESIGN 4.29)
 };
 
 struct lfd_context {
@@ -92,7 +93,7 @@ struct lfd_context {
     DeviceBuffer sel_chain;                      // lfd_triangulate_sampled_chain: chain block, the stream's ring of doubles, the keys of its twists
     DeviceBuffer stamps;           // profiling builds: phase stamps of the dense kernel
     DeviceBuffer seg_scan;         // tile segments: exclusive prefix of the last table handed to lfd_order_segments / lfd_pack_*_segments
-    // The one scratch area of the stages on the final cloud (lfd_voxel_downsample, lfd_consensus_filter, lfd_freespace_filter, lfd_fuse_oriented,
+    // The one scratch area of the stages on the final cloud (lfd_voxel_downsample, lfd_consensus_filter, lfd_component_filter, lfd_freespace_filter, lfd_fuse_oriented,
     // lfd_knn_dist2, lfd_render_depth), grown on demand.  Each call carves it anew (lfd_api.hip: carve_cloud_ws) and writes or clears every word before it reads it;
     // the stages may share it because each of them returns with the stream idle.
     DeviceBuffer cloud_ws;

@@ -32,6 +32,7 @@
 #include "lfd_audit.hpp"
 #include "lfd_pose.hpp"
 #include "lfd_consensus.hpp"
+#include "lfd_component.hpp"
 #include "lfd_undistort.hpp"
 #include "lfd_freespace.hpp"
 #include "lfd_depth.hpp"
@@ -1172,6 +1173,86 @@ int lfd_consensus_filter_host(lfd_context* ctx, const float* xyz, const float* r
         if (i == n) break;
         if (consensus) consensus[i] = cnt[(size_t)i];
         if ((int)cnt[(size_t)i] < (int)min_refs) continue;
+        std::memcpy(xyz_out + 3 * o, xyz + 3 * i, 12);
+        if (rgb) std::memcpy(rgb_out + 3 * o, rgb + 3 * i, 12);
+        if (err) std::memcpy(err_out + o, err + i, 4);
+        ++o;
+    }
+    *n_out_host = o;
+    return LFD_OK;
+}
+
+// The twin of lfd_component_filter: the same keys, a stable sort, lfd_component_links per sorted point into a SEQUENTIAL union-find
+// (the partition does not depend on the order of the unions, so one thread gives what the device's thousands give), then sizes, labels, the
+// summary and the stable compaction.
+int lfd_component_filter_host(lfd_context* ctx, const float* xyz, const float* rgb, const float* err, int64_t n, const int64_t* ref_offsets_host,
+                              int32_t n_refs, float radius, int32_t min_points, float* xyz_out, float* rgb_out, float* err_out,
+                              int64_t* ref_offsets_out_host, uint32_t* size, uint32_t* label, int64_t* summary_host, int64_t* n_out_host) {
+    if (!ctx) return lfd_fail(nullptr, LFD_ERR_INVALID, "null context");
+    if (!ctx->is_host) return lfd_fail(ctx, LFD_ERR_STATE, "the *_host entry points need a context made by lfd_create_host");
+    if (const char* why = lfd_component_check(xyz, rgb, err, n, ref_offsets_host, n_refs, radius, min_points, xyz_out, rgb_out, err_out,
+                                              ref_offsets_out_host, size, label, n_out_host))
+        return lfd_fail(ctx, LFD_ERR_INVALID, std::string("lfd_component_filter_host: ") + why);
+    for (int32_t r = 0; r <= n_refs; ++r) ref_offsets_out_host[r] = 0;
+    *n_out_host = 0;
+    if (summary_host) std::memset(summary_host, 0, LFD_COMPONENT_SUMMARY * sizeof(int64_t));
+    if (n == 0) return LFD_OK;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (long long i = 0; i < n; ++i) {
+        if (!lfd_consensus_finite(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2])) continue;
+        for (int c = 0; c < 3; ++c) { lo[c] = std::min(lo[c], xyz[3 * i + c]); hi[c] = std::max(hi[c], xyz[3 * i + c]); }
+    }
+    LfdConsensusGrid g;
+    if (!lfd_component_grid(lo, hi, radius, g))
+        return lfd_fail(ctx, LFD_ERR_INVALID, "lfd_component_filter_host: key range: more than 2^30 cells along an axis or a linear cell key beyond 63 bits");
+    const long long* offs = reinterpret_cast<const long long*>(ref_offsets_host);
+    const int n_chunks = (int)((n + kChunk - 1) / kChunk);
+    std::vector<std::pair<unsigned long long, unsigned>> order((size_t)n);
+    parallel_chunks(ctx, n_chunks, [&](int c) {
+        const long long i1 = std::min<long long>(n, (long long)(c + 1) * kChunk);
+        for (long long i = (long long)c * kChunk; i < i1; ++i)
+            order[(size_t)i] = {lfd_consensus_key(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], g.origin[0], g.origin[1], g.origin[2], g.h, g.e[1], g.e[2],
+                                                  g.sentinel), (unsigned)i};
+    });
+    std::sort(order.begin(), order.end());                             // (key, original index): the order of a stable sort by key
+    std::vector<unsigned long long> skey((size_t)n);
+    std::vector<LfdComponentPt> spt((size_t)n);
+    std::vector<uint32_t> parent((size_t)n), count((size_t)n, 0u), first((size_t)n, 0xffffffffu);
+    for (long long j = 0; j < n; ++j) {
+        const long long i = order[(size_t)j].second;
+        skey[(size_t)j] = order[(size_t)j].first;
+        spt[(size_t)j] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], (uint32_t)i};
+        parent[(size_t)j] = (uint32_t)j;
+    }
+    const float r2 = lfd_consensus_r2(radius);
+    for (long long j = 0; j < n && skey[(size_t)j] != g.sentinel; ++j) {       // the sentinel keys sort last
+        uint32_t mine = (uint32_t)j;
+        lfd_component_links(skey.data(), spt.data(), j, g.e[1], g.e[2], r2,
+                            [&](uint32_t q) { mine = lfd_component_unite<LfdComponentSeq, true>(parent.data(), mine, q); });
+    }
+    std::vector<uint32_t> root((size_t)n);
+    for (long long j = 0; j < n; ++j) {
+        const uint32_t r = lfd_component_find<LfdComponentSeq>(parent.data(), (uint32_t)j);
+        root[(size_t)j] = r;
+        count[r] += 1u;
+        first[r] = std::min(first[r], spt[(size_t)j].idx);
+    }
+    std::vector<uint8_t> keep((size_t)n);
+    for (long long j = 0; j < n; ++j) {
+        const uint32_t r = root[(size_t)j], s = count[r];
+        const long long i = spt[(size_t)j].idx;
+        keep[(size_t)i] = s >= (uint32_t)min_points ? 1 : 0;
+        if (size) size[i] = s;
+        if (label) label[i] = first[r];
+        if (summary_host && r == (uint32_t)j) lfd_component_summary_add(summary_host, s);
+    }
+    // stable compaction: the input order inside and across references, every value copied as bytes
+    long long o = 0;
+    int r_next = 0;
+    for (long long i = 0; i <= n; ++i) {
+        while (r_next <= n_refs && offs[r_next] <= i) ref_offsets_out_host[r_next++] = o;
+        if (i == n) break;
+        if (!keep[(size_t)i]) continue;
         std::memcpy(xyz_out + 3 * o, xyz + 3 * i, 12);
         if (rgb) std::memcpy(rgb_out + 3 * o, rgb + 3 * i, 12);
         if (err) std::memcpy(err_out + o, err + i, 4);

@@ -9,6 +9,7 @@ per-reference hot path runs on the GPU.
 from __future__ import annotations
 
 import argparse
+import json
 import math
 import os
 from typing import Callable, Dict, List, Optional, Tuple
@@ -642,6 +643,84 @@ def _apply_freespace_filter(result, config: DensePipelineConfig, camera_records,
                           clock=result._clock, loader=loader, device_normals=normals, match_grid=result.match_grid)
 
 
+def component_report(radius: float, min_points: int, n_in: int, n_out: int, summary) -> dict:
+    """What ``<output file>.components.json`` holds: the knobs, the points in and out, the number of components, the largest one and the two
+    histograms over the bins 2^b <= size < 2^(b + 1) (trailing empty bins left out).  No timing: a device run and a host run write the same
+    bytes."""
+    s = [int(v) for v in np.asarray(summary, np.int64).reshape(66)]
+    top = max([b + 1 for b in range(32) if s[2 + b]] or [0])
+    return {"component_radius": float(radius), "min_component_points": int(min_points), "points_in": int(n_in), "points_out": int(n_out),
+            "n_components": s[0], "largest_component": s[1],
+            "bins": [{"size_from": 1 << b, "size_below": 1 << (b + 1), "components": s[2 + b], "points": s[34 + b]} for b in range(top)]}
+
+
+def _apply_component_filter(result, config: DensePipelineConfig, progress_callback=None):
+    """The connected-component filter on the finished cloud (lfd_component_filter), where the points are, behind the consensus
+    and free-space filters and in front of the depth maps, thinning, cap, fusion, Gaussian output and voxel filter.  Returns the result with
+    the kept points (input order, same bits), their normals and their per-reference counts in place of the cloud, and writes
+    ``<output file>.components.json``.  Off (experimental['min_component_points'] = 0): the result itself, nothing runs."""
+    min_points = int(config.exp("min_component_points"))
+    if min_points <= 0 or result.streamed_path is not None:
+        return result
+    from .core import hip_backend as hb
+    from .core.sinks import PipelineResult
+    import torch
+    radius = float(config.exp("component_radius"))
+    pts = result.device_points
+    if pts is None:
+        pts = tuple(torch.from_numpy(np.ascontiguousarray(a)) for a in (result.xyz, result.rgb, result.err))
+    counts = np.asarray(result.points_per_reference, np.int64)
+    n_in = int(pts[0].shape[0])
+    if int(counts.sum()) != n_in:
+        raise RuntimeError(f"experimental['min_component_points'] needs the whole cloud with its per-reference counts: this result holds {n_in:,} "
+                           f"points, the counts add up to {int(counts.sum()):,} (a rank of a gather_to_root run that is not the root)")
+    if progress_callback:
+        progress_callback(93.5, "Applying component filter...")
+    on_gpu = bool(pts[0].is_cuda)
+    dens = hb.HipDensifier(pts[0].device) if on_gpu else hb.HostDensifier(int(config.exp("host_threads")))
+    normals = result.device_normals                  # experimental['estimate_normals']: the filter's keep decision applies to them as well
+    try:
+        xyz, rgb, err, kept, sizes, labels, summary = dens.component_filter(pts[0], pts[1], pts[2], counts, radius, min_points,
+                                                                            with_sizes=True, with_labels=True)
+        keep = sizes >= min_points
+        # a component's label is the index of one of its points: the dropped components are the dropped points that carry their own label
+        heads = labels.long() == torch.arange(n_in, device=labels.device)
+        n_dropped_components = int((heads & ~keep).sum())
+        if normals is not None:
+            # the compaction is the library's; its per-point size gives the rows it kept, and that is CHECKED, not assumed: the input
+            # positions under the mask must be the kept positions bit for bit before the mask is applied to the normals
+            if int(keep.sum()) != int(xyz.shape[0]) or not torch.equal(pts[0][keep].view(torch.int32), xyz.view(torch.int32)):
+                raise RuntimeError("component filter: the per-point sizes do not name the rows the filter kept; the normals cannot follow the points")
+            normals = normals[keep]
+    except hb.ConsensusInputRefused as exc:
+        raise RuntimeError(f"experimental['component_radius'] = {radius:g} is too small for the extent of this cloud: {exc}") from exc
+    finally:
+        dens.close()
+    n_kept = int(xyz.shape[0])
+    report = component_report(radius, min_points, n_in, n_kept, summary)
+    if _is_writer_rank():
+        with open(str(config.output_path) + ".components.json", "w") as f:
+            f.write(json.dumps(report, indent=1) + "\n")
+    log.info(f"Component filter (radius {radius:.4f}, at least {min_points:,} points): {n_in:,} points in {report['n_components']:,} components in; "
+             f"{n_in - n_kept:,} points in {n_dropped_components:,} components dropped, {n_kept:,} points kept (largest component "
+             f"{report['largest_component']:,} points)")
+    new_pts = (xyz, rgb, err)
+    if on_gpu:
+        clock = result._clock
+
+        def loader(p=new_pts, clk=clock):
+            if hasattr(clk, "stage"):
+                with clk.stage("d2h"):
+                    return tuple(t.cpu().numpy() for t in p)
+            return tuple(t.cpu().numpy() for t in p)
+        arrays = (None, None, None)
+    else:
+        loader, arrays = None, tuple(t.numpy() for t in new_pts)
+    return PipelineResult(xyz=arrays[0], rgb=arrays[1], err=arrays[2], elapsed_seconds=result.elapsed_seconds, pairs_processed=result.pairs_processed,
+                          pairs_matched=result.pairs_matched, points_per_reference=kept, device_points=new_pts, streamed_path=None,
+                          clock=result._clock, loader=loader, device_normals=normals, match_grid=result.match_grid)
+
+
 def footprint_rows(camera_records, refs_local, match_grid) -> np.ndarray:
     """(n_refs, 5) f64, one row per reference as lfd_thin_footprint takes it: the third row of its world-to-camera [R | t] and the tangent of one
     cell of the matcher's grid (``match_grid`` = (H, W)), max(width / (fx W), height / (fy H))."""
@@ -1007,6 +1086,7 @@ def dense_init(args, progress_callback: Optional[Callable[[float, str], None]] =
     result = _apply_gain_compensation(result, config, records, refs_local, progress_callback)      # (while the counts are still the loop's)
     result = _apply_consensus_filter(result, config, progress_callback)      # (in front of the point cap: it has to see the whole cloud)
     result = _apply_freespace_filter(result, config, records, refs_local, progress_callback)      # (behind it: what it removed cannot "see through" a surface)
+    result = _apply_component_filter(result, config, progress_callback)      # (behind the filters that need a second witness: what is left and isolated)
     _write_depth_maps(result, config, records, progress_callback)      # (a side output of the densest filtered cloud, in front of cap, fusion and voxel filter)
     result = _apply_footprint_thin(result, config, records, refs_local, progress_callback)      # (in front of cap, fusion, Gaussian output and voxel filter)
     if progress_callback:
@@ -1081,6 +1161,7 @@ def dense_init_from_lfs(camera_nodes, config: DensePipelineConfig,
         result = _apply_gain_compensation(result, config, records, refs_local, progress_callback)      # (while the counts are still the loop's)
         result = _apply_consensus_filter(result, config, progress_callback)  # (in front of the point cap and the voxel filter: it has to see the whole cloud)
         result = _apply_freespace_filter(result, config, records, refs_local, progress_callback)   # (behind it, in front of cap and voxel filter)
+        result = _apply_component_filter(result, config, progress_callback)   # (behind the filters that need a second witness)
         _write_depth_maps(result, config, records, progress_callback)      # (a side output of that cloud)
         result = _apply_footprint_thin(result, config, records, refs_local, progress_callback)   # (in front of cap, fusion, Gaussian output and voxel filter)
     except RuntimeError as exc:
@@ -1197,6 +1278,10 @@ def _experimental_from_args(args) -> dict:
         exp["min_consensus_refs"] = int(args.min_consensus_refs)
     if float(getattr(args, "consensus_radius", 0.0)) != 0.0:
         exp["consensus_radius"] = float(args.consensus_radius)
+    if int(getattr(args, "min_component_points", 0)) != 0:
+        exp["min_component_points"] = int(args.min_component_points)
+    if float(getattr(args, "component_radius", 0.0)) != 0.0:
+        exp["component_radius"] = float(args.component_radius)
     if int(getattr(args, "min_freespace_violations", 0)) != 0:
         exp["min_freespace_violations"] = int(args.min_freespace_violations)
     if getattr(args, "freespace_depth_tol_rel", None) is not None:
@@ -1317,6 +1402,12 @@ def build_argparser() -> argparse.ArgumentParser:
                          "within --consensus_radius of it (1 .. 8; runs in front of --max_points; 0 = off)")
     ap.add_argument("--consensus_radius", type=float, default=0.0,
                     help="... within this distance in scene units (required > 0 with --min_consensus_refs)")
+    ap.add_argument("--min_component_points", type=int, default=0,
+                    help="connected-component filter on the final cloud: keep a point only if the connected component it belongs to - points "
+                         "linked when within --component_radius of each other - has at least this many points (>= 2; runs behind "
+                         "--min_consensus_refs and --min_freespace_violations, in front of --max_points; 0 = off)")
+    ap.add_argument("--component_radius", type=float, default=0.0,
+                    help="... linked within this distance in scene units (required > 0 with --min_component_points)")
     ap.add_argument("--min_freespace_violations", type=int, default=0,
                     help="free-space filter on the final cloud: drop a point when at least this many OTHER references triangulated a surface behind it "
                          "on the same ray (they looked through it) and more refute than confirm it (1 .. 255; runs behind --min_consensus_refs and "
